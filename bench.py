@@ -1,6 +1,6 @@
 """Benchmark of the hot path: video-segments/sec on the stage-2 100-segment recursion at Vicuna-7B scale.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by the driver as ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...``)
 
 One "step" = one stage-2 recursion (zoom levels 4/2/1) of one query over this rank's 100 windows
@@ -16,19 +16,27 @@ block-partitioned, CLS rows and proposals exchanged by RCCL all-gathers inside e
 ``--scaling strong``: ONE 100-window recursion per step sharded over the N ranks (100/N windows each, the 7 calls dealt over the
 ranks with a rotating start: single-query latency).  Inputs are resident in HBM when the timed region starts.
 
-Prints ONE JSON line (rank 0) with the contract fields plus ``roofline`` (dominant kernel, timed with HIP events on
-the launch stream) and ``cpu_baseline`` (the torch-fp32 CPU oracle on a bounded sample, N = 1 only).
+Prints ONE JSON line (rank 0) with the contract fields (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``
+= milliseconds of one timed step).  A plain run does only what that headline needs: set-up, the untimed settle and W warm-up steps, the
+K timed steps, ``--dump-outputs DIR`` and the line.  ``--dump-outputs DIR`` writes the last timed step's record (what a caller of the
+recursion receives: inverted entropies, cosine scores, answers as code points, ...) as ``DIR/<name>.npy`` in float64; the inputs are
+hash-seeded, so two runs with the same arguments see the same inputs.
+
+``--full`` adds everything else, after the headline's timed region: ``roofline`` (dominant kernel, timed with HIP events on the launch
+stream), ``clocks_during_the_timed_region``, ``cpu_baseline`` (the torch-fp32 CPU oracle on a bounded sample, N = 1 only) and the
+``extra_measurements`` below.
 
 The timed region is exactly K steps after W warm-up steps (and ``--settle`` untimed steps that belong to the set-up), with
 ``--streams`` steps in flight whose generates decode through one ``serve.DecodeServer`` (``--merge-decode``: shared KV pool,
 every decode step ONE pass over the LLM weights for the rows of all steps in flight; records identical to running them one
-by one).  ``value`` is the bf16 path, one video per step.  At N = 1 the same loop is then timed again in
+by one).  ``value`` is the bf16 path, one video per step.  With ``--full``, at N = 1 the same loop is then timed again in
 other configurations and reported under ``extra_measurements`` (never ``value``): FP8 decode weights, the full opt-in FP8
 LLM path, two different videos batched per step, an EOS id configured (lagging device-side stop flag instead of a forced
 length), and the other BASELINE.json workloads (``stage2_long_33``, ``stage1_dense``, ``stage1_sparse``; ``--workload X`` times
 one of them alone as the line's ``value``).
 """
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -119,6 +127,11 @@ def parse():
                    help="CPU baseline = the whole recursion (7 calls x (100 segment encodings + prefill + G decode steps), 32 layers) through the "
                         "oracle, 1 warm-up + 3 repeats, median (minutes); default: ONE such call timed once, x 7 identical calls")
     p.add_argument("--cpu-sample", action="store_true", help="CPU baseline from a sample (16 segments, 4 of 32 layers), labelled extrapolated")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need, after its timed region: roofline legs, clocks, the CPU baseline, the extra legs "
+                        "(N = 1) or the other scaling modes and the same-box N = 1 reference (N > 1); --no-extras / --no-cpu-baseline still drop parts")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float64")
     return p.parse_args()
 
 
@@ -341,6 +354,15 @@ def host_cpu():
         cores = psutil.cpu_count(logical=False) or cores
     except Exception:  # noqa: BLE001
         pass
+    # the cores this process may use: a shared host hands a job a slice of its cores (affinity mask, OMP_NUM_THREADS), and a thread
+    # pool sized by the whole host only slows itself down
+    try:
+        cores = min(cores, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        cores = min(cores, int(omp))
     model = "unknown"
     try:
         with open("/proc/cpuinfo") as f:
@@ -434,6 +456,33 @@ def cpu_baseline(args, n_calls, P):
     return info
 
 
+def dump_outputs(path, rec):
+    """``--dump-outputs``: what the timed path handed its caller in the last timed step, one float64 ``<name>.npy`` per array under
+    ``path``.  A stage-2 record: per call (in plan order) the inverted entropies, the window group (start, zoom), the answer as unicode
+    code points (-1 padded) and the window indexes, plus the proposals' cosine scores (rank 0's own record at N > 1).  A stage-1
+    workload: every tensor of the last generate's output."""
+    import numpy as np
+    arrays = {}
+    if isinstance(rec, dict) and "answers" in rec:
+        for k in ("max_entropy", "mean_entropy", "score_cos", "starts", "hierarchy_zooms"):
+            arrays[k] = np.asarray(rec[k], dtype=np.float64)
+        n = max([len(a) for a in rec["answers"]] + [1])
+        arrays["answers_codepoints"] = np.array([[ord(c) for c in a] + [-1] * (n - len(a)) for a in rec["answers"]], dtype=np.float64).reshape(-1, n)
+        arrays["window_indexes"] = np.concatenate([np.asarray(i, dtype=np.float64).ravel() for i in rec["indexes"]])
+    else:
+        for k, v in rec.items():
+            if isinstance(v, (list, tuple)) and v and all(torch.is_tensor(t) for t in v):
+                v = torch.stack(list(v))
+            if torch.is_tensor(v):
+                arrays[k] = v.detach().cpu().double().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError(f"bench: --dump-outputs would write {total} bytes (limit 64 MiB)")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def spawn_ranks(args):
     """``python bench.py --gpus N`` without a launcher: start N ranks with ``torch.distributed.run`` as a CHILD process (this
     process has not touched the GPU), relay what it prints and return its exit status."""
@@ -511,9 +560,9 @@ def main():
     model.get_model().initialize_vision_modules(hier_args())
     eng = model.engine
     headline = args.workload == "stage2_long_100"
-    # extra legs (single GPU, after the headline's timed region).  The FP8 copies are resident from the start and switched off
+    # extra legs (--full, single GPU, after the headline's timed region).  The FP8 copies are resident from the start and switched off
     # for the headline.
-    extras = (world == 1 and headline and not args.no_extras and not args.fp8_decode and not args.fp8_prefill and args.queries == 1
+    extras = (args.full and world == 1 and headline and not args.no_extras and not args.fp8_decode and not args.fp8_prefill and args.queries == 1
               and not args.eos)
     eng.init_synthetic(seed=args.seed, llm=True, clip=True, fp8_decode=args.fp8_decode or extras, fp8_prefill=args.fp8_prefill or extras,
                        parity=extras or args.parity)
@@ -767,7 +816,7 @@ def main():
         return run1, dict(prompt_tokens=int(ids.shape[1]), prefill_len=int(S), frames=frames, windows_per_step=1)
 
     sync()       # weights / inputs were written on the default stream; the step streams do not wait for it implicitly
-    headline_clocks = n1_ref = None
+    headline_clocks = n1_ref = out1 = None
     if args.workload.startswith("stage1"):
         run1, wl_cfg = stage1_runner(args.workload)
         if args.settle > 0:
@@ -780,10 +829,12 @@ def main():
     else:
         if args.settle > 0:
             # set-up, untimed: at least one whole K-step run, so that every gang shape, pass size, pinned-buffer size and host code path of the timed
-            # region has run once (the first process on a fresh box paged parts of them in inside a 10-step timed region: 22.1 vs 18.0 ms per step)
-            run(max(args.settle, args.steps))
+            # region has run once (the first process on a fresh box paged parts of them in inside a 10-step timed region: 22.1 vs 18.0 ms per step).
+            # Beyond 64 steps the pipeline repeats itself: 64 steps plus the remainder of K over the steps in flight end in the timed region's tail
+            # shape, and the set-up stays bounded however long the timed region is
+            run(max(args.settle, args.steps if args.steps <= 64 else 64 + args.steps % max(1, args.streams)))
             sync()
-        if world > 1:
+        if world > 1 and args.full:
             # the same box's N = 1 value, measured in THIS process tree: rank 0 runs the 1-GPU pipeline alone (its own videos / queries, no collective) while
             # the other ranks wait at the barrier below - the denominator of every per-mode efficiency in this line
             if rank == 0:
@@ -798,10 +849,10 @@ def main():
                 work.clear()
                 work.update(saved_w)
             sync()
-        sampler = ClockSampler(dev)
-        with sampler:
+        sampler = ClockSampler(dev) if args.full else None
+        with sampler or contextlib.nullcontext():
             dt, rec = timed(run, tag="headline")
-        headline_clocks = sampler.summary()
+        headline_clocks = sampler.summary() if sampler is not None else None
         if any(e != e for e in rec["max_entropy"]) or not all(rec["answers"]):
             raise RuntimeError(f"bench: the last record is not finite / empty: {rec['answers']} {rec['max_entropy']}")
         value = W * args.queries * args.steps * (world if by_query else 1) / dt
@@ -809,8 +860,11 @@ def main():
         if by_query and work["gathered"].shape[0] != world * args.steps:
             raise RuntimeError(f"bench: the final all-gather returned {tuple(work['gathered'].shape)} proposals rows for {world} ranks x {args.steps} steps")
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec if rec is not None else out1)
+
     extra = {}
-    if headline and world == 1 and not args.no_extras:
+    if args.full and headline and world == 1 and not args.no_extras:
         # SUSTAINED: the headline is a K-step burst (20 steps = 0.3 s: pipeline fill and drain included, clocks not yet settled under the socket power
         # limit).  The same run() for >= 10 s right behind it, with the shader clock and socket power sampled next to it
         try:
@@ -1012,7 +1066,7 @@ def main():
         other_fl = "bf16" if hip.flavour() == "f16" else "f16"
         try:
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-extras", "--no-cpu-baseline",
+            cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-extras", "--no-cpu-baseline",
                    "--op-dtype", other_fl, "--seed", str(args.seed), "--streams", str(args.streams), "--prefill-batch", str(args.prefill_batch), "--encode-batch", str(args.encode_batch), "--pools", str(args.pools)]
             r_ = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, REVISION_BENCH_CHILD="1"))
             line = [l for l in r_.stdout.splitlines() if l.startswith("{")][-1]
@@ -1026,7 +1080,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extra["operands_" + other_fl] = {"error": f"{type(e).__name__}: {e}"[:300]}
     rccl_seen = None
-    if world > 1 and headline and not args.no_extras and not args.workload.startswith("stage1"):
+    if args.full and world > 1 and headline and not args.no_extras and not args.workload.startswith("stage1"):
         # The one multi-GPU run the driver makes must also measure the split the north star's 60 % target is about: after the headline
         # (whatever --scaling asked for) the OTHER modes are timed on the same ranks - ``segments`` (a 100 * N-window video per step, windows
         # block-partitioned, all-gather #1 of the CLS rows and #2 of the proposals inside every recursion) and ``strong`` (ONE 100-window
@@ -1128,57 +1182,68 @@ def main():
         row_map = model.build_row_map(ids1.repeat(n_calls_rank, 1), batch)
         P0 = model._common_text_prefix(row_map) if n_calls_rank > 1 else 0
         M_prefill = P0 + n_calls_rank * (S - P0)
-        eng.set_option("fp8_decode", 0)
-        eng.set_option("fp8_prefill", 0)
-        # generates per merged decode step of the timed region: a full pool under the gang policy, else what the run averaged
-        gang = max(1, args.pool_rows // n_calls_rank) if (server is not None and args.pools > 1) else 1
-        if server is not None and args.pools <= 1:
-            gang = max(1, min(args.pool_rows // n_calls_rank, round(server.rows_served / max(1, server.steps_run) / n_calls_rank)))
-        pf_groups = 1
-        if server is not None and server.prefill_batch > 1 and server.pf_batches:
-            pf_groups = max(server.pf_hist, key=server.pf_hist.get)       # the pass size that served most steps of this run: 1, 2, 4 or 8 prefills
-        legs = roofline_legs(model, n_calls_rank, M_prefill, dec_rows=min(144, gang * n_calls_rank), prefill_groups=pf_groups)
-        # dominant = the larger share of a recursion: 32 prefill launches shared by `pf_groups` recursions, or 32 x G decode launches
-        # shared by `gang` recursions
-        dom = max((legs[k] for k in ("prefill_gateup_gemm", "decode_gateup_gemv")),
-                  key=lambda l: l["ms"] * (32 / pf_groups if l["bound"] == "mfma" else 32 * G / gang))
-        traffic = pmc_traffic(dom["kernel"], dom["grid_threads"])
-        other = {k: {"kernel": v["kernel"], "achieved": v["achieved"], "unit": v["unit"], "frac": v["achieved"] / v["peak"], "avg_launch_ms": v["ms"],
-                     **({"tflops": v["tflops"]} if "tflops" in v else {}), **({"rows": v["rows"]} if "rows" in v else {}),
-                     **({"timing": v["timing"]} if "timing" in v else {}),
-                     **({"prefills_per_launch": v["prefills_per_launch"]} if "prefills_per_launch" in v else {})} for k, v in legs.items()}
-        for fname in ("r6_pmc_mfma.json", "r5_pmc_mfma.json", "r4_pmc_mfma.json", "r3_pmc_mfma.json", "r2_pmc_mfma.json"):
-            pmc = committed_profile(fname)
-            if pmc is not None:
-                other["prefill_gemm_pmc"] = dict(pmc.get("summary") or {}, source="profiles/" + fname)
-                break
-        # the decode gate/up kernel INSIDE a decode step (rocprofv3 kernel trace of isolated steps, committed): the number to price it with
-        for fname in ("r6_decode_steps.json", "r5_decode_steps.json", "r4_decode_steps.json", "r3_decode_steps.json", "r2_decode_steps.json"):
-            prof = committed_profile(fname)
-            ks = [] if prof is None else prof.get("rows", {}).get(str(legs["decode_gateup_gemv"]["rows"]), {}).get("kernels", [])
-            want = legs["decode_gateup_gemv"]["kernel"].replace(" ", "")
-            row = next((r_ for r_ in ks if r_["kernel"].replace(" ", "") == want), None)
-            if row is not None:
-                nb = legs["decode_gateup_gemv"]["algorithmic"]
-                other["decode_gateup_gemv"]["in_step"] = {"avg_launch_ms": row["avg_us"] / 1e3, "achieved": nb / row["avg_us"] / 1e3, "unit": "GB/s",
-                                                          "frac": nb / row["avg_us"] / 1e3 / HBM_PEAK_GBS,
-                                                          "source": f"profiles/{fname} (rocprofv3 kernel trace of isolated {legs['decode_gateup_gemv']['rows']}-row steps)"}
-                break
-        # the dominant kernel inside a batched prefill pass (other kernels between its launches: the clock is not pinned at the power cap
-        # by one kernel), from the committed rocprofv3 summary of tools/prefill_prof.sh - next to the live back-to-back figure above
-        pf_name = next((n_ for n_ in ("r6_prefill_pass.json", "r5_prefill_pass.json", "r4_prefill_pass.json") if committed_profile(n_) is not None), "r3_prefill_pass.json")
-        pf = committed_profile(pf_name)
-        if pf is not None and pf.get("rows") == dom.get("rows"):
-            row = next((r_ for r_ in pf.get("kernels", []) if r_["kernel"].replace(" ", "") == dom["kernel"].replace(" ", "")), None)
-            if row is not None:
-                fl = dom["algorithmic"]
-                roof_in_situ = {"avg_launch_ms": row["avg_us"] / 1e3, "achieved": fl / row["avg_us"] / 1e6, "unit": "TFLOP/s",
-                                "frac": fl / row["avg_us"] / 1e6 / MFMA_BF16_PEAK_TF,
-                                "source": f"profiles/{pf_name} (rocprofv3 kernel trace of batched prefill passes at this row count)"}
+        roof = None
+        if args.full:
+            eng.set_option("fp8_decode", 0)
+            eng.set_option("fp8_prefill", 0)
+            # generates per merged decode step of the timed region: a full pool under the gang policy, else what the run averaged
+            gang = max(1, args.pool_rows // n_calls_rank) if (server is not None and args.pools > 1) else 1
+            if server is not None and args.pools <= 1:
+                gang = max(1, min(args.pool_rows // n_calls_rank, round(server.rows_served / max(1, server.steps_run) / n_calls_rank)))
+            pf_groups = 1
+            if server is not None and server.prefill_batch > 1 and server.pf_batches:
+                pf_groups = max(server.pf_hist, key=server.pf_hist.get)       # the pass size that served most steps of this run: 1, 2, 4 or 8 prefills
+            legs = roofline_legs(model, n_calls_rank, M_prefill, dec_rows=min(144, gang * n_calls_rank), prefill_groups=pf_groups)
+            # dominant = the larger share of a recursion: 32 prefill launches shared by `pf_groups` recursions, or 32 x G decode launches
+            # shared by `gang` recursions
+            dom = max((legs[k] for k in ("prefill_gateup_gemm", "decode_gateup_gemv")),
+                      key=lambda l: l["ms"] * (32 / pf_groups if l["bound"] == "mfma" else 32 * G / gang))
+            traffic = pmc_traffic(dom["kernel"], dom["grid_threads"])
+            other = {k: {"kernel": v["kernel"], "achieved": v["achieved"], "unit": v["unit"], "frac": v["achieved"] / v["peak"], "avg_launch_ms": v["ms"],
+                         **({"tflops": v["tflops"]} if "tflops" in v else {}), **({"rows": v["rows"]} if "rows" in v else {}),
+                         **({"timing": v["timing"]} if "timing" in v else {}),
+                         **({"prefills_per_launch": v["prefills_per_launch"]} if "prefills_per_launch" in v else {})} for k, v in legs.items()}
+            for fname in ("r6_pmc_mfma.json", "r5_pmc_mfma.json", "r4_pmc_mfma.json", "r3_pmc_mfma.json", "r2_pmc_mfma.json"):
+                pmc = committed_profile(fname)
+                if pmc is not None:
+                    other["prefill_gemm_pmc"] = dict(pmc.get("summary") or {}, source="profiles/" + fname)
+                    break
+            # the decode gate/up kernel INSIDE a decode step (rocprofv3 kernel trace of isolated steps, committed): the number to price it with
+            for fname in ("r6_decode_steps.json", "r5_decode_steps.json", "r4_decode_steps.json", "r3_decode_steps.json", "r2_decode_steps.json"):
+                prof = committed_profile(fname)
+                ks = [] if prof is None else prof.get("rows", {}).get(str(legs["decode_gateup_gemv"]["rows"]), {}).get("kernels", [])
+                want = legs["decode_gateup_gemv"]["kernel"].replace(" ", "")
+                row = next((r_ for r_ in ks if r_["kernel"].replace(" ", "") == want), None)
+                if row is not None:
+                    nb = legs["decode_gateup_gemv"]["algorithmic"]
+                    other["decode_gateup_gemv"]["in_step"] = {"avg_launch_ms": row["avg_us"] / 1e3, "achieved": nb / row["avg_us"] / 1e3, "unit": "GB/s",
+                                                              "frac": nb / row["avg_us"] / 1e3 / HBM_PEAK_GBS,
+                                                              "source": f"profiles/{fname} (rocprofv3 kernel trace of isolated {legs['decode_gateup_gemv']['rows']}-row steps)"}
+                    break
+            # the dominant kernel inside a batched prefill pass (other kernels between its launches: the clock is not pinned at the power cap
+            # by one kernel), from the committed rocprofv3 summary of tools/prefill_prof.sh - next to the live back-to-back figure above
+            pf_name = next((n_ for n_ in ("r6_prefill_pass.json", "r5_prefill_pass.json", "r4_prefill_pass.json") if committed_profile(n_) is not None), "r3_prefill_pass.json")
+            pf = committed_profile(pf_name)
+            if pf is not None and pf.get("rows") == dom.get("rows"):
+                row = next((r_ for r_ in pf.get("kernels", []) if r_["kernel"].replace(" ", "") == dom["kernel"].replace(" ", "")), None)
+                if row is not None:
+                    fl = dom["algorithmic"]
+                    roof_in_situ = {"avg_launch_ms": row["avg_us"] / 1e3, "achieved": fl / row["avg_us"] / 1e6, "unit": "TFLOP/s",
+                                    "frac": fl / row["avg_us"] / 1e6 / MFMA_BF16_PEAK_TF,
+                                    "source": f"profiles/{pf_name} (rocprofv3 kernel trace of batched prefill passes at this row count)"}
+                else:
+                    roof_in_situ = None
             else:
                 roof_in_situ = None
-        else:
-            roof_in_situ = None
+            roof = {"kernel": dom["kernel"], "bound": dom["bound"], "achieved": dom["achieved"], "peak": dom["peak"],
+                    "unit": dom["unit"], "frac": dom["achieved"] / dom["peak"], "traffic": traffic,
+                    "avg_launch_ms": dom["ms"], "algorithmic_per_launch": dom["algorithmic"],
+                    "timing": "64 back-to-back launches of this kernel alone, HIP events on the launch stream (sustained: the socket power limit sets the clock)",
+                    **({"clocks": dom["clocks"], "clock_adjusted_frac": (dom["algorithmic"] / dom["clocks"]["avg_launch_ms_over_the_sampled_run"] / 1e9) / (dom["peak"] * dom["clocks"]["sclk_mhz_mean"] / 2400.0),
+                        "clock_adjusted_note": "frac against the peak AT THE CLOCK THE KERNEL RAN AT (peak x mean sclk / 2400 MHz): what the kernel leaves on the table "
+                                               "apart from the socket power limit"}
+                       if dom.get("clocks", {}).get("available") and dom["bound"] == "mfma" else {}),
+                    **({"in_situ": roof_in_situ} if roof_in_situ else {}), "other": other}
         out = {
             "metric": METRIC,
             "value": value, "unit": "segments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1209,16 +1274,9 @@ def main():
                                        f"{'one recursion sharded' if strong else 'segments'} x{world} + RCCL all-gather of CLS rows and proposals in every recursion")
                                       + (f" [PLUMBING RUN: {world} ranks share {torch.cuda.device_count()} GPU(s), backend {backend}, stream-K GEMMs off - not a measurement]"
                                          if shared_gpu else "")},
-            "roofline": {"kernel": dom["kernel"], "bound": dom["bound"], "achieved": dom["achieved"], "peak": dom["peak"],
-                         "unit": dom["unit"], "frac": dom["achieved"] / dom["peak"], "traffic": traffic,
-                         "avg_launch_ms": dom["ms"], "algorithmic_per_launch": dom["algorithmic"],
-                         "timing": "64 back-to-back launches of this kernel alone, HIP events on the launch stream (sustained: the socket power limit sets the clock)",
-                         **({"clocks": dom["clocks"], "clock_adjusted_frac": (dom["algorithmic"] / dom["clocks"]["avg_launch_ms_over_the_sampled_run"] / 1e9) / (dom["peak"] * dom["clocks"]["sclk_mhz_mean"] / 2400.0),
-                             "clock_adjusted_note": "frac against the peak AT THE CLOCK THE KERNEL RAN AT (peak x mean sclk / 2400 MHz): what the kernel leaves on the table "
-                                                    "apart from the socket power limit"}
-                            if dom.get("clocks", {}).get("available") and dom["bound"] == "mfma" else {}),
-                         **({"in_situ": roof_in_situ} if roof_in_situ else {}), "other": other},
         }
+        if roof is not None:
+            out["roofline"] = roof
         if headline_clocks is not None:
             out["clocks_during_the_timed_region"] = headline_clocks
         if world > 1:
@@ -1233,7 +1291,7 @@ def main():
             out["answers_sample"] = rec["answers"][:2] if not os.environ.get("REVISION_BENCH_ALL_ANSWERS") else rec["answers"]
         if extra:
             out["extra_measurements"] = extra       # NOT the headline: a different batch per step / reduced-precision weights / other workloads
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, len(stage2.plan_groups(100, 100)), int(P))
             except Exception as e:  # noqa: BLE001 - the reported baseline must never cost the line

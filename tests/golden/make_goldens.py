@@ -98,7 +98,9 @@ def g3_clip_encoder(M):
                     if y.shape[1] > 1:  # temporal output: keep a few rows
                         y = y[:, :: max(1, y.shape[1] // 8)]
                     out[key] = y
-    save("g3_clip_encoder", **out)
+    for t in (0, 1):              # four parts (text x Tn), each under the size limit of a committed file
+        for Tn in (16, 256):
+            save(f"g3_clip_encoder_text{t}_T{Tn}", **{k: v for k, v in out.items() if k.startswith(f"text{t}_") and k.split("_")[2] == f"T{Tn}"})
 
 
 def tiny_model(M, shape, args, seed=SEED, w_round=False, cond=None):
@@ -904,6 +906,37 @@ def g12_clip_tokenizer(M):
         json.dump({"texts": TOKENIZER_TEXTS, "ids_full_vocab": [full.encode(t) for t in TOKENIZER_TEXTS],
                    "ids_synthetic_merges": [small.encode(t) for t in TOKENIZER_TEXTS], "n_synthetic_merges": len(merges)}, f, indent=1)
     print("wrote g12_clip_tokenizer.json", len(merges), "merges")
+    g12_full_vocab_subset(full)
+
+
+def g12_full_vocab_subset(full):
+    """The real merge table reduced to what the g12 texts need: every merge the full tokenizer looks up while encoding them
+    keeps its line (so its rank and its token id), every other line becomes a filler pair of two symbols outside the byte
+    alphabet, which never occur next to each other in a word.  Greedy lowest-rank merging then takes the same steps as with
+    the full table, and the ids (the specials 49406 / 49407 included) stay those of ``ids_full_vocab``."""
+    import gzip
+    used = set()
+
+    class _Seen(dict):
+        def get(self, k, d=None):
+            if k in self:
+                used.add(self[k])
+            return dict.get(self, k, d)
+    ranks, full.bpe_ranks = full.bpe_ranks, _Seen(full.bpe_ranks)
+    full.cache = {k: v for k, v in full.cache.items() if k.startswith("<|")}      # encode from scratch: every lookup is seen
+    try:
+        for t in TOKENIZER_TEXTS + ["a person opens the door"]:
+            full.encode(t)
+    finally:
+        full.bpe_ranks = ranks
+    with gzip.open(os.path.join(CLIP_DIR, "bpe_simple_vocab_16e6.txt.gz"), "rt", encoding="utf-8") as f:
+        lines = f.read().split("\n")
+    n = 49152 - 256 - 2
+    out = [lines[0]] + [lines[1 + i] if i in used else "␀ ␁" for i in range(n)]
+    with open(os.path.join(HERE, "g12_bpe_full_vocab_subset.txt.gz"), "wb") as f:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0, compresslevel=9) as z:
+            z.write(("\n".join(out) + "\n").encode("utf-8"))
+    print("wrote g12_bpe_full_vocab_subset.txt.gz", len(used), "merges kept")
 
 
 def g13_loader(M):

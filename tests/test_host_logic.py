@@ -482,6 +482,24 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus():
     assert r.returncode != 0 and "--gpus 4 but the launcher started 2 rank(s)" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_writes_the_record_as_float64_arrays(tmp_path):
+    """``bench.py --dump-outputs DIR``: a stage-2 record (host side, as parallel.collect_queries assembles it) -> one float64 .npy per
+    array; the answers come back from their code points, the per-call window indexes are concatenated in plan order."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rec = dict(answers=["From 3 to 7.", "Not Present In video."], starts=[0, 25], indexes=[torch.tensor([2, 0, 1]), torch.tensor([1, 0])],
+               hierarchy_zooms=[4, 4], max_entropy=[1.25, 2.5], mean_entropy=[3.0, 4.5], score_cos=[0.5, -0.25, 0.125], plan=[(4, 0, 25), (4, 25, 50)])
+    bench.dump_outputs(str(tmp_path / "out"), rec)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == ["answers_codepoints", "hierarchy_zooms", "max_entropy", "mean_entropy", "score_cos", "starts", "window_indexes"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert ["".join(chr(int(c)) for c in row if c >= 0) for row in got["answers_codepoints"]] == rec["answers"]
+    assert got["max_entropy"].tolist() == [1.25, 2.5] and got["score_cos"].tolist() == [0.5, -0.25, 0.125]
+    assert got["window_indexes"].tolist() == [2, 0, 1, 1, 0] and got["starts"].tolist() == [0, 25]
+
+
 def test_finalize_routes_the_cross_attn_dense_checkpoint_keys():
     """cross_attn=True without pretrain_clip_adapter (vtimellm_arch.py:42,52-57): the checkpoint carries the Linear under 'model.mm_projector.*'
     AND the hidden-wide ClipEncoder under 'model.cross_attn.*' - ``builder.finalize`` hands each module its own keys (host logic; stub engine)."""

@@ -3,7 +3,7 @@
 # the tool abort and then hang) and gets the program itself after `--`.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 # default pipeline (16 steps in flight, 56-row pools, up to 4 prefills per pass): 16 steps = 4 full prefill passes of 4020 rows, 2 gangs of 8
-B="bench.py --steps 16 --warmup 0 --settle 0 --no-cpu-baseline --no-extras"
+B="bench.py --steps 16 --warmup 0 --settle 0 --full --no-cpu-baseline --no-extras"
 mkdir -p gpurun_out
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r2_stats -o bench -- python3 bench.py --steps 32 --warmup 16 --settle 0 --no-cpu-baseline --no-extras > gpurun_out/r2_stats.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/r2_fetch -o bench -- python3 $B > gpurun_out/r2_fetch.log 2>&1

@@ -3,7 +3,7 @@
 # GEMM and the recursion.  Every rocprofv3 call sits under `timeout` and gets the program itself after `--`.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export PYTHONPATH=.
-B="bench.py --steps 16 --warmup 0 --settle 0 --no-cpu-baseline --no-extras"
+B="bench.py --steps 16 --warmup 0 --settle 0 --full --no-cpu-baseline --no-extras"
 mkdir -p gpurun_out
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r4_stats -o bench -- python3 bench.py --steps 32 --warmup 16 --settle 0 --no-cpu-baseline --no-extras > gpurun_out/r4_stats.log 2>&1
 find gpurun_out/r4_stats -name '*trace.csv' -delete
