@@ -314,6 +314,18 @@ int rv_llm_prefill_pool_groups(rv_ctx* ctx, float* h, int32_t G, int32_t B, int3
 int rv_llm_prefill_pool_groups_ragged(rv_ctx* ctx, float* h, int32_t G, int32_t B, int32_t P0, int32_t S, void* kv, int32_t kv_rows,
                                       const int32_t* kv_row0, int32_t Smax, const int32_t* last_rows, float* logits, void* ws, size_t ws_bytes,
                                       void* stream);
+/* rv_llm_prefill_pool_mixed: G (<= 8) prefills of DIFFERENT geometry in one pass (vtimellm_llama.py:38-90 run once per generate): group g has its own
+ *   (B, P0, S) and cache rows kv_row0 .. kv_row0 + B - 1 of the pool (groups: HOST array of G entries).  h f32 [sum_g (P0_g + B_g * S_g), D]: block g =
+ *   [P0_g shared-prefix rows ; B_g x S_g rows], the blocks back to back with no pad rows; logits f32 [sum_g B_g, V] in group order, then sequence order.
+ *   last_rows (DEVICE int32 [sum_g B_g], or NULL): as in the ragged entry, per sequence the index into h of the row that feeds the lm_head; NULL = the last
+ *   row of every sequence.  Limits (anything else returns RV_ERR_ARG, nothing falls back): non-empty groups inside the pool whose cache-row ranges do not
+ *   overlap; Smax % 32 == 0 and P0_g + S_g <= Smax; S_g > 16 and (P0_g == 0 or P0_g > 16); sequences shorter than 32 positions (P0_g + S_g) only among
+ *   themselves (their last block takes another form, and a sequence's logits must not depend on what shares its pass); the plain 16-bit path only (RV_ERR_ARG with precision = 1 or
+ *   with the FP8 prefill weights in use).  Workspace: rv_llm_ws_bytes(ctx, total rows, 1).  Per-row results equal the separate prefills up to the
+ *   summation order of the GEMMs; G groups of ONE geometry give the bytes of rv_llm_prefill_pool_groups. */
+typedef struct rv_prefill_group { int32_t B, P0, S, kv_row0; } rv_prefill_group;
+int rv_llm_prefill_pool_mixed(rv_ctx* ctx, float* h, int32_t G, const rv_prefill_group* groups, void* kv, int32_t kv_rows, int32_t Smax,
+                              const int32_t* last_rows, float* logits, void* ws, size_t ws_bytes, void* stream);
 int rv_llm_decode_rows(rv_ctx* ctx, float* h, int32_t R, const int32_t* row_pos, void* kv, int32_t Smax, float* logits, void* ws,
                        size_t ws_bytes, void* stream);
 /* rv_llm_decode_rows_shared: rv_llm_decode_rows + a hint about cache contents (round 4): row_share (device int32 [R], or NULL) holds, per

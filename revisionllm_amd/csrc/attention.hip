@@ -686,6 +686,51 @@ __global__ __launch_bounds__(256, 2) void attn_kernel_pair_lds(AttnArgs a, AttnA
     attn_body_lds1<DH>(p, bx, h, z < a.B ? z : z - a.B, smem);
 }
 
+// Mixed-geometry prefill passes: every group brings its own pair of problems (AttnMixed).  Workgroup -> (problem, head, query tile) as attn_map does it; the problem
+// -> (group, prefix problem or sequence) through the prefix sum of the groups' problem counts.  `tiles` counts the LONGEST problem of the pass: a workgroup whose
+// tile lies beyond its own problem leaves (uniformly, before any barrier).  The bodies are those of the pair kernels, fed the AttnArgs the pair launch would build
+// for this group alone: a row's arithmetic does not depend on what shares the pass.
+__device__ __forceinline__ void attn_mixed_problem(AttnArgs& p, const AttnMixed& mx, int z, int& b) {
+    int g = 0;
+    for (int i = 1; i < mx.G; ++i) g += z >= mx.first[i] ? 1 : 0;      // (z is workgroup-uniform)
+    const QkvGroup e = mx.gt[g];
+    const int zl = z - mx.first[g], hasp = e.P0 > 0 ? 1 : 0;
+    const bool prefix = hasp && zl == 0;
+    const int64_t row0 = prefix ? e.base : e.base + e.P0;
+    p.q = (const op16_t*)p.q + row0 * p.q_rs;
+    p.out = (op16_t*)p.out + row0 * p.o_rs;
+    p.k = (const op16_t*)p.k + (int64_t)e.row * p.k_bs;
+    p.vt = (const op16_t*)p.vt + (int64_t)e.row * p.vt_bs;
+    if (prefix) { p.B = 1; p.Lq = p.Lk = e.P0; p.q_pos0 = 0; p.q_bs = (int64_t)e.P0 * p.q_rs; p.o_bs = (int64_t)e.P0 * p.o_rs; b = 0; }
+    else { p.B = e.B; p.Lq = e.S; p.Lk = e.P0 + e.S; p.q_pos0 = e.P0; p.q_bs = (int64_t)e.S * p.q_rs; p.o_bs = (int64_t)e.S * p.o_rs; b = zl - hasp; }
+}
+template <int DH>
+__global__ __launch_bounds__(256, 2) void attn_kernel_mixed_lds(AttnArgs a, AttnMixed mx, int tiles) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * (2 * (DH / 32) + DH / 16) * 1024];
+    int bx, h, z, b;
+    if (!attn_map(tiles, a.H, a.H * mx.problems, bx, h, z)) return;
+    attn_mixed_problem(a, mx, z, b);
+    if (bx * 64 >= a.Lq) return;       // (workgroup-uniform)
+    attn_body_lds1<DH>(a, bx, h, b, smem);
+}
+template <int DH>
+__global__ __launch_bounds__(256, 3) void attn_kernel_mixed(AttnArgs a, AttnMixed mx, int tiles) {
+    int bx, h, z, b;
+    if (!attn_map(tiles, a.H, a.H * mx.problems, bx, h, z)) return;
+    attn_mixed_problem(a, mx, z, b);
+    if (bx * 64 >= a.Lq) return;
+    attn_body<DH, false, false, false>(a, bx, h, b);
+}
+__global__ void mixed_tables_kernel(AttnMixed mx, QkvGroup* gt, int* last_rows) {
+    if (threadIdx.x >= (unsigned)mx.G) return;
+    const QkvGroup e = mx.gt[threadIdx.x];
+    gt[threadIdx.x] = e;
+    if (!last_rows) return;
+    int o = 0;
+    for (int i = 0; i < (int)threadIdx.x; ++i) o += mx.gt[i].B;
+    for (int b = 0; b < e.B; ++b) last_rows[o + b] = e.base + e.P0 + (b + 1) * e.S - 1;
+}
+
 }  // namespace
 
 static int attn_check(const AttnArgs& a) {
@@ -728,6 +773,39 @@ int k_attention_groups(const AttnArgs& b, hipStream_t st, const AttnGroups& gr) 
     else if (lds) hipLaunchKernelGGL((attn_kernel_pair_lds<128>), dim3(attn_grid(tiles, b.H * b.B * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
     else hipLaunchKernelGGL((attn_kernel_pair<128>), dim3(attn_grid(tiles, b.H * b.B * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
     RV_CHECK_LAUNCH("attention groups");
+    return RV_OK;
+}
+
+int k_attention_mixed(const AttnArgs& a, const AttnMixed& mx, hipStream_t st) {
+    RV_CHECK_ARG(a.q && a.k && a.vt && a.out, "attention mixed: null tensor");
+    RV_CHECK_ARG(a.dh == 128 && a.H > 0 && !a.key_pad && !a.row_pos && !a.q_lo && !a.out_lo && a.causal && a.kv_div == 1,
+                 "attention mixed: causal 128-wide heads, no key padding, no per-row positions, no split operands");
+    RV_CHECK_ARG(a.q_rs % 8 == 0 && a.k_rs % 8 == 0 && a.k_hs % 8 == 0 && a.vt_ds % 8 == 0 && a.vt_hs % 8 == 0 && a.vt_bs % 8 == 0 && a.o_rs % 4 == 0,
+                 "attention: stride alignment");
+    RV_CHECK_ARG(mx.G >= 1 && mx.G <= RV_MAX_PREFILL_GROUPS, "attention mixed: 1 .. %d groups", RV_MAX_PREFILL_GROUPS);
+    int longest = 0, problems = 0;
+    for (int g = 0; g < mx.G; ++g) {
+        const QkvGroup& e = mx.gt[g];
+        RV_CHECK_ARG(e.B > 0 && e.S > 16 && (e.P0 == 0 || e.P0 > 16) && e.row >= 0 && e.base >= 0, "attention mixed: group %d: prefill lengths only (S > 16, P0 == 0 or > 16)", g);
+        RV_CHECK_ARG(a.vt_ks != 8 || a.vt_ds >= ((e.P0 + e.S + 31) / 32) * 32, "attention: V^T rows must be padded to a multiple of 32 keys");
+        RV_CHECK_ARG(mx.first[g] == problems, "attention mixed: group %d: first problem %d, expected %d", g, mx.first[g], problems);
+        problems += (e.P0 > 0 ? 1 : 0) + e.B;
+        longest = e.S > longest ? e.S : longest;
+        longest = e.P0 > longest ? e.P0 : longest;
+    }
+    RV_CHECK_ARG(mx.problems == problems, "attention mixed: %d problems, expected %d", mx.problems, problems);
+    const int tiles = (int)cdiv(longest, 64);
+    const dim3 grid(attn_grid(tiles, a.H * problems));
+    if (rv_cur_opts().attn_lds) hipLaunchKernelGGL((attn_kernel_mixed_lds<128>), grid, dim3(256), 0, st, a, mx, tiles);
+    else hipLaunchKernelGGL((attn_kernel_mixed<128>), grid, dim3(256), 0, st, a, mx, tiles);
+    RV_CHECK_LAUNCH("attention mixed");
+    return RV_OK;
+}
+
+int k_mixed_tables(const AttnMixed& mx, QkvGroup* gt, int* last_rows, hipStream_t st) {
+    RV_CHECK_ARG(gt && mx.G >= 1 && mx.G <= RV_MAX_PREFILL_GROUPS, "mixed tables: bad argument");
+    hipLaunchKernelGGL(mixed_tables_kernel, dim3(1), dim3(64), 0, st, mx, gt, last_rows);
+    RV_CHECK_LAUNCH("mixed tables");
     return RV_OK;
 }
 

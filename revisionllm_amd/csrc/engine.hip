@@ -613,6 +613,9 @@ struct LlmWs {
     size_t sk_bytes;
     size_t bytes;
 };
+// device tables of a mixed-geometry pass, at the head of LlmWs::ss: RV_MAX_PREFILL_GROUPS group entries, then the default last rows
+inline const int* mixed_last_rows(const LlmWs& w) { return (const int*)((const char*)w.ss + sizeof(QkvGroup) * RV_MAX_PREFILL_GROUPS); }
+inline size_t mixed_tables_bytes(const rv_ctx* c) { return (size_t)RV_XP_MAX_BLOCKS * (c->cfg.hidden / 16) * 16 * 4; }
 LlmWs carve_llm(const rv_ctx* c, void* ws, size_t cap, int B, int S) {
     const int64_t M = (int64_t)B * S, D = c->cfg.hidden, F = c->cfg.inter;
     Carver k(ws, cap);
@@ -654,7 +657,10 @@ namespace {
 // is left holding the residual stream behind block l1 - 1 (rv_llm_layers).
 int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* kv, int Smax, float* logits, void* ws,
                      size_t ws_bytes, hipStream_t st, int kv_rows = 0, int kv_row0 = 0, const int* row_pos = nullptr, int G = 1,
-                     const int* grow = nullptr, int l0 = 0, int l1 = -1, const int* row_share = nullptr, const int* last_rows = nullptr) {
+                     const int* grow = nullptr, int l0 = 0, int l1 = -1, const int* row_share = nullptr, const int* last_rows = nullptr,
+                     const AttnMixed* mx = nullptr) {
+    // mx (rv_llm_prefill_pool_mixed): groups of DIFFERENT geometry packed back to back - the caller passes B = 1, S = all rows of the pass, P0 = pos0 = 0,
+    // G = 1, kv_row0 = 0 (the GEMMs only see M rows; the q/k/v epilogues and the attention decode a row through the group table) and last_rows
     RV_TRY(resolve_llm(c));
     const rv_config& g = c->cfg;
     if (G > 1) kv_row0 = grow[0];
@@ -670,10 +676,21 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
     op16_t* kbase = (op16_t*)kv + (int64_t)kv_row0 * D * Smax;
     op16_t* vbase = (op16_t*)kv + (int64_t)g.layers * per_layer + (int64_t)kv_row0 * D * Smax;
     const float scale = 1.0f / sqrtf((float)dh);
+    int mx_len = 0, mx_min = 0;          // mixed pass: its longest / shortest sequence (prefix included)
+    int64_t nseq = (int64_t)G * B;       // sequences of the pass = rows of the head
+    if (mx) {
+        nseq = 0;
+        for (int gi = 0; gi < mx->G; ++gi) {
+            const int len = mx->gt[gi].P0 + mx->gt[gi].S;
+            mx_len = len > mx_len ? len : mx_len;
+            mx_min = (gi == 0 || len < mx_min) ? len : mx_min;
+            nseq += mx->gt[gi].B;
+        }
+    }
     // (cos, sin) table for positions [P0 ? 0 : pos0, pos0 + S)
     const int tab0 = P0 > 0 ? 0 : pos0;
     if (row_pos) RV_TRY(k_rope_table_rows(w.cs, row_pos, B, dh, g.rope_theta, st));
-    else RV_TRY(k_rope_table(w.cs, pos0 + S - tab0, tab0, dh, g.rope_theta, st));
+    else RV_TRY(k_rope_table(w.cs, mx ? mx_len : pos0 + S - tab0, tab0, dh, g.rope_theta, st));
     // Decode steps (M <= 32 rows) fuse every RMSNorm but the first into the projections around it (GemvNorm, kernels.h):
     // o-proj / down-proj emit the pre-scaled activation + per-workgroup sums of squares, qkv / gate-up / lm_head apply r[b].
     // Parity precision: every GEMM operand is the split pair [hi | lo] (16 mantissa bits) against
@@ -713,7 +730,10 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
     // SEQUENCE length P0 + S: it must not depend on how many prefills share the pass, nor on whether the prompt prefix is shared (a recursion's calls
     // run one by one in the reference mode and as one shared-prefix batch in the batched mode: both must take the same kernels)
     const bool tail_block = logits && l1 == g.layers && !par && !p8 && !fuse_norm && !row_pos && (S > 1 || P0 > 0) && c->opt.last_block_rows &&
-                            (int64_t)P0 + S >= 32 && (size_t)M * F * 2 >= (((size_t)G * B * D * 4 + 255) & ~(size_t)255) + (size_t)G * B * F * 2;
+                            (mx ? (int64_t)mx_min : (int64_t)P0 + S) >= 32 && (size_t)M * F * 2 >= (((size_t)nseq * D * 4 + 255) & ~(size_t)255) + (size_t)nseq * F * 2;
+    // mixed pass: its device tables at the head of the decode steps' sum-of-squares buffer (free in a prefill): the group entries, then the default last rows
+    QkvGroup* mx_gt = (QkvGroup*)w.ss;
+    if (mx) RV_TRY(k_mixed_tables(*mx, mx_gt, last_rows == mixed_last_rows(w) ? (int*)mixed_last_rows(w) : nullptr, st));
     for (int l = l0; l < l1; ++l) {
         const LlmLayer& L = c->layers[l];
         op16_t* kc = kbase + l * per_layer;
@@ -732,6 +752,10 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
         qr.G = G;
         qr.Mg = (int)Mg;
         for (int gi = 1; gi < G; ++gi) qr.grow[gi] = grow[gi] - grow[0];
+        if (mx) {
+            qr.ng = mx->G;
+            qr.gt = mx_gt;
+        }
         if (par) {   // f32 q/k/v, then RoPE + Q as a split pair + cache append in their own kernel (the fused epilogues keep their bf16 Q)
             qr.q_ld = (int)(2 * D);
             qr.q_lo = (int)D;
@@ -757,7 +781,15 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
         const int64_t od = par ? 2 * D : D, olo = par ? D : 0;   // attention output rows (and query rows): [hi | lo] in the parity precision
         const int64_t qd = od, qlo = olo;
         auto blocked_vt = [&](AttnArgs& x) { x.vt_ds = 8; x.vt_ks = (int64_t)dh * 8; };   // the V^T cache is blocked by 8 positions (rv_vt_index)
-        if (P0 > 0 && P0 > 16 && S > 16 && dh == 128) {
+        if (mx) {
+            // every group's prefix problem + per-sequence problems in ONE launch, each with its own lengths
+            RV_CHECK_ARG(dh == 128, "rv_llm_prefill_pool_mixed: 128-wide heads only");
+            AttnArgs am{w.q16, D, 0, kc, dh, (int64_t)H * Smax * dh, (int64_t)Smax * dh, vtc, (int64_t)H * dh * Smax, (int64_t)dh * Smax, Smax, w.a16, D, 0, nullptr, 1, H, dh,
+                        1, 1, 1, 0, 1, scale};
+            blocked_vt(am);
+            RV_TRY(k_attention_mixed(am, *mx, st));
+            prefix_done = true;
+        } else if (P0 > 0 && P0 > 16 && S > 16 && dh == 128) {
             // prefix rows + per-call rows in ONE launch (the prefix problem alone is a ~9 us launch) - for all G groups of a batched prefill
             AttnArgs ap{w.q16, qd, (int64_t)P0 * qd, kc, dh, (int64_t)H * Smax * dh, (int64_t)Smax * dh, vtc, (int64_t)H * dh * Smax,
                         (int64_t)dh * Smax, Smax, w.a16, od, (int64_t)P0 * od, nullptr, 1, H, dh, P0, P0, 1, 0, 1, scale};
@@ -831,7 +863,7 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
                 // The LAST block of a prefill with a head: behind its attention nothing reads the block's output rows but the last row of every
                 // sequence (its K / V are in the cache already; logits come from the last positions).  o / norm / gate-up / down and the head run on
                 // those G x B rows alone, through the few-row weight-streaming kernels: 0.98 ms of 4096-row GEMMs per pass -> 0.07 ms.
-                const int64_t nr = (int64_t)G * B;
+                const int64_t nr = nseq;
                 op16_t* a_last = w.q16;                                   // (Q is dead behind the attention)
                 float* h_last = (float*)w.act16;                          // (the gated-activation buffer is free until gate/up)
                 op16_t* act_last = (op16_t*)((char*)w.act16 + (((size_t)nr * D * 4 + 255) & ~(size_t)255));
@@ -922,11 +954,11 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
             return rv_gemm_impl(w.xl16, 2 * D, c->lm_head2, 2 * D, 1, nullptr, nullptr, 0, logits, V, RV_F32, RV_ACT_NONE, B, V, 2 * D, w.sk, w.sk_bytes, st, &hn);
         }
         if (last_rows)      // right-padded (ragged) sequences: row i of the head's input = input row last_rows[i], the last VALID position of sequence i
-            RV_TRY(k_rmsnorm_split(h, D, c->final_norm, w.xl16, (int64_t)G * B, (int)D, g.rms_eps, st, 0, last_rows));
+            RV_TRY(k_rmsnorm_split(h, D, c->final_norm, w.xl16, nseq, (int)D, g.rms_eps, st, 0, last_rows));
         else
             for (int gi = 0; gi < G; ++gi)
                 RV_TRY(k_rmsnorm_split(h + (gi * Mg + P0 + S - 1) * D, (int64_t)S * D, c->final_norm, w.xl16 + (int64_t)gi * B * 2 * D, B, (int)D, g.rms_eps, st));
-        return rv_gemm_impl(w.xl16, 2 * D, c->lm_head2, 2 * D, 1, nullptr, nullptr, 0, logits, V, RV_F32, RV_ACT_NONE, (int64_t)G * B, V, 2 * D, w.sk, w.sk_bytes, st);
+        return rv_gemm_impl(w.xl16, 2 * D, c->lm_head2, 2 * D, 1, nullptr, nullptr, 0, logits, V, RV_F32, RV_ACT_NONE, nseq, V, 2 * D, w.sk, w.sk_bytes, st);
     }
     if (par) {
         rv_set_error("rv_llm_forward: the parity precision needs the split lm_head (option lm_head_split = 1)");
@@ -942,11 +974,11 @@ int llm_forward_impl(rv_ctx* c, float* h, int B, int S, int pos0, int P0, void* 
                             &consume);
     // final norm + lm_head on the last position of every sequence only
     if (last_rows)
-        RV_TRY(k_rmsnorm(h, D, c->final_norm, w.xl16, (int64_t)G * B, (int)D, g.rms_eps, st, 0, last_rows));
+        RV_TRY(k_rmsnorm(h, D, c->final_norm, w.xl16, nseq, (int)D, g.rms_eps, st, 0, last_rows));
     else
         for (int gi = 0; gi < G; ++gi)
             RV_TRY(k_rmsnorm(h + (gi * Mg + P0 + S - 1) * D, (int64_t)S * D, c->final_norm, w.xl16 + (int64_t)gi * B * D, B, (int)D, g.rms_eps, st));
-    return rv_gemm_impl(w.xl16, D, c->lm_head, D, 1, nullptr, nullptr, 0, logits, V, RV_F32, RV_ACT_NONE, (int64_t)G * B, V, D, w.sk, w.sk_bytes, st);
+    return rv_gemm_impl(w.xl16, D, c->lm_head, D, 1, nullptr, nullptr, 0, logits, V, RV_F32, RV_ACT_NONE, nseq, V, D, w.sk, w.sk_bytes, st);
 }
 }  // namespace
 
@@ -1018,6 +1050,57 @@ extern "C" int rv_llm_prefill_pool_groups_ragged(rv_ctx* c, float* h, int32_t G,
                      kv_row0[gi] + B, kv_rows);
     RV_CHECK_ARG(Smax % 32 == 0 && P0 + S <= Smax, "rv_llm_prefill_pool_groups_ragged: Smax=%d must be a multiple of 32 and >= P0+S=%d", Smax, P0 + S);
     return llm_forward_impl(c, h, B, S, P0, P0, kv, Smax, logits, ws, ws_bytes, as_stream(stream), kv_rows, kv_row0[0], nullptr, G, kv_row0, 0, -1, nullptr, last_rows);
+}
+
+// Prefills of DIFFERENT geometry in one pass: group g's [P0_g ; B_g x S_g] block follows group g - 1's with no pad rows.
+extern "C" int rv_llm_prefill_pool_mixed(rv_ctx* c, float* h, int32_t G, const rv_prefill_group* groups, void* kv, int32_t kv_rows, int32_t Smax,
+                                         const int32_t* last_rows, float* logits, void* ws, size_t ws_bytes, void* stream) {
+    RV_CHECK_ARG(c && h && groups && kv && logits && ws, "rv_llm_prefill_pool_mixed: null argument");
+    RvOptScope scope(&c->opt);
+    RV_CHECK_ARG(G >= 1 && G <= RV_MAX_PREFILL_GROUPS, "rv_llm_prefill_pool_mixed: 1 .. %d groups (got %d)", RV_MAX_PREFILL_GROUPS, G);
+    RV_CHECK_ARG(Smax > 0 && Smax % 32 == 0 && kv_rows > 0, "rv_llm_prefill_pool_mixed: Smax=%d must be a positive multiple of 32, the pool non-empty", Smax);
+    RV_TRY(resolve_llm(c));
+    RV_CHECK_ARG(c->opt.precision != 1 && !(c->fp8_prefill && c->opt.fp8_prefill),
+                 "rv_llm_prefill_pool_mixed: mixed-geometry passes run on the plain 16-bit path only (not with precision = 1, not with the FP8 prefill weights in use)");
+    int n_short = 0;      // groups whose sequences are shorter than 32 positions: their last block runs on all rows (llm_forward_impl, tail_block)
+    AttnMixed mx;
+    mx.G = G;
+    int64_t rows = 0;
+    for (int gi = 0; gi < G; ++gi) {
+        const rv_prefill_group& e = groups[gi];
+        RV_CHECK_ARG(e.B > 0 && e.S > 0 && e.P0 >= 0, "rv_llm_prefill_pool_mixed: group %d is empty", gi);
+        RV_CHECK_ARG(e.S > 16 && (e.P0 == 0 || e.P0 > 16), "rv_llm_prefill_pool_mixed: group %d: S=%d must exceed 16 and P0=%d be 0 or exceed 16", gi, e.S, e.P0);
+        RV_CHECK_ARG(e.kv_row0 >= 0 && (int64_t)e.kv_row0 + e.B <= kv_rows, "rv_llm_prefill_pool_mixed: group %d: rows %d..%d outside a pool of %d rows", gi, e.kv_row0,
+                     e.kv_row0 + e.B, kv_rows);
+        RV_CHECK_ARG((int64_t)e.P0 + e.S <= Smax, "rv_llm_prefill_pool_mixed: group %d: P0+S=%d exceeds Smax=%d", gi, e.P0 + e.S, Smax);
+        n_short += e.P0 + e.S < 32 ? 1 : 0;
+        for (int gj = 0; gj < gi; ++gj)
+            RV_CHECK_ARG(e.kv_row0 >= groups[gj].kv_row0 + groups[gj].B || groups[gj].kv_row0 >= e.kv_row0 + e.B,
+                         "rv_llm_prefill_pool_mixed: the cache rows of groups %d and %d overlap", gj, gi);
+        mx.first[gi] = mx.problems;
+        mx.problems += (e.P0 > 0 ? 1 : 0) + e.B;
+        mx.gt[gi] = QkvGroup{(int)rows, e.B, e.S, e.P0, e.kv_row0};
+        rows += (int64_t)e.P0 + (int64_t)e.B * e.S;
+        RV_CHECK_ARG(rows <= 0x3fffffff, "rv_llm_prefill_pool_mixed: too many rows");
+    }
+    // The last block runs on the last rows alone for sequences of >= 32 positions and on all rows for shorter ones - a property of the SEQUENCE, whatever it
+    // shares a pass with; one pass takes one form, so it holds sequences of one kind only
+    RV_CHECK_ARG(n_short == 0 || n_short == G, "rv_llm_prefill_pool_mixed: sequences shorter than 32 positions (P0+S) do not share a pass with longer ones");
+    // last_rows == NULL: the last row of every sequence, written into the workspace ahead of the pass (behind the group table)
+    const int* last = last_rows;
+    if (!last) {
+        const LlmWs w = carve_llm(c, ws, ws_bytes, 1, (int)rows);
+        if (w.bytes > ws_bytes) {
+            rv_set_error("rv_llm_prefill_pool_mixed: workspace %zu < required %zu", ws_bytes, w.bytes);
+            return RV_ERR_WORKSPACE;
+        }
+        int64_t nb = 0;
+        for (int gi = 0; gi < G; ++gi) nb += groups[gi].B;
+        RV_CHECK_ARG((size_t)nb * 4 + sizeof(QkvGroup) * RV_MAX_PREFILL_GROUPS <= mixed_tables_bytes(c), "rv_llm_prefill_pool_mixed: %lld sequences: too many for the default last rows",
+                     (long long)nb);
+        last = mixed_last_rows(w);
+    }
+    return llm_forward_impl(c, h, 1, (int)rows, 0, 0, kv, Smax, logits, ws, ws_bytes, as_stream(stream), kv_rows, 0, nullptr, 1, nullptr, 0, -1, nullptr, last, &mx);
 }
 
 extern "C" int rv_llm_decode_rows(rv_ctx* c, float* h, int32_t R, const int32_t* row_pos, void* kv, int32_t Smax, float* logits, void* ws,

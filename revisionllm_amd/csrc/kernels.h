@@ -85,6 +85,11 @@ constexpr int RV_MAX_PREFILL_GROUPS = 8;
 // is for - the 128 values a decode step appends for ONE position land in 2 KiB = 16 lines instead of 128 lines 2 * Smax bytes apart
 // (probe without the append, plain [dh, Smax] layout: 140-row step 9.37 -> 8.94 ms; the batched prefill's QKV epilogue 348 -> 327 us).
 __host__ __device__ __forceinline__ int64_t rv_vt_index(int d, int pos) { return ((int64_t)(pos >> 3) * 128 + d) * 8 + (pos & 7); }
+// One group of a MIXED-geometry prefill pass (rv_llm_prefill_pool_mixed): rows [base, base + P0 + B * S) of the pass are the group's
+// [P0 shared-prefix rows ; B x S] block (base = the prefix sum of the groups' row counts), its cache rows are row .. row + B - 1 of the pool
+struct alignas(32) QkvGroup {
+    int base, B, S, P0, row, pad_[3];      // (32 bytes: an entry is two 16-byte loads)
+};
 struct QkvRope {
     const float* cs = nullptr;  // (cos, sin) table [pos - cs_pos0][dh/2]
     void* q16 = nullptr;        // bf16 [M, D]
@@ -101,7 +106,21 @@ struct QkvRope {
     // parity precision only (read by qkv_rope_store_t<true>, i.e. by the stand-alone RoPE / append kernel - never by the fused GEMM
     // epilogues): q16 rows are q_ld elements apart and also receive the LOW half bf16(q - bf16(q)) q_lo elements behind the high half
     int q_ld = 0, q_lo = 0;
+    // Several prefills of DIFFERENT geometry packed back to back into one pass (no pad rows): ng > 0 groups, each with its own (B, S, P0); the
+    // fields B / S / P0 / pos0 / G / Mg / grow above are not read then, positions start at 0 (cs_pos0 = 0) and kc / vtc point at row 0 of the pool.
+    // The table (<= RV_MAX_PREFILL_GROUPS entries) lives in DEVICE memory (the pass writes it into its workspace, k_mixed_tables): lanes index it with their own
+    // row's group, and a kernel-argument array indexed per lane would be copied to scratch
+    int ng = 0;
+    const QkvGroup* gt = nullptr;
 };
+// The group of row m of a mixed pass (a short scan of the row bases); m becomes the row inside the group's block.
+static __device__ __forceinline__ QkvGroup qkv_rope_group(const QkvRope& q, int& m) {
+    int gi = 0;
+    for (int i = 1; i < q.ng; ++i) gi += m >= q.gt[i].base ? 1 : 0;      // (uniform addresses: broadcast loads)
+    const QkvGroup e = q.gt[gi];
+    m -= e.base;
+    return e;
+}
 // (timing probes of the wide decode kernel, tools/rows_probe.sh: RS_PROBE & 256 / 512 / 1024 = no V^T / K / Q stores; garbage results)
 #ifndef RS_PROBE
 #define RS_PROBE_K_ 0
@@ -117,10 +136,12 @@ static __device__ __forceinline__ f32x4 qkv_rope_coeffs(const QkvRope& q, int m,
     if (sec >= 2) return f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr ((RS_PROBE_K_ & 4096) != 0) return f32x4{1.f, 0.f, 1.f, 0.f};   // (timing probe: no coefficient loads)
     if (q.row_pos) return *(const f32x4*)(q.cs + ((int64_t)m * 64 + (p >> 1)) * 2);   // per-row table
-    if (q.G > 1) m -= (m / q.Mg) * q.Mg;
+    int P0 = q.P0, S = q.S, pos0 = q.pos0;
+    if (q.ng) { const QkvGroup e = qkv_rope_group(q, m); P0 = pos0 = e.P0; S = e.S; }
+    else if (q.G > 1) m -= (m / q.Mg) * q.Mg;
     int pos;
-    if (m < q.P0) pos = m;
-    else { const int r = m - q.P0; const int b = r / q.S; pos = q.pos0 + (r - b * q.S); }
+    if (m < P0) pos = m;
+    else { const int r = m - P0; const int b = r / S; pos = pos0 + (r - b * S); }
     return *(const f32x4*)(q.cs + ((int64_t)(pos - q.cs_pos0) * 64 + (p >> 1)) * 2);  // (c0, s0, c1, s1)
 }
 template <bool QSPLIT>
@@ -130,10 +151,12 @@ static __device__ __forceinline__ void qkv_rope_store_t(const QkvRope& q, int m,
     int b, pos, goff = 0;
     bool prefix = false;
     const int mrow = m;      // row of q16 (the batch-wide row)
-    if (q.G > 1) { const int gi = m / q.Mg; m -= gi * q.Mg; goff = q.grow[gi]; }
+    int B = q.B, P0 = q.P0, S = q.S, pos0 = q.pos0;
+    if (q.ng) { const QkvGroup e = qkv_rope_group(q, m); B = e.B; P0 = pos0 = e.P0; S = e.S; goff = e.row; }
+    else if (q.G > 1) { const int gi = m / q.Mg; m -= gi * q.Mg; goff = q.grow[gi]; }
     if (q.row_pos) { b = m; pos = (RS_PROBE_K_ & 8192) ? 170 + (m & 7) : q.row_pos[m]; if (pos < 0 || pos >= q.Smax) return; }   // (& 8192, timing probe: no position load)   // inactive, or past the pool's capacity (would land in another row's blocks of the blocked V^T cache): nothing is stored
-    else if (m < q.P0) { b = 0; pos = m; prefix = true; }
-    else { const int r = m - q.P0; b = r / q.S; pos = q.pos0 + (r - b * q.S); }
+    else if (m < P0) { b = 0; pos = m; prefix = true; }
+    else { const int r = m - P0; b = r / S; pos = pos0 + (r - b * S); }
     if (sec < 2) {
         // explicit product + fma: the contraction hipcc picks for a*b - c*d may differ between the template instantiations this
         // inlines into, and a rotated value must not depend on which kernel (or how many rows) produced it
@@ -151,13 +174,13 @@ static __device__ __forceinline__ void qkv_rope_store_t(const QkvRope& q, int m,
             }
         } else {
             if constexpr ((RS_PROBE_K_ & 512) != 0) return;
-            const int b0_ = (prefix ? 0 : b) + goff, b1_ = (prefix ? q.B : b + 1) + goff;
+            const int b0_ = (prefix ? 0 : b) + goff, b1_ = (prefix ? B : b + 1) + goff;
             for (int bb = b0_; bb < b1_; ++bb)
                 *(u32x2*)((op16_t*)q.kc + (((int64_t)bb * q.H + head) * q.Smax + pos) * 128 + p) = o;
         }
     } else {
         if constexpr ((RS_PROBE_K_ & 256) != 0) return;
-        const int b0_ = (prefix ? 0 : b) + goff, b1_ = (prefix ? q.B : b + 1) + goff;
+        const int b0_ = (prefix ? 0 : b) + goff, b1_ = (prefix ? B : b + 1) + goff;
         for (int bb = b0_; bb < b1_; ++bb) {
             op16_t* dst = (op16_t*)q.vtc + ((int64_t)bb * q.H + head) * 128 * q.Smax + rv_vt_index(p, pos);
 #pragma unroll
@@ -179,15 +202,17 @@ static __device__ __forceinline__ QkvRow qkv_rope_row(const QkvRope& q, int m) {
     int goff = 0, b;
     bool prefix = false;
     int mt = m;
-    if (q.G > 1) { const int gi = m / q.Mg; mt = m - gi * q.Mg; goff = q.grow[gi]; }
+    int B = q.B, P0 = q.P0, S = q.S, pos0 = q.pos0;
+    if (q.ng) { const QkvGroup e = qkv_rope_group(q, mt); B = e.B; P0 = pos0 = e.P0; S = e.S; goff = e.row; }
+    else if (q.G > 1) { const int gi = m / q.Mg; mt = m - gi * q.Mg; goff = q.grow[gi]; }
     if (q.row_pos) { b = mt; r.pos = q.row_pos[mt]; r.cs = q.cs + (int64_t)mt * 128; }
     else {
-        if (mt < q.P0) { b = 0; r.pos = mt; prefix = true; }
-        else { const int rr = mt - q.P0; b = rr / q.S; r.pos = q.pos0 + (rr - b * q.S); }
+        if (mt < P0) { b = 0; r.pos = mt; prefix = true; }
+        else { const int rr = mt - P0; b = rr / S; r.pos = pos0 + (rr - b * S); }
         r.cs = q.cs + (int64_t)(r.pos - q.cs_pos0) * 128;
     }
     r.b0 = (prefix ? 0 : b) + goff;
-    r.b1 = (prefix ? q.B : b + 1) + goff;
+    r.b1 = (prefix ? B : b + 1) + goff;
     if (q.row_pos && (r.pos < 0 || r.pos >= q.Smax)) r.b1 = r.b0 - 1;   // inactive row: nothing is stored (b1 < b0; Q is skipped through pos < 0)
     return r;
 }
@@ -301,3 +326,14 @@ struct AttnGroups {
 };
 int k_attention_pair(const AttnArgs& a, const AttnArgs& b, hipStream_t st, const AttnGroups* groups = nullptr);   // two prefill problems (dh 128) in one launch
 int k_attention_groups(const AttnArgs& a, hipStream_t st, const AttnGroups& groups);   // G copies of ONE prefill problem (dh 128, no shared prefix) in one launch
+// The prefill attention of a MIXED pass in one launch: group g is the pair of problems of k_attention_pair with its own (B, S, P0) - a prefix problem (P0 rows among
+// themselves; none when P0 == 0) and B sequences of S rows over P0 + S keys.  q / out: row 0 of the pass; k / vt: cache row 0 of the pool (this layer).
+struct AttnMixed {
+    int G = 0, problems = 0;                   // problems = sum over the groups of (P0 > 0) + B
+    int first[RV_MAX_PREFILL_GROUPS] = {};     // first problem of group g (prefix sum)
+    QkvGroup gt[RV_MAX_PREFILL_GROUPS] = {};   // (indexed by the workgroup's group only: uniform, no scratch copy)
+};
+int k_attention_mixed(const AttnArgs& a, const AttnMixed& mx, hipStream_t st);   // a: pointers, strides, H, dh = 128, scale (B / Lq / Lk / q_pos0 come from the groups)
+// The device tables of a mixed pass: gt[g] = the group entries (QkvRope::gt) and, with last_rows != nullptr, last_rows[i] of sequence i (group order, then
+// sequence order) = base + P0 + (b + 1) * S - 1
+int k_mixed_tables(const AttnMixed& mx, QkvGroup* gt, int* last_rows, hipStream_t st);

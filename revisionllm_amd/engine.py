@@ -488,6 +488,32 @@ class Engine:
         self._persist_end()
         return logits
 
+    def mixed_prefill_supported(self):
+        """Mixed-geometry passes run on the plain 16-bit path only: not in the parity precision, not with the FP8 prefill weights in use."""
+        return not (self.get_option("precision") == 1 or (getattr(self, "fp8_prefill", False) and self.get_option("fp8_prefill")))
+
+    def llm_prefill_pool_mixed(self, h, groups, kv, R, Smax, last_rows=None, logits=None):
+        """Prefills of DIFFERENT geometry in one pass (rv_llm_prefill_pool_mixed): ``groups`` = [(B, P0, S, kv_row0), ..] (<= 8), h f32
+        [sum (P0 + B * S), D] = the groups' [P0 shared-prefix rows ; B x S rows] blocks back to back, ``R`` the pool's rows.
+        -> logits f32 [sum B, V] in group order, then sequence order.  ``last_rows`` (device int32 [sum B]): the row of h that feeds the head,
+        per sequence (right-padded sequences); None = the last row of every sequence."""
+        groups = [tuple(int(v) for v in g) for g in groups]
+        rows, nb = sum(P0 + B * S for B, P0, S, _ in groups), sum(g[0] for g in groups)
+        assert h.dtype == torch.float32 and h.is_contiguous() and h.shape[0] == rows, (tuple(h.shape), rows)
+        if logits is None:
+            logits = torch.empty(nb, self.shape.vocab, dtype=torch.float32, device=self.device)
+        ws = self._workspace("llm", self.lib.rv_llm_ws_bytes(self._ctx, max(rows, 1), 1))
+        tab = (hip.RvPrefillGroup * max(len(groups), 1))(*[hip.RvPrefillGroup(*g) for g in groups])
+        if last_rows is not None:
+            assert last_rows.dtype == torch.int32 and last_rows.is_cuda and last_rows.numel() == nb
+        self._persist_begin()
+        try:
+            hip.check(self.lib.rv_llm_prefill_pool_mixed(self._ctx, hip.ptr(h), len(groups), tab, hip.ptr(kv), R, Smax, hip.ptr(last_rows), hip.ptr(logits), hip.ptr(ws),
+                                                         ws.numel(), hip.stream()), "rv_llm_prefill_pool_mixed")
+        finally:
+            self._persist_end()
+        return logits
+
     def llm_decode_rows(self, h, row_pos, kv, Smax, logits=None, row_share=None):
         """One merged decode step: h f32 [R, D] (clobbered), row_pos int32 [R] on the device (< 0: inactive) -> logits f32 [R, V].
         ``row_share`` int32 [R] on the device (optional): sibling | len << 16 per row - its first ``len`` cache positions are bit-identical to row

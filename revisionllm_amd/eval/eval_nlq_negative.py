@@ -80,6 +80,9 @@ def parse_args(argv=None):
     p.add_argument("--in_flight", type=int, default=1,
                    help="queries processed concurrently: > 1 runs them as scheduler tasks on their own HIP streams; their window batches prefill in "
                         "the DecodeServer's batched passes and decode in its merged steps (what bench.py's stage-1 workloads time); 1 = the reference's loop")
+    p.add_argument("--mixed_prefill", action="store_true",
+                   help="(build-defined; --in_flight > 1) prefills of different geometry (query length, window count) share a pass, adapter calls of different query "
+                        "lengths a call (serve.DecodeServer(mixed_prefill=True)); default off")
     p.add_argument("--pool_rows", type=int, default=32, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per generate at most (--in_flight > 1; answers are a dozen tokens)")
     return p.parse_args(argv)
@@ -202,7 +205,8 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, predicti
     from .. import sched, serve
     dev = model.device
     smax = (128 + args.num_frames + args.max_new_tokens + 63) // 64 * 64      # prompt + up to num_frames video tokens (dense projector) + answer
-    server = serve.DecodeServer(model, rows=args.pool_rows, smax=smax, gmax=max(16, args.max_new_tokens), pools=2, gang=True, prefill_batch=4)
+    server = serve.DecodeServer(model, rows=args.pool_rows, smax=smax, gmax=max(16, args.max_new_tokens), pools=2, gang=True, prefill_batch=4,
+                                mixed_prefill=getattr(args, "mixed_prefill", False))
     inter = sched.Interleaver(servers=[server])
     streams = [torch.cuda.Stream(dev) for _ in range(args.in_flight)]
     pending, errors, written, k = [], [], 0, 0

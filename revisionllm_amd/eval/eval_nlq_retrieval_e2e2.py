@@ -90,6 +90,9 @@ def parse_args(argv=None):
                    help="queries processed concurrently (batched mode): > 1 runs them as scheduler tasks on their own HIP streams whose LLM prefills "
                         "ride up to four to a pass and whose decode steps are merged (serve.DecodeServer: two KV pools filled and stepped in turn) - "
                         "the pipeline bench.py measures; 1 = one query at a time, as the reference loops")
+    p.add_argument("--mixed_prefill", action="store_true",
+                   help="(build-defined; --in_flight > 1) prefills of different geometry (query length, window count) share a pass, adapter calls of different query "
+                        "lengths a call (serve.DecodeServer(mixed_prefill=True)); default off")
     p.add_argument("--pool_rows", type=int, default=56, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per call at most (--in_flight > 1; answers are a dozen tokens)")
     return p.parse_args(argv)
@@ -243,7 +246,8 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, groundin
     stages = parallel.HipStages(model, tokenizer)
     smax = (128 + args.batch + args.max_new_tokens + 63) // 64 * 64          # prompt (<= ~100 tokens with a long sentence) + video tokens + answer;
                                                                              # a generate that does not fit decodes on its own (generate_steps)
-    server = serve.DecodeServer(model, rows=args.pool_rows, smax=smax, gmax=max(16, args.max_new_tokens), pools=2, gang=True, prefill_batch=4)
+    server = serve.DecodeServer(model, rows=args.pool_rows, smax=smax, gmax=max(16, args.max_new_tokens), pools=2, gang=True, prefill_batch=4,
+                                mixed_prefill=getattr(args, "mixed_prefill", False))
     stages.server = server
     inter = sched.Interleaver(servers=[server])
     streams = [torch.cuda.Stream(dev) for _ in range(args.in_flight)]

@@ -34,6 +34,11 @@ class RvConfig(C.Structure):
                 ("adapter_text", C.c_int32)]
 
 
+class RvPrefillGroup(C.Structure):
+    """``rv_prefill_group``: one group of a mixed-geometry prefill pass (rv_llm_prefill_pool_mixed)."""
+    _fields_ = [("B", C.c_int32), ("P0", C.c_int32), ("S", C.c_int32), ("kv_row0", C.c_int32)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -116,6 +121,7 @@ SIGNATURES = {
     "rv_llm_prefill_pool": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _sz, _p]),
     "rv_llm_prefill_pool_groups": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _p, _sz, _p]),
     "rv_llm_prefill_pool_groups_ragged": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _p, _p, _sz, _p]),
+    "rv_llm_prefill_pool_mixed": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _i32, _p, _p, _p, _sz, _p]),
     "rv_llm_decode_rows": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _p, _p, _sz, _p]),
     "rv_llm_decode_rows_shared": (C.c_int, [_p, _p, _i32, _p, _p, _p, _i32, _p, _p, _sz, _p]),
     "rv_sample": (C.c_int, [_p, _p, _i32, _i32, _p, _i32, _f, _i32, _f, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -319,6 +319,20 @@ def best_prefill_batch(avail, rows, per_x=32):
     return best
 
 
+def best_prefill_count(rows, per_x=32):
+    """``best_prefill_batch`` for waiting prefills of DIFFERENT row counts (``rows``: one count per ticket, in queue order): how many of the leading
+    tickets go into one mixed pass - the same cost rule on the actual cumulative row counts (the groups are packed back to back: no pad rows but the
+    last row tile's); ties go to the larger batch.  Equal row counts give ``best_prefill_batch(len(rows), rows[0])``."""
+    best, best_cost, total = 1, None, 0
+    for n, r in enumerate(rows, 1):
+        total += int(r)
+        tiles = -(-total // 256)
+        cost = tiles / (team_fill(tiles, per_x) * n)
+        if best_cost is None or cost <= best_cost * 1.0001:
+            best, best_cost = n, cost
+    return best
+
+
 class PrefillTicket:
     """One generate's prefill handed to the server (``DecodeServer.submit_prefill``): ``ready`` (event) / ``first`` (its last-position
     logits [B, V]) are set once the batch it rides in has been enqueued."""
@@ -331,6 +345,16 @@ class PrefillTicket:
     @property
     def key(self):
         return (id(self.job.pool), self.B, self.P0, self.h.shape[0], self.lens)
+
+    @property
+    def S(self):
+        return (self.h.shape[0] - self.P0) // self.B
+
+    @property
+    def mixable(self):
+        """Inside the limits of ``rv_llm_prefill_pool_mixed`` (the pair attention kernel's own: S > 16, P0 == 0 or P0 > 16; the pool's length), and a sequence
+        of at least 32 positions: shorter ones take another form of the last block and the entry does not put the two kinds into one pass."""
+        return self.S > 16 and (self.P0 == 0 or self.P0 > 16) and 32 <= self.P0 + self.S <= self.job.pool.Smax
 
 
 class EncodeTicket:
@@ -345,13 +369,19 @@ class EncodeTicket:
     def key(self):
         return (tuple(self.features.shape), tuple(self.query_feats.shape), self.features.dtype)
 
+    @property
+    def key_any_length(self):
+        """``key`` without the query length (mixed batches zero-pad the queries to the longest and mask the pad tokens)."""
+        return (tuple(self.features.shape), tuple(self.query_feats.shape[1:]), self.features.dtype, self.query_feats.dtype)
+
 
 class DecodeServer:
     """The pools + the stepping policy (module docstring).  ``gang=False``: one pool, greedy steps.  What ``generate_steps``
     uses: ``fits``, ``reserve`` (-> ``Job`` with ``job.pool``; ``None``: no room - wait if ``blocking`` else decode alone), ``join``;
     what ``sched.Interleaver`` uses: ``pump`` / ``wait_one``."""
 
-    def __init__(self, model, rows=32, smax=256, gmax=64, max_ahead=2, slot=97, pools=1, gang=False, prefill_batch=1, pool_factory=None, encode_batch=1):
+    def __init__(self, model, rows=32, smax=256, gmax=64, max_ahead=2, slot=97, pools=1, gang=False, prefill_batch=1, pool_factory=None, encode_batch=1,
+                 mixed_prefill=False):
         """``prefill_batch`` > 1: the generates' LLM prefills go through the server too - up to that many waiting prefills of identical
         geometry (rows, shared-prefix length, length) ride in ONE pass (``rv_llm_prefill_pool_groups``: the GEMMs see G x 1005 rows
         instead of 1005, which the N = 4096 projections in particular are too small for), on one prefill stream in submission order.
@@ -360,7 +390,13 @@ class DecodeServer:
         (``best_prefill_batch``: row-tile padding and the CU fill of the stream-K teams).  Per-row results equal the separate prefills up to GEMM summation order.
         ``encode_batch`` > 1 (round 6): the recursions' ADAPTER calls go through the server too - up to that many waiting encodes of identical geometry
         (windows, frames, text tokens) run as ONE ``rv_clip_encoder`` call with one query per recursion (``submit_encode``): 1.55 ms per recursion alone,
-        1.33 four to a call, 1.25 eight (the K = 768 GEMMs fill more whole rounds, the CLS-only tail of six latency-bound launches is paid once per call)."""
+        1.33 four to a call, 1.25 eight (the K = 768 GEMMs fill more whole rounds, the CLS-only tail of six latency-bound launches is paid once per call).
+        ``mixed_prefill`` (default off: nothing changes): waiting prefills of DIFFERENT geometry (rows B, shared-prefix length, length) share a pass too -
+        the leading tickets of one pool that lie inside the limits of ``rv_llm_prefill_pool_mixed``, packed back to back with no pad rows, the count chosen
+        by ``best_prefill_count``; a batch that turns out to have ONE geometry goes through the entries above exactly as before.  Adapter calls that differ
+        only in the number of text tokens are batched as well: the queries are zero-padded to the longest and the pad tokens masked.  Real annotation
+        files need this: their queries tokenise to different lengths and their videos have different window counts, so identical geometry is the exception."""
+        self.mixed_prefill = bool(mixed_prefill)
         assert pools >= 1 and (pools >= 2 or not gang), "the gang policy alternates between at least two pools"
         assert 1 <= prefill_batch <= 8
         self.prefill_batch, self.pf_queue, self.pf_inflight = prefill_batch, [], []
@@ -465,13 +501,22 @@ class DecodeServer:
         self.pf_inflight = [e for e in self.pf_inflight if not e.query()]
         lead = self.pf_queue[0]
         n = 1
-        while n < len(self.pf_queue) and n < self.prefill_batch and self.pf_queue[n].key == lead.key:
-            n += 1
-        full = n == self.prefill_batch or n < len(self.pf_queue)      # (a ticket of another geometry behind the group closes it)
+        mix = self._mix_ok() and lead.mixable
+        if mix:       # the leading tickets of the lead's pool that the mixed entry takes, whatever their B / P0 / row count
+            while n < len(self.pf_queue) and n < self.prefill_batch and self.pf_queue[n].job.pool is lead.job.pool and self.pf_queue[n].mixable:
+                n += 1
+        else:
+            while n < len(self.pf_queue) and n < self.prefill_batch and self.pf_queue[n].key == lead.key:
+                n += 1
+        full = n == self.prefill_batch or n < len(self.pf_queue)      # (a ticket of another geometry - mixed: of another pool / outside the limits - behind the group closes it)
         if not full and not force and not (partial and not self.pf_inflight):
             return False
-        n = best_prefill_batch(n, int(lead.h.shape[0]), self.cus_per_xcd)
+        if mix:
+            n = best_prefill_count([int(t.h.shape[0]) for t in self.pf_queue[:n]], self.cus_per_xcd)
+        else:
+            n = best_prefill_batch(n, int(lead.h.shape[0]), self.cus_per_xcd)
         batch, self.pf_queue = self.pf_queue[:n], self.pf_queue[n:]
+        mix = mix and any(t.key != lead.key for t in batch)           # one geometry: the existing entries, exactly as without mixing
         eng, pool = self.model.engine, lead.job.pool
         prev = eng.slot
         eng.slot = self.pf_slot
@@ -479,7 +524,16 @@ class DecodeServer:
             for t in batch:
                 self.pf_stream.wait_event(t.event)
                 t.h.record_stream(self.pf_stream)
-            if lead.lens is not None:     # right-padded sequences: the head reads every sequence's last VALID row
+            if mix:
+                groups, last, base = [], [], 0
+                for t in batch:
+                    groups.append((t.B, t.P0, t.S, t.job.r0))
+                    last += [base + t.P0 + b * t.S + ((t.lens[b] - t.P0) if t.lens is not None else t.S) - 1 for b in range(t.B)]
+                    base += int(t.h.shape[0])
+                ragged = any(t.lens is not None for t in batch)      # (tickets with right-padded sequences contribute their last VALID rows)
+                logits = eng.llm_prefill_pool_mixed(torch.cat([t.h for t in batch]), groups, pool.kv, pool.R, pool.Smax,
+                                                    last_rows=ops.h2d(torch.tensor(last, dtype=torch.int32), eng.device) if ragged else None)
+            elif lead.lens is not None:     # right-padded sequences: the head reads every sequence's last VALID row
                 Mg = lead.h.shape[0]
                 S_ = (Mg - lead.P0) // lead.B
                 last = [g * Mg + lead.P0 + b * S_ + (lead.lens[b] - lead.P0 - 1) for g in range(n) for b in range(lead.B)]
@@ -493,8 +547,10 @@ class DecodeServer:
             ev = torch.cuda.Event()
             ev.record(self.pf_stream)
         eng.slot = prev
-        for i, t in enumerate(batch):
-            t.first = logits[i * t.B:(i + 1) * t.B]
+        row = 0
+        for t in batch:
+            t.first = logits[row:row + t.B]
+            row += t.B
             t.ready = ev
             t.h = None
         self.pf_inflight.append(ev)
@@ -502,6 +558,13 @@ class DecodeServer:
         self.pf_tickets += n
         self.pf_hist[n] = self.pf_hist.get(n, 0) + n
         return True
+
+    def _mix_ok(self):
+        """Mixing is on and the engine's current options allow it (the mixed entry refuses the parity precision and the FP8 prefill weights)."""
+        if not self.mixed_prefill:
+            return False
+        ok = getattr(self.model.engine, "mixed_prefill_supported", None)
+        return True if ok is None else bool(ok())
 
     # ---- batched adapter calls ---------------------------------------------------------------------------------------------------
     def submit_encode(self, features, query_feats):
@@ -521,7 +584,8 @@ class DecodeServer:
         self.enc_inflight = [e for e in self.enc_inflight if not e.query()]
         lead = self.enc_queue[0]
         n = 1
-        while n < len(self.enc_queue) and n < self.encode_batch and self.enc_queue[n].key == lead.key:
+        key = (lambda t: t.key_any_length) if self.mixed_prefill else (lambda t: t.key)
+        while n < len(self.enc_queue) and n < self.encode_batch and key(self.enc_queue[n]) == key(lead):
             n += 1
         full = n == self.encode_batch or n < len(self.enc_queue)
         if not full and not force and not (partial and not self.enc_inflight):
@@ -537,8 +601,14 @@ class DecodeServer:
                 t.query_feats.record_stream(self.enc_stream)
             N = lead.features.shape[0]
             x = torch.cat([t.features for t in batch]) if n > 1 else lead.features
-            txt = torch.stack([t.query_feats for t in batch])
-            cls = eng.clip_encoder(x, txt, torch.ones(n, txt.shape[1]), "cls")
+            Lq = max(t.query_feats.shape[0] for t in batch)
+            if all(t.query_feats.shape[0] == Lq for t in batch):
+                txt = torch.stack([t.query_feats for t in batch])
+                mask = torch.ones(n, txt.shape[1])
+            else:      # (mixed batches) queries of different lengths: zero-padded to the longest, the pad tokens masked
+                txt = torch.stack([torch.nn.functional.pad(t.query_feats, (0, 0, 0, Lq - t.query_feats.shape[0])) for t in batch])
+                mask = torch.tensor([[1.0] * t.query_feats.shape[0] + [0.0] * (Lq - t.query_feats.shape[0]) for t in batch])
+            cls = eng.clip_encoder(x, txt, mask, "cls")
             ev = torch.cuda.Event()
             ev.record(self.enc_stream)
         eng.slot = prev
