@@ -566,6 +566,44 @@ def test_attention(dev, case):
     assert rel_err(y.float().cpu(), ref) < tol(BF16_TOL)
 
 
+_EDGE_LK = (1, 2, 31, 32, 33, 63, 64, 65, 127, 128, 129, 159, 160)
+
+
+@pytest.mark.parametrize("Lq,Lk", [(Lq, Lk) for Lq in (1, 16) for Lk in _EDGE_LK if Lq <= Lk])
+def test_decode_attention_at_key_block_edges(dev, Lq, Lk):
+    """The key-split decode form (Lq <= 16: wave w of a workgroup takes the 32-key blocks w, w + 4, .. and the four partial (m, l, O) are merged
+    through LDS) with the key count at every edge of that split, against float64: fewer blocks than waves (the idle waves enter the merge with
+    m = -inf), an exactly full last block, a last block of ONE key, one key in all, a second round of blocks that only wave 0 has (129, 159, 160).
+    Causal with the queries at the END of the keys (q_pos0 = Lk - Lq), as a KV-cached step has them; Lq = 16: every query row its own key count."""
+    from revisionllm_amd import ops
+    B, H, dh = 3, 4, 128
+    q = feats(f"ate.q.{Lq}.{Lk}", (B, Lq, H, dh), bf16=fl())
+    k = feats(f"ate.k.{Lq}.{Lk}", (B, Lk, H, dh), bf16=fl())
+    v = feats(f"ate.v.{Lq}.{Lk}", (B, Lk, H, dh), bf16=fl())
+    y = ops.attention(bf(q).to(dev), bf(k).to(dev), bf(v).to(dev), causal=True, q_pos0=Lk - Lq)
+    ref = _ref_attn(q, k, v, True, None, Lk - Lq, 1)
+    assert torch.isfinite(y).all() and rel_err(y.float().cpu(), ref) < tol(BF16_TOL)
+
+
+@pytest.mark.parametrize("Lk,hidden_from", [(13, 9), (32, 20), (33, 32), (128, 96), (129, 128)])
+def test_padded_split_attention_at_key_block_edges(dev, Lk, hidden_from):
+    """The key-split form with a key-padding mask (the adapter's text cross-attention: 96-wide heads, 9 queries, not causal, 4 query batches over
+    2 key batches) at the block edges, against float64.  The mask hides the keys hidden_from .. Lk - 1 of key batch 1 and none of batch 0: a tail
+    inside the only block, the whole single-key last block (33: hidden in one batch, live in the other), a whole block of one wave (128: wave 3
+    merges with m = -inf), the single key of a second round (129)."""
+    from revisionllm_amd import ops
+    B, Bk, Lq, H, dh = 4, 2, 9, 8, 96
+    q = feats(f"atp.q.{Lk}", (B, Lq, H, dh), bf16=fl())
+    k = feats(f"atp.k.{Lk}", (Bk, Lk, H, dh), bf16=fl())
+    v = feats(f"atp.v.{Lk}", (Bk, Lk, H, dh), bf16=fl())
+    pad = torch.zeros(Bk, Lk, dtype=torch.uint8)
+    pad[1, hidden_from:] = 1
+    assert 0 < hidden_from < Lk
+    y = ops.attention(bf(q).to(dev), bf(k).to(dev), bf(v).to(dev), causal=False, key_pad=pad.to(dev))
+    ref = _ref_attn(q, k, v, False, pad, 0, B // Bk)
+    assert torch.isfinite(y).all() and rel_err(y.float().cpu(), ref) < tol(BF16_TOL)
+
+
 @pytest.mark.parametrize("Tn,N", [(256, 5), (1024, 2), (130, 3)])
 def test_attention_with_lds_staged_keys_is_bit_identical(dev, Tn, N):
     """The long-key attention form (attention.hip attn_body_lds: key blocks staged in LDS once per 128 query rows, option ``attn_lds``) performs the per-tile
