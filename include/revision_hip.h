@@ -233,6 +233,7 @@ int rv_sine_pos(float* pos, int32_t T, int32_t d, void* stream);
  * causal: query i (absolute position q_pos0 + i) sees keys <= its position.
  * key_pad: u8 [B/kv_batch_div,Lk] (1 = ignore) or NULL (nn.MultiheadAttention key_padding_mask,
  * transformer.py:293-294).  Query batch b reads K/V batch b / kv_batch_div (one text for v segments).
+ * A key batch whose keys are ALL padded has no key: its query rows come out as zeros (nn.MultiheadAttention yields NaN there).
  * V^T rows (vt_d_stride) must be padded with finite values to a multiple of 32 keys. */
 int rv_attention(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride,
                  int64_t k_batch_stride, int64_t k_head_stride, const void* vt, int64_t vt_batch_stride,
@@ -247,6 +248,7 @@ int rv_project_dense(rv_ctx* ctx, const void* x_bf16, void* y, int out_dtype, in
  * x [N,T,d] bf16; txt [Nq,Lq,d] bf16 (d = adapter_dim: 768, or 4096 for the hidden-wide cross_attn encoder, whose callers project frames and
  * text first - mm_projector / text_mm_projector, vtimellm_arch.py:125, transformer.py:105-106) and txt_mask u8 [Nq,Lq] (1 = valid) with sequence n using text
  * row n / (N/Nq) (hierarchy: '(b v) t d', vtimellm_arch.py:115-121); ignored when adapter_text == 0.
+ * A query whose every token is masked has no key: its text -> video attention output is zero in every option form, so its sequences stay finite.
  * out f32: RV_FEAT_CLS [N,D]; RV_FEAT_ALL [N,T+1,D] (row 0 = CLS; the 'temporal' feature is rows 1..T,
  * sliced by the caller). */
 size_t rv_clip_encoder_ws_bytes(const rv_ctx* ctx, int32_t N, int32_t T, int32_t Nq, int32_t Lq);

@@ -180,7 +180,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int 
             sc[w] = sm_m[w][q] == -INFINITY ? 0.f : __expf(sm_m[w][q] - mm);
             lt += sm_l[w][q] * sc[w];
         }
-        const float inv = 1.0f / lt;
+        const float inv = PAD && lt == 0.f ? 0.f : 1.0f / lt;      // (every key padded: no key - a zero row, as t2v_softmax_kernel yields)
         op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)(q0 + q) * a.o_rs + h * DH + dc;
 #pragma unroll
         for (int j = 0; j < DH / 16; j += 2) {
@@ -197,7 +197,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int 
         return;
     }
     if (q0 + fr >= a.Lq) return;
-    const float inv = 1.0f / l_run;
+    const float inv = PAD && l_run == 0.f ? 0.f : 1.0f / l_run;      // (every key padded: a zero row)
     op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)(q0 + fr) * a.o_rs + h * DH + g * 4;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt)

@@ -516,8 +516,12 @@ extern "C" int rv_clip_encoder(rv_ctx* c, const void* x, const void* txt, const 
         if (feature == RV_FEAT_CLS && l + 1 == c->enc.size() && N > 16 && T >= 3) {
             // Last layer, CLS feature: only row 0 of every sequence is read afterwards, so only K and V are computed for all
             // rows; the query, the attention row, out-proj, LN1, FFN and LN2 run on the N CLS rows alone (78 % of the layer's
-            // GEMM work gone).  Same kernels and summation orders as the full-length launches (N > 16 keeps the GEMMs on the
-            // tiled kernel, the attention keeps the non-split variant), so the CLS rows are bit-identical to the full layer's.
+            // GEMM work gone).  The N-row GEMMs stay on the kernels the full-length launches take: N > 16, and for 17 .. 32 rows
+            // rv_gemm_impl's no_stream (its weight-streaming kernel splits K across waves: with it the CLS rows of 17 / 18 sequences
+            // were up to 9e-4 of the largest output away from the full layer's); the attention keeps the non-split variant (at
+            // T + 1 <= 16 the full layer's key-split form has ONE key block: the same operations).  Asserted: the CLS rows have the bits
+            // of the full layer's at 17 x 3, 18 x 40, 32 x 128, 33 x 16 and 36 x 40 frames, both builds; no guarantee for every shape -
+            // rv_gemm_impl picks its M > 32 kernel (A-resident, ping-pong / stream-K, ring) by M, N and K.
             const int64_t sx = (int64_t)(T + 1) * d;   // row stride between the CLS rows of consecutive sequences
             op16_t* kk16 = w.qk16;                      // K  [R1, d]
             op16_t* qc16 = w.h16;                       // Q of the CLS rows [N, d] (h16 is free until the FFN)
@@ -525,7 +529,7 @@ extern "C" int rv_clip_encoder(rv_ctx* c, const void* x, const void* txt, const 
             float* y1 = w.y32 + (int64_t)N * d;         // [N, d] LN1 output (FFN residual)
             float* y2 = w.y32 + (int64_t)2 * N * d;     // [N, d] FFN + residual
             RV_TRY(rv_gemm_impl(w.xp16, d, L.w_in + d * d, d, 1, L.b_in + d, nullptr, 0, kk16, d, RV_OP16, RV_ACT_NONE, R1, d, d, w.sk, w.sk_bytes, st));
-            RV_TRY(rv_gemm_impl(w.xp16, sx, L.w_in, d, 1, L.b_in, nullptr, 0, qc16, d, RV_OP16, RV_ACT_NONE, N, d, d, w.sk, w.sk_bytes, st));
+            RV_TRY(rv_gemm_impl(w.xp16, sx, L.w_in, d, 1, L.b_in, nullptr, 0, qc16, d, RV_OP16, RV_ACT_NONE, N, d, d, w.sk, w.sk_bytes, st, nullptr, 0, 1));
             RV_TRY(rv_gemm_impl(w.x16, d, L.w_in + 2 * d * d, d, 1, L.b_in + 2 * d, nullptr, 0, w.vv16, d, RV_OP16, RV_ACT_NONE, R1, d, d, w.sk, w.sk_bytes, st));
             RV_TRY(k_transpose_v(w.vv16, d, w.vt16, N, T + 1, w.Lpad, H, dh, st));
             AttnArgs a{qc16, d, d, kk16, d, (int64_t)(T + 1) * d, dh, w.vt16, (int64_t)d * w.Lpad, (int64_t)dh * w.Lpad, w.Lpad, w.a16, d, d,
@@ -539,16 +543,16 @@ extern "C" int rv_clip_encoder(rv_ctx* c, const void* x, const void* txt, const 
                 cls_res = y3;
                 cls_ld = d;
             }
-            RV_TRY(rv_gemm_impl(w.a16, d, L.w_out, d, 1, L.b_out, cls_res, cls_ld, y0, d, RV_F32, RV_ACT_NONE, N, d, d, w.sk, w.sk_bytes, st));
+            RV_TRY(rv_gemm_impl(w.a16, d, L.w_out, d, 1, L.b_out, cls_res, cls_ld, y0, d, RV_F32, RV_ACT_NONE, N, d, d, w.sk, w.sk_bytes, st, nullptr, 0, 1));
             // (16-bit stream: y0 / y2 are read THROUGH the operand type and y1 - the FFN-2 residual - holds operand-representable values: the same values the
             //  full-length form of this layer stores as fp16, so the CLS rows do not depend on which form ran)
             RV_TRY(k_layernorm(y0, L.ln1_w, L.ln1_b, y1, w.x16, nullptr, nullptr, 0, N, (int)d, st, 0, nullptr, s16 ? 3 : 0));
-            RV_TRY(rv_gemm_impl(w.x16, d, L.w1, d, 1, L.b1, nullptr, 0, w.h16, ff, RV_OP16, RV_ACT_RELU, N, ff, d, w.sk, w.sk_bytes, st));
-            RV_TRY(rv_gemm_impl(w.h16, ff, L.w2, ff, 1, L.b2, y1, d, y2, d, RV_F32, RV_ACT_NONE, N, d, ff, w.sk, w.sk_bytes, st));
+            RV_TRY(rv_gemm_impl(w.x16, d, L.w1, d, 1, L.b1, nullptr, 0, w.h16, ff, RV_OP16, RV_ACT_RELU, N, ff, d, w.sk, w.sk_bytes, st, nullptr, 0, 1));
+            RV_TRY(rv_gemm_impl(w.h16, ff, L.w2, ff, 1, L.b2, y1, d, y2, d, RV_F32, RV_ACT_NONE, N, d, ff, w.sk, w.sk_bytes, st, nullptr, 0, 1));
             if (!c->adp_proj_w)      // identity projector: the CLS rows' last LayerNorm IS the output
                 return k_layernorm(y2, L.ln2_w, L.ln2_b, (float*)out, nullptr, nullptr, nullptr, 0, N, (int)d, st);
             RV_TRY(k_layernorm(y2, L.ln2_w, L.ln2_b, nullptr, w.x16, nullptr, nullptr, 0, N, (int)d, st, 0, nullptr, s16 ? 1 : 0));
-            return rv_gemm_impl(w.x16, d, c->adp_proj_w, d, 1, c->adp_proj_b, nullptr, 0, out, D, RV_F32, RV_ACT_NONE, N, D, d, w.sk, w.sk_bytes, st);
+            return rv_gemm_impl(w.x16, d, c->adp_proj_w, d, 1, c->adp_proj_b, nullptr, 0, out, D, RV_F32, RV_ACT_NONE, N, D, d, w.sk, w.sk_bytes, st, nullptr, 0, 1);
         }
         RV_TRY(rv_gemm_impl(w.xp16, d, L.w_in, d, 1, L.b_in, nullptr, 0, w.qk16, 2 * d, RV_OP16, RV_ACT_NONE, R1, 2 * d, d, w.sk, w.sk_bytes, st));
         RV_TRY(rv_gemm_impl(w.x16, d, L.w_in + 2 * d * d, d, 1, L.b_in + 2 * d, nullptr, 0, w.vv16, d, RV_OP16, RV_ACT_NONE, R1, d, d, w.sk, w.sk_bytes, st));

@@ -784,7 +784,7 @@ void launch_gemv(const op16_t* A, int64_t lda, const op16_t* W, int64_t ldw, con
 
 int rv_gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, int w_layout, const float* bias,
                  const float* residual, int64_t ldr, void* C, int64_t ldc, int out_dtype, int act, int64_t M, int64_t N,
-                 int64_t K, void* ws, size_t ws_bytes, hipStream_t st, const GemvNorm* norm, int res16) {
+                 int64_t K, void* ws, size_t ws_bytes, hipStream_t st, const GemvNorm* norm, int res16, int no_stream) {
     RV_CHECK_ARG(A && W && C, "rv_gemm: null operand");
     if (res16) {   // a residual of 16-bit operand rows: the tile kernels read it through rv_residual4 (common.h), told by a negative row stride
         RV_CHECK_ARG(residual && M > 32 && !norm && w_layout <= 1 && ldr > 0 && ldr % 4 == 0, "rv_gemm: a 16-bit residual needs M > 32, bf16 / fp16 weights, ldr %% 4 == 0");
@@ -804,7 +804,9 @@ int rv_gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, int w_l
     RV_CHECK_ARG(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "rv_gemm: dims exceed int32");
     const op16_t* a = (const op16_t*)A;
     const op16_t* w = (const op16_t*)W;
-    const bool gemv = (M <= 32) && (K % 128 == 0) && (N % 16 == 0);   // 17 .. 32 rows: two MFMA column blocks per weight fragment
+    RV_CHECK_ARG(!no_stream || (!norm && w_layout <= 1), "rv_gemm: no_stream goes with plain bf16 / fp16 weights");
+    // 17 .. 32 rows: two MFMA column blocks per weight fragment; no_stream keeps them on the M > 32 kernels (the adapter's CLS-only layer: the sums of the full-length launch)
+    const bool gemv = (M <= (no_stream ? 16 : 32)) && (K % 128 == 0) && (N % 16 == 0);
     if (norm && norm->planes && M > 32 && M <= RV_ROWS_MAX && w_layout >= 1)   // 33 .. 144 rows of a merged decode step: the split-K kernel (bf16 or fp8 W)
         return gemm_rows(a, w, bias, residual, ldr, C, ldc, out_dtype, act, (int)M, (int)N, (int)K, st, *norm, nullptr, w_layout);
     RV_CHECK_ARG(!norm || gemv, "rv_gemm: RMSNorm fusion / fp8 weights are only available in the M <= 32 kernel");

@@ -226,7 +226,8 @@ int gemm_qkv_rope(const void* A, int64_t lda, const void* Wp, int64_t M, int64_t
 // ws: optional zero-initialised stream-K workspace (>= gemm_pp_ws_bytes()); NULL -> output-tiled kernels only
 int rv_gemm_impl(const void* A, int64_t lda, const void* W, int64_t ldw, int w_layout, const float* bias,
                  const float* residual, int64_t ldr, void* C, int64_t ldc, int out_dtype, int act, int64_t M, int64_t N,
-                 int64_t K, void* ws, size_t ws_bytes, hipStream_t st, const GemvNorm* norm = nullptr, int res16 = 0);   // res16: `residual` points at 16-bit operand rows (M > 32 only)
+                 int64_t K, void* ws, size_t ws_bytes, hipStream_t st, const GemvNorm* norm = nullptr, int res16 = 0, int no_stream = 0);   // res16: `residual` points at 16-bit operand rows (M > 32 only)
+                 // (last argument) no_stream: 17 .. 32 rows go to the kernels of M > 32 (same sums as a launch with more rows), not to the weight-streaming one
 // grouped form of the 128 x 128 ring kernel (gemm.hip gemm_tile_p4): rows per group, row tiles per group, element strides between the groups' weights / biases
 struct GemmGroups {
     int rows = 0, tiles = 0;
