@@ -241,6 +241,25 @@ int rv_attention(const void* q, int64_t q_row_stride, int64_t q_batch_stride, co
                  const uint8_t* key_pad, int32_t B, int32_t H, int32_t dh, int32_t Lq, int32_t Lk, int32_t causal,
                  int32_t q_pos0, int32_t kv_batch_div, float scale, void* stream);
 
+/* ---- CLIP front end: decoded frames -> patch matrix ------------------------------------------ */
+/* Resize(R, BICUBIC) / CenterCrop(R) / Normalize on decoded uint8 frames (inference.py:108-117; Preprocessing, clip_extractor.py:76-97) and the conv1
+ * unfold of VisualTransformer.forward (clip/model.py:223-226) in one pass over the source bytes of the cropped region.
+ * frames: u8, layout 0 = NCHW [n,3,H,W] (channel planes frame_stride / 3 elements apart) or 1 = NHWC [n,H,W,3] (the 3 bytes of a pixel adjacent);
+ * frame_stride / row_stride in elements, so a window of a larger decode buffer is passed as it lies.  mean / std: HOST pointers, read at launch.
+ * Values (f32 throughout, no clamp, no u8 intermediate):
+ *   resize   shorter side -> R, longer side -> int(R * long / short); antialiased bicubic, a = -0.5, align_corners = False: per axis scale = in / out,
+ *            support = 2 * max(scale, 1), centre = scale * (i + 0.5), taps [max(0, int(centre - support + 0.5)), min(in, int(centre + support + 0.5))),
+ *            weight cubic((j - centre + 0.5) / max(scale, 1)) / (sum over the taps); separable (torch's interpolate(mode="bicubic", antialias=True))
+ *   crop     R x R at top = round_half_even((h' - R) / 2), left likewise
+ *   norm     (v / 255 - mean[c]) / (std[c] + 1e-8)
+ * Outputs (either may be NULL, not both): image f32 [n,3,R,R]; patches [n*g*g, Kp] of the library's operand type with row stride ldp >= Kp, g = R / patch,
+ * Kp = ceil(3 * patch^2 / 128) * 128: patches[(f*g + gy)*g + gx, (c*patch + py)*patch + px] = the image value rounded once, columns 3 * patch^2 .. Kp - 1 zero
+ * (columns from Kp on are not touched) - the A matrix of the conv1 GEMM.
+ * Refused (RV_ERR_ARG, nothing launched): R % patch != 0, H or W outside 1 .. 8192, null frames, both outputs null, ldp < Kp, a layout other than 0 / 1,
+ * and a downscale whose filter taps do not fit a workgroup's LDS (beyond 8192 -> 224 territory).  n = 0 returns 0 and launches nothing. */
+int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t R,
+                         int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */
 int rv_project_dense(rv_ctx* ctx, const void* x_bf16, void* y, int out_dtype, int64_t rows, void* stream);

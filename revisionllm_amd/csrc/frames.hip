@@ -1,0 +1,311 @@
+// CLIP front end: decoded uint8 frames -> resize (antialiased bicubic) -> centre crop -> normalise -> patch matrix, one kernel (rv_frames_to_patches).
+// What the reference does with Resize(R, BICUBIC) / CenterCrop(R) / Normalize on the decoded tensor (inference.py:108-117) followed by the
+// conv1 unfold of VisualTransformer.forward (clip/model.py:223-226).  A bandwidth kernel: no MFMA, the source bytes of the cropped region are read once
+// per workgroup tile (neighbouring tiles overlap by the filter support and meet in L2).
+//
+// One workgroup owns TY x TX output pixels of one frame, all three channels:
+//   phase 0  the tile's tap tables (first tap, count, normalised f32 weights; computed in f64) for its TX columns and TY rows into LDS
+//   phase 1  per chunk of FR_SR source rows: stage the bytes the tile needs in LDS (16-byte loads where the address allows, single bytes at the
+//            ends of a row segment), then the horizontal pass into f32 LDS rows  inter[source row][channel][column]
+//   phase 2  vertical pass over inter, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
+// Tap counts depend on the geometry (4 * scale + 1 per axis): every tap loop is a runtime loop over LDS-resident weights.  The host picks TY / TX so that
+// a workgroup stays under FR_LDS_BUDGET bytes (two workgroups per CU) and refuses a geometry that does not fit with TY = TX = 1.
+#include <math.h>
+
+#include <atomic>
+
+#include "common.h"
+
+#pragma clang fp contract(off)   // host and device must place the taps identically; the tap loops ask for their fma by name
+
+namespace {
+
+constexpr int FR_THREADS = 256;
+constexpr int FR_SR = 16;                   // source rows staged per chunk
+constexpr int FR_LDS_BUDGET = 76 * 1024;    // per workgroup: two fit a CU's 160 KiB
+constexpr int FR_MAX_SIDE = 8192;
+
+// taps of output index i of an axis (torch's antialiased resampling, align_corners = False): [t0, t0 + nt)
+__host__ __device__ inline void fr_taps(double scale, int in, int i, int& t0, int& nt) {
+    const double support = scale >= 1.0 ? 2.0 * scale : 2.0;
+    const double centre = scale * (i + 0.5);
+    long long lo = (long long)(centre - support + 0.5), hi = (long long)(centre + support + 0.5);
+    if (lo < 0) lo = 0;
+    if (hi > in) hi = in;
+    t0 = (int)lo;
+    nt = hi > lo ? (int)(hi - lo) : 0;
+}
+
+// Keys' cubic, a = -0.5
+__device__ inline double fr_cubic(double x) {
+    x = fabs(x);
+    if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
+    if (x < 2.0) return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
+    return 0.0;
+}
+
+struct FrParams {
+    const uint8_t* src;
+    int64_t fstride, rstride, cstride;   // elements between frames, rows and channels (cstride: 1 for NHWC, frame_stride / 3 for NCHW)
+    int pix;                             // elements between neighbouring pixels of a row: 3 (NHWC) or 1 (NCHW)
+    int H, W, R, patch, g, K, Kp, top, left;
+    double sy, sx;                       // in / out per axis (out = the resized size, before the crop)
+    int TY, TX, tilesX, bands;
+    int NTX, NTXp, NTY, NR, SEGPX, SEG;  // tap capacities, rows of inter, pixels / bytes (16-byte multiple + 16) of a staged row segment
+    int o_wv, o_idx, o_inter, o_stage;   // LDS offsets (wh sits at 0)
+    float mean[3], den[3];
+    op16_t* patches;
+    int64_t ldp;
+    float* image;
+};
+
+__global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrParams p) {
+    extern __shared__ __attribute__((aligned(16))) char fr_smem[];
+    float* wh = (float*)fr_smem;                       // [TX][NTXp]
+    float* wv = (float*)(fr_smem + p.o_wv);            // [TY][NTY]
+    int* xmin = (int*)(fr_smem + p.o_idx);             // [TX], then nx [TX], ymin [TY], ny [TY]
+    int* nx = xmin + p.TX;
+    int* ymin = nx + p.TX;
+    int* ny = ymin + p.TY;
+    float* inter = (float*)(fr_smem + p.o_inter);      // [NR][3][TX]
+    uint8_t* stage = (uint8_t*)(fr_smem + p.o_stage);  // [planes][FR_SR][SEG]
+    const int tid = threadIdx.x;
+    uint32_t b = blockIdx.x;
+    const int tile = b % p.tilesX;
+    b /= p.tilesX;
+    const int band = b % p.bands;
+    const int64_t f = b / p.bands;
+    const int y0 = band * p.TY, x0 = tile * p.TX;
+    const int ty = min(p.TY, p.R - y0), tx = min(p.TX, p.R - x0);
+
+    // ---- phase 0: tap tables --------------------------------------------------------------------------------------------------
+    for (int i = tid; i < tx + ty; i += FR_THREADS) {
+        const bool isx = i < tx;
+        const int o = isx ? i : i - tx;
+        const double scale = isx ? p.sx : p.sy;
+        const int idx = isx ? x0 + o + p.left : y0 + o + p.top;
+        int t0, nt;
+        fr_taps(scale, isx ? p.W : p.H, idx, t0, nt);
+        nt = min(nt, isx ? p.NTX : p.NTY);
+        float* w = isx ? wh + o * p.NTXp : wv + o * p.NTY;
+        const double inv = scale >= 1.0 ? 1.0 / scale : 1.0, centre = scale * (idx + 0.5);
+        double tot = 0.0;
+        for (int t = 0; t < nt; ++t) tot += fr_cubic((t0 + t - centre + 0.5) * inv);
+        const double rt = tot != 0.0 ? 1.0 / tot : 1.0;
+        for (int t = 0; t < nt; ++t) w[t] = (float)(fr_cubic((t0 + t - centre + 0.5) * inv) * rt);
+        (isx ? xmin : ymin)[o] = t0;
+        (isx ? nx : ny)[o] = nt;
+    }
+    __syncthreads();
+    const int rmin = ymin[0], cmin = xmin[0];
+    const int nrows = min(ymin[ty - 1] + ny[ty - 1] - rmin, p.NR);
+    const int segpx = min(xmin[tx - 1] + nx[tx - 1] - cmin, p.SEGPX);
+    const int segbytes = segpx * p.pix;
+    const int planes = p.pix == 1 ? 3 : 1;
+    const int nck = p.SEG >> 4;
+    const uint8_t* fsrc = p.src + f * p.fstride + (int64_t)cmin * p.pix;
+
+    // ---- phase 1: stage source bytes, horizontal pass ---------------------------------------------------------------------------
+    for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
+        const int nr = min(FR_SR, nrows - r0);
+        __syncthreads();   // the previous chunk's readers are done with `stage`
+        for (int it = tid; it < nr * planes * nck; it += FR_THREADS) {
+            const int k = it % nck, rr = it / nck;
+            const int r = rr % nr, pl = rr / nr;
+            const uint8_t* gs = fsrc + pl * p.cstride + (int64_t)(rmin + r0 + r) * p.rstride;
+            const uint8_t* ge = gs + segbytes;
+            const uint8_t* gc = (const uint8_t*)((uintptr_t)gs & ~(uintptr_t)15) + 16 * k;   // the segment keeps its position inside a 16-byte line
+            uint8_t* d = stage + (pl * FR_SR + r) * p.SEG + 16 * k;
+            if (gc >= gs && gc + 16 <= ge) {
+                *(uint4*)d = *(const uint4*)gc;
+            } else if (gc + 16 > gs && gc < ge) {
+                for (int j = 0; j < 16; ++j)
+                    if (gc + j >= gs && gc + j < ge) d[j] = gc[j];
+            }
+        }
+        __syncthreads();
+        for (int it = tid; it < nr * tx; it += FR_THREADS) {
+            const int col = it % tx, r = it / tx;
+            const uint8_t* gs = fsrc + (int64_t)(rmin + r0 + r) * p.rstride;
+            const int xo = (xmin[col] - cmin) * p.pix;
+            const uint8_t *s0, *s1, *s2;
+            if (planes == 1) {
+                s0 = stage + r * p.SEG + (int)((uintptr_t)gs & 15) + xo;
+                s1 = s0 + 1;
+                s2 = s0 + 2;
+            } else {
+                s0 = stage + r * p.SEG + (int)((uintptr_t)gs & 15) + xo;
+                s1 = stage + (FR_SR + r) * p.SEG + (int)((uintptr_t)(gs + p.cstride) & 15) + xo;
+                s2 = stage + (2 * FR_SR + r) * p.SEG + (int)((uintptr_t)(gs + 2 * p.cstride) & 15) + xo;
+            }
+            const float* w = wh + col * p.NTXp;
+            const int n = min(nx[col], segpx - (xmin[col] - cmin));
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            for (int t = 0; t < n; ++t) {
+                const float wt = w[t];
+                const int o = t * p.pix;
+                a0 = fmaf(wt, (float)s0[o], a0);
+                a1 = fmaf(wt, (float)s1[o], a1);
+                a2 = fmaf(wt, (float)s2[o], a2);
+            }
+            float* q = inter + (r0 + r) * 3 * p.TX + col;
+            q[0] = a0;
+            q[p.TX] = a1;
+            q[2 * p.TX] = a2;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: vertical pass, normalise, store --------------------------------------------------------------------------------
+    for (int it = tid; it < ty * 3 * tx; it += FR_THREADS) {
+        const int col = it % tx, c = (it / tx) % 3, yy = it / (3 * tx);
+        const int rb = ymin[yy] - rmin;
+        const int n = min(ny[yy], nrows - rb);
+        const float* w = wv + yy * p.NTY;
+        const float* q = inter + (rb * 3 + c) * p.TX + col;
+        float acc = 0.f;
+        for (int t = 0; t < n; ++t) acc = fmaf(w[t], q[t * 3 * p.TX], acc);
+        const float v = (acc / 255.0f - (c == 0 ? p.mean[0] : c == 1 ? p.mean[1] : p.mean[2])) / (c == 0 ? p.den[0] : c == 1 ? p.den[1] : p.den[2]);
+        const int y = y0 + yy, x = x0 + col;
+        if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = v;
+        if (p.patches)
+            p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(v);
+    }
+    // pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile
+    if (p.patches && p.Kp > p.K) {
+        const int gy0 = (y0 + p.patch - 1) / p.patch, gy1 = (y0 + ty + p.patch - 1) / p.patch;
+        const int gx0 = (x0 + p.patch - 1) / p.patch, gx1 = (x0 + tx + p.patch - 1) / p.patch;
+        const int pad = p.Kp - p.K, ngx = gx1 - gx0;
+        for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
+            const int j = it % pad, pr = it / pad;
+            p.patches[((f * p.g + gy0 + pr / ngx) * p.g + gx0 + pr % ngx) * p.ldp + p.K + j] = 0;
+        }
+    }
+}
+
+// Largest tap count of an axis over the R cropped outputs.
+int fr_max_taps(double scale, int in, int first, int R) {
+    int cap = 0;
+    for (int o = 0; o < R; ++o) {
+        int lo, n;
+        fr_taps(scale, in, first + o, lo, n);
+        if (n > cap) cap = n;
+    }
+    return cap;
+}
+
+// Largest span of source rows / columns a tile of t outputs touches.
+int fr_max_span(double scale, int in, int first, int R, int t) {
+    int span = 0;
+    for (int o0 = 0; o0 < R; o0 += t) {
+        const int o1 = (o0 + t < R ? o0 + t : R) - 1;
+        int lo, n0, hi, n1;
+        fr_taps(scale, in, first + o0, lo, n0);
+        fr_taps(scale, in, first + o1, hi, n1);
+        if (hi + n1 - lo > span) span = hi + n1 - lo;
+    }
+    return span;
+}
+
+// Tile plan: capacities from the exact tap placement of the crop's rows and columns (the kernel clamps to them all the same); false = over the LDS budget.
+bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
+    p.TY = ty;
+    p.TX = tx;
+    p.tilesX = (p.R + tx - 1) / tx;
+    p.bands = (p.R + ty - 1) / ty;
+    p.NR = fr_max_span(p.sy, p.H, p.top, p.R, ty);
+    p.SEGPX = fr_max_span(p.sx, p.W, p.left, p.R, tx);
+    p.SEG = ((p.SEGPX * p.pix + 15) & ~15) + 16;
+    int64_t o = (int64_t)tx * p.NTXp * 4;
+    p.o_wv = (int)o;
+    o += (int64_t)ty * p.NTY * 4;
+    p.o_idx = (int)o;
+    o += (int64_t)(2 * tx + 2 * ty) * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_inter = (int)o;
+    o += (int64_t)p.NR * 3 * tx * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_stage = (int)o;
+    o += (int64_t)(p.pix == 1 ? 3 : 1) * FR_SR * p.SEG;
+    if (o > FR_LDS_BUDGET) return false;
+    // source rows the horizontal pass computes per output row, plus the (cheaper) bytes staged per output pixel
+    cost = (double)p.NR / ty * (3.0 + (double)p.SEGPX / (tx * (p.sx > 1.0 ? p.sx : 1.0)));
+    return true;
+}
+
+int fr_lds_bytes(const FrParams& p) { return p.o_stage + (p.pix == 1 ? 3 : 1) * FR_SR * p.SEG; }
+
+}  // namespace
+
+extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
+                                    int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image,
+                                    void* stream) {
+    RV_CHECK_ARG(layout == 0 || layout == 1, "rv_frames_to_patches: layout %d (0 = NCHW, 1 = NHWC)", layout);
+    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "rv_frames_to_patches: R = %d is not a multiple of patch = %d", R, patch);
+    RV_CHECK_ARG(H >= 1 && W >= 1 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "rv_frames_to_patches: frame size %d x %d outside 1 .. %d", H, W, FR_MAX_SIDE);
+    RV_CHECK_ARG(R <= FR_MAX_SIDE, "rv_frames_to_patches: R = %d above %d", R, FR_MAX_SIDE);
+    RV_CHECK_ARG(n >= 0, "rv_frames_to_patches: n = %d", n);
+    if (n == 0) return RV_OK;
+    RV_CHECK_ARG(frames, "rv_frames_to_patches: null frames");
+    RV_CHECK_ARG(patches || image, "rv_frames_to_patches: both outputs null");
+    RV_CHECK_ARG(mean && std, "rv_frames_to_patches: null mean / std");
+    FrParams p{};
+    p.K = 3 * patch * patch;
+    p.Kp = (p.K + 127) / 128 * 128;
+    RV_CHECK_ARG(!patches || ldp >= p.Kp, "rv_frames_to_patches: ldp = %lld below Kp = %d", (long long)ldp, p.Kp);
+    RV_CHECK_ARG(layout == 1 || frame_stride % 3 == 0, "rv_frames_to_patches: NCHW channel planes lie frame_stride / 3 apart; frame_stride = %lld", (long long)frame_stride);
+    p.src = frames;
+    p.fstride = frame_stride;
+    p.rstride = row_stride;
+    p.cstride = layout == 1 ? 1 : frame_stride / 3;
+    p.pix = layout == 1 ? 3 : 1;
+    p.H = H;
+    p.W = W;
+    p.R = R;
+    p.patch = patch;
+    p.g = R / patch;
+    // Resize(R): shorter side -> R, longer side -> int(R * long / short); CenterCrop(R): offset round-half-even((size - R) / 2)
+    const int hr = H <= W ? R : (int)((int64_t)R * H / W), wr = H <= W ? (int)((int64_t)R * W / H) : R;
+    p.sy = (double)H / hr;
+    p.sx = (double)W / wr;
+    p.top = (int)nearbyint((hr - R) / 2.0);
+    p.left = (int)nearbyint((wr - R) / 2.0);
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean[c];
+        p.den[c] = std[c] + 1e-8f;
+    }
+    p.patches = (op16_t*)patches;
+    p.ldp = ldp;
+    p.image = image;
+    p.NTX = fr_max_taps(p.sx, W, p.left, R);
+    p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
+    p.NTY = fr_max_taps(p.sy, H, p.top, R);
+    FrParams best{};
+    double best_cost = 0.0;
+    bool have = false;
+    for (int ty = 16; ty >= 1; ty >>= 1)
+        for (int tx = 256; tx >= 1; tx >>= 1) {
+            const int tyc = ty < R ? ty : R, txc = tx < R ? tx : R;
+            double cost;
+            FrParams q = p;
+            if (fr_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
+        }
+    RV_CHECK_ARG(have, "rv_frames_to_patches: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", H, W, R);
+    const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
+    RV_CHECK_ARG(wgs < (1ll << 31), "rv_frames_to_patches: %lld workgroups (n = %d) exceed one launch", (long long)wgs, n);
+    const int lds = fr_lds_bytes(best);
+    static std::atomic<uint64_t> have_lds{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {   // the dynamic-LDS opt-in is a per-device attribute of the function
+        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+            rv_set_error("rv_frames_to_patches: cannot reserve %d bytes of LDS", FR_LDS_BUDGET);
+            return RV_ERR_HIP;
+        }
+        have_lds.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(frames_to_patches_kernel, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), best);
+    RV_CHECK_LAUNCH("frames_to_patches");
+    return RV_OK;
+}

@@ -1,18 +1,19 @@
 """Frame / query feature extraction with the CLIP towers - mirror of ``ClipFeatureExtractor``
 (revisionllm/data/feature_extraction/clip_extractor.py:13-54) on the HIP kernels.
 
-Differences from the reference, all at the IO edge: frames are handed over as a tensor [T,3,H,W] (what its ``VideoLoader``
-produces from ffmpeg; video decoding is not part of this build) and the CLIP weights come from ``ClipTowers`` (a loaded
-checkpoint or synthetic).  The on-disk format of the results is what ``data.feature_store`` reads back (f-2).
+Differences from the reference, all at the IO edge: frames are handed over as tensors (video decoding is not part of this
+build) - either already at the towers' resolution [T,3,R,R] (what its ``VideoLoader`` produces from ffmpeg's scale + crop), or as
+decoded uint8 frames of any size, NCHW or NHWC, in one tensor or in chunks: those are resized, centre-cropped, normalised and
+unfolded on the device by one kernel (``ops.frames_to_patches``; the reference's Resize / CenterCrop / Normalize,
+inference.py:108-117).  The CLIP weights come from ``ClipTowers`` (a loaded checkpoint or synthetic).  The on-disk format of the results is what ``data.feature_store`` reads back (f-2).
 """
 import math
 
 import torch
 
+from .. import ops
+from ..ops import CLIP_MEAN, CLIP_STD  # noqa: F401  (the constants' home is next to the kernel wrapper that defaults to them)
 from .clip_model import ClipTowers
-
-CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
-CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def preprocess(frames):
@@ -30,11 +31,42 @@ class ClipFeatureExtractor:
         self.device = towers.device
 
     @torch.no_grad()
-    def encode_video(self, frames, bsz=60):
-        """frames [T,3,H,W] (0..255) -> f32 [T, d]: batches of ``bsz`` frames through ``encode_image`` (clip_extractor.py:22-37)."""
-        x = preprocess(frames)
-        out = [self.clip_extractor.encode_image(x[i * bsz:(i + 1) * bsz]) for i in range(int(math.ceil(len(x) / bsz)))]
-        return torch.cat(out, 0) if out else torch.empty(0, self.clip_extractor.cfg["embed_dim"], device=self.device)
+    def encode_video(self, frames, bsz=60, layout=None):
+        """-> f32 [T, d], ``bsz`` frames at a time (clip_extractor.py:22-37).  ``frames``: a tensor [T,3,R,R] (0..255, float or uint8) at the towers'
+        resolution R - normalised here and handed to ``encode_image`` -, or DECODED uint8 frames of any size, [T,3,H,W] or [T,H,W,3] (``layout``
+        "NCHW" / "NHWC" where the shape leaves it open), as one tensor or as an iterable of such chunks (what a decoder hands over): those go through
+        ``encode_frames``, so no float copy at the source resolution ever exists."""
+        tw, R = self.clip_extractor, self.clip_extractor.cfg["image_res"]
+        if torch.is_tensor(frames):
+            native = frames.dim() == 4 and tuple(frames.shape[1:]) == (3, R, R) and layout in (None, "NCHW")
+            if native or frames.dtype != torch.uint8:
+                if not native:
+                    raise ValueError(f"float frames must be [T,3,{R},{R}] (got {tuple(frames.shape)}): frames of another size or layout are taken as "
+                                     "decoded uint8 frames")
+                x = preprocess(frames)
+                out = [tw.encode_image(x[i * bsz:(i + 1) * bsz]) for i in range(int(math.ceil(len(x) / bsz)))]
+                return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+            frames = (frames,)
+        out = [tw.encode_frames(b, layout=layout) for b in self._batches(frames, bsz)]
+        return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+
+    def _batches(self, chunks, bsz):
+        """Decoded uint8 chunks of any lengths -> device batches of exactly ``bsz`` frames (the last one shorter): the batching does not depend on
+        how the decoder cut the video."""
+        held, n = [], 0
+        for c in chunks:
+            if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 4:
+                raise ValueError("decoded frames come as uint8 tensors [t,3,H,W] or [t,H,W,3]")
+            c = ops.h2d(c, self.device)
+            while len(c):
+                take = c[:bsz - n]
+                held.append(take)
+                n, c = n + len(take), c[len(take):]
+                if n == bsz:
+                    yield held[0] if len(held) == 1 else torch.cat(held, 0)
+                    held, n = [], 0
+        if n:
+            yield held[0] if len(held) == 1 else torch.cat(held, 0)
 
     @torch.no_grad()
     def encode_text(self, text_list, bsz=60, tokens=None):

@@ -3,8 +3,9 @@
 What the reference's feature extractors run upstream of the grounding path (``clip.load("ViT-L/14")`` ->
 ``encode_image`` / ``encode_text``; data/feature_extraction/clip_extractor.py:13-54, clip/model.py:223-242, 339-352).
 Every matrix product, LayerNorm and attention goes through the C ABI (``rv_gemm`` with fused bias / QuickGELU / residual
-epilogues, ``rv_layernorm``, ``rv_attention`` with 64-wide heads); torch only moves rows around (patch unfold, class
-token concat, embedding gather).  Residual stream f32, GEMM inputs bf16, weights fragment-packed bf16 - as in the engine.
+epilogues, ``rv_layernorm``, ``rv_attention`` with 64-wide heads; ``rv_frames_to_patches`` in front of them for decoded uint8
+frames); torch only moves rows around (patch unfold of float frames, class token concat, embedding gather).  Residual stream
+f32, GEMM inputs bf16, weights fragment-packed bf16 - as in the engine.
 State-dict names are the checkpoint's own (``visual.conv1.weight``, ``transformer.resblocks.3.mlp.c_fc.weight``, ...).
 """
 import torch
@@ -81,15 +82,29 @@ class ClipTowers:
     @torch.no_grad()
     def encode_image(self, img):
         """img [n,3,R,R] (normalised, any float dtype) -> f32 [n, embed_dim]   (VisualTransformer.forward)."""
-        c, w = self.cfg, self.w
-        n, p, W = img.shape[0], c["patch"], c["v_width"]
+        c = self.cfg
+        n, p = img.shape[0], c["patch"]
         g = c["image_res"] // p
         if tuple(img.shape[1:]) != (3, c["image_res"], c["image_res"]):
             raise ValueError(f"expected [n,3,{c['image_res']},{c['image_res']}] frames, got {tuple(img.shape)}")
         x = img.to(self.device, torch.float32)
         # stride = kernel convolution == GEMM over unfolded patches: rows (frame, gy, gx), columns (channel, py, px)
         patches = x.view(n, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(n * g * g, 3 * p * p)
-        tokens = ops.gemm(_pad_k(patches).to(self.op_dtype), w["visual.conv1.weight"], out_dtype=torch.float32, w_packed=True)
+        return self._encode_patches(_pad_k(patches).to(self.op_dtype), n)
+
+    @torch.no_grad()
+    def encode_frames(self, frames_u8, layout=None):
+        """Decoded uint8 frames [n,3,H,W] / [n,H,W,3] of any size (on the device) -> f32 [n, embed_dim]: resize, centre crop, normalise and unfold in one
+        kernel (``ops.frames_to_patches``: the reference's Resize / CenterCrop / Normalize, inference.py:108-117), then what ``encode_image`` runs."""
+        c = self.cfg
+        patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype)
+        return self._encode_patches(patches, frames_u8.shape[0])
+
+    def _encode_patches(self, patches, n):
+        """patches [n*g*g, Kp] operand type (the unfolded, K-padded frames) -> f32 [n, embed_dim]: conv1 as a GEMM and everything behind it."""
+        c, w = self.cfg, self.w
+        W, g = c["v_width"], c["image_res"] // c["patch"]
+        tokens = ops.gemm(patches, w["visual.conv1.weight"], out_dtype=torch.float32, w_packed=True)
         L = g * g + 1
         x = torch.cat([w["visual.class_embedding"].expand(n, 1, W), tokens.view(n, g * g, W)], 1) + w["visual.positional_embedding"]
         x, _, _ = ops.layernorm(x.view(n * L, W).contiguous(), w["visual.ln_pre.weight"], w["visual.ln_pre.bias"], want=("f32",), op_dtype=self.op_dtype)

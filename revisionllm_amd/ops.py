@@ -239,6 +239,50 @@ def attention(q, k, v, causal=False, key_pad=None, q_pos0=0, scale=None):
     return out
 
 
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+_LAYOUTS = {"NCHW": 0, "NHWC": 1}
+
+
+def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",)):
+    """Decoded uint8 frames -> the CLIP front end in one launch (rv_frames_to_patches): Resize(R, antialiased bicubic) / CenterCrop(R) /
+    (x / 255 - mean) / (std + 1e-8), then -> (patches, image): ``patches`` [n*g*g, Kp] of the operand type (the conv1 GEMM's A matrix: rows (frame, gy, gx),
+    columns (channel, py, px), zero-padded from 3 * patch^2 to a multiple of 128), ``image`` f32 [n,3,R,R]; the one ``want`` does not name is None.
+    frames: uint8 device tensor [n,3,H,W] ("NCHW") or [n,H,W,3] ("NHWC"); ``layout`` is inferred when only one reading fits.  A window of a larger buffer
+    is passed by its strides (pixels of a row adjacent, NCHW channel planes a third of the frame stride apart); any other view is copied first."""
+    if not torch.is_tensor(frames) or not frames.is_cuda:
+        raise hip.HipLibraryError("frames_to_patches needs a device tensor (got a CPU tensor); there is no CPU path")
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise hip.HipLibraryError(f"frames_to_patches takes uint8 frames [n,3,H,W] or [n,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+    nchw, nhwc = frames.shape[1] == 3, frames.shape[3] == 3
+    if layout is None:
+        if nchw == nhwc:
+            raise ValueError(f"frames of shape {tuple(frames.shape)} read as " + ("NCHW and as NHWC: pass layout=" if nchw else "neither NCHW nor NHWC"))
+        layout = "NCHW" if nchw else "NHWC"
+    if layout not in _LAYOUTS or not (nchw if layout == "NCHW" else nhwc):
+        raise ValueError(f"layout {layout!r} does not fit frames of shape {tuple(frames.shape)}")
+    n = frames.shape[0]
+    if layout == "NCHW":
+        H, W = frames.shape[2], frames.shape[3]
+        ok = frames.stride(3) == 1 and frames.stride(2) >= W and frames.stride(1) > 0 and (n <= 1 or frames.stride(0) == 3 * frames.stride(1))
+        frames = frames if ok else frames.contiguous()
+        fs, rs = 3 * frames.stride(1), frames.stride(2)
+    else:
+        H, W = frames.shape[1], frames.shape[2]
+        ok = frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) >= 3 * W and (n <= 1 or frames.stride(0) > 0)
+        frames = frames if ok else frames.contiguous()
+        fs, rs = (frames.stride(0) if n > 1 else frames.stride(1) * H), frames.stride(1)
+    dt = hip.op_dtype(op_dtype)
+    g = R // max(patch, 1)
+    kp = (3 * patch * patch + 127) // 128 * 128
+    patches = torch.empty(n * g * g, kp, dtype=dt, device=frames.device) if "patches" in want else None
+    image = torch.empty(n, 3, R, R, dtype=torch.float32, device=frames.device) if "image" in want else None
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_frames_to_patches(hip.ptr(frames), _LAYOUTS[layout], fs, rs, n, H, W, R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
+                                               hip.ptr(image), hip.stream()), "rv_frames_to_patches")
+    return patches, image
+
+
 def h2d(t, device, dtype=None):
     """Host -> device without stalling the host: a pageable ``.to(device)`` blocks until everything queued before it has
     run (the launch queue then runs dry after every upload); a pinned, non-blocking copy just joins the stream."""
