@@ -260,6 +260,32 @@ int rv_attention(const void* q, int64_t q_row_stride, int64_t q_batch_stride, co
 int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t R,
                          int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
 
+/* The same front end on the bytes a video decoder hands over: 8-bit 4:2:0 YCbCr (NV12 / NV21 / I420 surfaces).  No RGB frame exists anywhere: the kernel
+ * resamples Y at full and Cb / Cr at half resolution and applies the colour matrix once per output pixel (resampling is linear, the conversion affine).
+ * y: u8 [n,H,W]; cb, cr: u8 planes of H/2 x W/2 samples, neighbouring samples of one plane c_pix bytes apart: c_pix = 1 planar (I420: two planes), c_pix = 2
+ * interleaved (NV12: cr == cb + 1; NV21: cb == cr + 1).  All strides in BYTES (cb and cr share theirs), so a window of a larger decode surface with a padded
+ * pitch is passed as it lies (INTEGRATION.md has the pointer arithmetic).  matrix: 0 = BT.601 (Kr 0.299, Kb 0.114), 1 = BT.709 (Kr 0.2126, Kb 0.0722);
+ * full_range: 0 = studio, 1 = full; chroma_loc: 0 = left (MPEG-2 / H.264 default), 1 = centre (JPEG / MPEG-1).  mean / std / patches / ldp / image / R /
+ * patch: as in rv_frames_to_patches.
+ * Values (f32 throughout, no clamp, no u8 or RGB intermediate); i = an output index of the RESIZED image, scale = in / out per axis, the resized size and the
+ * crop offsets are rv_frames_to_patches' own:
+ *   luma     Y' = rv_frames_to_patches' resampling of the Y plane (the same taps, the same normalised f32 weights computed in f64)
+ *   chroma   Cb', Cr' = the same filter in chroma-plane coordinates: in_c = in / 2, scale_c = scale / 2, centre_c = scale * (i + 0.5) / 2 + off, off = 0.25 on
+ *            the horizontal axis when chroma_loc = 0, else 0 (both sitings are vertically centred); support_c = 2 * max(scale_c, 1), taps
+ *            [max(0, int(centre_c - support_c + 0.5)), min(in_c, int(centre_c + support_c + 0.5))), weight cubic((j - centre_c + 0.5) / max(scale_c, 1)) /
+ *            (sum over the taps).  A source below 2R per axis has scale_c < 1: chroma is then interpolated.
+ *   colour   studio range: yl = (Y' - 16) * 255/219, c = (C' - 128) * 255/224; full range: yl = Y', c = C' - 128;  Kg = 1 - Kr - Kb;
+ *            Rv = yl + 2(1-Kr) cr,  Bv = yl + 2(1-Kb) cb,  Gv = yl - (2Kb(1-Kb)/Kg) cb - (2Kr(1-Kr)/Kg) cr;  coefficients computed in f64, rounded once to f32
+ *   norm     (v / 255 - mean[c]) / (std[c] + 1e-8); image and patches laid out, rounded once and zero-padded exactly as by rv_frames_to_patches
+ * This is the library's OWN definition - the chroma planes are resampled directly, which is linear and exact.  It is NOT swscale's integer conversion to rgb24
+ * followed by a resize; no parity with ffmpeg's RGB bytes is claimed.
+ * Refused (RV_ERR_ARG, nothing launched): odd H or W, H or W outside 2 .. 8192, c_pix outside {1, 2} (or c_pix = 2 with planes that are not one byte apart),
+ * matrix / full_range / chroma_loc outside {0, 1}, a null plane, R % patch != 0, both outputs null, ldp < Kp, a geometry whose tap tables and staging do not
+ * fit a workgroup's LDS, more workgroups than one launch holds.  n = 0 returns 0 and launches nothing. */
+int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_stride, const uint8_t* cb, const uint8_t* cr, int64_t c_frame_stride,
+                      int64_t c_row_stride, int32_t c_pix, int32_t n, int32_t H, int32_t W, int32_t matrix, int32_t full_range, int32_t chroma_loc,
+                      int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */
 int rv_project_dense(rv_ctx* ctx, const void* x_bf16, void* y, int out_dtype, int64_t rows, void* stream);

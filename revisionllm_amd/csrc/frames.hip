@@ -10,39 +10,11 @@
 //   phase 2  vertical pass over inter, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
 // Tap counts depend on the geometry (4 * scale + 1 per axis): every tap loop is a runtime loop over LDS-resident weights.  The host picks TY / TX so that
 // a workgroup stays under FR_LDS_BUDGET bytes (two workgroups per CU) and refuses a geometry that does not fit with TY = TX = 1.
-#include <math.h>
-
 #include <atomic>
 
-#include "common.h"
-
-#pragma clang fp contract(off)   // host and device must place the taps identically; the tap loops ask for their fma by name
+#include "frames_taps.h"   // the tap definition, FR_* constants and capacity helpers (shared with frames_yuv.hip); fp contraction is off from there on
 
 namespace {
-
-constexpr int FR_THREADS = 256;
-constexpr int FR_SR = 16;                   // source rows staged per chunk
-constexpr int FR_LDS_BUDGET = 76 * 1024;    // per workgroup: two fit a CU's 160 KiB
-constexpr int FR_MAX_SIDE = 8192;
-
-// taps of output index i of an axis (torch's antialiased resampling, align_corners = False): [t0, t0 + nt)
-__host__ __device__ inline void fr_taps(double scale, int in, int i, int& t0, int& nt) {
-    const double support = scale >= 1.0 ? 2.0 * scale : 2.0;
-    const double centre = scale * (i + 0.5);
-    long long lo = (long long)(centre - support + 0.5), hi = (long long)(centre + support + 0.5);
-    if (lo < 0) lo = 0;
-    if (hi > in) hi = in;
-    t0 = (int)lo;
-    nt = hi > lo ? (int)(hi - lo) : 0;
-}
-
-// Keys' cubic, a = -0.5
-__device__ inline double fr_cubic(double x) {
-    x = fabs(x);
-    if (x < 1.0) return (1.5 * x - 2.5) * x * x + 1.0;
-    if (x < 2.0) return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
-    return 0.0;
-}
 
 struct FrParams {
     const uint8_t* src;
@@ -183,38 +155,14 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrP
     }
 }
 
-// Largest tap count of an axis over the R cropped outputs.
-int fr_max_taps(double scale, int in, int first, int R) {
-    int cap = 0;
-    for (int o = 0; o < R; ++o) {
-        int lo, n;
-        fr_taps(scale, in, first + o, lo, n);
-        if (n > cap) cap = n;
-    }
-    return cap;
-}
-
-// Largest span of source rows / columns a tile of t outputs touches.
-int fr_max_span(double scale, int in, int first, int R, int t) {
-    int span = 0;
-    for (int o0 = 0; o0 < R; o0 += t) {
-        const int o1 = (o0 + t < R ? o0 + t : R) - 1;
-        int lo, n0, hi, n1;
-        fr_taps(scale, in, first + o0, lo, n0);
-        fr_taps(scale, in, first + o1, hi, n1);
-        if (hi + n1 - lo > span) span = hi + n1 - lo;
-    }
-    return span;
-}
-
 // Tile plan: capacities from the exact tap placement of the crop's rows and columns (the kernel clamps to them all the same); false = over the LDS budget.
 bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
     p.TY = ty;
     p.TX = tx;
     p.tilesX = (p.R + tx - 1) / tx;
     p.bands = (p.R + ty - 1) / ty;
-    p.NR = fr_max_span(p.sy, p.H, p.top, p.R, ty);
-    p.SEGPX = fr_max_span(p.sx, p.W, p.left, p.R, tx);
+    p.NR = fr_max_span(FrAxis{p.sy, 1.0, 0.0, p.H}, p.top, p.R, ty);
+    p.SEGPX = fr_max_span(FrAxis{p.sx, 1.0, 0.0, p.W}, p.left, p.R, tx);
     p.SEG = ((p.SEGPX * p.pix + 15) & ~15) + 16;
     int64_t o = (int64_t)tx * p.NTXp * 4;
     p.o_wv = (int)o;
@@ -277,9 +225,9 @@ extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t f
     p.patches = (op16_t*)patches;
     p.ldp = ldp;
     p.image = image;
-    p.NTX = fr_max_taps(p.sx, W, p.left, R);
+    p.NTX = fr_max_taps(FrAxis{p.sx, 1.0, 0.0, W}, p.left, R);
     p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
-    p.NTY = fr_max_taps(p.sy, H, p.top, R);
+    p.NTY = fr_max_taps(FrAxis{p.sy, 1.0, 0.0, H}, p.top, R);
     FrParams best{};
     double best_cost = 0.0;
     bool have = false;

@@ -1,0 +1,373 @@
+// CLIP front end on the bytes a video decoder hands over: 4:2:0 YCbCr planes (NV12 / NV21 / I420 surfaces) -> resize (antialiased bicubic) -> YCbCr -> RGB ->
+// centre crop -> normalise -> patch matrix, one kernel (rv_yuv_to_patches).  No RGB frame exists anywhere: resampling is linear and the colour conversion
+// affine, so the kernel filters Y at full and Cb / Cr at half resolution and applies the colour matrix once per OUTPUT pixel.
+//
+// Values (f32 throughout, no clamp, no u8 intermediate); i = an output index of the RESIZED image (before the crop), scale = in / out per axis, the resized
+// size and the crop offsets are rv_frames_to_patches' own:
+//   luma     Y' = rv_frames_to_patches' resampling of the Y plane: the same taps, the same normalised f32 weights (computed in f64)
+//   chroma   Cb', Cr' = the same filter in chroma-plane coordinates: in_c = in / 2, scale_c = scale / 2, centre_c = scale * (i + 0.5) / 2 + off with
+//            off = 0.25 on the horizontal axis for chroma_loc 0 (left: MPEG-2 / H.264), else 0 (both sitings are vertically centred);
+//            support_c = 2 * max(scale_c, 1), taps [max(0, int(centre_c - support_c + 0.5)), min(in_c, int(centre_c + support_c + 0.5))), weight
+//            cubic((j - centre_c + 0.5) / max(scale_c, 1)) / (sum over the taps).  scale_c < 1 (a source below 2R per axis) interpolates chroma.
+//   colour   Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709), Kg = 1 - Kr - Kb;
+//            studio range: yl = (Y' - 16) * 255 / 219, c = (C' - 128) * 255 / 224; full range: yl = Y', c = C' - 128;
+//            Rv = yl + 2 (1 - Kr) cr,  Bv = yl + 2 (1 - Kb) cb,  Gv = yl - (2 Kb (1 - Kb) / Kg) cb - (2 Kr (1 - Kr) / Kg) cr;
+//            the five coefficients (255 / 219 and the four chroma factors with 255 / 224 folded in) are computed on the host in f64 and rounded once to f32
+//   norm     (v / 255 - mean[c]) / (std[c] + 1e-8); image and patches laid out, rounded and zero-padded as by rv_frames_to_patches
+// This is the project's OWN definition: the chroma planes are resampled directly, which is linear and exact.  It is NOT swscale's integer conversion to
+// rgb24 followed by a resize, and no parity with ffmpeg's RGB bytes is claimed.
+//
+// The kernel follows frames_to_patches_kernel.  One workgroup owns TY x TX output pixels of one frame:
+//   phase 0  four tap tables (luma x / y, chroma x / y: first tap, count, normalised f32 weights; computed in f64) into LDS
+//   phase 1  per chunk of FR_SR source rows, first of the Y plane, then of the chroma planes: stage the bytes the tile needs in LDS (16-byte loads where the
+//            address allows, single bytes at the ends of a row segment; an interleaved chroma segment holds both planes), then the horizontal pass into
+//            f32 LDS rows  interY[source row][column],  interC[chroma row][Cb | Cr][column]
+//   phase 2  vertical pass over both, colour matrix, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
+// Half the horizontal-pass work of three RGB planes (one full plane + two quarter planes filtered with half the taps), and two thirds of its `inter` rows.
+#include <atomic>
+
+#include "frames_taps.h"   // fp contraction is off from there on
+
+namespace {
+
+struct FyParams {
+    const uint8_t *y, *c;                 // c: the Cb plane (planar) or the lower of the two interleaved planes
+    int64_t yfs, yrs, cfs, crs, cdelta;   // bytes between frames / rows of the Y and the chroma planes; cdelta: Cr plane - Cb plane (planar)
+    int cpix, ocb, ocr;                   // bytes between neighbouring samples of a chroma plane; offsets of Cb / Cr inside an interleaved pair (planar: 0)
+    int R, patch, g, K, Kp, top, left;
+    FrAxis ax, ay, cx, cy;                // luma and chroma axes
+    int TY, TX, tilesX, bands;
+    int NTX, NTXp, NTY, NCX, NCXp, NCY;   // tap capacities (x rows padded to an odd pitch)
+    int NRY, NRC, SPY, SPC, SEGY, SEGC;   // rows of interY / interC, samples / bytes (16-byte multiple + 16) of a staged luma / chroma row segment
+    int o_wy, o_cwx, o_cwy, o_idx, o_iy, o_ic, o_stage;   // LDS offsets (the luma x weights sit at 0)
+    float yoff, ky, krcr, kgcb, kgcr, kbcb;
+    float mean[3], den[3];
+    op16_t* patches;
+    int64_t ldp;
+    float* image;
+};
+
+// Entry o of the tile's tap table of one axis (output index first + o): first tap, count (clamped to the host's capacity) and normalised f32 weights.
+__device__ inline void fy_tap_table(const FrAxis& a, int first, int cap, int pitch, float* w, int* t0s, int* nts, int o) {
+    const double fscale = a.scale / a.div, centre = fr_axis_centre(a, first + o);
+    int t0, nt;
+    fr_taps_at(centre, fscale, a.in, t0, nt);
+    nt = min(nt, cap);
+    const double inv = fscale >= 1.0 ? 1.0 / fscale : 1.0;
+    double tot = 0.0;
+    for (int t = 0; t < nt; ++t) tot += fr_cubic((t0 + t - centre + 0.5) * inv);
+    const double rt = tot != 0.0 ? 1.0 / tot : 1.0;
+    for (int t = 0; t < nt; ++t) w[o * pitch + t] = (float)(fr_cubic((t0 + t - centre + 0.5) * inv) * rt);
+    t0s[o] = t0;
+    nts[o] = nt;
+}
+
+// Stage `nr` rows of `planes` planes: the `segbytes` bytes from `g0` on (row r of plane pl: g0 + pl * pdelta + r * rstride) into stage[(pl * FR_SR + r) * SEG ..],
+// each segment keeping its position inside a 16-byte line.  Reads [segment start, segment end) and nothing else.
+__device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelta, int64_t rstride, int planes, int nr, int segbytes, int SEG, int tid) {
+    const int nck = SEG >> 4;
+    for (int it = tid; it < nr * planes * nck; it += FR_THREADS) {
+        const int k = it % nck, rr = it / nck;
+        const int r = rr % nr, pl = rr / nr;
+        const uint8_t* gs = g0 + pl * pdelta + (int64_t)r * rstride;
+        const uint8_t* ge = gs + segbytes;
+        const uint8_t* gc = (const uint8_t*)((uintptr_t)gs & ~(uintptr_t)15) + 16 * k;
+        uint8_t* d = stage + (pl * FR_SR + r) * SEG + 16 * k;
+        if (gc >= gs && gc + 16 <= ge) {
+            *(uint4*)d = *(const uint4*)gc;
+        } else if (gc + 16 > gs && gc < ge) {
+            for (int j = 0; j < 16; ++j)
+                if (gc + j >= gs && gc + j < ge) d[j] = gc[j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyParams p) {
+    extern __shared__ __attribute__((aligned(16))) char fy_smem[];
+    float* wx = (float*)fy_smem;                       // [TX][NTXp]
+    float* wy = (float*)(fy_smem + p.o_wy);            // [TY][NTY]
+    float* cwx = (float*)(fy_smem + p.o_cwx);          // [TX][NCXp]
+    float* cwy = (float*)(fy_smem + p.o_cwy);          // [TY][NCY]
+    int* xmin = (int*)(fy_smem + p.o_idx);             // [TX], then nx, cxmin, cnx [TX], ymin, ny, cymin, cny [TY]
+    int* nx = xmin + p.TX;
+    int* cxmin = nx + p.TX;
+    int* cnx = cxmin + p.TX;
+    int* ymin = cnx + p.TX;
+    int* ny = ymin + p.TY;
+    int* cymin = ny + p.TY;
+    int* cny = cymin + p.TY;
+    float* iy = (float*)(fy_smem + p.o_iy);            // [NRY][TX]
+    float* ic = (float*)(fy_smem + p.o_ic);            // [NRC][2][TX]
+    uint8_t* stage = (uint8_t*)(fy_smem + p.o_stage);  // [planes][FR_SR][SEG]
+    const int tid = threadIdx.x;
+    uint32_t b = blockIdx.x;
+    const int tile = b % p.tilesX;
+    b /= p.tilesX;
+    const int band = b % p.bands;
+    const int64_t f = b / p.bands;
+    const int y0 = band * p.TY, x0 = tile * p.TX;
+    const int ty = min(p.TY, p.R - y0), tx = min(p.TX, p.R - x0);
+
+    // ---- phase 0: tap tables --------------------------------------------------------------------------------------------------
+    for (int i = tid; i < 2 * (tx + ty); i += FR_THREADS) {
+        if (i < tx) fy_tap_table(p.ax, x0 + p.left, p.NTX, p.NTXp, wx, xmin, nx, i);
+        else if (i < 2 * tx) fy_tap_table(p.cx, x0 + p.left, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
+        else if (i < 2 * tx + ty) fy_tap_table(p.ay, y0 + p.top, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
+        else fy_tap_table(p.cy, y0 + p.top, p.NCY, p.NCY, cwy, cymin, cny, i - 2 * tx - ty);
+    }
+    __syncthreads();
+
+    // ---- phase 1a: luma - stage source bytes, horizontal pass ---------------------------------------------------------------------
+    const int rmin = ymin[0], cmin = xmin[0];
+    const int nrows = min(ymin[ty - 1] + ny[ty - 1] - rmin, p.NRY);
+    const int segpx = min(xmin[tx - 1] + nx[tx - 1] - cmin, p.SPY);
+    const uint8_t* ysrc = p.y + f * p.yfs + (int64_t)rmin * p.yrs + cmin;
+    for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
+        const int nr = min(FR_SR, nrows - r0);
+        const uint8_t* g0 = ysrc + (int64_t)r0 * p.yrs;
+        __syncthreads();   // the previous chunk's readers are done with `stage`
+        fy_stage(stage, g0, 0, p.yrs, 1, nr, segpx, p.SEGY, tid);
+        __syncthreads();
+        for (int it = tid; it < nr * tx; it += FR_THREADS) {
+            const int col = it % tx, r = it / tx;
+            const int xo = xmin[col] - cmin;
+            const uint8_t* s = stage + r * p.SEGY + (int)((uintptr_t)(g0 + (int64_t)r * p.yrs) & 15) + xo;
+            const float* w = wx + col * p.NTXp;
+            const int n = min(nx[col], segpx - xo);
+            float a = 0.f;
+            for (int t = 0; t < n; ++t) a = fmaf(w[t], (float)s[t], a);
+            iy[(r0 + r) * p.TX + col] = a;
+        }
+    }
+
+    // ---- phase 1b: chroma ----------------------------------------------------------------------------------------------------------
+    const int crmin = cymin[0], ccmin = cxmin[0];
+    const int cnrows = min(cymin[ty - 1] + cny[ty - 1] - crmin, p.NRC);
+    const int csegpx = min(cxmin[tx - 1] + cnx[tx - 1] - ccmin, p.SPC);
+    const int cplanes = p.cpix == 1 ? 2 : 1;
+    const uint8_t* csrc = p.c + f * p.cfs + (int64_t)crmin * p.crs + (int64_t)ccmin * p.cpix;
+    for (int r0 = 0; r0 < cnrows; r0 += FR_SR) {
+        const int nr = min(FR_SR, cnrows - r0);
+        const uint8_t* g0 = csrc + (int64_t)r0 * p.crs;
+        __syncthreads();
+        fy_stage(stage, g0, p.cdelta, p.crs, cplanes, nr, csegpx * p.cpix, p.SEGC, tid);
+        __syncthreads();
+        for (int it = tid; it < nr * tx; it += FR_THREADS) {
+            const int col = it % tx, r = it / tx;
+            const int xo = cxmin[col] - ccmin;
+            const uint8_t* gs = g0 + (int64_t)r * p.crs;
+            const uint8_t *sb, *sr;
+            if (cplanes == 1) {
+                sb = stage + r * p.SEGC + (int)((uintptr_t)gs & 15) + xo * 2 + p.ocb;
+                sr = sb - p.ocb + p.ocr;
+            } else {
+                sb = stage + r * p.SEGC + (int)((uintptr_t)gs & 15) + xo;
+                sr = stage + (FR_SR + r) * p.SEGC + (int)((uintptr_t)(gs + p.cdelta) & 15) + xo;
+            }
+            const float* w = cwx + col * p.NCXp;
+            const int n = min(cnx[col], csegpx - xo);
+            float a0 = 0.f, a1 = 0.f;
+            for (int t = 0; t < n; ++t) {
+                const float wt = w[t];
+                const int o = t * p.cpix;
+                a0 = fmaf(wt, (float)sb[o], a0);
+                a1 = fmaf(wt, (float)sr[o], a1);
+            }
+            float* q = ic + (r0 + r) * 2 * p.TX + col;
+            q[0] = a0;
+            q[p.TX] = a1;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: vertical pass, colour matrix, normalise, store -----------------------------------------------------------------------
+    for (int it = tid; it < ty * tx; it += FR_THREADS) {
+        const int col = it % tx, yy = it / tx;
+        float yv = 0.f, cb = 0.f, cr = 0.f;
+        {
+            const int rb = ymin[yy] - rmin;
+            const int n = min(ny[yy], nrows - rb);
+            const float* w = wy + yy * p.NTY;
+            const float* q = iy + rb * p.TX + col;
+            for (int t = 0; t < n; ++t) yv = fmaf(w[t], q[t * p.TX], yv);
+        }
+        {
+            const int rb = cymin[yy] - crmin;
+            const int n = min(cny[yy], cnrows - rb);
+            const float* w = cwy + yy * p.NCY;
+            const float* q = ic + rb * 2 * p.TX + col;
+            for (int t = 0; t < n; ++t) {
+                cb = fmaf(w[t], q[t * 2 * p.TX], cb);
+                cr = fmaf(w[t], q[(t * 2 + 1) * p.TX], cr);
+            }
+        }
+        const float yl = (yv - p.yoff) * p.ky;
+        cb -= 128.0f;
+        cr -= 128.0f;
+        float v[3];
+        v[0] = fmaf(p.krcr, cr, yl);
+        v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
+        v[2] = fmaf(p.kbcb, cb, yl);
+        const int y = y0 + yy, x = x0 + col;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float o = (v[c] / 255.0f - p.mean[c]) / p.den[c];
+            if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = o;
+            if (p.patches)
+                p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(o);
+        }
+    }
+    // pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile
+    if (p.patches && p.Kp > p.K) {
+        const int gy0 = (y0 + p.patch - 1) / p.patch, gy1 = (y0 + ty + p.patch - 1) / p.patch;
+        const int gx0 = (x0 + p.patch - 1) / p.patch, gx1 = (x0 + tx + p.patch - 1) / p.patch;
+        const int pad = p.Kp - p.K, ngx = gx1 - gx0;
+        for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
+            const int j = it % pad, pr = it / pad;
+            p.patches[((f * p.g + gy0 + pr / ngx) * p.g + gx0 + pr % ngx) * p.ldp + p.K + j] = 0;
+        }
+    }
+}
+
+int fy_stage_bytes(const FyParams& p) {
+    const int y = FR_SR * p.SEGY, c = (p.cpix == 1 ? 2 : 1) * FR_SR * p.SEGC;   // one buffer: luma chunks first, chroma chunks after them
+    return y > c ? y : c;
+}
+
+// Tile plan: capacities from the exact tap placement of the crop's rows and columns (the kernel clamps to them all the same); false = over the LDS budget.
+bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
+    p.TY = ty;
+    p.TX = tx;
+    p.tilesX = (p.R + tx - 1) / tx;
+    p.bands = (p.R + ty - 1) / ty;
+    p.NRY = fr_max_span(p.ay, p.top, p.R, ty);
+    p.NRC = fr_max_span(p.cy, p.top, p.R, ty);
+    p.SPY = fr_max_span(p.ax, p.left, p.R, tx);
+    p.SPC = fr_max_span(p.cx, p.left, p.R, tx);
+    p.SEGY = ((p.SPY + 15) & ~15) + 16;
+    p.SEGC = ((p.SPC * p.cpix + 15) & ~15) + 16;
+    int64_t o = (int64_t)tx * p.NTXp * 4;
+    p.o_wy = (int)o;
+    o += (int64_t)ty * p.NTY * 4;
+    p.o_cwx = (int)o;
+    o += (int64_t)tx * p.NCXp * 4;
+    p.o_cwy = (int)o;
+    o += (int64_t)ty * p.NCY * 4;
+    p.o_idx = (int)o;
+    o += (int64_t)(4 * tx + 4 * ty) * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_iy = (int)o;
+    o += (int64_t)p.NRY * tx * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_ic = (int)o;
+    o += (int64_t)p.NRC * 2 * tx * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_stage = (int)o;
+    o += fy_stage_bytes(p);
+    if (o > FR_LDS_BUDGET) return false;
+    // per output row: the source rows the horizontal pass computes, one luma plane and two chroma planes, plus the (cheaper) staged samples per output pixel -
+    // the RGB planner's measure, where staging three planes weighs SEGPX / (tx * scale): a third of that per plane here
+    const double fx = p.ax.scale > 1.0 ? p.ax.scale : 1.0, fcx = p.ax.scale > 2.0 ? p.ax.scale / 2.0 : 1.0;
+    cost = (double)p.NRY / ty * (1.0 + (double)p.SPY / (tx * fx) / 3.0) + (double)p.NRC / ty * (2.0 + 2.0 * p.SPC / (tx * fcx) / 3.0);
+    return true;
+}
+
+}  // namespace
+
+extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_stride, const uint8_t* cb, const uint8_t* cr, int64_t c_frame_stride,
+                                 int64_t c_row_stride, int32_t c_pix, int32_t n, int32_t H, int32_t W, int32_t matrix, int32_t full_range, int32_t chroma_loc,
+                                 int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    RV_CHECK_ARG(c_pix == 1 || c_pix == 2, "rv_yuv_to_patches: c_pix = %d (1 = planar, 2 = interleaved)", c_pix);
+    RV_CHECK_ARG(matrix == 0 || matrix == 1, "rv_yuv_to_patches: matrix %d (0 = BT.601, 1 = BT.709)", matrix);
+    RV_CHECK_ARG(full_range == 0 || full_range == 1, "rv_yuv_to_patches: full_range %d (0 = studio, 1 = full)", full_range);
+    RV_CHECK_ARG(chroma_loc == 0 || chroma_loc == 1, "rv_yuv_to_patches: chroma_loc %d (0 = left, 1 = centre)", chroma_loc);
+    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "rv_yuv_to_patches: R = %d is not a multiple of patch = %d", R, patch);
+    RV_CHECK_ARG(H >= 2 && W >= 2 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "rv_yuv_to_patches: frame size %d x %d outside 2 .. %d", H, W, FR_MAX_SIDE);
+    RV_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "rv_yuv_to_patches: frame size %d x %d is odd (4:2:0 chroma covers 2 x 2 luma samples)", H, W);
+    RV_CHECK_ARG(R <= FR_MAX_SIDE, "rv_yuv_to_patches: R = %d above %d", R, FR_MAX_SIDE);
+    RV_CHECK_ARG(n >= 0, "rv_yuv_to_patches: n = %d", n);
+    if (n == 0) return RV_OK;
+    RV_CHECK_ARG(y && cb && cr, "rv_yuv_to_patches: null plane (y %p, cb %p, cr %p)", (const void*)y, (const void*)cb, (const void*)cr);
+    RV_CHECK_ARG(c_pix == 1 || (intptr_t)cr - (intptr_t)cb == 1 || (intptr_t)cb - (intptr_t)cr == 1, "rv_yuv_to_patches: c_pix = 2 takes interleaved planes (cr = cb + 1 or cb = cr + 1)");
+    RV_CHECK_ARG(patches || image, "rv_yuv_to_patches: both outputs null");
+    RV_CHECK_ARG(mean && std, "rv_yuv_to_patches: null mean / std");
+    FyParams p{};
+    p.K = 3 * patch * patch;
+    p.Kp = (p.K + 127) / 128 * 128;
+    RV_CHECK_ARG(!patches || ldp >= p.Kp, "rv_yuv_to_patches: ldp = %lld below Kp = %d", (long long)ldp, p.Kp);
+    p.y = y;
+    p.yfs = y_frame_stride;
+    p.yrs = y_row_stride;
+    p.cfs = c_frame_stride;
+    p.crs = c_row_stride;
+    p.cpix = c_pix;
+    if (c_pix == 1) {
+        p.c = cb;
+        p.cdelta = cr - cb;
+    } else {
+        p.c = cb < cr ? cb : cr;
+        p.ocb = (int)(cb - p.c);
+        p.ocr = (int)(cr - p.c);
+    }
+    p.R = R;
+    p.patch = patch;
+    p.g = R / patch;
+    // Resize(R): shorter side -> R, longer side -> int(R * long / short); CenterCrop(R): offset round-half-even((size - R) / 2)
+    const int hr = H <= W ? R : (int)((int64_t)R * H / W), wr = H <= W ? (int)((int64_t)R * W / H) : R;
+    const double sy = (double)H / hr, sx = (double)W / wr;
+    p.top = (int)nearbyint((hr - R) / 2.0);
+    p.left = (int)nearbyint((wr - R) / 2.0);
+    p.ay = FrAxis{sy, 1.0, 0.0, H};
+    p.ax = FrAxis{sx, 1.0, 0.0, W};
+    p.cy = FrAxis{sy, 2.0, 0.0, H / 2};
+    p.cx = FrAxis{sx, 2.0, chroma_loc == 0 ? 0.25 : 0.0, W / 2};
+    const double kr = matrix == 0 ? 0.299 : 0.2126, kb = matrix == 0 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double cs = full_range ? 1.0 : 255.0 / 224.0;
+    p.yoff = full_range ? 0.0f : 16.0f;
+    p.ky = (float)(full_range ? 1.0 : 255.0 / 219.0);
+    p.krcr = (float)(2.0 * (1.0 - kr) * cs);
+    p.kbcb = (float)(2.0 * (1.0 - kb) * cs);
+    p.kgcb = (float)(-(2.0 * kb * (1.0 - kb) / kg) * cs);
+    p.kgcr = (float)(-(2.0 * kr * (1.0 - kr) / kg) * cs);
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean[c];
+        p.den[c] = std[c] + 1e-8f;
+    }
+    p.patches = (op16_t*)patches;
+    p.ldp = ldp;
+    p.image = image;
+    p.NTX = fr_max_taps(p.ax, p.left, R);
+    p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
+    p.NTY = fr_max_taps(p.ay, p.top, R);
+    p.NCX = fr_max_taps(p.cx, p.left, R);
+    p.NCXp = p.NCX | 1;
+    p.NCY = fr_max_taps(p.cy, p.top, R);
+    FyParams best{};
+    double best_cost = 0.0;
+    bool have = false;
+    for (int ty = 16; ty >= 1; ty >>= 1)
+        for (int tx = 256; tx >= 1; tx >>= 1) {
+            const int tyc = ty < R ? ty : R, txc = tx < R ? tx : R;
+            double cost;
+            FyParams q = p;
+            if (fy_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
+        }
+    RV_CHECK_ARG(have, "rv_yuv_to_patches: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", H, W, R);
+    const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
+    RV_CHECK_ARG(wgs < (1ll << 31), "rv_yuv_to_patches: %lld workgroups (n = %d) exceed one launch", (long long)wgs, n);
+    const int lds = best.o_stage + fy_stage_bytes(best);
+    static std::atomic<uint64_t> have_lds{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {   // the dynamic-LDS opt-in is a per-device attribute of the function
+        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+            rv_set_error("rv_yuv_to_patches: cannot reserve %d bytes of LDS", FR_LDS_BUDGET);
+            return RV_ERR_HIP;
+        }
+        have_lds.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(yuv_to_patches_kernel, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), best);
+    RV_CHECK_LAUNCH("yuv_to_patches");
+    return RV_OK;
+}

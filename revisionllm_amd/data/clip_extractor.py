@@ -5,7 +5,8 @@ Differences from the reference, all at the IO edge: frames are handed over as te
 build) - either already at the towers' resolution [T,3,R,R] (what its ``VideoLoader`` produces from ffmpeg's scale + crop), or as
 decoded uint8 frames of any size, NCHW or NHWC, in one tensor or in chunks: those are resized, centre-cropped, normalised and
 unfolded on the device by one kernel (``ops.frames_to_patches``; the reference's Resize / CenterCrop / Normalize,
-inference.py:108-117).  The CLIP weights come from ``ClipTowers`` (a loaded checkpoint or synthetic).  The on-disk format of the results is what ``data.feature_store`` reads back (f-2).
+inference.py:108-117) - or as the 4:2:0 YCbCr bytes a decoder really emits (NV12 / NV21 / I420; ``encode_video_yuv``, ``ops.yuv_to_patches``), which are
+resampled plane by plane and converted per output pixel in one kernel of the same shape.  The CLIP weights come from ``ClipTowers`` (a loaded checkpoint or synthetic).  The on-disk format of the results is what ``data.feature_store`` reads back (f-2).
 """
 import math
 
@@ -22,6 +23,11 @@ def preprocess(frames):
     mean = torch.tensor(CLIP_MEAN, device=x.device).view(1, 3, 1, 1)
     std = torch.tensor(CLIP_STD, device=x.device).view(1, 3, 1, 1)
     return (x - mean) / (std + 1e-8)
+
+
+def yuv_colour_defaults(H):
+    """What ffmpeg (swscale) assumes for a stream that carries no colour tags: BT.601 below 720 lines, BT.709 from 720 on; studio range; chroma sited left."""
+    return dict(matrix="bt601" if H < 720 else "bt709", full_range=False, chroma_loc="left")
 
 
 class ClipFeatureExtractor:
@@ -50,13 +56,25 @@ class ClipFeatureExtractor:
         out = [tw.encode_frames(b, layout=layout) for b in self._batches(frames, bsz)]
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
 
-    def _batches(self, chunks, bsz):
+    @torch.no_grad()
+    def encode_video_yuv(self, chunks, H, W, fmt, bsz=60, **colour):
+        """-> f32 [T, d] from the bytes of a rawvideo pipe (``ffmpeg -f rawvideo -pix_fmt nv12 | nv21 | yuv420p``; ``fmt`` "nv12" | "nv21" | "i420"): ``chunks``
+        is one packed uint8 buffer [t, H*3//2, W] (``torch.frombuffer(data, dtype=torch.uint8).view(-1, H * 3 // 2, W)``) or an iterable of them, CPU or
+        device.  They are regrouped into batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv420``) and go through
+        ``encode_frames_yuv``: no RGB frame exists anywhere.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_colour_defaults(H)``."""
+        tw = self.clip_extractor
+        colour = {**yuv_colour_defaults(H), **colour}
+        out = [tw.encode_frames_yuv(*ops.split_yuv420(b, H, W, fmt), **colour)
+               for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]")]
+        return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+
+    def _batches(self, chunks, bsz, ndim=4, shapes="[t,3,H,W] or [t,H,W,3]"):
         """Decoded uint8 chunks of any lengths -> device batches of exactly ``bsz`` frames (the last one shorter): the batching does not depend on
         how the decoder cut the video."""
         held, n = [], 0
         for c in chunks:
-            if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 4:
-                raise ValueError("decoded frames come as uint8 tensors [t,3,H,W] or [t,H,W,3]")
+            if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != ndim:
+                raise ValueError(f"decoded frames come as uint8 tensors {shapes}")
             c = ops.h2d(c, self.device)
             while len(c):
                 take = c[:bsz - n]

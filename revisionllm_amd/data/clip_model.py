@@ -3,8 +3,8 @@
 What the reference's feature extractors run upstream of the grounding path (``clip.load("ViT-L/14")`` ->
 ``encode_image`` / ``encode_text``; data/feature_extraction/clip_extractor.py:13-54, clip/model.py:223-242, 339-352).
 Every matrix product, LayerNorm and attention goes through the C ABI (``rv_gemm`` with fused bias / QuickGELU / residual
-epilogues, ``rv_layernorm``, ``rv_attention`` with 64-wide heads; ``rv_frames_to_patches`` in front of them for decoded uint8
-frames); torch only moves rows around (patch unfold of float frames, class token concat, embedding gather).  Residual stream
+epilogues, ``rv_layernorm``, ``rv_attention`` with 64-wide heads; ``rv_frames_to_patches`` / ``rv_yuv_to_patches`` in front of them for decoded
+uint8 RGB / 4:2:0 YCbCr frames); torch only moves rows around (patch unfold of float frames, class token concat, embedding gather).  Residual stream
 f32, GEMM inputs bf16, weights fragment-packed bf16 - as in the engine.
 State-dict names are the checkpoint's own (``visual.conv1.weight``, ``transformer.resblocks.3.mlp.c_fc.weight``, ...).
 """
@@ -99,6 +99,14 @@ class ClipTowers:
         c = self.cfg
         patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype)
         return self._encode_patches(patches, frames_u8.shape[0])
+
+    @torch.no_grad()
+    def encode_frames_yuv(self, y, cb, cr=None, **colour):
+        """Decoded 8-bit 4:2:0 frames (Y [n,H,W] and the chroma planes as ``ops.yuv_to_patches`` takes them, on the device; ``colour``: its ``matrix`` /
+        ``full_range`` / ``chroma_loc``) -> f32 [n, embed_dim]: resample, convert, crop, normalise and unfold in one kernel, then what ``encode_image`` runs."""
+        c = self.cfg
+        patches, _ = ops.yuv_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **colour)
+        return self._encode_patches(patches, y.shape[0])
 
     def _encode_patches(self, patches, n):
         """patches [n*g*g, Kp] operand type (the unfolded, K-padded frames) -> f32 [n, embed_dim]: conv1 as a GEMM and everything behind it."""

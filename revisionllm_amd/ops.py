@@ -283,6 +283,100 @@ def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_ST
     return patches, image
 
 
+_MATRICES = {"bt601": 0, "bt709": 1}
+_CHROMA_LOCS = {"left": 0, "centre": 1}
+_YUV_FORMATS = ("nv12", "nv21", "i420")
+
+
+def _rows_of_samples(t, n, rows, cols, pix):
+    """Can a plane [n,rows,cols] be passed by its strides?  Samples of a row ``pix`` bytes apart, rows and frames in ascending order (a dimension of
+    extent 1 has no stride to speak of)."""
+    return (cols == 1 or t.stride(2) == pix) and (rows == 1 or t.stride(1) >= pix * cols) and (n <= 1 or t.stride(0) > 0)
+
+
+def _plane_strides(t, n, rows, cols, pix):
+    """(frame stride, row stride) in bytes of a plane ``_rows_of_samples`` accepted."""
+    rs = t.stride(1) if rows > 1 else pix * cols
+    return (t.stride(0) if n > 1 else rs * rows), rs
+
+
+def yuv_to_patches(y, cb, cr=None, *, R, patch, matrix="bt601", full_range=False, chroma_loc="left", mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None,
+                   want=("patches",)):
+    """Decoded 8-bit 4:2:0 YCbCr frames -> the CLIP front end in one launch (rv_yuv_to_patches; the header has the definition of the values): Y resampled at
+    full, Cb / Cr at half resolution, colour matrix per output pixel, then everything ``frames_to_patches`` does -> (patches, image) as it returns them.
+    y: uint8 device tensor [n,H,W] (H, W even).  Chroma, either of
+      * ``cb`` [n,H/2,W/2,2] with ``cr=None``: interleaved CbCr (NV12);
+      * ``cb`` and ``cr`` [n,H/2,W/2] each: two planes (I420), or two views one byte apart with a sample stride of 2 (NV21 / NV12 as ``split_yuv420``
+        hands them over): those are read as the interleaved surface they are.
+    Planes are passed by their strides when each row's bytes are adjacent (a window of a larger decode surface, a padded pitch); any other view is copied first.
+    matrix "bt601" | "bt709"; full_range False = studio; chroma_loc "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1)."""
+    for t in (y, cb) + (() if cr is None else (cr,)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise hip.HipLibraryError("yuv_to_patches needs device tensors (got a CPU tensor); there is no CPU path")
+        if t.dtype != torch.uint8:
+            raise hip.HipLibraryError(f"yuv_to_patches takes uint8 planes, got {t.dtype} {tuple(t.shape)}")
+    if matrix not in _MATRICES or chroma_loc not in _CHROMA_LOCS:
+        raise ValueError(f"matrix {matrix!r} / chroma_loc {chroma_loc!r}: one of {sorted(_MATRICES)} / {sorted(_CHROMA_LOCS)}")
+    if y.dim() != 3 or y.shape[1] % 2 or y.shape[2] % 2:
+        raise hip.HipLibraryError(f"yuv_to_patches takes a Y plane [n,H,W] with even H and W, got {tuple(y.shape)}")
+    n, H, W = y.shape
+    h2, w2 = H // 2, W // 2
+    if cr is None:
+        if tuple(cb.shape) != (n, h2, w2, 2):
+            raise hip.HipLibraryError(f"interleaved CbCr of {n} frames {H} x {W} is [{n},{h2},{w2},2], got {tuple(cb.shape)}")
+        if not (cb.stride(3) == 1 and _rows_of_samples(cb, n, h2, w2, 2)):
+            cb = cb.contiguous()
+        cb, cr = cb[..., 0], cb[..., 1]
+    elif tuple(cb.shape) != (n, h2, w2) or tuple(cr.shape) != (n, h2, w2):
+        raise hip.HipLibraryError(f"Cb and Cr of {n} frames {H} x {W} are [{n},{h2},{w2}] each, got {tuple(cb.shape)} and {tuple(cr.shape)}")
+    if not _rows_of_samples(y, n, H, W, 1):
+        y = y.contiguous()
+    # cb, cr: [n,h2,w2] views from here on; one stride pair serves both planes
+    if abs(cb.data_ptr() - cr.data_ptr()) == 1 and cb.stride() == cr.stride() and _rows_of_samples(cb, n, h2, w2, 2):
+        c_pix = 2
+    else:
+        c_pix = 1
+        if not (cb.stride() == cr.stride() and _rows_of_samples(cb, n, h2, w2, 1)):
+            cb, cr = cb.contiguous(), cr.contiguous()
+    yfs, yrs = _plane_strides(y, n, H, W, 1)
+    cfs, crs = _plane_strides(cb, n, h2, w2, c_pix)
+    dt = hip.op_dtype(op_dtype)
+    g = R // max(patch, 1)
+    kp = (3 * patch * patch + 127) // 128 * 128
+    patches = torch.empty(n * g * g, kp, dtype=dt, device=y.device) if "patches" in want else None
+    image = torch.empty(n, 3, R, R, dtype=torch.float32, device=y.device) if "image" in want else None
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_yuv_to_patches(hip.ptr(y), yfs, yrs, hip.ptr(cb), hip.ptr(cr), cfs, crs, c_pix, n, H, W, _MATRICES[matrix], int(bool(full_range)),
+                                            _CHROMA_LOCS[chroma_loc], R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp, hip.ptr(image), hip.stream()),
+              "rv_yuv_to_patches")
+    return patches, image
+
+
+def split_yuv420(buf, H, W, fmt):
+    """The bytes of a rawvideo pipe (``ffmpeg -f rawvideo -pix_fmt nv12 | nv21 | yuv420p``) -> zero-copy views ``(y, cb, cr_or_None)`` that ``yuv_to_patches``
+    takes without a copy.  buf: uint8 [n, H*3//2, W] (CPU or device; each frame's H * W * 3 / 2 bytes adjacent), H and W even.
+      nv12: y [n,H,W], cbcr [n,H/2,W/2,2], None        nv21: y, cb = vu[..., 1], cr = vu[..., 0] (sample stride 2, one byte apart)
+      i420: y, cb [n,H/2,W/2] at byte H * W of each frame, cr at H * W * 5 / 4"""
+    if fmt not in _YUV_FORMATS:
+        raise ValueError(f"fmt {fmt!r}: one of {_YUV_FORMATS}")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"4:2:0 frames have even sides of at least 2, got {H} x {W}")
+    if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.dim() != 3 or tuple(buf.shape[1:]) != (H * 3 // 2, W):
+        raise ValueError(f"{fmt} frames of {H} x {W} come as a uint8 tensor [n,{H * 3 // 2},{W}], got "
+                         + (f"{buf.dtype} {tuple(buf.shape)}" if torch.is_tensor(buf) else type(buf).__name__))
+    if buf.stride(2) != 1 or buf.stride(1) != W:
+        raise ValueError("split_yuv420 returns views: the bytes of each frame must be adjacent (a padded surface is passed to yuv_to_patches plane by plane)")
+    n, h2, w2 = buf.shape[0], H // 2, W // 2
+    y = buf[:, :H]
+    if fmt == "i420":
+        fs, at = buf.stride(0), buf.storage_offset()
+        cb = buf.as_strided((n, h2, w2), (fs, w2, 1), at + H * W)
+        cr = buf.as_strided((n, h2, w2), (fs, w2, 1), at + H * W + h2 * w2)
+        return y, cb, cr
+    pairs = buf[:, H:].unflatten(2, (w2, 2))
+    return (y, pairs, None) if fmt == "nv12" else (y, pairs[..., 1], pairs[..., 0])
+
+
 def h2d(t, device, dtype=None):
     """Host -> device without stalling the host: a pageable ``.to(device)`` blocks until everything queued before it has
     run (the launch queue then runs dry after every upload); a pinned, non-blocking copy just joins the stream."""

@@ -1,0 +1,118 @@
+"""CLIP front end at 1080p on decoder output: rv_yuv_to_patches on NV12 against rv_frames_to_patches on the same frames as NCHW RGB, and against the torch
+composition (colour conversion + resize) a user would otherwise write on the GPU.
+
+60 NV12 frames of 1080 x 1920 (noise) -> R = 224, patch = 14 (one encode_video_yuv batch).  The RGB frames are the NV12 frames converted once, outside the
+timed region (nearest chroma, BT.709 studio, rounded to uint8): the RGB entry is timed on bytes a conversion pass would have had to write first.  The three
+forms run in one process, alternating, each launch between two device events: 5 warm-up + 20 timed launches per form.  Reported: median, min .. max per form,
+yuv / rgb (the yardstick: the RGB entry on the same box; the YUV entry reads half the bytes and filters half the plane area), and the source bytes the crop
+uses over the YUV call's median as a fraction of the 8 TB/s HBM figure.  Writes one JSON object to --out (default profiles/frontend_yuv_1080p.json).
+
+    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--out FILE] [--once]   (--once: one YUV launch, for a kernel trace)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from revisionllm_amd import hip, ops  # noqa: E402
+
+HBM_PEAK = 8.0e12
+KR, KB = 0.2126, 0.0722          # BT.709, studio range, as encode_video_yuv assumes at 1080 lines
+
+
+def to_rgb_float(y, cbcr):
+    """NV12 planes -> float RGB [n,3,H,W] in 0..255 (unclamped): nearest chroma, BT.709 studio range."""
+    n, H, W = y.shape
+    c = cbcr.permute(0, 3, 1, 2).float().repeat_interleave(2, 2).repeat_interleave(2, 3)
+    yl = (y.float() - 16.0) * (255.0 / 219.0)
+    cb, cr = (c[:, 0] - 128.0) * (255.0 / 224.0), (c[:, 1] - 128.0) * (255.0 / 224.0)
+    kg = 1.0 - KR - KB
+    return torch.stack([yl + 2 * (1 - KR) * cr, yl - (2 * KB * (1 - KB) / kg) * cb - (2 * KR * (1 - KR) / kg) * cr, yl + 2 * (1 - KB) * cb], 1)
+
+
+def torch_composition(y, cbcr, R, patch, dt):
+    """convert -> antialiased bicubic resize -> centre crop -> normalise -> unfold -> pad -> operand type."""
+    n, H, W = y.shape
+    x = to_rgb_float(y, cbcr)
+    hr, wr = (R, int(R * W / H)) if H <= W else (int(R * H / W), R)
+    x = F.interpolate(x, size=(hr, wr), mode="bicubic", align_corners=False, antialias=True)
+    top, left = int(round((hr - R) / 2.0)), int(round((wr - R) / 2.0))
+    x = x[:, :, top:top + R, left:left + R]
+    mean = torch.tensor(ops.CLIP_MEAN, device=x.device).view(1, 3, 1, 1)
+    std = torch.tensor(ops.CLIP_STD, device=x.device).view(1, 3, 1, 1)
+    x = (x / 255.0 - mean) / (std + 1e-8)
+    g = R // patch
+    p = x.reshape(n, 3, g, patch, g, patch).permute(0, 2, 4, 1, 3, 5).reshape(n * g * g, 3 * patch * patch)
+    kp = (p.shape[1] + 127) // 128 * 128
+    return F.pad(p, (0, kp - p.shape[1])).to(dt)
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e-3, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--res", type=int, default=224)
+    ap.add_argument("--patch", type=int, default=14)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_yuv_1080p.json"))
+    ap.add_argument("--once", action="store_true")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "frontend_yuv_prof needs the GPU: a CPU run says nothing about time"
+    dt = hip.op_dtype()
+    n, H, W, R = a.frames, a.height, a.width, a.res
+    buf = torch.randint(0, 256, (n, H * 3 // 2, W), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).cuda()
+    y, cbcr, _ = ops.split_yuv420(buf, H, W, "nv12")
+    colour = dict(matrix="bt709", full_range=False, chroma_loc="left")
+    yuv = lambda: ops.yuv_to_patches(y, cbcr, R=R, patch=a.patch, op_dtype=dt, **colour)[0]
+    if a.once:
+        yuv()
+        torch.cuda.synchronize()
+        return
+    rgb_u8 = torch.cat([to_rgb_float(y[i:i + 4], cbcr[i:i + 4]).round().clamp(0, 255).to(torch.uint8) for i in range(0, n, 4)], 0)
+    rgb = lambda: ops.frames_to_patches(rgb_u8, R, a.patch, layout="NCHW", op_dtype=dt)[0]
+    comp = lambda: torch_composition(y, cbcr, R, a.patch, dt)
+    forms = (("yuv", yuv), ("rgb", rgb), ("torch", comp))
+    t, first = {k: [] for k, _ in forms}, {}
+    for i in range(a.warmup + a.iters):
+        for name, fn in forms:
+            s, out = timed(fn)
+            if i >= a.warmup:
+                t[name].append(s)
+            if i == 0:
+                first[name] = out
+    # source bytes the crop uses: the centred square (the shorter side) of every frame, 1.5 bytes a pixel (3 for the RGB entry)
+    used = n * min(H, W) ** 2 * 3 // 2
+    med = {k: statistics.median(v) for k, v in t.items()}
+    ms = lambda k: dict(median=med[k] * 1e3, min=min(t[k]) * 1e3, max=max(t[k]) * 1e3)
+    res = dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), frames=n, height=H, width=W, res=R, patch=a.patch, warmup=a.warmup, iters=a.iters,
+               yuv_ms=ms("yuv"), rgb_ms=ms("rgb"), torch_ms=ms("torch"), yuv_over_rgb=med["yuv"] / med["rgb"], speedup_vs_torch=med["torch"] / med["yuv"],
+               used_source_bytes=used, yuv_bytes_per_s=used / med["yuv"], yuv_fraction_of_8TBps=used / med["yuv"] / HBM_PEAK,
+               # not an error figure: the composition upsamples chroma (nearest) before it filters, the kernel filters the chroma planes themselves
+               max_abs_diff_yuv_vs_torch=float((first["yuv"].float() - first["torch"].float()).abs().max()),
+               max_abs_diff_yuv_vs_rgb_entry_on_rounded_rgb=float((first["yuv"].float() - first["rgb"].float()).abs().max()))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
