@@ -286,6 +286,47 @@ int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_st
                       int64_t c_row_stride, int32_t c_pix, int32_t n, int32_t H, int32_t W, int32_t matrix, int32_t full_range, int32_t chroma_loc,
                       int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
 
+/* The same front end on every planar or semi-planar surface a decoder produces: 8-bit or 16-bit samples, 4:2:0 / 4:2:2 / 4:4:4, interleaved or separate chroma
+ * planes (NV12 / NV21 / I420, P010 / P012 / P016, yuv420p10le / yuv420p12le, nv16 / yuv422p / p210, nv24 / yuv444p / p410 ...), described by one struct.
+ * rv_yuv_to_patches is this entry on {sample_bytes 1, depth 8, sub 2,2} and gives the same bits.  All strides in BYTES, so a window of a larger decode surface
+ * with a padded pitch is passed as it lies (INTEGRATION.md has the pointer arithmetic for P010).  mean / std / patches / ldp / image / R / patch: as in
+ * rv_frames_to_patches.
+ * Values (f32 throughout, no clamp, no integer or RGB intermediate; f32 holds every 16-bit sample exactly):
+ *   sample   the byte, or the little-endian 16-bit word: word >> (16 - depth) when msb_aligned (the low bits are discarded: whatever a decoder leaves there
+ *            cannot matter), else the word as it lies (a word >= 2^depth is taken at face value)
+ *   luma     Y' = rv_frames_to_patches' resampling of the Y plane (the same taps, the same normalised f32 weights computed in f64)
+ *   chroma   per axis, with sub = sub_x or sub_y: in_c = in / sub, scale_c = scale / sub, centre_c = scale * (i + 0.5) / sub + off; off = 0.25 when the axis is
+ *            subsampled (sub = 2) AND the chroma sample is sited on the even luma sample of that axis - the horizontal axis for chroma_loc 0 and 2, the vertical
+ *            axis for chroma_loc 2 only - else 0; support_c = 2 * max(scale_c, 1), taps [max(0, int(centre_c - support_c + 0.5)),
+ *            min(in_c, int(centre_c + support_c + 0.5))), weight cubic((j - centre_c + 0.5) / max(scale_c, 1)) / (sum over the taps).  An axis with sub = 1
+ *            is the luma axis unchanged.
+ *   colour   s = 2^(depth - 8); studio range: yl = (Y' - 16 s) * 255 / (219 s), c = (C' - 128 s) * 255 / (224 s); full range: yl = Y' * 255 / (2^depth - 1),
+ *            c = (C' - 128 s) * 255 / (2^depth - 1); then rv_yuv_to_patches' Rv / Gv / Bv equations with the matrix's Kr, Kb (matrix 2: BT.2020
+ *            non-constant luminance, Kr 0.2627, Kb 0.0593); the five coefficients are computed in f64 and rounded once to f32
+ *   norm     (v / 255 - mean[c]) / (std[c] + 1e-8); crop, image and patches laid out, rounded once and zero-padded exactly as by rv_frames_to_patches
+ * matrix 2 applies the BT.2020 MATRIX only: there is no PQ / HLG transfer conversion and no tone mapping, so HDR-coded values reach CLIP as coded.
+ * Not taken: packed 4:2:2 (YUY2 / Y210), 4:1:1, big-endian words, alpha planes.
+ * Refused (RV_ERR_ARG, nothing launched): a null struct or plane; sample_bytes outside {1, 2}; a depth that does not go with it; msb_aligned outside {0, 1}, or 1
+ * with sample_bytes 1; (sub_x, sub_y) outside the three pairs; H or W odd along a subsampled axis (odd sizes are legal along an axis with sub = 1), below sub or
+ * above 8192; c_pix outside {sample_bytes, 2 * sample_bytes}; interleaved planes that are not sample_bytes apart; with sample_bytes 2 an odd plane pointer or
+ * stride; matrix outside 0 .. 2; full_range outside {0, 1}; chroma_loc outside 0 .. 2; R % patch != 0; both outputs null; ldp < Kp; a geometry whose tap tables
+ * and staging (16-bit rows take twice the bytes) do not fit a workgroup's LDS; more workgroups than one launch holds.  n = 0 returns 0 and launches nothing. */
+typedef struct rv_yuv_surface {
+    const void *y, *cb, *cr;          /* device pointers */
+    int64_t y_frame_stride, y_row_stride, c_frame_stride, c_row_stride;   /* BYTES; cb and cr share theirs */
+    int32_t sample_bytes;             /* 1, or 2 = little-endian 16-bit words */
+    int32_t depth;                    /* 8 with sample_bytes 1; 9 .. 16 with sample_bytes 2 */
+    int32_t msb_aligned;              /* 16-bit words only: 0 = value in the low bits (yuv420p10le), 1 = in the high bits (P010 / P012 / P016) */
+    int32_t c_pix;                    /* bytes between neighbouring samples of ONE chroma plane: sample_bytes (planar) or 2 * sample_bytes (interleaved) */
+    int32_t sub_x, sub_y;             /* 2,2 = 4:2:0   2,1 = 4:2:2   1,1 = 4:4:4 */
+    int32_t n, H, W;
+    int32_t matrix;                   /* 0 BT.601, 1 BT.709, 2 BT.2020 non-constant luminance (Kr 0.2627, Kb 0.0593) */
+    int32_t full_range;               /* 0 studio, 1 full */
+    int32_t chroma_loc;               /* 0 left, 1 centre, 2 top-left */
+} rv_yuv_surface;
+int rv_yuv_surface_to_patches(const rv_yuv_surface* s, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
+                              float* image, void* stream);
+
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */
 int rv_project_dense(rv_ctx* ctx, const void* x_bf16, void* y, int out_dtype, int64_t rows, void* stream);

@@ -1,4 +1,4 @@
-// What the CLIP front-end kernels (frames.hip: uint8 RGB; frames_yuv.hip: 4:2:0 YCbCr) share: the tap definition of the antialiased bicubic resampler, the
+// What the CLIP front-end kernels (frames.hip: uint8 RGB; frames_yuv.hip: YCbCr surfaces) share: the tap definition of the antialiased bicubic resampler, the
 // workgroup constants and the host's capacity helpers.  Host and device place the taps with the same f64
 // expressions, so fp contraction is off from here to the end of the including translation unit; the tap loops ask for their fma by name.
 #pragma once

@@ -1,6 +1,12 @@
-// CLIP front end on the bytes a video decoder hands over: 4:2:0 YCbCr planes (NV12 / NV21 / I420 surfaces) -> resize (antialiased bicubic) -> YCbCr -> RGB ->
-// centre crop -> normalise -> patch matrix, one kernel (rv_yuv_to_patches).  No RGB frame exists anywhere: resampling is linear and the colour conversion
-// affine, so the kernel filters Y at full and Cb / Cr at half resolution and applies the colour matrix once per OUTPUT pixel.
+// CLIP front end on the bytes a video decoder hands over: YCbCr planes of 8-bit or 16-bit samples, 4:2:0 / 4:2:2 / 4:4:4, planar or with interleaved chroma
+// (NV12 / NV21 / I420, P010 / P016, yuv420p10le, nv16, yuv444p10le ...: rv_yuv_surface) -> resize (antialiased bicubic) -> YCbCr -> RGB -> centre crop ->
+// normalise -> patch matrix, one kernel (rv_yuv_surface_to_patches; rv_yuv_to_patches is the same code on an 8-bit 4:2:0 surface).  No RGB frame exists
+// anywhere: resampling is linear and the colour conversion affine, so the kernel filters Y at full and Cb / Cr at their own resolution and applies the colour
+// matrix once per OUTPUT pixel.
+//
+// The values below are those of the 8-bit 4:2:0 surface; include/revision_hip.h has the general definition (sample = word >> (16 - depth) when the value sits
+// in the high bits; per axis in_c = in / sub, scale_c = scale / sub, off = 0.25 where a subsampled axis is sited on the even luma sample; s = 2^(depth - 8)
+// scales 16, 128, 219, 224, and full range divides by 2^depth - 1).
 //
 // Values (f32 throughout, no clamp, no u8 intermediate); i = an output index of the RESIZED image (before the crop), scale = in / out per axis, the resized
 // size and the crop offsets are rv_frames_to_patches' own:
@@ -20,10 +26,11 @@
 // The kernel follows frames_to_patches_kernel.  One workgroup owns TY x TX output pixels of one frame:
 //   phase 0  four tap tables (luma x / y, chroma x / y: first tap, count, normalised f32 weights; computed in f64) into LDS
 //   phase 1  per chunk of FR_SR source rows, first of the Y plane, then of the chroma planes: stage the bytes the tile needs in LDS (16-byte loads where the
-//            address allows, single bytes at the ends of a row segment; an interleaved chroma segment holds both planes), then the horizontal pass into
+//            address allows, single samples at the ends of a row segment; an interleaved chroma segment holds both planes), then the horizontal pass into
 //            f32 LDS rows  interY[source row][column],  interC[chroma row][Cb | Cr][column]
 //   phase 2  vertical pass over both, colour matrix, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
-// Half the horizontal-pass work of three RGB planes (one full plane + two quarter planes filtered with half the taps), and two thirds of its `inter` rows.
+// At 4:2:0: half the horizontal-pass work of three RGB planes (one full plane + two quarter planes filtered with half the taps), and two thirds of its
+// `inter` rows.  The kernel is compiled per sample type (uint8_t; uint16_t with a run-time shift), so the 8-bit instance is the 8-bit kernel it was.
 #include <atomic>
 
 #include "frames_taps.h"   // fp contraction is off from there on
@@ -33,14 +40,15 @@ namespace {
 struct FyParams {
     const uint8_t *y, *c;                 // c: the Cb plane (planar) or the lower of the two interleaved planes
     int64_t yfs, yrs, cfs, crs, cdelta;   // bytes between frames / rows of the Y and the chroma planes; cdelta: Cr plane - Cb plane (planar)
-    int cpix, ocb, ocr;                   // bytes between neighbouring samples of a chroma plane; offsets of Cb / Cr inside an interleaved pair (planar: 0)
+    int cpix, ocb, ocr;                   // bytes between neighbouring samples of a chroma plane; byte offsets of Cb / Cr inside an interleaved pair (planar: 0)
+    int sbytes, cplanes, shift;           // bytes of a sample; planes staged apart (planar: 2, interleaved: 1); 16-bit words: sample = word >> shift
     int R, patch, g, K, Kp, top, left;
     FrAxis ax, ay, cx, cy;                // luma and chroma axes
     int TY, TX, tilesX, bands;
     int NTX, NTXp, NTY, NCX, NCXp, NCY;   // tap capacities (x rows padded to an odd pitch)
     int NRY, NRC, SPY, SPC, SEGY, SEGC;   // rows of interY / interC, samples / bytes (16-byte multiple + 16) of a staged luma / chroma row segment
     int o_wy, o_cwx, o_cwy, o_idx, o_iy, o_ic, o_stage;   // LDS offsets (the luma x weights sit at 0)
-    float yoff, ky, krcr, kgcb, kgcr, kbcb;
+    float yoff, cmid, ky, krcr, kgcb, kgcr, kbcb;   // cmid: the chroma zero, 128 * 2^(depth - 8)
     float mean[3], den[3];
     op16_t* patches;
     int64_t ldp;
@@ -63,7 +71,9 @@ __device__ inline void fy_tap_table(const FrAxis& a, int first, int cap, int pit
 }
 
 // Stage `nr` rows of `planes` planes: the `segbytes` bytes from `g0` on (row r of plane pl: g0 + pl * pdelta + r * rstride) into stage[(pl * FR_SR + r) * SEG ..],
-// each segment keeping its position inside a 16-byte line.  Reads [segment start, segment end) and nothing else.
+// each segment keeping its position inside a 16-byte line.  Reads [segment start, segment end) and nothing else: whole 16-byte lines inside it, single
+// samples of type S (segments start and end on a sample) at its two ends.
+template <typename S>
 __device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelta, int64_t rstride, int planes, int nr, int segbytes, int SEG, int tid) {
     const int nck = SEG >> 4;
     for (int it = tid; it < nr * planes * nck; it += FR_THREADS) {
@@ -76,12 +86,17 @@ __device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelt
         if (gc >= gs && gc + 16 <= ge) {
             *(uint4*)d = *(const uint4*)gc;
         } else if (gc + 16 > gs && gc < ge) {
-            for (int j = 0; j < 16; ++j)
-                if (gc + j >= gs && gc + j < ge) d[j] = gc[j];
+            for (int j = 0; j < 16; j += (int)sizeof(S))
+                if (gc + j >= gs && gc + j < ge) *(S*)(d + j) = *(const S*)(gc + j);
         }
     }
 }
 
+// A staged sample as f32: the 16-bit instance drops the low bits of a word whose value sits in the high bits (shift = 0 otherwise).
+__device__ inline float fy_sample(uint8_t v, int) { return (float)v; }
+__device__ inline float fy_sample(uint16_t v, int shift) { return (float)(v >> shift); }
+
+template <typename S>
 __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyParams p) {
     extern __shared__ __attribute__((aligned(16))) char fy_smem[];
     float* wx = (float*)fy_smem;                       // [TX][NTXp]
@@ -121,21 +136,22 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
     const int rmin = ymin[0], cmin = xmin[0];
     const int nrows = min(ymin[ty - 1] + ny[ty - 1] - rmin, p.NRY);
     const int segpx = min(xmin[tx - 1] + nx[tx - 1] - cmin, p.SPY);
-    const uint8_t* ysrc = p.y + f * p.yfs + (int64_t)rmin * p.yrs + cmin;
+    constexpr int SB = (int)sizeof(S);
+    const uint8_t* ysrc = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
     for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
         const int nr = min(FR_SR, nrows - r0);
         const uint8_t* g0 = ysrc + (int64_t)r0 * p.yrs;
         __syncthreads();   // the previous chunk's readers are done with `stage`
-        fy_stage(stage, g0, 0, p.yrs, 1, nr, segpx, p.SEGY, tid);
+        fy_stage<S>(stage, g0, 0, p.yrs, 1, nr, segpx * SB, p.SEGY, tid);
         __syncthreads();
         for (int it = tid; it < nr * tx; it += FR_THREADS) {
             const int col = it % tx, r = it / tx;
             const int xo = xmin[col] - cmin;
-            const uint8_t* s = stage + r * p.SEGY + (int)((uintptr_t)(g0 + (int64_t)r * p.yrs) & 15) + xo;
+            const S* s = (const S*)(stage + r * p.SEGY + (int)((uintptr_t)(g0 + (int64_t)r * p.yrs) & 15) + xo * SB);
             const float* w = wx + col * p.NTXp;
             const int n = min(nx[col], segpx - xo);
             float a = 0.f;
-            for (int t = 0; t < n; ++t) a = fmaf(w[t], (float)s[t], a);
+            for (int t = 0; t < n; ++t) a = fmaf(w[t], fy_sample(s[t], p.shift), a);
             iy[(r0 + r) * p.TX + col] = a;
         }
     }
@@ -144,34 +160,35 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
     const int crmin = cymin[0], ccmin = cxmin[0];
     const int cnrows = min(cymin[ty - 1] + cny[ty - 1] - crmin, p.NRC);
     const int csegpx = min(cxmin[tx - 1] + cnx[tx - 1] - ccmin, p.SPC);
-    const int cplanes = p.cpix == 1 ? 2 : 1;
+    const int cplanes = p.cplanes, cstep = p.cpix / SB;   // cstep: samples between neighbours of one chroma plane
     const uint8_t* csrc = p.c + f * p.cfs + (int64_t)crmin * p.crs + (int64_t)ccmin * p.cpix;
     for (int r0 = 0; r0 < cnrows; r0 += FR_SR) {
         const int nr = min(FR_SR, cnrows - r0);
         const uint8_t* g0 = csrc + (int64_t)r0 * p.crs;
         __syncthreads();
-        fy_stage(stage, g0, p.cdelta, p.crs, cplanes, nr, csegpx * p.cpix, p.SEGC, tid);
+        fy_stage<S>(stage, g0, p.cdelta, p.crs, cplanes, nr, csegpx * p.cpix, p.SEGC, tid);
         __syncthreads();
         for (int it = tid; it < nr * tx; it += FR_THREADS) {
             const int col = it % tx, r = it / tx;
             const int xo = cxmin[col] - ccmin;
             const uint8_t* gs = g0 + (int64_t)r * p.crs;
-            const uint8_t *sb, *sr;
+            const uint8_t* b0 = stage + r * p.SEGC + (int)((uintptr_t)gs & 15) + xo * p.cpix;
+            const S *sb, *sr;
             if (cplanes == 1) {
-                sb = stage + r * p.SEGC + (int)((uintptr_t)gs & 15) + xo * 2 + p.ocb;
-                sr = sb - p.ocb + p.ocr;
+                sb = (const S*)(b0 + p.ocb);
+                sr = (const S*)(b0 + p.ocr);
             } else {
-                sb = stage + r * p.SEGC + (int)((uintptr_t)gs & 15) + xo;
-                sr = stage + (FR_SR + r) * p.SEGC + (int)((uintptr_t)(gs + p.cdelta) & 15) + xo;
+                sb = (const S*)b0;
+                sr = (const S*)(stage + (FR_SR + r) * p.SEGC + (int)((uintptr_t)(gs + p.cdelta) & 15) + xo * p.cpix);
             }
             const float* w = cwx + col * p.NCXp;
             const int n = min(cnx[col], csegpx - xo);
             float a0 = 0.f, a1 = 0.f;
             for (int t = 0; t < n; ++t) {
                 const float wt = w[t];
-                const int o = t * p.cpix;
-                a0 = fmaf(wt, (float)sb[o], a0);
-                a1 = fmaf(wt, (float)sr[o], a1);
+                const int o = t * cstep;
+                a0 = fmaf(wt, fy_sample(sb[o], p.shift), a0);
+                a1 = fmaf(wt, fy_sample(sr[o], p.shift), a1);
             }
             float* q = ic + (r0 + r) * 2 * p.TX + col;
             q[0] = a0;
@@ -202,8 +219,8 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
             }
         }
         const float yl = (yv - p.yoff) * p.ky;
-        cb -= 128.0f;
-        cr -= 128.0f;
+        cb -= p.cmid;
+        cr -= p.cmid;
         float v[3];
         v[0] = fmaf(p.krcr, cr, yl);
         v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
@@ -230,7 +247,7 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
 }
 
 int fy_stage_bytes(const FyParams& p) {
-    const int y = FR_SR * p.SEGY, c = (p.cpix == 1 ? 2 : 1) * FR_SR * p.SEGC;   // one buffer: luma chunks first, chroma chunks after them
+    const int y = FR_SR * p.SEGY, c = p.cplanes * FR_SR * p.SEGC;   // one buffer: luma chunks first, chroma chunks after them
     return y > c ? y : c;
 }
 
@@ -244,7 +261,7 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
     p.NRC = fr_max_span(p.cy, p.top, p.R, ty);
     p.SPY = fr_max_span(p.ax, p.left, p.R, tx);
     p.SPC = fr_max_span(p.cx, p.left, p.R, tx);
-    p.SEGY = ((p.SPY + 15) & ~15) + 16;
+    p.SEGY = ((p.SPY * p.sbytes + 15) & ~15) + 16;
     p.SEGC = ((p.SPC * p.cpix + 15) & ~15) + 16;
     int64_t o = (int64_t)tx * p.NTXp * 4;
     p.o_wy = (int)o;
@@ -267,44 +284,79 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
     if (o > FR_LDS_BUDGET) return false;
     // per output row: the source rows the horizontal pass computes, one luma plane and two chroma planes, plus the (cheaper) staged samples per output pixel -
     // the RGB planner's measure, where staging three planes weighs SEGPX / (tx * scale): a third of that per plane here
-    const double fx = p.ax.scale > 1.0 ? p.ax.scale : 1.0, fcx = p.ax.scale > 2.0 ? p.ax.scale / 2.0 : 1.0;
+    const double fx = p.ax.scale > 1.0 ? p.ax.scale : 1.0, fcx = p.ax.scale > p.cx.div ? p.ax.scale / p.cx.div : 1.0;
     cost = (double)p.NRY / ty * (1.0 + (double)p.SPY / (tx * fx) / 3.0) + (double)p.NRC / ty * (2.0 + 2.0 * p.SPC / (tx * fcx) / 3.0);
     return true;
 }
 
-}  // namespace
+// One launch of the instance for sample type S; the dynamic-LDS opt-in is a per-device attribute of each instance.
+template <typename S>
+int fy_launch(const FyParams& p, int64_t wgs, int lds, void* stream, const char* who) {
+    static std::atomic<uint64_t> have_lds{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
+        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+            rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
+            return RV_ERR_HIP;
+        }
+        have_lds.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(yuv_to_patches_kernel<S>, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    RV_CHECK_LAUNCH("yuv_to_patches");
+    return RV_OK;
+}
 
-extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_stride, const uint8_t* cb, const uint8_t* cr, int64_t c_frame_stride,
-                                 int64_t c_row_stride, int32_t c_pix, int32_t n, int32_t H, int32_t W, int32_t matrix, int32_t full_range, int32_t chroma_loc,
-                                 int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
-    RV_CHECK_ARG(c_pix == 1 || c_pix == 2, "rv_yuv_to_patches: c_pix = %d (1 = planar, 2 = interleaved)", c_pix);
-    RV_CHECK_ARG(matrix == 0 || matrix == 1, "rv_yuv_to_patches: matrix %d (0 = BT.601, 1 = BT.709)", matrix);
-    RV_CHECK_ARG(full_range == 0 || full_range == 1, "rv_yuv_to_patches: full_range %d (0 = studio, 1 = full)", full_range);
-    RV_CHECK_ARG(chroma_loc == 0 || chroma_loc == 1, "rv_yuv_to_patches: chroma_loc %d (0 = left, 1 = centre)", chroma_loc);
-    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "rv_yuv_to_patches: R = %d is not a multiple of patch = %d", R, patch);
-    RV_CHECK_ARG(H >= 2 && W >= 2 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "rv_yuv_to_patches: frame size %d x %d outside 2 .. %d", H, W, FR_MAX_SIDE);
-    RV_CHECK_ARG(H % 2 == 0 && W % 2 == 0, "rv_yuv_to_patches: frame size %d x %d is odd (4:2:0 chroma covers 2 x 2 luma samples)", H, W);
-    RV_CHECK_ARG(R <= FR_MAX_SIDE, "rv_yuv_to_patches: R = %d above %d", R, FR_MAX_SIDE);
-    RV_CHECK_ARG(n >= 0, "rv_yuv_to_patches: n = %d", n);
+// Both entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages.
+int fy_run(const rv_yuv_surface& s, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream,
+           const char* who) {
+    const int sb = s.sample_bytes, H = s.H, W = s.W, n = s.n;
+    RV_CHECK_ARG(sb == 1 || sb == 2, "%s: sample_bytes = %d (1, or 2 = little-endian 16-bit words)", who, sb);
+    RV_CHECK_ARG(sb == 1 ? s.depth == 8 : (s.depth >= 9 && s.depth <= 16), "%s: depth = %d does not go with sample_bytes = %d (8 with 1; 9 .. 16 with 2)", who,
+                 s.depth, sb);
+    RV_CHECK_ARG(s.msb_aligned == 0 || (s.msb_aligned == 1 && sb == 2), "%s: msb_aligned = %d (0 or 1, and 1 with 16-bit words only)", who, s.msb_aligned);
+    RV_CHECK_ARG((s.sub_x == 2 && s.sub_y == 2) || (s.sub_x == 2 && s.sub_y == 1) || (s.sub_x == 1 && s.sub_y == 1),
+                 "%s: sub_x, sub_y = %d, %d (2,2 = 4:2:0; 2,1 = 4:2:2; 1,1 = 4:4:4)", who, s.sub_x, s.sub_y);
+    RV_CHECK_ARG(s.c_pix == sb || s.c_pix == 2 * sb, "%s: c_pix = %d (%d = planar, %d = interleaved)", who, s.c_pix, sb, 2 * sb);
+    RV_CHECK_ARG(s.matrix >= 0 && s.matrix <= 2, "%s: matrix %d (0 = BT.601, 1 = BT.709, 2 = BT.2020 non-constant luminance)", who, s.matrix);
+    RV_CHECK_ARG(s.full_range == 0 || s.full_range == 1, "%s: full_range %d (0 = studio, 1 = full)", who, s.full_range);
+    RV_CHECK_ARG(s.chroma_loc >= 0 && s.chroma_loc <= 2, "%s: chroma_loc %d (0 = left, 1 = centre, 2 = top-left)", who, s.chroma_loc);
+    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
+    RV_CHECK_ARG(H >= s.sub_y && W >= s.sub_x && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside %d x %d .. %d", who, H, W, s.sub_y,
+                 s.sub_x, FR_MAX_SIDE);
+    RV_CHECK_ARG(H % s.sub_y == 0 && W % s.sub_x == 0, "%s: frame size %d x %d is odd (a chroma sample covers %d x %d luma samples)", who, H, W, s.sub_y, s.sub_x);
+    RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
+    RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
     if (n == 0) return RV_OK;
-    RV_CHECK_ARG(y && cb && cr, "rv_yuv_to_patches: null plane (y %p, cb %p, cr %p)", (const void*)y, (const void*)cb, (const void*)cr);
-    RV_CHECK_ARG(c_pix == 1 || (intptr_t)cr - (intptr_t)cb == 1 || (intptr_t)cb - (intptr_t)cr == 1, "rv_yuv_to_patches: c_pix = 2 takes interleaved planes (cr = cb + 1 or cb = cr + 1)");
-    RV_CHECK_ARG(patches || image, "rv_yuv_to_patches: both outputs null");
-    RV_CHECK_ARG(mean && std, "rv_yuv_to_patches: null mean / std");
+    const uint8_t *y = (const uint8_t*)s.y, *cb = (const uint8_t*)s.cb, *cr = (const uint8_t*)s.cr;
+    RV_CHECK_ARG(y && cb && cr, "%s: null plane (y %p, cb %p, cr %p)", who, s.y, s.cb, s.cr);
+    RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes)", who,
+                 s.c_pix, sb, sb);
+    RV_CHECK_ARG(sb == 1 || (((uintptr_t)y | (uintptr_t)cb | (uintptr_t)cr | (uintptr_t)s.y_frame_stride | (uintptr_t)s.y_row_stride |
+                               (uintptr_t)s.c_frame_stride | (uintptr_t)s.c_row_stride) & 1) == 0,
+                 "%s: 16-bit planes and strides must be aligned to 2 bytes (y %p, cb %p, cr %p, strides %lld %lld %lld %lld)", who, s.y, s.cb, s.cr,
+                 (long long)s.y_frame_stride, (long long)s.y_row_stride, (long long)s.c_frame_stride, (long long)s.c_row_stride);
+    RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
+    RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
     FyParams p{};
     p.K = 3 * patch * patch;
     p.Kp = (p.K + 127) / 128 * 128;
-    RV_CHECK_ARG(!patches || ldp >= p.Kp, "rv_yuv_to_patches: ldp = %lld below Kp = %d", (long long)ldp, p.Kp);
+    RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
     p.y = y;
-    p.yfs = y_frame_stride;
-    p.yrs = y_row_stride;
-    p.cfs = c_frame_stride;
-    p.crs = c_row_stride;
-    p.cpix = c_pix;
-    if (c_pix == 1) {
+    p.yfs = s.y_frame_stride;
+    p.yrs = s.y_row_stride;
+    p.cfs = s.c_frame_stride;
+    p.crs = s.c_row_stride;
+    p.cpix = s.c_pix;
+    p.sbytes = sb;
+    p.shift = s.msb_aligned ? 16 - s.depth : 0;
+    if (s.c_pix == sb) {
+        p.cplanes = 2;
         p.c = cb;
         p.cdelta = cr - cb;
     } else {
+        p.cplanes = 1;
         p.c = cb < cr ? cb : cr;
         p.ocb = (int)(cb - p.c);
         p.ocr = (int)(cr - p.c);
@@ -319,12 +371,16 @@ extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64
     p.left = (int)nearbyint((wr - R) / 2.0);
     p.ay = FrAxis{sy, 1.0, 0.0, H};
     p.ax = FrAxis{sx, 1.0, 0.0, W};
-    p.cy = FrAxis{sy, 2.0, 0.0, H / 2};
-    p.cx = FrAxis{sx, 2.0, chroma_loc == 0 ? 0.25 : 0.0, W / 2};
-    const double kr = matrix == 0 ? 0.299 : 0.2126, kb = matrix == 0 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-    const double cs = full_range ? 1.0 : 255.0 / 224.0;
-    p.yoff = full_range ? 0.0f : 16.0f;
-    p.ky = (float)(full_range ? 1.0 : 255.0 / 219.0);
+    // a subsampled axis whose chroma sample sits on the even luma sample lies a quarter of a chroma sample off: horizontally for left and top-left siting,
+    // vertically for top-left; an axis that is not subsampled is the luma axis
+    p.cy = FrAxis{sy, (double)s.sub_y, s.sub_y == 2 && s.chroma_loc == 2 ? 0.25 : 0.0, H / s.sub_y};
+    p.cx = FrAxis{sx, (double)s.sub_x, s.sub_x == 2 && s.chroma_loc != 1 ? 0.25 : 0.0, W / s.sub_x};
+    const double kr = s.matrix == 0 ? 0.299 : s.matrix == 1 ? 0.2126 : 0.2627, kb = s.matrix == 0 ? 0.114 : s.matrix == 1 ? 0.0722 : 0.0593, kg = 1.0 - kr - kb;
+    const double sc = (double)(1 << (s.depth - 8)), top = (double)((1 << s.depth) - 1);   // 2^(depth - 8); the largest code
+    const double cs = s.full_range ? 255.0 / top : 255.0 / (224.0 * sc);
+    p.yoff = s.full_range ? 0.0f : (float)(16.0 * sc);
+    p.cmid = (float)(128.0 * sc);
+    p.ky = (float)(s.full_range ? 255.0 / top : 255.0 / (219.0 * sc));
     p.krcr = (float)(2.0 * (1.0 - kr) * cs);
     p.kbcb = (float)(2.0 * (1.0 - kb) * cs);
     p.kgcb = (float)(-(2.0 * kb * (1.0 - kb) / kg) * cs);
@@ -352,22 +408,47 @@ extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64
             FyParams q = p;
             if (fy_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
         }
-    RV_CHECK_ARG(have, "rv_yuv_to_patches: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", H, W, R);
+    RV_CHECK_ARG(have, "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
-    RV_CHECK_ARG(wgs < (1ll << 31), "rv_yuv_to_patches: %lld workgroups (n = %d) exceed one launch", (long long)wgs, n);
+    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = best.o_stage + fy_stage_bytes(best);
-    static std::atomic<uint64_t> have_lds{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {   // the dynamic-LDS opt-in is a per-device attribute of the function
-        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
-            rv_set_error("rv_yuv_to_patches: cannot reserve %d bytes of LDS", FR_LDS_BUDGET);
-            return RV_ERR_HIP;
-        }
-        have_lds.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(yuv_to_patches_kernel, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), best);
-    RV_CHECK_LAUNCH("yuv_to_patches");
-    return RV_OK;
+    return sb == 1 ? fy_launch<uint8_t>(best, wgs, lds, stream, who) : fy_launch<uint16_t>(best, wgs, lds, stream, who);
+}
+
+}  // namespace
+
+extern "C" int rv_yuv_surface_to_patches(const rv_yuv_surface* s, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
+                                         float* image, void* stream) {
+    RV_CHECK_ARG(s, "rv_yuv_surface_to_patches: null surface");
+    return fy_run(*s, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
+}
+
+// The 8-bit 4:2:0 surface of the first entry point: its own two-valued matrix and chroma_loc, then the same code.
+extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_stride, const uint8_t* cb, const uint8_t* cr, int64_t c_frame_stride,
+                                 int64_t c_row_stride, int32_t c_pix, int32_t n, int32_t H, int32_t W, int32_t matrix, int32_t full_range, int32_t chroma_loc,
+                                 int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    RV_CHECK_ARG(c_pix == 1 || c_pix == 2, "rv_yuv_to_patches: c_pix = %d (1 = planar, 2 = interleaved)", c_pix);
+    RV_CHECK_ARG(matrix == 0 || matrix == 1, "rv_yuv_to_patches: matrix %d (0 = BT.601, 1 = BT.709)", matrix);
+    RV_CHECK_ARG(full_range == 0 || full_range == 1, "rv_yuv_to_patches: full_range %d (0 = studio, 1 = full)", full_range);
+    RV_CHECK_ARG(chroma_loc == 0 || chroma_loc == 1, "rv_yuv_to_patches: chroma_loc %d (0 = left, 1 = centre)", chroma_loc);
+    rv_yuv_surface s{};
+    s.y = y;
+    s.cb = cb;
+    s.cr = cr;
+    s.y_frame_stride = y_frame_stride;
+    s.y_row_stride = y_row_stride;
+    s.c_frame_stride = c_frame_stride;
+    s.c_row_stride = c_row_stride;
+    s.sample_bytes = 1;
+    s.depth = 8;
+    s.msb_aligned = 0;
+    s.c_pix = c_pix;
+    s.sub_x = s.sub_y = 2;
+    s.n = n;
+    s.H = H;
+    s.W = W;
+    s.matrix = matrix;
+    s.full_range = full_range;
+    s.chroma_loc = chroma_loc;
+    return fy_run(s, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
 }

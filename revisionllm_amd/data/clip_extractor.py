@@ -5,7 +5,8 @@ Differences from the reference, all at the IO edge: frames are handed over as te
 build) - either already at the towers' resolution [T,3,R,R] (what its ``VideoLoader`` produces from ffmpeg's scale + crop), or as
 decoded uint8 frames of any size, NCHW or NHWC, in one tensor or in chunks: those are resized, centre-cropped, normalised and
 unfolded on the device by one kernel (``ops.frames_to_patches``; the reference's Resize / CenterCrop / Normalize,
-inference.py:108-117) - or as the 4:2:0 YCbCr bytes a decoder really emits (NV12 / NV21 / I420; ``encode_video_yuv``, ``ops.yuv_to_patches``), which are
+inference.py:108-117) - or as the YCbCr bytes a decoder really emits (8-bit 4:2:0 NV12 / NV21 / I420: ``encode_video_yuv``, ``ops.yuv_to_patches``; 10 / 12 /
+16-bit words, 4:2:2 and 4:4:4 by ffmpeg's pix_fmt name: ``encode_video_pix_fmt``, ``ops.yuv_surface_to_patches``), which are
 resampled plane by plane and converted per output pixel in one kernel of the same shape.  The CLIP weights come from ``ClipTowers`` (a loaded checkpoint or synthetic).  The on-disk format of the results is what ``data.feature_store`` reads back (f-2).
 """
 import math
@@ -28,6 +29,12 @@ def preprocess(frames):
 def yuv_colour_defaults(H):
     """What ffmpeg (swscale) assumes for a stream that carries no colour tags: BT.601 below 720 lines, BT.709 from 720 on; studio range; chroma sited left."""
     return dict(matrix="bt601" if H < 720 else "bt709", full_range=False, chroma_loc="left")
+
+
+def yuv_surface_colour_defaults(H, bt2020=False):
+    """``yuv_colour_defaults(H)`` for a stream that carries no colour tags; for one the caller knows to be BT.2020 (HEVC Main10 / AV1 10-bit UHD): its
+    non-constant-luminance matrix, studio range and the top-left chroma siting that is BT.2020's default for 4:2:0."""
+    return dict(matrix="bt2020", full_range=False, chroma_loc="topleft") if bt2020 else yuv_colour_defaults(H)
 
 
 class ClipFeatureExtractor:
@@ -66,6 +73,22 @@ class ClipFeatureExtractor:
         colour = {**yuv_colour_defaults(H), **colour}
         out = [tw.encode_frames_yuv(*ops.split_yuv420(b, H, W, fmt), **colour)
                for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]")]
+        return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+
+    @torch.no_grad()
+    def encode_video_pix_fmt(self, chunks, H, W, pix_fmt, bsz=60, **colour):
+        """-> f32 [T, d] from the bytes of a rawvideo pipe in any of ``ops.PIX_FMTS`` (``ffmpeg -f rawvideo -pix_fmt p010le | yuv420p10le | nv16 | yuv444p10le
+        ...``): ``chunks`` is one uint8 buffer [t, ops.yuv_frame_bytes(H, W, pix_fmt)] or an iterable of them, CPU or device.  They are regrouped into
+        batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv``) and go through ``encode_surfaces_yuv``: no conversion pass, no RGB
+        frame.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_surface_colour_defaults``; ``matrix="bt2020"`` says the stream is
+        BT.2020 and brings top-left siting with it."""
+        tw = self.clip_extractor
+        fb = ops.yuv_frame_bytes(H, W, pix_fmt)
+        colour = {**yuv_surface_colour_defaults(H, bt2020=colour.get("matrix") == "bt2020"), **colour}
+        out = []
+        for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=2, shapes=f"[t,{fb}]"):
+            planes, kw = ops.split_yuv(b, H, W, pix_fmt)
+            out.append(tw.encode_surfaces_yuv(*planes, **kw, **colour))
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
 
     def _batches(self, chunks, bsz, ndim=4, shapes="[t,3,H,W] or [t,H,W,3]"):

@@ -108,6 +108,14 @@ class ClipTowers:
         patches, _ = ops.yuv_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **colour)
         return self._encode_patches(patches, y.shape[0])
 
+    @torch.no_grad()
+    def encode_surfaces_yuv(self, y, cb, cr=None, **surface):
+        """Decoded frames of any surface ``ops.yuv_surface_to_patches`` takes (uint8 or uint16 planes on the device; ``surface``: its ``depth`` /
+        ``msb_aligned`` / ``subsampling`` / ``matrix`` / ``full_range`` / ``chroma_loc``) -> f32 [n, embed_dim], as ``encode_frames_yuv``."""
+        c = self.cfg
+        patches, _ = ops.yuv_surface_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
+        return self._encode_patches(patches, y.shape[0])
+
     def _encode_patches(self, patches, n):
         """patches [n*g*g, Kp] operand type (the unfolded, K-padded frames) -> f32 [n, embed_dim]: conv1 as a GEMM and everything behind it."""
         c, w = self.cfg, self.w

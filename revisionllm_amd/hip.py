@@ -39,6 +39,14 @@ class RvPrefillGroup(C.Structure):
     _fields_ = [("B", C.c_int32), ("P0", C.c_int32), ("S", C.c_int32), ("kv_row0", C.c_int32)]
 
 
+class RvYuvSurface(C.Structure):
+    """``rv_yuv_surface``: the planes, strides (bytes), sample format, subsampling and colour tags of a decoder surface (rv_yuv_surface_to_patches)."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("y_frame_stride", C.c_int64), ("y_row_stride", C.c_int64),
+                ("c_frame_stride", C.c_int64), ("c_row_stride", C.c_int64), ("sample_bytes", C.c_int32), ("depth", C.c_int32), ("msb_aligned", C.c_int32),
+                ("c_pix", C.c_int32), ("sub_x", C.c_int32), ("sub_y", C.c_int32), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("matrix", C.c_int32), ("full_range", C.c_int32), ("chroma_loc", C.c_int32)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -111,6 +119,7 @@ SIGNATURES = {
     "rv_frames_to_patches": (C.c_int, [_p, C.c_int, _i64, _i64, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
     "rv_yuv_to_patches": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p,
                                     _i64, _p, _p]),
+    "rv_yuv_surface_to_patches": (C.c_int, [C.POINTER(RvYuvSurface), _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
     "rv_project_dense": (C.c_int, [_p, _p, _p, C.c_int, _i64, _p]),
     "rv_clip_encoder_ws_bytes": (_sz, [_p, _i32, _i32, _i32, _i32]),
     "rv_clip_encoder": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),

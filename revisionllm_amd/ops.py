@@ -377,6 +377,116 @@ def split_yuv420(buf, H, W, fmt):
     return (y, pairs, None) if fmt == "nv12" else (y, pairs[..., 1], pairs[..., 0])
 
 
+_SURFACE_MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}
+_SURFACE_LOCS = {"left": 0, "centre": 1, "topleft": 2}
+_SUBSAMPLINGS = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}
+#: ffmpeg's pix_fmt names -> (bytes per sample, depth, value in the high bits, subsampling, chroma layout: "planar" Cb plane then Cr plane | "cbcr" | "crcb"
+#: interleaved pairs)
+PIX_FMTS = {
+    "nv12": (1, 8, False, "420", "cbcr"), "nv21": (1, 8, False, "420", "crcb"), "nv16": (1, 8, False, "422", "cbcr"), "nv24": (1, 8, False, "444", "cbcr"),
+    "yuv420p": (1, 8, False, "420", "planar"), "yuv422p": (1, 8, False, "422", "planar"), "yuv444p": (1, 8, False, "444", "planar"),
+    "yuv420p10le": (2, 10, False, "420", "planar"), "yuv422p10le": (2, 10, False, "422", "planar"), "yuv444p10le": (2, 10, False, "444", "planar"),
+    "yuv420p12le": (2, 12, False, "420", "planar"), "yuv444p12le": (2, 12, False, "444", "planar"), "yuv420p16le": (2, 16, False, "420", "planar"),
+    "p010le": (2, 10, True, "420", "cbcr"), "p016le": (2, 16, True, "420", "cbcr"), "p210le": (2, 10, True, "422", "cbcr"), "p410le": (2, 10, True, "444", "cbcr"),
+}
+
+
+def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=False, subsampling="420", matrix="bt601", full_range=False, chroma_loc="left",
+                           mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",)):
+    """Decoded YCbCr frames of any planar / semi-planar surface -> the CLIP front end in one launch (rv_yuv_surface_to_patches; the header has the definition of
+    the values) -> (patches, image) as ``frames_to_patches`` returns them.
+    Planes are ``torch.uint8`` (depth 8) or ``torch.uint16`` (depth 9 .. 16; ``msb_aligned``: the value sits in the high bits of the word, as in P010 /
+    P016) device tensors, all of one dtype.  y [n,H,W]; with ``subsampling`` "420" | "422" | "444" the chroma planes hold h x w = H/2 x W/2 | H x W/2 | H x W
+    samples (H, W even along a halved axis only), either of
+      * ``cb`` [n,h,w,2] with ``cr=None``: interleaved CbCr (NV12, NV16, P010 ...);
+      * ``cb`` and ``cr`` [n,h,w] each: two planes, or two views one sample apart with a sample stride of 2 (as ``split_yuv`` hands over NV21): those are
+        read as the interleaved surface they are.
+    Planes are passed by their strides when each row's samples are adjacent (a window of a larger decode surface, a padded pitch); any other view is copied
+    first.  matrix "bt601" | "bt709" | "bt2020" (the non-constant-luminance matrix alone: no transfer conversion); full_range False = studio; chroma_loc
+    "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1) | "topleft" (BT.2020 / HEVC 4:2:0)."""
+    for t in (y, cb) + (() if cr is None else (cr,)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise hip.HipLibraryError("yuv_surface_to_patches needs device tensors (got a CPU tensor); there is no CPU path")
+        if t.dtype not in (torch.uint8, torch.uint16) or t.dtype != y.dtype:
+            raise hip.HipLibraryError(f"yuv_surface_to_patches takes planes of one dtype, uint8 or uint16, got {t.dtype} {tuple(t.shape)}")
+    if matrix not in _SURFACE_MATRICES or chroma_loc not in _SURFACE_LOCS or subsampling not in _SUBSAMPLINGS:
+        raise ValueError(f"matrix {matrix!r} / chroma_loc {chroma_loc!r} / subsampling {subsampling!r}: one of {sorted(_SURFACE_MATRICES)} / "
+                         f"{sorted(_SURFACE_LOCS)} / {sorted(_SUBSAMPLINGS)}")
+    sx, sy = _SUBSAMPLINGS[subsampling]
+    if y.dim() != 3 or y.shape[1] % sy or y.shape[2] % sx:
+        raise hip.HipLibraryError(f"yuv_surface_to_patches takes a Y plane [n,H,W] with H a multiple of {sy} and W of {sx} ({subsampling}), got {tuple(y.shape)}")
+    n, H, W = y.shape
+    h, w, es = H // sy, W // sx, y.element_size()
+    if cr is None:
+        if tuple(cb.shape) != (n, h, w, 2):
+            raise hip.HipLibraryError(f"interleaved CbCr of {n} frames {H} x {W} ({subsampling}) is [{n},{h},{w},2], got {tuple(cb.shape)}")
+        if not (cb.stride(3) == 1 and _rows_of_samples(cb, n, h, w, 2)):
+            cb = cb.contiguous()
+        cb, cr = cb[..., 0], cb[..., 1]
+    elif tuple(cb.shape) != (n, h, w) or tuple(cr.shape) != (n, h, w):
+        raise hip.HipLibraryError(f"Cb and Cr of {n} frames {H} x {W} ({subsampling}) are [{n},{h},{w}] each, got {tuple(cb.shape)} and {tuple(cr.shape)}")
+    if not _rows_of_samples(y, n, H, W, 1):
+        y = y.contiguous()
+    # cb, cr: [n,h,w] views from here on; one stride pair serves both planes.  Strides are in samples up to the call.
+    if abs(cb.data_ptr() - cr.data_ptr()) == es and cb.stride() == cr.stride() and _rows_of_samples(cb, n, h, w, 2):
+        c_pix = 2
+    else:
+        c_pix = 1
+        if not (cb.stride() == cr.stride() and _rows_of_samples(cb, n, h, w, 1)):
+            cb, cr = cb.contiguous(), cr.contiguous()
+    yfs, yrs = _plane_strides(y, n, H, W, 1)
+    cfs, crs = _plane_strides(cb, n, h, w, c_pix)
+    dt = hip.op_dtype(op_dtype)
+    g = R // max(patch, 1)
+    kp = (3 * patch * patch + 127) // 128 * 128
+    patches = torch.empty(n * g * g, kp, dtype=dt, device=y.device) if "patches" in want else None
+    image = torch.empty(n, 3, R, R, dtype=torch.float32, device=y.device) if "image" in want else None
+    s = hip.RvYuvSurface(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), yfs * es, yrs * es, cfs * es, crs * es, es, int(depth), int(bool(msb_aligned)), c_pix * es,
+                         sx, sy, n, H, W, _SURFACE_MATRICES[matrix], int(bool(full_range)), _SURFACE_LOCS[chroma_loc])
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_yuv_surface_to_patches(hip.C.byref(s), R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp, hip.ptr(image), hip.stream()),
+              "rv_yuv_surface_to_patches")
+    return patches, image
+
+
+def yuv_frame_bytes(H, W, pix_fmt):
+    """Bytes of one ``H`` x ``W`` frame of a rawvideo pipe in ffmpeg's ``pix_fmt`` (one of ``PIX_FMTS``)."""
+    if pix_fmt not in PIX_FMTS:
+        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(PIX_FMTS)}")
+    sb, _, _, sub, _ = PIX_FMTS[pix_fmt]
+    sx, sy = _SUBSAMPLINGS[sub]
+    if H < sy or W < sx or H % sy or W % sx:
+        raise ValueError(f"{pix_fmt} frames ({sub}) have H a multiple of {sy} and W a multiple of {sx}, got {H} x {W}: odd along a subsampled axis")
+    return (H * W + 2 * (H // sy) * (W // sx)) * sb
+
+
+def split_yuv(buf, H, W, pix_fmt):
+    """The bytes of a rawvideo pipe (``ffmpeg -f rawvideo -pix_fmt <one of PIX_FMTS>``) -> ``((y, cb, cr_or_None), kw)``: zero-copy views of the planes (uint8,
+    or uint16 for the 16-bit formats) and the keyword arguments (``depth``, ``msb_aligned``, ``subsampling``) that go with them, so that
+    ``yuv_surface_to_patches(*planes, R=R, patch=patch, **kw, **colour)`` reads the buffer as it lies.  buf: uint8 [n, yuv_frame_bytes(H, W, pix_fmt)], CPU
+    or device, each frame's bytes adjacent.  Interleaved CbCr comes as ``cb`` [n,h,w,2] with ``cr`` None; CrCb (nv21) as two views one sample apart."""
+    fb = yuv_frame_bytes(H, W, pix_fmt)
+    sb, depth, msb, sub, layout = PIX_FMTS[pix_fmt]
+    if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.dim() != 2 or buf.shape[1] != fb:
+        raise ValueError(f"{pix_fmt} frames of {H} x {W} come as a uint8 tensor [n,{fb}], got "
+                         + (f"{buf.dtype} {tuple(buf.shape)}" if torch.is_tensor(buf) else type(buf).__name__))
+    if buf.stride(1) != 1:
+        raise ValueError("split_yuv returns views: the bytes of each frame must be adjacent (a padded surface is passed to yuv_surface_to_patches plane by plane)")
+    if sb == 2:
+        if buf.stride(0) % 2 or buf.storage_offset() % 2:
+            raise ValueError(f"{pix_fmt}: 16-bit words must be adjacent bytes at an even offset (frame stride {buf.stride(0)}, offset {buf.storage_offset()})")
+        buf = buf.view(torch.uint16)
+    sx, sy = _SUBSAMPLINGS[sub]
+    n, h, w = buf.shape[0], H // sy, W // sx
+    fs, at = buf.stride(0), buf.storage_offset()
+    y = buf.as_strided((n, H, W), (fs, W, 1), at)
+    kw = dict(depth=depth, msb_aligned=msb, subsampling=sub)
+    if layout == "planar":
+        return (y, buf.as_strided((n, h, w), (fs, w, 1), at + H * W), buf.as_strided((n, h, w), (fs, w, 1), at + H * W + h * w)), kw
+    pairs = buf.as_strided((n, h, w, 2), (fs, 2 * w, 2, 1), at + H * W)
+    return ((y, pairs, None) if layout == "cbcr" else (y, pairs[..., 1], pairs[..., 0])), kw
+
+
 def h2d(t, device, dtype=None):
     """Host -> device without stalling the host: a pageable ``.to(device)`` blocks until everything queued before it has
     run (the launch queue then runs dry after every upload); a pinned, non-blocking copy just joins the stream."""

@@ -7,7 +7,11 @@ forms run in one process, alternating, each launch between two device events: 5 
 yuv / rgb (the yardstick: the RGB entry on the same box; the YUV entry reads half the bytes and filters half the plane area), and the source bytes the crop
 uses over the YUV call's median as a fraction of the 8 TB/s HBM figure.  Writes one JSON object to --out (default profiles/frontend_yuv_1080p.json).
 
-    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--out FILE] [--once]   (--once: one YUV launch, for a kernel trace)"""
+--pix-fmt NAME (one of ops.PIX_FMTS: p010le, yuv444p10le, nv16 ...) times rv_yuv_surface_to_patches on noise frames of that format instead, alone, with the
+same warm-up and launch counts: median, min .. max, and the source bytes the crop uses over the median.  ``--pix-fmt nv12`` is the same bytes as the default
+run through the surface entry, for a like-for-like figure next to P010.
+
+    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME] [--out FILE] [--once]   (--once: one launch, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -62,6 +66,39 @@ def timed(fn):
     return a.elapsed_time(b) * 1e-3, out
 
 
+def surface_run(a, dt):
+    """--pix-fmt: the surface entry alone on one format."""
+    n, H, W, R = a.frames, a.height, a.width, a.res
+    fb = ops.yuv_frame_bytes(H, W, a.pix_fmt)
+    buf = torch.randint(0, 256, (n, fb), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+    sb, depth, msb, sub, _ = ops.PIX_FMTS[a.pix_fmt]
+    if sb == 2 and not msb and depth < 16:      # value in the low bits: keep the words inside [0, 2^depth) as a decoder would
+        buf[:, 1::2] &= (1 << (depth - 8)) - 1
+    planes, kw = ops.split_yuv(buf.cuda(), H, W, a.pix_fmt)
+    colour = dict(matrix="bt709", full_range=False, chroma_loc="left")
+    call = lambda: ops.yuv_surface_to_patches(*planes, R=R, patch=a.patch, op_dtype=dt, **kw, **colour)[0]
+    if a.once:
+        call()
+        torch.cuda.synchronize()
+        return
+    t = []
+    for i in range(a.warmup + a.iters):
+        s, _ = timed(call)
+        if i >= a.warmup:
+            t.append(s)
+    med = statistics.median(t)
+    sx, sy = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}[sub]
+    used = n * (min(H, W) ** 2 + 2 * (min(H, W) // sx) * (min(H, W) // sy)) * sb      # the centred square of every plane
+    res = dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), pix_fmt=a.pix_fmt, frames=n, height=H, width=W, res=R, patch=a.patch,
+               warmup=a.warmup, iters=a.iters, yuv_ms=dict(median=med * 1e3, min=min(t) * 1e3, max=max(t) * 1e3), used_source_bytes=used,
+               yuv_bytes_per_s=used / med, yuv_fraction_of_8TBps=used / med / HBM_PEAK)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
@@ -73,9 +110,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_yuv_1080p.json"))
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--pix-fmt", default=None, help="time rv_yuv_surface_to_patches on this ffmpeg pix_fmt instead (ops.PIX_FMTS)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "frontend_yuv_prof needs the GPU: a CPU run says nothing about time"
     dt = hip.op_dtype()
+    if a.pix_fmt is not None:
+        return surface_run(a, dt)
     n, H, W, R = a.frames, a.height, a.width, a.res
     buf = torch.randint(0, 256, (n, H * 3 // 2, W), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).cuda()
     y, cbcr, _ = ops.split_yuv420(buf, H, W, "nv12")
