@@ -304,7 +304,8 @@ int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_st
  *            c = (C' - 128 s) * 255 / (2^depth - 1); then rv_yuv_to_patches' Rv / Gv / Bv equations with the matrix's Kr, Kb (matrix 2: BT.2020
  *            non-constant luminance, Kr 0.2627, Kb 0.0593); the five coefficients are computed in f64 and rounded once to f32
  *   norm     (v / 255 - mean[c]) / (std[c] + 1e-8); crop, image and patches laid out, rounded once and zero-padded exactly as by rv_frames_to_patches
- * matrix 2 applies the BT.2020 MATRIX only: there is no PQ / HLG transfer conversion and no tone mapping, so HDR-coded values reach CLIP as coded.
+ * matrix 2 applies the BT.2020 MATRIX only: this entry converts no transfer function and maps no tones, so PQ / HLG-coded values would reach CLIP as coded -
+ * HDR surfaces go through rv_yuv_surface_to_patches_hdr (below), which converts them to SDR inside the same kernel.
  * Not taken: packed 4:2:2 (YUY2 / Y210), 4:1:1, big-endian words, alpha planes.
  * Refused (RV_ERR_ARG, nothing launched): a null struct or plane; sample_bytes outside {1, 2}; a depth that does not go with it; msb_aligned outside {0, 1}, or 1
  * with sample_bytes 1; (sub_x, sub_y) outside the three pairs; H or W odd along a subsampled axis (odd sizes are legal along an axis with sub = 1), below sub or
@@ -326,6 +327,41 @@ typedef struct rv_yuv_surface {
 } rv_yuv_surface;
 int rv_yuv_surface_to_patches(const rv_yuv_surface* s, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                               float* image, void* stream);
+
+/* rv_yuv_surface_to_patches on an HDR surface (BT.2100 PQ or HLG, typically P010 / yuv420p10le with matrix 2): the same kernel, the same resampling and
+ * YCbCr -> R'G'B' equations, then per OUTPUT pixel a conversion to BT.709-coded SDR values in front of the normalisation.  No pass over the source is added.
+ * Values (f32 throughout); E'c = v[c] / 255 of the colour step above, with no clamp up to here:
+ *   1 clamp    E' = clamp(E'c, 0, 1) per channel
+ *   2 transfer to display light F in nits, Lw = peak_nits
+ *              PQ (SMPTE ST 2084)  m1 = 2610/16384, m2 = 2523/4096*128, c1 = 3424/4096, c2 = 2413/4096*32, c3 = 2392/4096*32; p = E'^(1/m2);
+ *                                  F = 10000 * (max(p - c1, 0) / (c2 - c3 p))^(1/m1), clamped to [0, Lw]
+ *              HLG (ARIB STD-B67 / BT.2100)  a = 0.17883277, b = 1 - 4a, c = 0.5 - a ln(4a); scene light E = E'^2 / 3 for E' <= 0.5, else
+ *                                  (exp((E' - c) / a) + b) / 12; Ys = 0.2627 Er + 0.6780 Eg + 0.0593 Eb; gamma = 1.2 + 0.42 log10(Lw / 1000);
+ *                                  F = Lw * Ys^(gamma - 1) * E, and 0 where Ys = 0
+ *   3 tone map the BT.2390 EETF on the brightest channel (hue-preserving), black level 0, Lt = sdr_white_nits;
+ *              PQinv(Y) = ((c1 + c2 y) / (1 + c3 y))^m2 with y = (Y / 10000)^m1; mx = max(Fr, Fg, Fb); e = PQinv(mx) / PQinv(Lw);
+ *              maxLum = PQinv(Lt) / PQinv(Lw); KS = 1.5 maxLum - 0.5; if KS >= 1, e <= KS or mx = 0 the ratio is 1 (so peak_nits <= sdr_white_nits maps no
+ *              tones); otherwise t = (e - KS) / (1 - KS), e2 = (2t^3 - 3t^2 + 1) KS + (t^3 - 2t^2 + t)(1 - KS) + (-2t^3 + 3t^2) maxLum,
+ *              ratio = PQ_EOTF(e2 * PQinv(Lw)) / mx; L = F * ratio / Lt per channel
+ *   4 gamut    gamut = 1: BT.2020 -> BT.709 primaries with BT.2087's matrix (rows 1.6605 -0.5876 -0.0728 / -0.1246 1.1329 -0.0083 / -0.0182 -0.1006 1.1187);
+ *              gamut = 0: none; then clamp to [0, 1]
+ *   5 OETF     BT.709's, not a pure power: V = 4.5 L for L < 0.018, else 1.099 L^0.45 - 0.099; v[c] = 255 V.  The linear toe keeps the slope finite at black,
+ *              and it is how SDR video, which the other entries pass as coded, was encoded.
+ *   6 norm     crop, normalisation, rounding, image and patch layout and zero padding exactly as by rv_yuv_surface_to_patches
+ * Constants that are quotients, and the scalars that depend on peak_nits / sdr_white_nits (1 / Lt, PQinv(Lw), maxLum, KS, gamma - 1), are computed in f64 and
+ * rounded once to f32; powers are exp2(k * log2(x)) in f32.  This is the library's OWN definition, as the SDR one is; no parity with another tool is claimed.
+ * No dynamic metadata is read: no MaxCLL / mastering-display parsing, no Dolby Vision, no inverse tone mapping.  peak_nits is the caller's number (1000 is the
+ * usual HDR10 grade and HLG's nominal peak; 203 is BT.2408's reference white).
+ * Refused (RV_ERR_ARG, nothing launched): a null map; transfer outside {1, 2}; gamut outside {0, 1}; peak_nits or sdr_white_nits not finite or outside
+ * 1 .. 10000; and everything rv_yuv_surface_to_patches refuses.  n = 0 returns 0 and launches nothing. */
+typedef struct rv_hdr_map {
+    int32_t transfer;                 /* 1 PQ (SMPTE ST 2084), 2 HLG (ARIB STD-B67) */
+    int32_t gamut;                    /* 0 none, 1 BT.2020 -> BT.709 primaries */
+    float peak_nits;                  /* Lw: the display peak the content was graded for */
+    float sdr_white_nits;             /* Lt: the luminance that becomes SDR white (1.0) */
+} rv_hdr_map;
+int rv_yuv_surface_to_patches_hdr(const rv_yuv_surface* s, const rv_hdr_map* m, int32_t R, int32_t patch, const float mean[3], const float std[3],
+                                  void* patches, int64_t ldp, float* image, void* stream);
 
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */

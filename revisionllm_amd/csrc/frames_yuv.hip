@@ -23,6 +23,25 @@
 // This is the project's OWN definition: the chroma planes are resampled directly, which is linear and exact.  It is NOT swscale's integer conversion to
 // rgb24 followed by a resize, and no parity with ffmpeg's RGB bytes is claimed.
 //
+//
+// HDR surfaces (rv_yuv_surface_to_patches_hdr): PQ- or HLG-coded BT.2100 values are converted to SDR BT.709-coded values per OUTPUT pixel, between the colour
+// matrix and the normalisation.  The library's own definition again (include/revision_hip.h has it in full); E'c = v[c] / 255 with no clamp up to here:
+//   1 clamp    E' = clamp(E'c, 0, 1) per channel
+//   2 transfer to display light F in nits, Lw = peak_nits
+//              PQ (ST 2084)  m1 = 2610/16384, m2 = 2523/4096*128, c1 = 3424/4096, c2 = 2413/4096*32, c3 = 2392/4096*32; p = E'^(1/m2);
+//                            F = 10000 (max(p - c1, 0) / (c2 - c3 p))^(1/m1), clamped to [0, Lw]
+//              HLG (B67)     a = 0.17883277, b = 1 - 4a, c = 0.5 - a ln(4a); scene light E = E'^2 / 3 for E' <= 0.5, else (exp((E' - c) / a) + b) / 12;
+//                            Ys = 0.2627 Er + 0.6780 Eg + 0.0593 Eb; gamma = 1.2 + 0.42 log10(Lw / 1000); F = Lw Ys^(gamma - 1) E, 0 where Ys = 0
+//   3 tone map BT.2390 EETF on the brightest channel, black level 0, Lt = sdr_white_nits; PQinv(Y) = ((c1 + c2 y) / (1 + c3 y))^m2, y = (Y / 10000)^m1;
+//              mx = max(Fr, Fg, Fb), e = PQinv(mx) / PQinv(Lw), maxLum = PQinv(Lt) / PQinv(Lw), KS = 1.5 maxLum - 0.5; ratio = 1 when KS >= 1, e <= KS or
+//              mx = 0; else t = (e - KS) / (1 - KS), e2 = (2t^3 - 3t^2 + 1) KS + (t^3 - 2t^2 + t)(1 - KS) + (-2t^3 + 3t^2) maxLum,
+//              ratio = PQ_EOTF(e2 PQinv(Lw)) / mx; L = F ratio / Lt per channel
+//   4 gamut    gamut = 1: BT.2087's BT.2020 -> BT.709 matrix (1.6605 -0.5876 -0.0728 / -0.1246 1.1329 -0.0083 / -0.0182 -0.1006 1.1187), gamut = 0: none;
+//              then clamp to [0, 1]
+//   5 OETF     BT.709's, with its linear toe: V = 4.5 L for L < 0.018, else 1.099 L^0.45 - 0.099; v[c] = 255 V
+// Powers are exp2f(k * log2f(x)); constants that are quotients are evaluated in f64 and rounded once to f32; the scalars that depend on peak_nits /
+// sdr_white_nits (1 / Lt, PQinv(Lw), maxLum, KS, gamma - 1) are computed on the host in f64.  No dynamic metadata is read; peak_nits is the caller's number.
+//
 // The kernel follows frames_to_patches_kernel.  One workgroup owns TY x TX output pixels of one frame:
 //   phase 0  four tap tables (luma x / y, chroma x / y: first tap, count, normalised f32 weights; computed in f64) into LDS
 //   phase 1  per chunk of FR_SR source rows, first of the Y plane, then of the chroma planes: stage the bytes the tile needs in LDS (16-byte loads where the
@@ -30,7 +49,8 @@
 //            f32 LDS rows  interY[source row][column],  interC[chroma row][Cb | Cr][column]
 //   phase 2  vertical pass over both, colour matrix, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
 // At 4:2:0: half the horizontal-pass work of three RGB planes (one full plane + two quarter planes filtered with half the taps), and two thirds of its
-// `inter` rows.  The kernel is compiled per sample type (uint8_t; uint16_t with a run-time shift), so the 8-bit instance is the 8-bit kernel it was.
+// `inter` rows.  The kernel is compiled per sample type (uint8_t; uint16_t with a run-time shift), so the 8-bit instance is the 8-bit kernel it was, and per
+// transfer (TRC: 0 = none, 1 = PQ, 2 = HLG): the HDR steps exist in the HDR instances only, the TRC = 0 instances are the code they were.
 #include <atomic>
 
 #include "frames_taps.h"   // fp contraction is off from there on
@@ -53,7 +73,68 @@ struct FyParams {
     op16_t* patches;
     int64_t ldp;
     float* image;
+    // HDR instances only (behind everything the TRC = 0 instances read): Lw, 1 / Lt, PQinv(Lw), maxLum, KS, gamma - 1, the gamut matrix by rows (or the identity)
+    float Lw, rLt, pqLw, maxLum, KS, gm1, gam[9];
 };
+
+// ---- HDR -> SDR per output pixel (the head of the file has the definition) ---------------------------------------------------------------------------
+constexpr int FY_TRC_NONE = 0, FY_TRC_PQ = 1, FY_TRC_HLG = 2;
+constexpr double PQ_M1_D = 2610.0 / 16384.0, PQ_M2_D = 2523.0 / 4096.0 * 128.0, PQ_C1_D = 3424.0 / 4096.0, PQ_C2_D = 2413.0 / 4096.0 * 32.0,
+                 PQ_C3_D = 2392.0 / 4096.0 * 32.0;
+constexpr float PQ_M1 = (float)PQ_M1_D, PQ_M2 = (float)PQ_M2_D, PQ_RM1 = (float)(1.0 / PQ_M1_D), PQ_RM2 = (float)(1.0 / PQ_M2_D), PQ_C1 = (float)PQ_C1_D,
+                PQ_C2 = (float)PQ_C2_D, PQ_C3 = (float)PQ_C3_D;
+constexpr double HLG_A_D = 0.17883277, HLG_B_D = 1.0 - 4.0 * HLG_A_D, HLG_LN4A_D = -0.3350097945111627;   // ln(4a)
+constexpr float HLG_B = (float)HLG_B_D, HLG_C = (float)(0.5 - HLG_A_D * HLG_LN4A_D), HLG_K = (float)(1.4426950408889634 / HLG_A_D);   // log2(e) / a
+
+// x^k, x >= 0 and k > 0 (0 -> 0: log2f gives -inf, exp2f of it 0)
+__device__ inline float fy_pow(float x, float k) { return exp2f(k * log2f(x)); }
+
+// ST 2084: code value in [0, 1] -> nits, and back
+__device__ inline float fy_pq_eotf(float e) {
+    const float p = fy_pow(e, PQ_RM2);
+    return 10000.0f * fy_pow(fmaxf(p - PQ_C1, 0.0f) / (PQ_C2 - PQ_C3 * p), PQ_RM1);
+}
+__device__ inline float fy_pq_inv(float nits) {
+    const float y = fy_pow(nits / 10000.0f, PQ_M1);
+    return fy_pow((PQ_C1 + PQ_C2 * y) / (1.0f + PQ_C3 * y), PQ_M2);
+}
+
+// Steps 1 to 5 on the three values of one output pixel, in place (v / 255 = E'c on entry, the BT.709-coded SDR value on exit).
+template <int TRC>
+__device__ inline void fy_hdr_to_sdr(float v[3], const FyParams& p) {
+    float F[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) F[c] = fminf(fmaxf(v[c] / 255.0f, 0.0f), 1.0f);
+    if (TRC == FY_TRC_PQ) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) F[c] = fminf(fmaxf(fy_pq_eotf(F[c]), 0.0f), p.Lw);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) F[c] = F[c] <= 0.5f ? F[c] * F[c] / 3.0f : (exp2f((F[c] - HLG_C) * HLG_K) + HLG_B) / 12.0f;
+        const float ys = 0.2627f * F[0] + 0.6780f * F[1] + 0.0593f * F[2];
+        const float sys = ys > 0.0f ? p.Lw * fy_pow(ys, p.gm1) : 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) F[c] = sys * F[c];
+    }
+    const float mx = fmaxf(F[0], fmaxf(F[1], F[2]));
+    float ratio = 1.0f;
+    if (p.KS < 1.0f && mx > 0.0f) {
+        const float e = fy_pq_inv(mx) / p.pqLw;
+        if (e > p.KS) {
+            const float omk = 1.0f - p.KS, t = (e - p.KS) / omk, t2 = t * t, t3 = t2 * t;
+            const float e2 = (2.0f * t3 - 3.0f * t2 + 1.0f) * p.KS + (t3 - 2.0f * t2 + t) * omk + (-2.0f * t3 + 3.0f * t2) * p.maxLum;
+            ratio = fy_pq_eotf(e2 * p.pqLw) / mx;
+        }
+    }
+    float L[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) L[c] = F[c] * ratio * p.rLt;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float l = fminf(fmaxf(p.gam[3 * c] * L[0] + p.gam[3 * c + 1] * L[1] + p.gam[3 * c + 2] * L[2], 0.0f), 1.0f);
+        v[c] = 255.0f * (l < 0.018f ? 4.5f * l : 1.099f * fy_pow(l, 0.45f) - 0.099f);
+    }
+}
 
 // Entry o of the tile's tap table of one axis (output index first + o): first tap, count (clamped to the host's capacity) and normalised f32 weights.
 __device__ inline void fy_tap_table(const FrAxis& a, int first, int cap, int pitch, float* w, int* t0s, int* nts, int o) {
@@ -96,7 +177,7 @@ __device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelt
 __device__ inline float fy_sample(uint8_t v, int) { return (float)v; }
 __device__ inline float fy_sample(uint16_t v, int shift) { return (float)(v >> shift); }
 
-template <typename S>
+template <typename S, int TRC>
 __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyParams p) {
     extern __shared__ __attribute__((aligned(16))) char fy_smem[];
     float* wx = (float*)fy_smem;                       // [TX][NTXp]
@@ -225,6 +306,7 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
         v[0] = fmaf(p.krcr, cr, yl);
         v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
         v[2] = fmaf(p.kbcb, cb, yl);
+        if constexpr (TRC != FY_TRC_NONE) fy_hdr_to_sdr<TRC>(v, p);
         const int y = y0 + yy, x = x0 + col;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -289,28 +371,33 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
     return true;
 }
 
-// One launch of the instance for sample type S; the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <typename S>
+// One launch of the instance for sample type S and transfer TRC; the dynamic-LDS opt-in is a per-device attribute of each instance.
+template <typename S, int TRC>
 int fy_launch(const FyParams& p, int64_t wgs, int lds, void* stream, const char* who) {
     static std::atomic<uint64_t> have_lds{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S, TRC>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
             rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
             return RV_ERR_HIP;
         }
         have_lds.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(yuv_to_patches_kernel<S>, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    hipLaunchKernelGGL((yuv_to_patches_kernel<S, TRC>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
     RV_CHECK_LAUNCH("yuv_to_patches");
     return RV_OK;
 }
 
-// Both entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages.
-int fy_run(const rv_yuv_surface& s, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream,
-           const char* who) {
+double fy_pq_inv64(double nits) {
+    const double y = pow(nits / 10000.0, PQ_M1_D);
+    return pow((PQ_C1_D + PQ_C2_D * y) / (1.0 + PQ_C3_D * y), PQ_M2_D);
+}
+
+// All entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m: the HDR entry's map (validated by it), else null.
+int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
+           void* stream, const char* who) {
     const int sb = s.sample_bytes, H = s.H, W = s.W, n = s.n;
     RV_CHECK_ARG(sb == 1 || sb == 2, "%s: sample_bytes = %d (1, or 2 = little-endian 16-bit words)", who, sb);
     RV_CHECK_ARG(sb == 1 ? s.depth == 8 : (s.depth >= 9 && s.depth <= 16), "%s: depth = %d does not go with sample_bytes = %d (8 with 1; 9 .. 16 with 2)", who,
@@ -392,6 +479,17 @@ int fy_run(const rv_yuv_surface& s, int32_t R, int32_t patch, const float* mean,
     p.patches = (op16_t*)patches;
     p.ldp = ldp;
     p.image = image;
+    if (m) {
+        const double lw = m->peak_nits, lt = m->sdr_white_nits, max_lum = fy_pq_inv64(lt) / fy_pq_inv64(lw);
+        static const double to709[9] = {1.6605, -0.5876, -0.0728, -0.1246, 1.1329, -0.0083, -0.0182, -0.1006, 1.1187};   // BT.2087
+        p.Lw = m->peak_nits;
+        p.rLt = (float)(1.0 / lt);
+        p.pqLw = (float)fy_pq_inv64(lw);
+        p.maxLum = (float)max_lum;
+        p.KS = (float)(1.5 * max_lum - 0.5);
+        p.gm1 = (float)(0.2 + 0.42 * log10(lw / 1000.0));
+        for (int i = 0; i < 9; ++i) p.gam[i] = m->gamut ? (float)to709[i] : (i % 4 == 0 ? 1.0f : 0.0f);
+    }
     p.NTX = fr_max_taps(p.ax, p.left, R);
     p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
     p.NTY = fr_max_taps(p.ay, p.top, R);
@@ -412,7 +510,10 @@ int fy_run(const rv_yuv_surface& s, int32_t R, int32_t patch, const float* mean,
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
     RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = best.o_stage + fy_stage_bytes(best);
-    return sb == 1 ? fy_launch<uint8_t>(best, wgs, lds, stream, who) : fy_launch<uint16_t>(best, wgs, lds, stream, who);
+    if (!m) return sb == 1 ? fy_launch<uint8_t, FY_TRC_NONE>(best, wgs, lds, stream, who) : fy_launch<uint16_t, FY_TRC_NONE>(best, wgs, lds, stream, who);
+    if (m->transfer == FY_TRC_PQ)
+        return sb == 1 ? fy_launch<uint8_t, FY_TRC_PQ>(best, wgs, lds, stream, who) : fy_launch<uint16_t, FY_TRC_PQ>(best, wgs, lds, stream, who);
+    return sb == 1 ? fy_launch<uint8_t, FY_TRC_HLG>(best, wgs, lds, stream, who) : fy_launch<uint16_t, FY_TRC_HLG>(best, wgs, lds, stream, who);
 }
 
 }  // namespace
@@ -420,7 +521,22 @@ int fy_run(const rv_yuv_surface& s, int32_t R, int32_t patch, const float* mean,
 extern "C" int rv_yuv_surface_to_patches(const rv_yuv_surface* s, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                                          float* image, void* stream) {
     RV_CHECK_ARG(s, "rv_yuv_surface_to_patches: null surface");
-    return fy_run(*s, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
+    return fy_run(*s, nullptr, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
+}
+
+// The surface entry with the HDR -> SDR steps between the colour matrix and the normalisation: the map is validated here, everything else by fy_run.
+extern "C" int rv_yuv_surface_to_patches_hdr(const rv_yuv_surface* s, const rv_hdr_map* m, int32_t R, int32_t patch, const float mean[3], const float std[3],
+                                             void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_yuv_surface_to_patches_hdr";
+    RV_CHECK_ARG(s, "%s: null surface", who);
+    RV_CHECK_ARG(m, "%s: null map", who);
+    RV_CHECK_ARG(m->transfer == FY_TRC_PQ || m->transfer == FY_TRC_HLG, "%s: transfer %d (1 = PQ, 2 = HLG)", who, m->transfer);
+    RV_CHECK_ARG(m->gamut == 0 || m->gamut == 1, "%s: gamut %d (0 = none, 1 = BT.2020 -> BT.709)", who, m->gamut);
+    RV_CHECK_ARG(isfinite(m->peak_nits) && m->peak_nits >= 1.0f && m->peak_nits <= 10000.0f, "%s: peak_nits %g outside 1 .. 10000", who,
+                 (double)m->peak_nits);
+    RV_CHECK_ARG(isfinite(m->sdr_white_nits) && m->sdr_white_nits >= 1.0f && m->sdr_white_nits <= 10000.0f, "%s: sdr_white_nits %g outside 1 .. 10000", who,
+                 (double)m->sdr_white_nits);
+    return fy_run(*s, m, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
 // The 8-bit 4:2:0 surface of the first entry point: its own two-valued matrix and chroma_loc, then the same code.
@@ -450,5 +566,5 @@ extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64
     s.matrix = matrix;
     s.full_range = full_range;
     s.chroma_loc = chroma_loc;
-    return fy_run(s, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
+    return fy_run(s, nullptr, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
 }

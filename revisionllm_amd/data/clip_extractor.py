@@ -31,9 +31,12 @@ def yuv_colour_defaults(H):
     return dict(matrix="bt601" if H < 720 else "bt709", full_range=False, chroma_loc="left")
 
 
-def yuv_surface_colour_defaults(H, bt2020=False):
+def yuv_surface_colour_defaults(H, bt2020=False, transfer=None):
     """``yuv_colour_defaults(H)`` for a stream that carries no colour tags; for one the caller knows to be BT.2020 (HEVC Main10 / AV1 10-bit UHD): its
-    non-constant-luminance matrix, studio range and the top-left chroma siting that is BT.2020's default for 4:2:0."""
+    non-constant-luminance matrix, studio range and the top-left chroma siting that is BT.2020's default for 4:2:0.  With ``transfer`` ("pq" | "hlg" or
+    ffmpeg's "smpte2084" | "arib-std-b67"): the tags of an HDR10 / HLG stream - those BT.2020 tags and the transfer itself."""
+    if transfer is not None:
+        return dict(matrix="bt2020", full_range=False, chroma_loc="topleft", transfer=transfer)
     return dict(matrix="bt2020", full_range=False, chroma_loc="topleft") if bt2020 else yuv_colour_defaults(H)
 
 
@@ -81,10 +84,14 @@ class ClipFeatureExtractor:
         ...``): ``chunks`` is one uint8 buffer [t, ops.yuv_frame_bytes(H, W, pix_fmt)] or an iterable of them, CPU or device.  They are regrouped into
         batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv``) and go through ``encode_surfaces_yuv``: no conversion pass, no RGB
         frame.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_surface_colour_defaults``; ``matrix="bt2020"`` says the stream is
-        BT.2020 and brings top-left siting with it."""
+        BT.2020 and brings top-left siting with it.  ``transfer="pq"`` | ``"hlg"`` says it is HDR10 / HLG: the BT.2020 tags become the defaults and the
+        frames are converted to SDR inside the kernel (``ops.yuv_surface_to_patches``; ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` go through with it)."""
         tw = self.clip_extractor
         fb = ops.yuv_frame_bytes(H, W, pix_fmt)
-        colour = {**yuv_surface_colour_defaults(H, bt2020=colour.get("matrix") == "bt2020"), **colour}
+        ops.hdr_map(colour.get("transfer"))                     # an unknown transfer is refused before anything is read
+        colour = {**yuv_surface_colour_defaults(H, bt2020=colour.get("matrix") == "bt2020", transfer=colour.get("transfer")), **colour}
+        if colour.get("transfer") is None:
+            colour.pop("transfer", None)                        # transfer=None is the SDR call as it always was
         out = []
         for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=2, shapes=f"[t,{fb}]"):
             planes, kw = ops.split_yuv(b, H, W, pix_fmt)

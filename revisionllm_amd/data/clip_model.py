@@ -111,7 +111,8 @@ class ClipTowers:
     @torch.no_grad()
     def encode_surfaces_yuv(self, y, cb, cr=None, **surface):
         """Decoded frames of any surface ``ops.yuv_surface_to_patches`` takes (uint8 or uint16 planes on the device; ``surface``: its ``depth`` /
-        ``msb_aligned`` / ``subsampling`` / ``matrix`` / ``full_range`` / ``chroma_loc``) -> f32 [n, embed_dim], as ``encode_frames_yuv``."""
+        ``msb_aligned`` / ``subsampling`` / ``matrix`` / ``full_range`` / ``chroma_loc``, and for an HDR surface its ``transfer`` / ``peak_nits`` /
+        ``sdr_white_nits`` / ``gamut``) -> f32 [n, embed_dim], as ``encode_frames_yuv``."""
         c = self.cfg
         patches, _ = ops.yuv_surface_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
         return self._encode_patches(patches, y.shape[0])

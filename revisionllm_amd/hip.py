@@ -47,6 +47,11 @@ class RvYuvSurface(C.Structure):
                 ("matrix", C.c_int32), ("full_range", C.c_int32), ("chroma_loc", C.c_int32)]
 
 
+class RvHdrMap(C.Structure):
+    """``rv_hdr_map``: how rv_yuv_surface_to_patches_hdr converts an HDR surface to SDR (transfer 1 = PQ, 2 = HLG; gamut 1 = BT.2020 -> BT.709 primaries)."""
+    _fields_ = [("transfer", C.c_int32), ("gamut", C.c_int32), ("peak_nits", C.c_float), ("sdr_white_nits", C.c_float)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -120,6 +125,7 @@ SIGNATURES = {
     "rv_yuv_to_patches": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p,
                                     _i64, _p, _p]),
     "rv_yuv_surface_to_patches": (C.c_int, [C.POINTER(RvYuvSurface), _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
+    "rv_yuv_surface_to_patches_hdr": (C.c_int, [C.POINTER(RvYuvSurface), C.POINTER(RvHdrMap), _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
     "rv_project_dense": (C.c_int, [_p, _p, _p, C.c_int, _i64, _p]),
     "rv_clip_encoder_ws_bytes": (_sz, [_p, _i32, _i32, _i32, _i32]),
     "rv_clip_encoder": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),

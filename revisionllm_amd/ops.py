@@ -391,8 +391,23 @@ PIX_FMTS = {
 }
 
 
+#: transfer characteristics of an HDR surface -> rv_hdr_map.transfer; ffmpeg's ``color_trc`` names are aliases
+_TRANSFERS = {"pq": 1, "smpte2084": 1, "hlg": 2, "arib-std-b67": 2}
+
+
+def hdr_map(transfer, matrix="bt2020", gamut=None, peak_nits=1000.0, sdr_white_nits=203.0):
+    """The ``hip.RvHdrMap`` that ``yuv_surface_to_patches`` hands to rv_yuv_surface_to_patches_hdr, or None for ``transfer=None`` (an SDR surface).
+    transfer "pq" | "hlg" ("smpte2084" | "arib-std-b67", ffmpeg's ``color_trc`` names, are aliases); ``gamut`` None = BT.2020 -> BT.709 primaries exactly
+    when ``matrix == "bt2020"``, else True / False.  The range of ``peak_nits`` / ``sdr_white_nits`` (1 .. 10000) is the library's check."""
+    if transfer is None:
+        return None
+    if transfer not in _TRANSFERS:
+        raise ValueError(f"transfer {transfer!r}: None or one of {sorted(_TRANSFERS)}")
+    return hip.RvHdrMap(_TRANSFERS[transfer], int(matrix == "bt2020" if gamut is None else bool(gamut)), float(peak_nits), float(sdr_white_nits))
+
+
 def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=False, subsampling="420", matrix="bt601", full_range=False, chroma_loc="left",
-                           mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",)):
+                           mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), transfer=None, peak_nits=1000.0, sdr_white_nits=203.0, gamut=None):
     """Decoded YCbCr frames of any planar / semi-planar surface -> the CLIP front end in one launch (rv_yuv_surface_to_patches; the header has the definition of
     the values) -> (patches, image) as ``frames_to_patches`` returns them.
     Planes are ``torch.uint8`` (depth 8) or ``torch.uint16`` (depth 9 .. 16; ``msb_aligned``: the value sits in the high bits of the word, as in P010 /
@@ -403,7 +418,12 @@ def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=Fal
         read as the interleaved surface they are.
     Planes are passed by their strides when each row's samples are adjacent (a window of a larger decode surface, a padded pitch); any other view is copied
     first.  matrix "bt601" | "bt709" | "bt2020" (the non-constant-luminance matrix alone: no transfer conversion); full_range False = studio; chroma_loc
-    "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1) | "topleft" (BT.2020 / HEVC 4:2:0)."""
+    "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1) | "topleft" (BT.2020 / HEVC 4:2:0).
+    HDR surfaces: ``transfer`` "pq" | "hlg" (``hdr_map`` has the aliases) converts the values to BT.709-coded SDR per output pixel inside the same kernel
+    (rv_yuv_surface_to_patches_hdr: transfer to display light with ``peak_nits`` as the display peak, BT.2390 tone mapping with ``sdr_white_nits`` becoming
+    SDR white, BT.2020 -> BT.709 primaries when ``gamut`` - None: exactly when ``matrix == "bt2020"`` -, BT.709 OETF).  No metadata is read: ``peak_nits`` is
+    the caller's number.  ``transfer=None`` is the SDR entry, which ignores the other three."""
+    hdr = hdr_map(transfer, matrix, gamut, peak_nits, sdr_white_nits)
     for t in (y, cb) + (() if cr is None else (cr,)):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise hip.HipLibraryError("yuv_surface_to_patches needs device tensors (got a CPU tensor); there is no CPU path")
@@ -444,6 +464,10 @@ def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=Fal
     s = hip.RvYuvSurface(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), yfs * es, yrs * es, cfs * es, crs * es, es, int(depth), int(bool(msb_aligned)), c_pix * es,
                          sx, sy, n, H, W, _SURFACE_MATRICES[matrix], int(bool(full_range)), _SURFACE_LOCS[chroma_loc])
     f3 = hip.C.c_float * 3
+    if hdr is not None:
+        hip.check(hip.lib(dt).rv_yuv_surface_to_patches_hdr(hip.C.byref(s), hip.C.byref(hdr), R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
+                                                            hip.ptr(image), hip.stream()), "rv_yuv_surface_to_patches_hdr")
+        return patches, image
     hip.check(hip.lib(dt).rv_yuv_surface_to_patches(hip.C.byref(s), R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp, hip.ptr(image), hip.stream()),
               "rv_yuv_surface_to_patches")
     return patches, image

@@ -11,7 +11,13 @@ uses over the YUV call's median as a fraction of the 8 TB/s HBM figure.  Writes 
 same warm-up and launch counts: median, min .. max, and the source bytes the crop uses over the median.  ``--pix-fmt nv12`` is the same bytes as the default
 run through the surface entry, for a like-for-like figure next to P010.
 
-    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME] [--out FILE] [--once]   (--once: one launch, for a kernel trace)"""
+--transfer pq|hlg times rv_yuv_surface_to_patches_hdr on P010 noise (BT.2020, top-left siting, peak 1000 / white 203 nits, BT.709 primaries) at 1080 x 1920
+and 2160 x 3840 against the SDR entry on the same bytes, alternating in one process with the same warm-up and launch counts: median, min .. max per form and
+hdr / sdr per size.  The extra work is R x R pixels against a whole source frame read, so the expectation is "within noise".  Default --out:
+profiles/frontend_hdr.json.
+
+    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME | --transfer pq|hlg] [--out FILE] [--once]
+    (--once: one launch, for a kernel trace)"""
 import argparse
 import json
 import os
@@ -99,6 +105,40 @@ def surface_run(a, dt):
     print(json.dumps(res))
 
 
+def hdr_run(a, dt):
+    """--transfer: the HDR entry against the SDR entry on the same P010 bytes, at 1080p and 2160p."""
+    n, R = a.frames, a.res
+    colour = dict(matrix="bt2020", full_range=False, chroma_loc="topleft")
+    res = dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), pix_fmt="p010le", transfer=a.transfer, peak_nits=1000.0, sdr_white_nits=203.0,
+               frames=n, res=R, patch=a.patch, warmup=a.warmup, iters=a.iters, sizes={})
+    for H, W in ((1080, 1920), (2160, 3840)):
+        buf = torch.randint(0, 256, (n, ops.yuv_frame_bytes(H, W, "p010le")), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+        planes, kw = ops.split_yuv(buf.cuda(), H, W, "p010le")
+        forms = (("sdr", lambda: ops.yuv_surface_to_patches(*planes, R=R, patch=a.patch, op_dtype=dt, **kw, **colour)[0]),
+                 ("hdr", lambda: ops.yuv_surface_to_patches(*planes, R=R, patch=a.patch, op_dtype=dt, transfer=a.transfer, **kw, **colour)[0]))
+        if a.once:
+            forms[1][1]()
+            torch.cuda.synchronize()
+            continue
+        t = {k: [] for k, _ in forms}
+        for i in range(a.warmup + a.iters):
+            for name, fn in forms:
+                s, _ = timed(fn)
+                if i >= a.warmup:
+                    t[name].append(s)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        ms = lambda k: dict(median=med[k] * 1e3, min=min(t[k]) * 1e3, max=max(t[k]) * 1e3)
+        res["sizes"][f"{H}x{W}"] = dict(sdr_ms=ms("sdr"), hdr_ms=ms("hdr"), hdr_over_sdr=med["hdr"] / med["sdr"])
+        del planes, buf
+    if a.once:
+        return
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
@@ -111,9 +151,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_yuv_1080p.json"))
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--pix-fmt", default=None, help="time rv_yuv_surface_to_patches on this ffmpeg pix_fmt instead (ops.PIX_FMTS)")
+    ap.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="time rv_yuv_surface_to_patches_hdr on P010 at 1080p and 2160p against the SDR entry")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "frontend_yuv_prof needs the GPU: a CPU run says nothing about time"
     dt = hip.op_dtype()
+    if a.transfer is not None:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "frontend_hdr.json")
+        return hdr_run(a, dt)
     if a.pix_fmt is not None:
         return surface_run(a, dt)
     n, H, W, R = a.frames, a.height, a.width, a.res
