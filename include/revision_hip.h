@@ -363,6 +363,35 @@ typedef struct rv_hdr_map {
 int rv_yuv_surface_to_patches_hdr(const rv_yuv_surface* s, const rv_hdr_map* m, int32_t R, int32_t patch, const float mean[3], const float std[3],
                                   void* patches, int64_t ldp, float* image, void* stream);
 
+/* The front end on the picture AS DISPLAYED.  Phone and action-camera streams are coded sideways or upside down and carry a display matrix (mp4's rotate tag);
+ * a hardware decoder or a -noautorotate pipe hands over the coded surface.  These two entries turn and flip inside the same kernels: the load side stays in
+ * coded orientation, each coded axis is resampled with the scale, crop offset and direction of the display axis it becomes, and only the store is permuted.
+ * No pass over the source is added.
+ * orient, 0 .. 7, the eight orientations of a rectangle: bit 0 transpose, bit 1 mirror display x, bit 2 mirror display y, applied in that order.  On a plane
+ * S[rows, cols]:   D = transpose(S) if orient & 1 else S;   D = D[:, ::-1] if orient & 2;   D = D[::-1, :] if orient & 4.
+ * So a turn by 90 degrees clockwise is 3, by 180 degrees 6, by 270 degrees clockwise 5; a horizontal flip is 2, a vertical flip 4; 1 and 7 are the two
+ * diagonal flips.  H, W, the strides and the surface struct describe the CODED frames (windows of larger surfaces and padded pitches as before); everything
+ * else is as in the un-oriented entry.
+ * Values: what the un-oriented entry defines on the oriented picture.
+ *   RGB      rv_frames_to_patches' definition on D of every channel plane.  The display size is (Hd, Wd) = (W, H) under transpose; the resized size, the crop
+ *            offsets (round half even, in display coordinates) and the tap windows are derived from it, in display coordinates.
+ *   YCbCr    every plane is oriented as above.  The display subsampling is (sub_x, sub_y) swapped under transpose: 4:2:2 turned by 90 degrees is a 1,2
+ *            surface on the display, which this entry handles (the coded surface is the legal 2,1) although the un-oriented entry refuses that pair.
+ *   siting   the chroma offset is computed per CODED axis as in rv_yuv_surface_to_patches (0.25 where a subsampled axis is sited on the even luma sample),
+ *            follows its axis to the display axis that axis becomes, and is NEGATED where that display axis is mirrored - a left-sited sample is
+ *            right-sited after a flip: centre_c = scale * (i + 0.5) / sub - 0.25.
+ *   the rest colour equations, the HDR steps of rv_yuv_surface_to_patches_hdr (m != NULL), normalisation, rounding, patch layout and zero padding: unchanged.
+ * The library's OWN definition, as the others are: no parity with swscale's or a transpose filter's bytes is claimed.  orient = 0 gives the bits of the
+ * un-oriented entries.
+ * Refused (RV_ERR_ARG, nothing launched): orient outside 0 .. 7; everything the un-oriented entry refuses (the parity of H / W is checked along the CODED
+ * subsampled axes; m, when given, as by rv_yuv_surface_to_patches_hdr); a geometry whose tap tables and staging do not fit a workgroup's LDS in the oriented
+ * plan.  n = 0 returns 0 and launches nothing. */
+int rv_frames_to_patches_oriented(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
+                                  int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
+                                  float* image, void* stream);
+int rv_yuv_surface_to_patches_oriented(const rv_yuv_surface* s, const rv_hdr_map* m /* NULL = SDR */, int32_t orient, int32_t R, int32_t patch,
+                                       const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */
 int rv_project_dense(rv_ctx* ctx, const void* x_bf16, void* y, int out_dtype, int64_t rows, void* stream);

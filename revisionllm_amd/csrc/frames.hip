@@ -10,6 +10,10 @@
 //   phase 2  vertical pass over inter, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
 // Tap counts depend on the geometry (4 * scale + 1 per axis): every tap loop is a runtime loop over LDS-resident weights.  The host picks TY / TX so that
 // a workgroup stays under FR_LDS_BUDGET bytes (two workgroups per CU) and refuses a geometry that does not fit with TY = TX = 1.
+//
+// Display orientation (rv_frames_to_patches_oriented): the kernel is compiled per ORI (0 = none: the code it was; 1 = mirrors; 2 = transpose, with or without
+// mirrors).  Loads, staging and the LDS plan stay in CODED orientation: a coded axis takes the scale, crop offset and mirror flag of the display axis it
+// serves, its tap table holds the display window reflected into coded sample indices, and only the store is permuted to image[f, c, yd, xd].
 #include <atomic>
 
 #include "frames_taps.h"   // the tap definition, FR_* constants and capacity helpers (shared with frames_yuv.hip); fp contraction is off from there on
@@ -29,8 +33,10 @@ struct FrParams {
     op16_t* patches;
     int64_t ldp;
     float* image;
+    int mirx, miry;                      // oriented instances only (behind everything the ORI = 0 instance reads): the coded x / y axis is mirrored
 };
 
+template <int ORI>
 __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrParams p) {
     extern __shared__ __attribute__((aligned(16))) char fr_smem[];
     float* wh = (float*)fr_smem;                       // [TX][NTXp]
@@ -57,14 +63,19 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrP
         const double scale = isx ? p.sx : p.sy;
         const int idx = isx ? x0 + o + p.left : y0 + o + p.top;
         int t0, nt;
-        fr_taps(scale, isx ? p.W : p.H, idx, t0, nt);
-        nt = min(nt, isx ? p.NTX : p.NTY);
-        float* w = isx ? wh + o * p.NTXp : wv + o * p.NTY;
-        const double inv = scale >= 1.0 ? 1.0 / scale : 1.0, centre = scale * (idx + 0.5);
-        double tot = 0.0;
-        for (int t = 0; t < nt; ++t) tot += fr_cubic((t0 + t - centre + 0.5) * inv);
-        const double rt = tot != 0.0 ? 1.0 / tot : 1.0;
-        for (int t = 0; t < nt; ++t) w[t] = (float)(fr_cubic((t0 + t - centre + 0.5) * inv) * rt);
+        if constexpr (ORI == 0) {
+            fr_taps(scale, isx ? p.W : p.H, idx, t0, nt);
+            nt = min(nt, isx ? p.NTX : p.NTY);
+            float* w = isx ? wh + o * p.NTXp : wv + o * p.NTY;
+            const double inv = scale >= 1.0 ? 1.0 / scale : 1.0, centre = scale * (idx + 0.5);
+            double tot = 0.0;
+            for (int t = 0; t < nt; ++t) tot += fr_cubic((t0 + t - centre + 0.5) * inv);
+            const double rt = tot != 0.0 ? 1.0 / tot : 1.0;
+            for (int t = 0; t < nt; ++t) w[t] = (float)(fr_cubic((t0 + t - centre + 0.5) * inv) * rt);
+        } else {
+            fr_tap_table_m(FrAxis{scale, 1.0, 0.0, isx ? p.W : p.H}, isx ? p.left : p.top, p.R, isx ? p.mirx : p.miry, (isx ? x0 : y0) + o,
+                           isx ? p.NTX : p.NTY, isx ? wh + o * p.NTXp : wv + o * p.NTY, t0, nt);
+        }
         (isx ? xmin : ymin)[o] = t0;
         (isx ? nx : ny)[o] = nt;
     }
@@ -138,15 +149,28 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrP
         float acc = 0.f;
         for (int t = 0; t < n; ++t) acc = fmaf(w[t], q[t * 3 * p.TX], acc);
         const float v = (acc / 255.0f - (c == 0 ? p.mean[0] : c == 1 ? p.mean[1] : p.mean[2])) / (c == 0 ? p.den[0] : c == 1 ? p.den[1] : p.den[2]);
-        const int y = y0 + yy, x = x0 + col;
+        int y = y0 + yy, x = x0 + col;
+        if constexpr (ORI != 0) {   // the display pixel this coded output is
+            const int dy = fr_disp_index(0, p.R, y, p.miry), dx = fr_disp_index(0, p.R, x, p.mirx);
+            y = ORI == 2 ? dx : dy;
+            x = ORI == 2 ? dy : dx;
+        }
         if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = v;
         if (p.patches)
             p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(v);
     }
     // pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile
     if (p.patches && p.Kp > p.K) {
-        const int gy0 = (y0 + p.patch - 1) / p.patch, gy1 = (y0 + ty + p.patch - 1) / p.patch;
-        const int gx0 = (x0 + p.patch - 1) / p.patch, gx1 = (x0 + tx + p.patch - 1) / p.patch;
+        int py0 = y0, pty = ty, px0 = x0, ptx = tx;   // the tile's rectangle of the display image
+        if constexpr (ORI != 0) {
+            const int cy0 = p.miry ? p.R - y0 - ty : y0, cx0 = p.mirx ? p.R - x0 - tx : x0;
+            py0 = ORI == 2 ? cx0 : cy0;
+            pty = ORI == 2 ? tx : ty;
+            px0 = ORI == 2 ? cy0 : cx0;
+            ptx = ORI == 2 ? ty : tx;
+        }
+        const int gy0 = (py0 + p.patch - 1) / p.patch, gy1 = (py0 + pty + p.patch - 1) / p.patch;
+        const int gx0 = (px0 + p.patch - 1) / p.patch, gx1 = (px0 + ptx + p.patch - 1) / p.patch;
         const int pad = p.Kp - p.K, ngx = gx1 - gx0;
         for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
             const int j = it % pad, pr = it / pad;
@@ -161,8 +185,8 @@ bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
     p.TX = tx;
     p.tilesX = (p.R + tx - 1) / tx;
     p.bands = (p.R + ty - 1) / ty;
-    p.NR = fr_max_span(FrAxis{p.sy, 1.0, 0.0, p.H}, p.top, p.R, ty);
-    p.SEGPX = fr_max_span(FrAxis{p.sx, 1.0, 0.0, p.W}, p.left, p.R, tx);
+    p.NR = fr_max_span(FrAxis{p.sy, 1.0, 0.0, p.H}, p.top, p.R, ty, p.miry);
+    p.SEGPX = fr_max_span(FrAxis{p.sx, 1.0, 0.0, p.W}, p.left, p.R, tx, p.mirx);
     p.SEG = ((p.SEGPX * p.pix + 15) & ~15) + 16;
     int64_t o = (int64_t)tx * p.NTXp * 4;
     p.o_wv = (int)o;
@@ -183,25 +207,42 @@ bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
 
 int fr_lds_bytes(const FrParams& p) { return p.o_stage + (p.pix == 1 ? 3 : 1) * FR_SR * p.SEG; }
 
-}  // namespace
+// One launch of the instance for orientation class ORI; the dynamic-LDS opt-in is a per-device attribute of each instance.
+template <int ORI>
+int fr_launch(const FrParams& p, int64_t wgs, int lds, void* stream, const char* who) {
+    static std::atomic<uint64_t> have_lds{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
+        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel<ORI>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+            rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
+            return RV_ERR_HIP;
+        }
+        have_lds.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(frames_to_patches_kernel<ORI>, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    RV_CHECK_LAUNCH("frames_to_patches");
+    return RV_OK;
+}
 
-extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
-                                    int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image,
-                                    void* stream) {
-    RV_CHECK_ARG(layout == 0 || layout == 1, "rv_frames_to_patches: layout %d (0 = NCHW, 1 = NHWC)", layout);
-    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "rv_frames_to_patches: R = %d is not a multiple of patch = %d", R, patch);
-    RV_CHECK_ARG(H >= 1 && W >= 1 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "rv_frames_to_patches: frame size %d x %d outside 1 .. %d", H, W, FR_MAX_SIDE);
-    RV_CHECK_ARG(R <= FR_MAX_SIDE, "rv_frames_to_patches: R = %d above %d", R, FR_MAX_SIDE);
-    RV_CHECK_ARG(n >= 0, "rv_frames_to_patches: n = %d", n);
+// Both entry points: validate, plan the tiles, launch.  `who` names the entry point in the messages; orient 0 is the un-oriented entry's plan and instance.
+int fr_run(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch,
+           const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream, const char* who) {
+    RV_CHECK_ARG(layout == 0 || layout == 1, "%s: layout %d (0 = NCHW, 1 = NHWC)", who, layout);
+    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
+    RV_CHECK_ARG(H >= 1 && W >= 1 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 .. %d", who, H, W, FR_MAX_SIDE);
+    RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
+    RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
     if (n == 0) return RV_OK;
-    RV_CHECK_ARG(frames, "rv_frames_to_patches: null frames");
-    RV_CHECK_ARG(patches || image, "rv_frames_to_patches: both outputs null");
-    RV_CHECK_ARG(mean && std, "rv_frames_to_patches: null mean / std");
+    RV_CHECK_ARG(frames, "%s: null frames", who);
+    RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
+    RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
     FrParams p{};
     p.K = 3 * patch * patch;
     p.Kp = (p.K + 127) / 128 * 128;
-    RV_CHECK_ARG(!patches || ldp >= p.Kp, "rv_frames_to_patches: ldp = %lld below Kp = %d", (long long)ldp, p.Kp);
-    RV_CHECK_ARG(layout == 1 || frame_stride % 3 == 0, "rv_frames_to_patches: NCHW channel planes lie frame_stride / 3 apart; frame_stride = %lld", (long long)frame_stride);
+    RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
+    RV_CHECK_ARG(layout == 1 || frame_stride % 3 == 0, "%s: NCHW channel planes lie frame_stride / 3 apart; frame_stride = %lld", who, (long long)frame_stride);
     p.src = frames;
     p.fstride = frame_stride;
     p.rstride = row_stride;
@@ -212,12 +253,17 @@ extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t f
     p.R = R;
     p.patch = patch;
     p.g = R / patch;
-    // Resize(R): shorter side -> R, longer side -> int(R * long / short); CenterCrop(R): offset round-half-even((size - R) / 2)
-    const int hr = H <= W ? R : (int)((int64_t)R * H / W), wr = H <= W ? (int)((int64_t)R * W / H) : R;
-    p.sy = (double)H / hr;
-    p.sx = (double)W / wr;
-    p.top = (int)nearbyint((hr - R) / 2.0);
-    p.left = (int)nearbyint((wr - R) / 2.0);
+    // Resize(R) / CenterCrop(R) of the DISPLAY picture (W x H under transpose); each coded axis then takes what the display axis it serves got
+    const FrOrient ori = fr_orient(orient);
+    double sy, sx;
+    int top, left;
+    fr_resize_crop(ori.tr ? W : H, ori.tr ? H : W, R, sy, sx, top, left);
+    p.sy = ori.tr ? sx : sy;
+    p.sx = ori.tr ? sy : sx;
+    p.top = ori.tr ? left : top;
+    p.left = ori.tr ? top : left;
+    p.mirx = ori.mx;
+    p.miry = ori.my;
     for (int c = 0; c < 3; ++c) {
         p.mean[c] = mean[c];
         p.den[c] = std[c] + 1e-8f;
@@ -238,22 +284,26 @@ extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t f
             FrParams q = p;
             if (fr_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
         }
-    RV_CHECK_ARG(have, "rv_frames_to_patches: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", H, W, R);
+    RV_CHECK_ARG(have, "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
-    RV_CHECK_ARG(wgs < (1ll << 31), "rv_frames_to_patches: %lld workgroups (n = %d) exceed one launch", (long long)wgs, n);
+    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = fr_lds_bytes(best);
-    static std::atomic<uint64_t> have_lds{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {   // the dynamic-LDS opt-in is a per-device attribute of the function
-        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
-            rv_set_error("rv_frames_to_patches: cannot reserve %d bytes of LDS", FR_LDS_BUDGET);
-            return RV_ERR_HIP;
-        }
-        have_lds.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(frames_to_patches_kernel, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), best);
-    RV_CHECK_LAUNCH("frames_to_patches");
-    return RV_OK;
+    if (orient == 0) return fr_launch<0>(best, wgs, lds, stream, who);
+    return ori.tr ? fr_launch<2>(best, wgs, lds, stream, who) : fr_launch<1>(best, wgs, lds, stream, who);
+}
+
+}  // namespace
+
+extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
+                                    int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image,
+                                    void* stream) {
+    return fr_run(frames, layout, frame_stride, row_stride, n, H, W, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches");
+}
+
+// The same front end on the picture as it is displayed: H, W and the strides describe the coded frames, orient (0 .. 7) turns and flips them.
+extern "C" int rv_frames_to_patches_oriented(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
+                                             int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
+                                             float* image, void* stream) {
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "rv_frames_to_patches_oriented: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", orient);
+    return fr_run(frames, layout, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches_oriented");
 }

@@ -51,6 +51,12 @@
 // At 4:2:0: half the horizontal-pass work of three RGB planes (one full plane + two quarter planes filtered with half the taps), and two thirds of its
 // `inter` rows.  The kernel is compiled per sample type (uint8_t; uint16_t with a run-time shift), so the 8-bit instance is the 8-bit kernel it was, and per
 // transfer (TRC: 0 = none, 1 = PQ, 2 = HLG): the HDR steps exist in the HDR instances only, the TRC = 0 instances are the code they were.
+//
+// Display orientation (rv_yuv_surface_to_patches_oriented; include/revision_hip.h has the definition): compiled per ORI as well (0 = none: the code it was;
+// 1 = mirrors; 2 = transpose, with or without mirrors).  Loads, staging and the LDS plan stay in CODED orientation.  Every coded axis takes the scale and
+// crop offset of the display axis it serves and a mirror flag; the chroma siting offset stays with its coded axis and changes sign where that axis is
+// mirrored; a tap table holds the display window reflected into coded sample indices; only the store is permuted to image[f, c, yd, xd].  So a 4:2:2
+// surface turned by 90 degrees (4:4:0 on the display) is still the 2,1 surface it was coded as.
 #include <atomic>
 
 #include "frames_taps.h"   // fp contraction is off from there on
@@ -75,6 +81,7 @@ struct FyParams {
     float* image;
     // HDR instances only (behind everything the TRC = 0 instances read): Lw, 1 / Lt, PQinv(Lw), maxLum, KS, gamma - 1, the gamut matrix by rows (or the identity)
     float Lw, rLt, pqLw, maxLum, KS, gm1, gam[9];
+    int mirx, miry;   // oriented instances only: the coded x / y axis is mirrored
 };
 
 // ---- HDR -> SDR per output pixel (the head of the file has the definition) ---------------------------------------------------------------------------
@@ -151,6 +158,11 @@ __device__ inline void fy_tap_table(const FrAxis& a, int first, int cap, int pit
     nts[o] = nt;
 }
 
+// The same entry of an oriented axis (coded output o0 + o of the R cropped outputs, mirrored or not): fr_tap_table_m has the reflection.
+__device__ inline void fy_tap_table_m(const FrAxis& a, int first, int R, int mir, int o0, int cap, int pitch, float* w, int* t0s, int* nts, int o) {
+    fr_tap_table_m(a, first, R, mir, o0 + o, cap, w + o * pitch, t0s[o], nts[o]);
+}
+
 // Stage `nr` rows of `planes` planes: the `segbytes` bytes from `g0` on (row r of plane pl: g0 + pl * pdelta + r * rstride) into stage[(pl * FR_SR + r) * SEG ..],
 // each segment keeping its position inside a 16-byte line.  Reads [segment start, segment end) and nothing else: whole 16-byte lines inside it, single
 // samples of type S (segments start and end on a sample) at its two ends.
@@ -177,7 +189,7 @@ __device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelt
 __device__ inline float fy_sample(uint8_t v, int) { return (float)v; }
 __device__ inline float fy_sample(uint16_t v, int shift) { return (float)(v >> shift); }
 
-template <typename S, int TRC>
+template <typename S, int TRC, int ORI>
 __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyParams p) {
     extern __shared__ __attribute__((aligned(16))) char fy_smem[];
     float* wx = (float*)fy_smem;                       // [TX][NTXp]
@@ -206,10 +218,17 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
 
     // ---- phase 0: tap tables --------------------------------------------------------------------------------------------------
     for (int i = tid; i < 2 * (tx + ty); i += FR_THREADS) {
-        if (i < tx) fy_tap_table(p.ax, x0 + p.left, p.NTX, p.NTXp, wx, xmin, nx, i);
-        else if (i < 2 * tx) fy_tap_table(p.cx, x0 + p.left, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
-        else if (i < 2 * tx + ty) fy_tap_table(p.ay, y0 + p.top, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
-        else fy_tap_table(p.cy, y0 + p.top, p.NCY, p.NCY, cwy, cymin, cny, i - 2 * tx - ty);
+        if constexpr (ORI == 0) {
+            if (i < tx) fy_tap_table(p.ax, x0 + p.left, p.NTX, p.NTXp, wx, xmin, nx, i);
+            else if (i < 2 * tx) fy_tap_table(p.cx, x0 + p.left, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
+            else if (i < 2 * tx + ty) fy_tap_table(p.ay, y0 + p.top, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
+            else fy_tap_table(p.cy, y0 + p.top, p.NCY, p.NCY, cwy, cymin, cny, i - 2 * tx - ty);
+        } else {
+            if (i < tx) fy_tap_table_m(p.ax, p.left, p.R, p.mirx, x0, p.NTX, p.NTXp, wx, xmin, nx, i);
+            else if (i < 2 * tx) fy_tap_table_m(p.cx, p.left, p.R, p.mirx, x0, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
+            else if (i < 2 * tx + ty) fy_tap_table_m(p.ay, p.top, p.R, p.miry, y0, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
+            else fy_tap_table_m(p.cy, p.top, p.R, p.miry, y0, p.NCY, p.NCY, cwy, cymin, cny, i - 2 * tx - ty);
+        }
     }
     __syncthreads();
 
@@ -307,7 +326,12 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
         v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
         v[2] = fmaf(p.kbcb, cb, yl);
         if constexpr (TRC != FY_TRC_NONE) fy_hdr_to_sdr<TRC>(v, p);
-        const int y = y0 + yy, x = x0 + col;
+        int y = y0 + yy, x = x0 + col;
+        if constexpr (ORI != 0) {   // the display pixel this coded output is
+            const int dy = fr_disp_index(0, p.R, y, p.miry), dx = fr_disp_index(0, p.R, x, p.mirx);
+            y = ORI == 2 ? dx : dy;
+            x = ORI == 2 ? dy : dx;
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float o = (v[c] / 255.0f - p.mean[c]) / p.den[c];
@@ -318,8 +342,16 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
     }
     // pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile
     if (p.patches && p.Kp > p.K) {
-        const int gy0 = (y0 + p.patch - 1) / p.patch, gy1 = (y0 + ty + p.patch - 1) / p.patch;
-        const int gx0 = (x0 + p.patch - 1) / p.patch, gx1 = (x0 + tx + p.patch - 1) / p.patch;
+        int py0 = y0, pty = ty, px0 = x0, ptx = tx;   // the tile's rectangle of the display image
+        if constexpr (ORI != 0) {
+            const int cy0 = p.miry ? p.R - y0 - ty : y0, cx0 = p.mirx ? p.R - x0 - tx : x0;
+            py0 = ORI == 2 ? cx0 : cy0;
+            pty = ORI == 2 ? tx : ty;
+            px0 = ORI == 2 ? cy0 : cx0;
+            ptx = ORI == 2 ? ty : tx;
+        }
+        const int gy0 = (py0 + p.patch - 1) / p.patch, gy1 = (py0 + pty + p.patch - 1) / p.patch;
+        const int gx0 = (px0 + p.patch - 1) / p.patch, gx1 = (px0 + ptx + p.patch - 1) / p.patch;
         const int pad = p.Kp - p.K, ngx = gx1 - gx0;
         for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
             const int j = it % pad, pr = it / pad;
@@ -339,10 +371,10 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
     p.TX = tx;
     p.tilesX = (p.R + tx - 1) / tx;
     p.bands = (p.R + ty - 1) / ty;
-    p.NRY = fr_max_span(p.ay, p.top, p.R, ty);
-    p.NRC = fr_max_span(p.cy, p.top, p.R, ty);
-    p.SPY = fr_max_span(p.ax, p.left, p.R, tx);
-    p.SPC = fr_max_span(p.cx, p.left, p.R, tx);
+    p.NRY = fr_max_span(p.ay, p.top, p.R, ty, p.miry);
+    p.NRC = fr_max_span(p.cy, p.top, p.R, ty, p.miry);
+    p.SPY = fr_max_span(p.ax, p.left, p.R, tx, p.mirx);
+    p.SPC = fr_max_span(p.cx, p.left, p.R, tx, p.mirx);
     p.SEGY = ((p.SPY * p.sbytes + 15) & ~15) + 16;
     p.SEGC = ((p.SPC * p.cpix + 15) & ~15) + 16;
     int64_t o = (int64_t)tx * p.NTXp * 4;
@@ -371,21 +403,21 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
     return true;
 }
 
-// One launch of the instance for sample type S and transfer TRC; the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <typename S, int TRC>
+// One launch of the instance for sample type S, transfer TRC and orientation class ORI; the dynamic-LDS opt-in is a per-device attribute of each instance.
+template <typename S, int TRC, int ORI>
 int fy_launch(const FyParams& p, int64_t wgs, int lds, void* stream, const char* who) {
     static std::atomic<uint64_t> have_lds{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S, TRC>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S, TRC, ORI>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
             rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
             return RV_ERR_HIP;
         }
         have_lds.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((yuv_to_patches_kernel<S, TRC>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    hipLaunchKernelGGL((yuv_to_patches_kernel<S, TRC, ORI>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
     RV_CHECK_LAUNCH("yuv_to_patches");
     return RV_OK;
 }
@@ -395,8 +427,16 @@ double fy_pq_inv64(double nits) {
     return pow((PQ_C1_D + PQ_C2_D * y) / (1.0 + PQ_C3_D * y), PQ_M2_D);
 }
 
-// All entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m: the HDR entry's map (validated by it), else null.
-int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
+// The instance of an orientation class: 0 = none, 1 = mirrors, 2 = transpose.
+template <typename S, int TRC>
+int fy_launch_ori(int ori_class, const FyParams& p, int64_t wgs, int lds, void* stream, const char* who) {
+    if (ori_class == 0) return fy_launch<S, TRC, 0>(p, wgs, lds, stream, who);
+    return ori_class == 1 ? fy_launch<S, TRC, 1>(p, wgs, lds, stream, who) : fy_launch<S, TRC, 2>(p, wgs, lds, stream, who);
+}
+
+// All entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m: the HDR entry's map (validated by it), else null;
+// orient: the oriented entry's code (validated by it), 0 for every other entry - the plan and the instances they always had.
+int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
            void* stream, const char* who) {
     const int sb = s.sample_bytes, H = s.H, W = s.W, n = s.n;
     RV_CHECK_ARG(sb == 1 || sb == 2, "%s: sample_bytes = %d (1, or 2 = little-endian 16-bit words)", who, sb);
@@ -451,17 +491,24 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t R, int32_t patc
     p.R = R;
     p.patch = patch;
     p.g = R / patch;
-    // Resize(R): shorter side -> R, longer side -> int(R * long / short); CenterCrop(R): offset round-half-even((size - R) / 2)
-    const int hr = H <= W ? R : (int)((int64_t)R * H / W), wr = H <= W ? (int)((int64_t)R * W / H) : R;
-    const double sy = (double)H / hr, sx = (double)W / wr;
-    p.top = (int)nearbyint((hr - R) / 2.0);
-    p.left = (int)nearbyint((wr - R) / 2.0);
+    // Resize(R) / CenterCrop(R) of the DISPLAY picture (W x H under transpose); each coded axis then takes what the display axis it serves got
+    const FrOrient ori = fr_orient(orient);
+    double dsy, dsx;
+    int dtop, dleft;
+    fr_resize_crop(ori.tr ? W : H, ori.tr ? H : W, R, dsy, dsx, dtop, dleft);
+    const double sy = ori.tr ? dsx : dsy, sx = ori.tr ? dsy : dsx;
+    p.top = ori.tr ? dleft : dtop;
+    p.left = ori.tr ? dtop : dleft;
+    p.mirx = ori.mx;
+    p.miry = ori.my;
     p.ay = FrAxis{sy, 1.0, 0.0, H};
     p.ax = FrAxis{sx, 1.0, 0.0, W};
     // a subsampled axis whose chroma sample sits on the even luma sample lies a quarter of a chroma sample off: horizontally for left and top-left siting,
-    // vertically for top-left; an axis that is not subsampled is the luma axis
-    p.cy = FrAxis{sy, (double)s.sub_y, s.sub_y == 2 && s.chroma_loc == 2 ? 0.25 : 0.0, H / s.sub_y};
-    p.cx = FrAxis{sx, (double)s.sub_x, s.sub_x == 2 && s.chroma_loc != 1 ? 0.25 : 0.0, W / s.sub_x};
+    // vertically for top-left; an axis that is not subsampled is the luma axis.  The offset belongs to the CODED axis; where that axis is mirrored the sample
+    // sits on the other side of its luma pair on the display, so the offset changes sign
+    const double offy = s.sub_y == 2 && s.chroma_loc == 2 ? 0.25 : 0.0, offx = s.sub_x == 2 && s.chroma_loc != 1 ? 0.25 : 0.0;
+    p.cy = FrAxis{sy, (double)s.sub_y, ori.my ? -offy : offy, H / s.sub_y};
+    p.cx = FrAxis{sx, (double)s.sub_x, ori.mx ? -offx : offx, W / s.sub_x};
     const double kr = s.matrix == 0 ? 0.299 : s.matrix == 1 ? 0.2126 : 0.2627, kb = s.matrix == 0 ? 0.114 : s.matrix == 1 ? 0.0722 : 0.0593, kg = 1.0 - kr - kb;
     const double sc = (double)(1 << (s.depth - 8)), top = (double)((1 << s.depth) - 1);   // 2^(depth - 8); the largest code
     const double cs = s.full_range ? 255.0 / top : 255.0 / (224.0 * sc);
@@ -510,10 +557,22 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t R, int32_t patc
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
     RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = best.o_stage + fy_stage_bytes(best);
-    if (!m) return sb == 1 ? fy_launch<uint8_t, FY_TRC_NONE>(best, wgs, lds, stream, who) : fy_launch<uint16_t, FY_TRC_NONE>(best, wgs, lds, stream, who);
+    const int oc = orient == 0 ? 0 : ori.tr ? 2 : 1;
+    if (!m) return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who);
     if (m->transfer == FY_TRC_PQ)
-        return sb == 1 ? fy_launch<uint8_t, FY_TRC_PQ>(best, wgs, lds, stream, who) : fy_launch<uint16_t, FY_TRC_PQ>(best, wgs, lds, stream, who);
-    return sb == 1 ? fy_launch<uint8_t, FY_TRC_HLG>(best, wgs, lds, stream, who) : fy_launch<uint16_t, FY_TRC_HLG>(best, wgs, lds, stream, who);
+        return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who);
+    return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_HLG>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_HLG>(oc, best, wgs, lds, stream, who);
+}
+
+// The HDR entry's checks of its map.
+int fy_check_map(const rv_hdr_map* m, const char* who) {
+    RV_CHECK_ARG(m->transfer == FY_TRC_PQ || m->transfer == FY_TRC_HLG, "%s: transfer %d (1 = PQ, 2 = HLG)", who, m->transfer);
+    RV_CHECK_ARG(m->gamut == 0 || m->gamut == 1, "%s: gamut %d (0 = none, 1 = BT.2020 -> BT.709)", who, m->gamut);
+    RV_CHECK_ARG(isfinite(m->peak_nits) && m->peak_nits >= 1.0f && m->peak_nits <= 10000.0f, "%s: peak_nits %g outside 1 .. 10000", who,
+                 (double)m->peak_nits);
+    RV_CHECK_ARG(isfinite(m->sdr_white_nits) && m->sdr_white_nits >= 1.0f && m->sdr_white_nits <= 10000.0f, "%s: sdr_white_nits %g outside 1 .. 10000", who,
+                 (double)m->sdr_white_nits);
+    return RV_OK;
 }
 
 }  // namespace
@@ -521,7 +580,7 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t R, int32_t patc
 extern "C" int rv_yuv_surface_to_patches(const rv_yuv_surface* s, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                                          float* image, void* stream) {
     RV_CHECK_ARG(s, "rv_yuv_surface_to_patches: null surface");
-    return fy_run(*s, nullptr, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
+    return fy_run(*s, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
 }
 
 // The surface entry with the HDR -> SDR steps between the colour matrix and the normalisation: the map is validated here, everything else by fy_run.
@@ -530,13 +589,20 @@ extern "C" int rv_yuv_surface_to_patches_hdr(const rv_yuv_surface* s, const rv_h
     const char* who = "rv_yuv_surface_to_patches_hdr";
     RV_CHECK_ARG(s, "%s: null surface", who);
     RV_CHECK_ARG(m, "%s: null map", who);
-    RV_CHECK_ARG(m->transfer == FY_TRC_PQ || m->transfer == FY_TRC_HLG, "%s: transfer %d (1 = PQ, 2 = HLG)", who, m->transfer);
-    RV_CHECK_ARG(m->gamut == 0 || m->gamut == 1, "%s: gamut %d (0 = none, 1 = BT.2020 -> BT.709)", who, m->gamut);
-    RV_CHECK_ARG(isfinite(m->peak_nits) && m->peak_nits >= 1.0f && m->peak_nits <= 10000.0f, "%s: peak_nits %g outside 1 .. 10000", who,
-                 (double)m->peak_nits);
-    RV_CHECK_ARG(isfinite(m->sdr_white_nits) && m->sdr_white_nits >= 1.0f && m->sdr_white_nits <= 10000.0f, "%s: sdr_white_nits %g outside 1 .. 10000", who,
-                 (double)m->sdr_white_nits);
-    return fy_run(*s, m, R, patch, mean, std, patches, ldp, image, stream, who);
+    if (const int rc = fy_check_map(m, who)) return rc;
+    return fy_run(*s, m, 0, R, patch, mean, std, patches, ldp, image, stream, who);
+}
+
+// The surface entry on the picture as it is displayed: the struct describes the coded surface, orient (0 .. 7) turns and flips it; m: NULL = SDR, else the
+// HDR entry's map.
+extern "C" int rv_yuv_surface_to_patches_oriented(const rv_yuv_surface* s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float mean[3],
+                                                  const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_yuv_surface_to_patches_oriented";
+    RV_CHECK_ARG(s, "%s: null surface", who);
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    if (m)
+        if (const int rc = fy_check_map(m, who)) return rc;
+    return fy_run(*s, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
 // The 8-bit 4:2:0 surface of the first entry point: its own two-valued matrix and chroma_loc, then the same code.
@@ -566,5 +632,5 @@ extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64
     s.matrix = matrix;
     s.full_range = full_range;
     s.chroma_loc = chroma_loc;
-    return fy_run(s, nullptr, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
+    return fy_run(s, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
 }

@@ -47,23 +47,31 @@ class ClipFeatureExtractor:
         self.device = towers.device
 
     @torch.no_grad()
-    def encode_video(self, frames, bsz=60, layout=None):
+    def encode_video(self, frames, bsz=60, layout=None, *, rotate=0, hflip=False, vflip=False):
         """-> f32 [T, d], ``bsz`` frames at a time (clip_extractor.py:22-37).  ``frames``: a tensor [T,3,R,R] (0..255, float or uint8) at the towers'
         resolution R - normalised here and handed to ``encode_image`` -, or DECODED uint8 frames of any size, [T,3,H,W] or [T,H,W,3] (``layout``
         "NCHW" / "NHWC" where the shape leaves it open), as one tensor or as an iterable of such chunks (what a decoder hands over): those go through
-        ``encode_frames``, so no float copy at the source resolution ever exists."""
+        ``encode_frames``, so no float copy at the source resolution ever exists.  ``rotate`` / ``hflip`` / ``vflip`` (``ops.orientation``: mp4's ``rotate``
+        tag, then flips) say how decoded uint8 frames that are CODED turned or flipped are displayed; the front-end kernel turns them.  Float frames at the
+        towers' resolution are past the front end: a non-identity orientation is refused for them."""
         tw, R = self.clip_extractor, self.clip_extractor.cfg["image_res"]
+        orient = ops.orientation(rotate, hflip, vflip)
         if torch.is_tensor(frames):
             native = frames.dim() == 4 and tuple(frames.shape[1:]) == (3, R, R) and layout in (None, "NCHW")
+            if orient and frames.dtype == torch.uint8:
+                native = False                                  # uint8 frames of the towers' size are decoded frames like any other: the kernel turns them
             if native or frames.dtype != torch.uint8:
                 if not native:
                     raise ValueError(f"float frames must be [T,3,{R},{R}] (got {tuple(frames.shape)}): frames of another size or layout are taken as "
                                      "decoded uint8 frames")
+                if orient:
+                    raise ValueError(f"rotate={rotate} / hflip={hflip} / vflip={vflip}: float frames at the towers' resolution are past the front end; turn "
+                                     "them before the call, or hand over the decoded uint8 frames")
                 x = preprocess(frames)
                 out = [tw.encode_image(x[i * bsz:(i + 1) * bsz]) for i in range(int(math.ceil(len(x) / bsz)))]
                 return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
             frames = (frames,)
-        out = [tw.encode_frames(b, layout=layout) for b in self._batches(frames, bsz)]
+        out = [tw.encode_frames(b, layout=layout, rotate=rotate, hflip=hflip, vflip=vflip) for b in self._batches(frames, bsz)]
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
 
     @torch.no_grad()
@@ -71,8 +79,10 @@ class ClipFeatureExtractor:
         """-> f32 [T, d] from the bytes of a rawvideo pipe (``ffmpeg -f rawvideo -pix_fmt nv12 | nv21 | yuv420p``; ``fmt`` "nv12" | "nv21" | "i420"): ``chunks``
         is one packed uint8 buffer [t, H*3//2, W] (``torch.frombuffer(data, dtype=torch.uint8).view(-1, H * 3 // 2, W)``) or an iterable of them, CPU or
         device.  They are regrouped into batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv420``) and go through
-        ``encode_frames_yuv``: no RGB frame exists anywhere.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_colour_defaults(H)``."""
+        ``encode_frames_yuv``: no RGB frame exists anywhere.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_colour_defaults(H)``;
+        ``rotate`` / ``hflip`` / ``vflip`` in it (``ops.orientation``) say how a ``-noautorotate`` pipe's coded frames are displayed.  H, W: the CODED size."""
         tw = self.clip_extractor
+        ops.orientation(colour.get("rotate", 0), colour.get("hflip", False), colour.get("vflip", False))     # refused before anything is read
         colour = {**yuv_colour_defaults(H), **colour}
         out = [tw.encode_frames_yuv(*ops.split_yuv420(b, H, W, fmt), **colour)
                for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]")]
@@ -85,8 +95,10 @@ class ClipFeatureExtractor:
         batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv``) and go through ``encode_surfaces_yuv``: no conversion pass, no RGB
         frame.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_surface_colour_defaults``; ``matrix="bt2020"`` says the stream is
         BT.2020 and brings top-left siting with it.  ``transfer="pq"`` | ``"hlg"`` says it is HDR10 / HLG: the BT.2020 tags become the defaults and the
-        frames are converted to SDR inside the kernel (``ops.yuv_surface_to_patches``; ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` go through with it)."""
+        frames are converted to SDR inside the kernel (``ops.yuv_surface_to_patches``; ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` go through with it).
+        ``rotate`` / ``hflip`` / ``vflip`` (``ops.orientation``) say how the coded frames of a ``-noautorotate`` pipe are displayed; H, W: the CODED size."""
         tw = self.clip_extractor
+        ops.orientation(colour.get("rotate", 0), colour.get("hflip", False), colour.get("vflip", False))     # refused before anything is read
         fb = ops.yuv_frame_bytes(H, W, pix_fmt)
         ops.hdr_map(colour.get("transfer"))                     # an unknown transfer is refused before anything is read
         colour = {**yuv_surface_colour_defaults(H, bt2020=colour.get("matrix") == "bt2020", transfer=colour.get("transfer")), **colour}

@@ -93,17 +93,19 @@ class ClipTowers:
         return self._encode_patches(_pad_k(patches).to(self.op_dtype), n)
 
     @torch.no_grad()
-    def encode_frames(self, frames_u8, layout=None):
+    def encode_frames(self, frames_u8, layout=None, *, rotate=0, hflip=False, vflip=False):
         """Decoded uint8 frames [n,3,H,W] / [n,H,W,3] of any size (on the device) -> f32 [n, embed_dim]: resize, centre crop, normalise and unfold in one
-        kernel (``ops.frames_to_patches``: the reference's Resize / CenterCrop / Normalize, inference.py:108-117), then what ``encode_image`` runs."""
+        kernel (``ops.frames_to_patches``: the reference's Resize / CenterCrop / Normalize, inference.py:108-117), then what ``encode_image`` runs.
+        ``rotate`` / ``hflip`` / ``vflip``: the display orientation of frames that are coded turned or flipped (``ops.orientation``), applied in that kernel."""
         c = self.cfg
-        patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype)
+        patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype, rotate=rotate, hflip=hflip, vflip=vflip)
         return self._encode_patches(patches, frames_u8.shape[0])
 
     @torch.no_grad()
     def encode_frames_yuv(self, y, cb, cr=None, **colour):
         """Decoded 8-bit 4:2:0 frames (Y [n,H,W] and the chroma planes as ``ops.yuv_to_patches`` takes them, on the device; ``colour``: its ``matrix`` /
-        ``full_range`` / ``chroma_loc``) -> f32 [n, embed_dim]: resample, convert, crop, normalise and unfold in one kernel, then what ``encode_image`` runs."""
+        ``full_range`` / ``chroma_loc``, and the display orientation ``rotate`` / ``hflip`` / ``vflip`` of a surface coded turned or flipped) -> f32
+        [n, embed_dim]: resample, convert, crop, normalise and unfold in one kernel, then what ``encode_image`` runs."""
         c = self.cfg
         patches, _ = ops.yuv_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **colour)
         return self._encode_patches(patches, y.shape[0])
@@ -112,7 +114,7 @@ class ClipTowers:
     def encode_surfaces_yuv(self, y, cb, cr=None, **surface):
         """Decoded frames of any surface ``ops.yuv_surface_to_patches`` takes (uint8 or uint16 planes on the device; ``surface``: its ``depth`` /
         ``msb_aligned`` / ``subsampling`` / ``matrix`` / ``full_range`` / ``chroma_loc``, and for an HDR surface its ``transfer`` / ``peak_nits`` /
-        ``sdr_white_nits`` / ``gamut``) -> f32 [n, embed_dim], as ``encode_frames_yuv``."""
+        ``sdr_white_nits`` / ``gamut``, and the display orientation ``rotate`` / ``hflip`` / ``vflip``) -> f32 [n, embed_dim], as ``encode_frames_yuv``."""
         c = self.cfg
         patches, _ = ops.yuv_surface_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
         return self._encode_patches(patches, y.shape[0])

@@ -126,6 +126,9 @@ SIGNATURES = {
                                     _i64, _p, _p]),
     "rv_yuv_surface_to_patches": (C.c_int, [C.POINTER(RvYuvSurface), _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
     "rv_yuv_surface_to_patches_hdr": (C.c_int, [C.POINTER(RvYuvSurface), C.POINTER(RvHdrMap), _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
+    "rv_frames_to_patches_oriented": (C.c_int, [_p, C.c_int, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
+    "rv_yuv_surface_to_patches_oriented": (C.c_int, [C.POINTER(RvYuvSurface), C.POINTER(RvHdrMap), _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p,
+                                                     _p]),
     "rv_project_dense": (C.c_int, [_p, _p, _p, C.c_int, _i64, _p]),
     "rv_clip_encoder_ws_bytes": (_sz, [_p, _i32, _i32, _i32, _i32]),
     "rv_clip_encoder": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),

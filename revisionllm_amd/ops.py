@@ -244,12 +244,31 @@ CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 _LAYOUTS = {"NCHW": 0, "NHWC": 1}
 
 
-def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",)):
+#: clockwise degrees by which the coded picture is turned to be displayed -> the orientation code of include/revision_hip.h (bit 0 transpose, bit 1 mirror
+#: display x, bit 2 mirror display y, applied in that order)
+_ROTATIONS = {0: 0, 90: 3, 180: 6, 270: 5}
+
+
+def orientation(rotate=0, hflip=False, vflip=False):
+    """The ``orient`` code (0 .. 7) of rv_frames_to_patches_oriented / rv_yuv_surface_to_patches_oriented.  ``rotate`` 0 | 90 | 180 | 270: the clockwise degrees
+    by which the coded picture must be turned to be displayed (mp4's ``rotate`` tag; the NEGATIVE of ffprobe's display-matrix ``rotation``); ``hflip`` /
+    ``vflip``: mirror the turned picture left-right / top-bottom.  Anything else is refused."""
+    if isinstance(rotate, bool) or not isinstance(rotate, int) or rotate not in _ROTATIONS:
+        raise ValueError(f"rotate {rotate!r}: one of {sorted(_ROTATIONS)} (clockwise degrees; ffprobe's display-matrix rotation is the negative)")
+    if not isinstance(hflip, bool) or not isinstance(vflip, bool):
+        raise ValueError(f"hflip {hflip!r} / vflip {vflip!r}: True or False")
+    return _ROTATIONS[rotate] ^ (2 if hflip else 0) ^ (4 if vflip else 0)      # the mirrors come last in the code and commute: a flip toggles its bit
+
+
+def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), *, rotate=0, hflip=False, vflip=False):
     """Decoded uint8 frames -> the CLIP front end in one launch (rv_frames_to_patches): Resize(R, antialiased bicubic) / CenterCrop(R) /
     (x / 255 - mean) / (std + 1e-8), then -> (patches, image): ``patches`` [n*g*g, Kp] of the operand type (the conv1 GEMM's A matrix: rows (frame, gy, gx),
     columns (channel, py, px), zero-padded from 3 * patch^2 to a multiple of 128), ``image`` f32 [n,3,R,R]; the one ``want`` does not name is None.
     frames: uint8 device tensor [n,3,H,W] ("NCHW") or [n,H,W,3] ("NHWC"); ``layout`` is inferred when only one reading fits.  A window of a larger buffer
-    is passed by its strides (pixels of a row adjacent, NCHW channel planes a third of the frame stride apart); any other view is copied first."""
+    is passed by its strides (pixels of a row adjacent, NCHW channel planes a third of the frame stride apart); any other view is copied first.
+    ``rotate`` / ``hflip`` / ``vflip`` (``orientation``): the frames are CODED sideways or upside down (a ``-noautorotate`` pipe, a hardware decoder) and are
+    turned and flipped inside the same launch (rv_frames_to_patches_oriented) - resize and crop are those of the displayed picture, no copy is made."""
+    orient = orientation(rotate, hflip, vflip)
     if not torch.is_tensor(frames) or not frames.is_cuda:
         raise hip.HipLibraryError("frames_to_patches needs a device tensor (got a CPU tensor); there is no CPU path")
     if frames.dtype != torch.uint8 or frames.dim() != 4:
@@ -278,6 +297,10 @@ def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_ST
     patches = torch.empty(n * g * g, kp, dtype=dt, device=frames.device) if "patches" in want else None
     image = torch.empty(n, 3, R, R, dtype=torch.float32, device=frames.device) if "image" in want else None
     f3 = hip.C.c_float * 3
+    if orient:
+        hip.check(hip.lib(dt).rv_frames_to_patches_oriented(hip.ptr(frames), _LAYOUTS[layout], fs, rs, n, H, W, orient, R, patch, f3(*mean), f3(*std),
+                                                            hip.ptr(patches), kp, hip.ptr(image), hip.stream()), "rv_frames_to_patches_oriented")
+        return patches, image
     hip.check(hip.lib(dt).rv_frames_to_patches(hip.ptr(frames), _LAYOUTS[layout], fs, rs, n, H, W, R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
                                                hip.ptr(image), hip.stream()), "rv_frames_to_patches")
     return patches, image
@@ -301,7 +324,7 @@ def _plane_strides(t, n, rows, cols, pix):
 
 
 def yuv_to_patches(y, cb, cr=None, *, R, patch, matrix="bt601", full_range=False, chroma_loc="left", mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None,
-                   want=("patches",)):
+                   want=("patches",), rotate=0, hflip=False, vflip=False):
     """Decoded 8-bit 4:2:0 YCbCr frames -> the CLIP front end in one launch (rv_yuv_to_patches; the header has the definition of the values): Y resampled at
     full, Cb / Cr at half resolution, colour matrix per output pixel, then everything ``frames_to_patches`` does -> (patches, image) as it returns them.
     y: uint8 device tensor [n,H,W] (H, W even).  Chroma, either of
@@ -309,7 +332,10 @@ def yuv_to_patches(y, cb, cr=None, *, R, patch, matrix="bt601", full_range=False
       * ``cb`` and ``cr`` [n,H/2,W/2] each: two planes (I420), or two views one byte apart with a sample stride of 2 (NV21 / NV12 as ``split_yuv420``
         hands them over): those are read as the interleaved surface they are.
     Planes are passed by their strides when each row's bytes are adjacent (a window of a larger decode surface, a padded pitch); any other view is copied first.
-    matrix "bt601" | "bt709"; full_range False = studio; chroma_loc "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1)."""
+    matrix "bt601" | "bt709"; full_range False = studio; chroma_loc "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1).
+    ``rotate`` / ``hflip`` / ``vflip`` (``orientation``): the planes are the CODED surface of a stream that is displayed turned or flipped; they go through
+    rv_yuv_surface_to_patches_oriented as the 8-bit 4:2:0 surface they are (``yuv_surface_to_patches`` says what orientation does to the siting)."""
+    orient = orientation(rotate, hflip, vflip)
     for t in (y, cb) + (() if cr is None else (cr,)):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise hip.HipLibraryError("yuv_to_patches needs device tensors (got a CPU tensor); there is no CPU path")
@@ -346,6 +372,12 @@ def yuv_to_patches(y, cb, cr=None, *, R, patch, matrix="bt601", full_range=False
     patches = torch.empty(n * g * g, kp, dtype=dt, device=y.device) if "patches" in want else None
     image = torch.empty(n, 3, R, R, dtype=torch.float32, device=y.device) if "image" in want else None
     f3 = hip.C.c_float * 3
+    if orient:
+        s = hip.RvYuvSurface(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), yfs, yrs, cfs, crs, 1, 8, 0, c_pix, 2, 2, n, H, W, _MATRICES[matrix], int(bool(full_range)),
+                             _CHROMA_LOCS[chroma_loc])
+        hip.check(hip.lib(dt).rv_yuv_surface_to_patches_oriented(hip.C.byref(s), None, orient, R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp, hip.ptr(image),
+                                                                 hip.stream()), "rv_yuv_surface_to_patches_oriented")
+        return patches, image
     hip.check(hip.lib(dt).rv_yuv_to_patches(hip.ptr(y), yfs, yrs, hip.ptr(cb), hip.ptr(cr), cfs, crs, c_pix, n, H, W, _MATRICES[matrix], int(bool(full_range)),
                                             _CHROMA_LOCS[chroma_loc], R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp, hip.ptr(image), hip.stream()),
               "rv_yuv_to_patches")
@@ -407,7 +439,8 @@ def hdr_map(transfer, matrix="bt2020", gamut=None, peak_nits=1000.0, sdr_white_n
 
 
 def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=False, subsampling="420", matrix="bt601", full_range=False, chroma_loc="left",
-                           mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), transfer=None, peak_nits=1000.0, sdr_white_nits=203.0, gamut=None):
+                           mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), transfer=None, peak_nits=1000.0, sdr_white_nits=203.0, gamut=None,
+                           rotate=0, hflip=False, vflip=False):
     """Decoded YCbCr frames of any planar / semi-planar surface -> the CLIP front end in one launch (rv_yuv_surface_to_patches; the header has the definition of
     the values) -> (patches, image) as ``frames_to_patches`` returns them.
     Planes are ``torch.uint8`` (depth 8) or ``torch.uint16`` (depth 9 .. 16; ``msb_aligned``: the value sits in the high bits of the word, as in P010 /
@@ -422,7 +455,12 @@ def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=Fal
     HDR surfaces: ``transfer`` "pq" | "hlg" (``hdr_map`` has the aliases) converts the values to BT.709-coded SDR per output pixel inside the same kernel
     (rv_yuv_surface_to_patches_hdr: transfer to display light with ``peak_nits`` as the display peak, BT.2390 tone mapping with ``sdr_white_nits`` becoming
     SDR white, BT.2020 -> BT.709 primaries when ``gamut`` - None: exactly when ``matrix == "bt2020"`` -, BT.709 OETF).  No metadata is read: ``peak_nits`` is
-    the caller's number.  ``transfer=None`` is the SDR entry, which ignores the other three."""
+    the caller's number.  ``transfer=None`` is the SDR entry, which ignores the other three.
+    Orientation: ``rotate`` 0 | 90 | 180 | 270 (clockwise degrees to display: mp4's ``rotate`` tag), then ``hflip`` / ``vflip`` (``orientation``).  The planes,
+    ``subsampling`` and ``chroma_loc`` describe the CODED surface; it is turned and flipped inside the same kernel (rv_yuv_surface_to_patches_oriented), SDR or
+    HDR: resize and crop are those of the displayed picture, the siting follows its axis and changes side where that axis is mirrored, and a turned 4:2:2
+    surface (4:4:0 on the display) is taken as the 4:2:2 surface it is.  The identity is the un-oriented entry."""
+    orient = orientation(rotate, hflip, vflip)
     hdr = hdr_map(transfer, matrix, gamut, peak_nits, sdr_white_nits)
     for t in (y, cb) + (() if cr is None else (cr,)):
         if not torch.is_tensor(t) or not t.is_cuda:
@@ -464,6 +502,10 @@ def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=Fal
     s = hip.RvYuvSurface(y.data_ptr(), cb.data_ptr(), cr.data_ptr(), yfs * es, yrs * es, cfs * es, crs * es, es, int(depth), int(bool(msb_aligned)), c_pix * es,
                          sx, sy, n, H, W, _SURFACE_MATRICES[matrix], int(bool(full_range)), _SURFACE_LOCS[chroma_loc])
     f3 = hip.C.c_float * 3
+    if orient:
+        hip.check(hip.lib(dt).rv_yuv_surface_to_patches_oriented(hip.C.byref(s), None if hdr is None else hip.C.byref(hdr), orient, R, patch, f3(*mean), f3(*std),
+                                                                 hip.ptr(patches), kp, hip.ptr(image), hip.stream()), "rv_yuv_surface_to_patches_oriented")
+        return patches, image
     if hdr is not None:
         hip.check(hip.lib(dt).rv_yuv_surface_to_patches_hdr(hip.C.byref(s), hip.C.byref(hdr), R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
                                                             hip.ptr(image), hip.stream()), "rv_yuv_surface_to_patches_hdr")

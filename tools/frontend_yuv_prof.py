@@ -16,7 +16,14 @@ and 2160 x 3840 against the SDR entry on the same bytes, alternating in one proc
 hdr / sdr per size.  The extra work is R x R pixels against a whole source frame read, so the expectation is "within noise".  Default --out:
 profiles/frontend_hdr.json.
 
-    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME | --transfer pq|hlg] [--out FILE] [--once]
+--rotate N [--hflip] [--vflip] times the display orientation inside the kernel (rv_yuv_surface_to_patches_oriented) on NV12 and P010 noise at 1080 x 1920
+against what a caller does without it on the same bytes - torch.rot90 / flip + .contiguous() of every plane, then the un-oriented entry - and, as information,
+against the un-oriented entry alone (another picture, the same bytes): three forms alternating in one process, the same warm-up and launch counts.  Centre
+siting, so that the one-call and the two-step form compute the same picture (a flip cannot carry left siting through the two-step form); their largest patch
+difference is reported.  The goal: oriented <= two-step.  The run is ADDED to --out (default profiles/frontend_orient.json) under its orientation.
+
+    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME | --transfer pq|hlg | --rotate N [--hflip] [--vflip]]
+                                      [--out FILE] [--once]
     (--once: one launch, for a kernel trace)"""
 import argparse
 import json
@@ -139,6 +146,59 @@ def hdr_run(a, dt):
     print(json.dumps(res))
 
 
+def orient_run(a, dt):
+    """--rotate / --hflip / --vflip: the oriented call against flip / rot90 + contiguous + the un-oriented entry, and against the un-oriented entry alone."""
+    n, H, W, R = a.frames, a.height, a.width, a.res
+    spell = dict(rotate=a.rotate, hflip=a.hflip, vflip=a.vflip)
+    colour = dict(matrix="bt709", full_range=False, chroma_loc="centre")
+    run = dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), orient=ops.orientation(**spell), frames=n, height=H, width=W, res=R, patch=a.patch,
+               warmup=a.warmup, iters=a.iters, formats={})
+
+    def turned(t):
+        """What a caller does today with one plane [n,rows,cols] or [n,rows,cols,2]: a copy in display orientation."""
+        t = torch.rot90(t, -(a.rotate // 90), (1, 2))                                     # rot90 turns counter-clockwise
+        t = t.flip(2) if a.hflip else t
+        t = t.flip(1) if a.vflip else t
+        return t.contiguous()
+
+    for pix_fmt in ("nv12", "p010le"):
+        buf = torch.randint(0, 256, (n, ops.yuv_frame_bytes(H, W, pix_fmt)), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+        (y, cbcr, _), kw = ops.split_yuv(buf.cuda(), H, W, pix_fmt)
+        call = lambda yy, cc, **o: ops.yuv_surface_to_patches(yy, cc, None, R=R, patch=a.patch, op_dtype=dt, **kw, **colour, **o)[0]
+        forms = (("oriented", lambda: call(y, cbcr, **spell)), ("two_step", lambda: call(turned(y), turned(cbcr))), ("unoriented", lambda: call(y, cbcr)))
+        if a.once:
+            forms[0][1]()
+            torch.cuda.synchronize()
+            continue
+        t, first = {k: [] for k, _ in forms}, {}
+        for i in range(a.warmup + a.iters):
+            for name, fn in forms:
+                s, out = timed(fn)
+                if i >= a.warmup:
+                    t[name].append(s)
+                if i == 0:
+                    first[name] = out
+        med = {k: statistics.median(v) for k, v in t.items()}
+        ms = lambda k: dict(median=med[k] * 1e3, min=min(t[k]) * 1e3, max=max(t[k]) * 1e3)
+        run["formats"][pix_fmt] = dict(oriented_ms=ms("oriented"), two_step_ms=ms("two_step"), unoriented_ms=ms("unoriented"),
+                                       oriented_over_two_step=med["oriented"] / med["two_step"], oriented_over_unoriented=med["oriented"] / med["unoriented"],
+                                       goal_met=bool(med["oriented"] <= med["two_step"]),
+                                       max_abs_patch_diff_oriented_vs_two_step=float((first["oriented"].float() - first["two_step"].float()).abs().max()))
+        del y, cbcr, buf, first
+    if a.once:
+        return
+    res = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            res = json.load(f)
+    res["rotate=%d hflip=%d vflip=%d" % (a.rotate, a.hflip, a.vflip)] = run
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(run))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
@@ -152,9 +212,16 @@ def main():
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--pix-fmt", default=None, help="time rv_yuv_surface_to_patches on this ffmpeg pix_fmt instead (ops.PIX_FMTS)")
     ap.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="time rv_yuv_surface_to_patches_hdr on P010 at 1080p and 2160p against the SDR entry")
+    ap.add_argument("--rotate", type=int, default=0, choices=(0, 90, 180, 270), help="time the oriented entry (clockwise degrees) against rot90 + the un-oriented entry")
+    ap.add_argument("--hflip", action="store_true")
+    ap.add_argument("--vflip", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "frontend_yuv_prof needs the GPU: a CPU run says nothing about time"
     dt = hip.op_dtype()
+    if a.rotate or a.hflip or a.vflip:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "frontend_orient.json")
+        return orient_run(a, dt)
     if a.transfer is not None:
         if a.out == ap.get_default("out"):
             a.out = os.path.join(ROOT, "profiles", "frontend_hdr.json")
