@@ -306,7 +306,10 @@ int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64_t y_row_st
  *   norm     (v / 255 - mean[c]) / (std[c] + 1e-8); crop, image and patches laid out, rounded once and zero-padded exactly as by rv_frames_to_patches
  * matrix 2 applies the BT.2020 MATRIX only: this entry converts no transfer function and maps no tones, so PQ / HLG-coded values would reach CLIP as coded -
  * HDR surfaces go through rv_yuv_surface_to_patches_hdr (below), which converts them to SDR inside the same kernel.
- * Not taken: packed 4:2:2 (YUY2 / Y210), 4:1:1, big-endian words, alpha planes.
+ * Packed surfaces (YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ...) go through rv_packed_to_patches, packed RGB in any byte order (BGR, BGRA, ARGB ...) through
+ * rv_frames_to_patches_packed (both below).
+ * Not taken: v210, 4:1:1, big-endian words, RGB deeper than 8 bits (rgb48le, x2rgb10le), Bayer, alpha (an alpha plane, byte or field is ignored, never blended),
+ * dynamic HDR metadata.
  * Refused (RV_ERR_ARG, nothing launched): a null struct or plane; sample_bytes outside {1, 2}; a depth that does not go with it; msb_aligned outside {0, 1}, or 1
  * with sample_bytes 1; (sub_x, sub_y) outside the three pairs; H or W odd along a subsampled axis (odd sizes are legal along an axis with sub = 1), below sub or
  * above 8192; c_pix outside {sample_bytes, 2 * sample_bytes}; interleaved planes that are not sample_bytes apart; with sample_bytes 2 an odd plane pointer or
@@ -391,6 +394,71 @@ int rv_frames_to_patches_oriented(const uint8_t* frames, int layout, int64_t fra
                                   float* image, void* stream);
 int rv_yuv_surface_to_patches_oriented(const rv_yuv_surface* s, const rv_hdr_map* m /* NULL = SDR */, int32_t orient, int32_t R, int32_t patch,
                                        const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+
+/* The front end on PACKED surfaces: what capture cards, webcams and V4L2 emit (YUY2 / UYVY), and the 4:2:2 / 4:4:4 surfaces of VAAPI / D3D11 / QSV decoders
+ * (Y210, AYUV / VUYA, Y410, XV36), read as they lie - no de-interleave pass, every source row read once for all three components.
+ * A packed surface has ONE base pointer; a row is a run of UNITS of unit_bytes bytes that cover pix_per_unit pixels each (all strides in BYTES: a window of a
+ * larger surface that starts on a unit boundary, with a padded pitch, is passed as it lies; INTEGRATION.md has the pointer arithmetic for Y210):
+ *   sample_bytes 1 or 2 (little-endian 16-bit words): a unit is 4 samples.  pix_per_unit 2 (4:2:2): Y0 at y_off, Y1 half a unit behind it, Cb at cb_off, Cr at
+ *                  cr_off (byte offsets in the unit), one chroma pair per two pixels.  pix_per_unit 1 (4:4:4): Y, Cb, Cr at their offsets, the fourth sample (A / X)
+ *                  is never read as a value.
+ *   sample_bytes 4 the unit is one little-endian 32-bit word of three 10-bit fields and covers one pixel; y_off / cb_off / cr_off are BIT shifts out of 0, 10, 20:
+ *                  sample = (word >> off) & 1023.  The top 2 bits are never part of a value.
+ *   by ffmpeg's pix_fmt name (memory order)           unit ppu sample  y cb cr   depth msb
+ *     yuyv422 (YUY2)   Y0 Cb Y1 Cr                       4   2    1     0  1  3     8    0
+ *     uyvy422          Cb Y0 Cr Y1                       4   2    1     1  0  2     8    0
+ *     yvyu422          Y0 Cr Y1 Cb                       4   2    1     0  3  1     8    0
+ *     y210le / y212le  words Y0 Cb Y1 Cr                 8   2    2     0  2  6   10/12  1
+ *     ayuv             A Y Cb Cr                         4   1    1     1  2  3     8    0
+ *     vuya / vuyx      Cr Cb Y A                         4   1    1     2  1  0     8    0
+ *     uyva             Cb Y Cr A                         4   1    1     1  0  2     8    0
+ *     ayuv64le         words A Y Cb Cr                   8   1    2     2  4  6    16    0
+ *     xv36le           words Cb Y Cr X                   8   1    2     2  0  4    12    1
+ *     xv48le           words Cb Y Cr X                   8   1    2     2  0  4    16    0
+ *     xv30le (Y410)    Cb bits 0-9, Y 10-19, Cr 20-29    4   1    4    10  0 20    10    0
+ * Values: EXACTLY what rv_yuv_surface_to_patches defines for the planar surface that holds the same samples - sub_x = pix_per_unit, sub_y = 1, the same
+ * sample_bytes (2 for the bit-field word), depth and msb_aligned: the sample rule (word >> (16 - depth) when msb_aligned: the low bits cannot matter), taps and
+ * f32 weights computed in f64, the siting offset (0.25 on the horizontal axis of a 4:2:2 surface for chroma_loc 0 and 2), the colour equations, with m != NULL the
+ * HDR steps of rv_yuv_surface_to_patches_hdr, with orient != 0 the orientation of rv_yuv_surface_to_patches_oriented (the struct describes the CODED surface),
+ * normalisation, rounding, image and patch layout and zero padding.  The sums run in the same order: the outputs are the bits of the planar entries.
+ * mean / std / patches / ldp / image / R / patch: as in rv_frames_to_patches.
+ * Refused (RV_ERR_ARG, nothing launched): a null struct or base pointer; sample_bytes outside {1, 2, 4}; unit_bytes other than 4 * sample_bytes (4 for the
+ * bit-field word); pix_per_unit outside {1, 2}, or 2 with the bit-field word; offsets that are negative, outside the unit, off a sample boundary, equal to one
+ * another or to the second Y sample's (bit-field word: not three distinct shifts out of 0, 10, 20); a depth that does not go with sample_bytes (8 with 1;
+ * 9 .. 16 with 2; 10 with 4); msb_aligned outside {0, 1}, or 1 with anything but 16-bit words; W odd with 2 pixels per unit (odd H is legal), H outside
+ * 1 .. 8192, W outside pix_per_unit .. 8192; with 16 / 32-bit words a base pointer or a stride that is not a multiple of the word size; matrix outside 0 .. 2;
+ * full_range outside {0, 1}; chroma_loc outside 0 .. 2; orient outside 0 .. 7; a map that rv_yuv_surface_to_patches_hdr refuses; R % patch != 0; both outputs
+ * null; null mean / std; ldp < Kp; a geometry whose tap tables and staged row segments (up to 8 bytes per pixel) do not fit a workgroup's LDS - every format above
+ * fits at 1080 x 1920 -> 224, the 4:2:2 formats and xv30le at 2160 x 3840 -> 224 -; more workgroups than one launch holds.  n = 0 returns 0 and launches
+ * nothing. */
+typedef struct rv_packed_surface {
+    const void* base;                 /* device pointer: the first unit of the first row of the first frame */
+    int64_t frame_stride, row_stride; /* BYTES */
+    int32_t unit_bytes;               /* 4 or 8 */
+    int32_t pix_per_unit;             /* 2 = 4:2:2, 1 = 4:4:4 */
+    int32_t sample_bytes;             /* 1, 2 = little-endian 16-bit words, 4 = one 32-bit word of three 10-bit fields */
+    int32_t y_off, cb_off, cr_off;    /* byte offsets inside the unit (y_off: the first Y sample); BIT shifts with sample_bytes 4 */
+    int32_t depth;                    /* 8 with sample_bytes 1; 9 .. 16 with 2; 10 with 4 */
+    int32_t msb_aligned;              /* 16-bit words only: 1 = value in the high bits (y210le, xv36le) */
+    int32_t n, H, W;
+    int32_t matrix;                   /* as rv_yuv_surface */
+    int32_t full_range;
+    int32_t chroma_loc;               /* matters for pix_per_unit 2 only */
+} rv_packed_surface;
+int rv_packed_to_patches(const rv_packed_surface* s, const rv_hdr_map* m /* NULL = SDR */, int32_t orient, int32_t R, int32_t patch, const float mean[3],
+                         const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+
+/* rv_frames_to_patches_oriented on packed 8-bit RGB in ANY byte order, with or without a fourth byte: what cv2.VideoCapture (bgr24), screen capture, compositors
+ * and hardware colour converters (bgra, rgba, argb ...) hand over - no channel-swap or repacking pass.  frames: u8 [n,H,W,pix_bytes]; a pixel is pix_bytes (3 or 4)
+ * adjacent bytes with R, G, B at byte offsets r_off, g_off, b_off inside it; frame_stride / row_stride in BYTES.
+ *   rgb24 3: 0 1 2   bgr24 3: 2 1 0   rgba / rgb0 4: 0 1 2   bgra / bgr0 4: 2 1 0   argb / 0rgb 4: 1 2 3   abgr / 0bgr 4: 3 2 1
+ * Values: the bits of rv_frames_to_patches (layout 1; with orient != 0 of rv_frames_to_patches_oriented) on a contiguous RGB copy of the frames.  A fourth byte is
+ * never read as a value (alpha is ignored, not blended).
+ * Refused (RV_ERR_ARG, nothing launched): pix_bytes outside {3, 4}; an offset outside 0 .. pix_bytes - 1 or two equal offsets; orient outside 0 .. 7; everything
+ * rv_frames_to_patches refuses.  n = 0 returns 0 and launches nothing. */
+int rv_frames_to_patches_packed(const uint8_t* frames, int32_t pix_bytes, int32_t r_off, int32_t g_off, int32_t b_off, int64_t frame_stride, int64_t row_stride,
+                                int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches,
+                                int64_t ldp, float* image, void* stream);
 
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */

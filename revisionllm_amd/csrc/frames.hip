@@ -14,6 +14,10 @@
 // Display orientation (rv_frames_to_patches_oriented): the kernel is compiled per ORI (0 = none: the code it was; 1 = mirrors; 2 = transpose, with or without
 // mirrors).  Loads, staging and the LDS plan stay in CODED orientation: a coded axis takes the scale, crop offset and mirror flag of the display axis it
 // serves, its tap table holds the display window reflected into coded sample indices, and only the store is permuted to image[f, c, yd, xd].
+//
+// Packed RGB in any byte order (rv_frames_to_patches_packed: bgr24, bgra, argb ...): compiled per PK as well (0: the code it was).  The PK = 1 instances are the
+// NHWC path with a pixel of 3 or 4 bytes and R, G, B at their own byte offsets inside it; the staged row segment covers the whole pixels, a fourth byte is staged
+// and never read.
 #include <atomic>
 
 #include "frames_taps.h"   // the tap definition, FR_* constants and capacity helpers (shared with frames_yuv.hip); fp contraction is off from there on
@@ -34,9 +38,10 @@ struct FrParams {
     int64_t ldp;
     float* image;
     int mirx, miry;                      // oriented instances only (behind everything the ORI = 0 instance reads): the coded x / y axis is mirrored
+    int off[3];                          // PK = 1 instances only: byte offsets of R, G, B inside a pixel of `pix` bytes
 };
 
-template <int ORI>
+template <int ORI, int PK>
 __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrParams p) {
     extern __shared__ __attribute__((aligned(16))) char fr_smem[];
     float* wh = (float*)fr_smem;                       // [TX][NTXp]
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrP
     const int nrows = min(ymin[ty - 1] + ny[ty - 1] - rmin, p.NR);
     const int segpx = min(xmin[tx - 1] + nx[tx - 1] - cmin, p.SEGPX);
     const int segbytes = segpx * p.pix;
-    const int planes = p.pix == 1 ? 3 : 1;
+    const int planes = PK ? 1 : p.pix == 1 ? 3 : 1;
     const int nck = p.SEG >> 4;
     const uint8_t* fsrc = p.src + f * p.fstride + (int64_t)cmin * p.pix;
 
@@ -112,7 +117,12 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrP
             const uint8_t* gs = fsrc + (int64_t)(rmin + r0 + r) * p.rstride;
             const int xo = (xmin[col] - cmin) * p.pix;
             const uint8_t *s0, *s1, *s2;
-            if (planes == 1) {
+            if constexpr (PK) {
+                const uint8_t* px = stage + r * p.SEG + (int)((uintptr_t)gs & 15) + xo;
+                s0 = px + p.off[0];
+                s1 = px + p.off[1];
+                s2 = px + p.off[2];
+            } else if (planes == 1) {
                 s0 = stage + r * p.SEG + (int)((uintptr_t)gs & 15) + xo;
                 s1 = s0 + 1;
                 s2 = s0 + 2;
@@ -207,27 +217,28 @@ bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
 
 int fr_lds_bytes(const FrParams& p) { return p.o_stage + (p.pix == 1 ? 3 : 1) * FR_SR * p.SEG; }
 
-// One launch of the instance for orientation class ORI; the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <int ORI>
+// One launch of the instance for orientation class ORI (PK: the packed-RGB instance); the dynamic-LDS opt-in is a per-device attribute of each instance.
+template <int ORI, int PK>
 int fr_launch(const FrParams& p, int64_t wgs, int lds, void* stream, const char* who) {
     static std::atomic<uint64_t> have_lds{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel<ORI>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel<ORI, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
             rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
             return RV_ERR_HIP;
         }
         have_lds.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(frames_to_patches_kernel<ORI>, dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    hipLaunchKernelGGL((frames_to_patches_kernel<ORI, PK>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
     RV_CHECK_LAUNCH("frames_to_patches");
     return RV_OK;
 }
 
-// Both entry points: validate, plan the tiles, launch.  `who` names the entry point in the messages; orient 0 is the un-oriented entry's plan and instance.
-int fr_run(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch,
+// All entry points: validate, plan the tiles, launch.  `who` names the entry point in the messages; orient 0 is the un-oriented entry's plan and instance.  off:
+// null, or the packed entry's R, G, B byte offsets inside a pixel of pix_bytes bytes (layout is 1 then).
+int fr_run(const uint8_t* frames, int layout, int pix_bytes, const int32_t* off, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch,
            const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream, const char* who) {
     RV_CHECK_ARG(layout == 0 || layout == 1, "%s: layout %d (0 = NCHW, 1 = NHWC)", who, layout);
     RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
@@ -247,7 +258,9 @@ int fr_run(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_
     p.fstride = frame_stride;
     p.rstride = row_stride;
     p.cstride = layout == 1 ? 1 : frame_stride / 3;
-    p.pix = layout == 1 ? 3 : 1;
+    p.pix = layout == 1 ? pix_bytes : 1;
+    if (off)
+        for (int c = 0; c < 3; ++c) p.off[c] = off[c];
     p.H = H;
     p.W = W;
     p.R = R;
@@ -288,8 +301,12 @@ int fr_run(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
     RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = fr_lds_bytes(best);
-    if (orient == 0) return fr_launch<0>(best, wgs, lds, stream, who);
-    return ori.tr ? fr_launch<2>(best, wgs, lds, stream, who) : fr_launch<1>(best, wgs, lds, stream, who);
+    if (off) {
+        if (orient == 0) return fr_launch<0, 1>(best, wgs, lds, stream, who);
+        return ori.tr ? fr_launch<2, 1>(best, wgs, lds, stream, who) : fr_launch<1, 1>(best, wgs, lds, stream, who);
+    }
+    if (orient == 0) return fr_launch<0, 0>(best, wgs, lds, stream, who);
+    return ori.tr ? fr_launch<2, 0>(best, wgs, lds, stream, who) : fr_launch<1, 0>(best, wgs, lds, stream, who);
 }
 
 }  // namespace
@@ -297,7 +314,7 @@ int fr_run(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_
 extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
                                     int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image,
                                     void* stream) {
-    return fr_run(frames, layout, frame_stride, row_stride, n, H, W, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches");
+    return fr_run(frames, layout, 3, nullptr, frame_stride, row_stride, n, H, W, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches");
 }
 
 // The same front end on the picture as it is displayed: H, W and the strides describe the coded frames, orient (0 .. 7) turns and flips them.
@@ -305,5 +322,19 @@ extern "C" int rv_frames_to_patches_oriented(const uint8_t* frames, int layout, 
                                              int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                                              float* image, void* stream) {
     RV_CHECK_ARG(orient >= 0 && orient <= 7, "rv_frames_to_patches_oriented: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", orient);
-    return fr_run(frames, layout, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches_oriented");
+    return fr_run(frames, layout, 3, nullptr, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches_oriented");
+}
+
+// Packed 8-bit RGB in any byte order, 3 or 4 bytes per pixel: the oriented NHWC entry with the channels at their own offsets inside the pixel.
+extern "C" int rv_frames_to_patches_packed(const uint8_t* frames, int32_t pix_bytes, int32_t r_off, int32_t g_off, int32_t b_off, int64_t frame_stride,
+                                           int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch, const float mean[3],
+                                           const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_frames_to_patches_packed";
+    RV_CHECK_ARG(pix_bytes == 3 || pix_bytes == 4, "%s: pix_bytes = %d (3, or 4 = a fourth byte that is never read)", who, pix_bytes);
+    RV_CHECK_ARG(r_off >= 0 && g_off >= 0 && b_off >= 0 && r_off < pix_bytes && g_off < pix_bytes && b_off < pix_bytes && r_off != g_off && r_off != b_off &&
+                     g_off != b_off,
+                 "%s: r_off, g_off, b_off = %d, %d, %d (three distinct byte offsets inside the %d-byte pixel)", who, r_off, g_off, b_off, pix_bytes);
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    const int32_t off[3] = {r_off, g_off, b_off};
+    return fr_run(frames, 1, pix_bytes, off, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }

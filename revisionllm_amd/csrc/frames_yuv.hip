@@ -57,6 +57,9 @@
 // crop offset of the display axis it serves and a mirror flag; the chroma siting offset stays with its coded axis and changes sign where that axis is
 // mirrored; a tap table holds the display window reflected into coded sample indices; only the store is permuted to image[f, c, yd, xd].  So a 4:2:2
 // surface turned by 90 degrees (4:4:0 on the display) is still the 2,1 surface it was coded as.
+//
+// Packed surfaces (rv_packed_to_patches: YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ...) have a kernel of their own behind the planar one, packed_to_patches_kernel:
+// one staged segment per source row serves the Y, Cb and Cr passes; its section has the layout.  The planar instances are untouched by it.
 #include <atomic>
 
 #include "frames_taps.h"   // fp contraction is off from there on
@@ -188,6 +191,56 @@ __device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelt
 // A staged sample as f32: the 16-bit instance drops the low bits of a word whose value sits in the high bits (shift = 0 otherwise).
 __device__ inline float fy_sample(uint8_t v, int) { return (float)v; }
 __device__ inline float fy_sample(uint16_t v, int shift) { return (float)(v >> shift); }
+
+// The packed kernel's copy of what yuv_to_patches_kernel does behind its vertical pass (that kernel keeps its own text, so that its instances stay the code they
+// were): the resampled Y', Cb', Cr' of coded output (y0 + yy, x0 + col) of frame f -> colour matrix, the HDR steps of the HDR instances, normalise, store the f32
+// image and / or op16 patch element at the display pixel this coded output is.
+template <int TRC, int ORI>
+__device__ inline void fy_colour_store(const FyParams& p, float yv, float cb, float cr, int64_t f, int y0, int yy, int x0, int col) {
+    const float yl = (yv - p.yoff) * p.ky;
+    cb -= p.cmid;
+    cr -= p.cmid;
+    float v[3];
+    v[0] = fmaf(p.krcr, cr, yl);
+    v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
+    v[2] = fmaf(p.kbcb, cb, yl);
+    if constexpr (TRC != FY_TRC_NONE) fy_hdr_to_sdr<TRC>(v, p);
+    int y = y0 + yy, x = x0 + col;
+    if constexpr (ORI != 0) {   // the display pixel this coded output is
+        const int dy = fr_disp_index(0, p.R, y, p.miry), dx = fr_disp_index(0, p.R, x, p.mirx);
+        y = ORI == 2 ? dx : dy;
+        x = ORI == 2 ? dy : dx;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float o = (v[c] / 255.0f - p.mean[c]) / p.den[c];
+        if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = o;
+        if (p.patches)
+            p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(o);
+    }
+}
+
+// ... and its zero fill of the pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile.
+template <int ORI>
+__device__ inline void fy_zero_pad(const FyParams& p, int64_t f, int y0, int ty, int x0, int tx, int tid) {
+    if (p.patches && p.Kp > p.K) {
+        int py0 = y0, pty = ty, px0 = x0, ptx = tx;   // the tile's rectangle of the display image
+        if constexpr (ORI != 0) {
+            const int cy0 = p.miry ? p.R - y0 - ty : y0, cx0 = p.mirx ? p.R - x0 - tx : x0;
+            py0 = ORI == 2 ? cx0 : cy0;
+            pty = ORI == 2 ? tx : ty;
+            px0 = ORI == 2 ? cy0 : cx0;
+            ptx = ORI == 2 ? ty : tx;
+        }
+        const int gy0 = (py0 + p.patch - 1) / p.patch, gy1 = (py0 + pty + p.patch - 1) / p.patch;
+        const int gx0 = (px0 + p.patch - 1) / p.patch, gx1 = (px0 + ptx + p.patch - 1) / p.patch;
+        const int pad = p.Kp - p.K, ngx = gx1 - gx0;
+        for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
+            const int j = it % pad, pr = it / pad;
+            p.patches[((f * p.g + gy0 + pr / ngx) * p.g + gx0 + pr % ngx) * p.ldp + p.K + j] = 0;
+        }
+    }
+}
 
 template <typename S, int TRC, int ORI>
 __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyParams p) {
@@ -434,6 +487,67 @@ int fy_launch_ori(int ori_class, const FyParams& p, int64_t wgs, int lds, void* 
     return ori_class == 1 ? fy_launch<S, TRC, 1>(p, wgs, lds, stream, who) : fy_launch<S, TRC, 2>(p, wgs, lds, stream, who);
 }
 
+// What every entry point derives from the frame geometry, the subsampling and the colour tags: resize / crop per coded axis, the luma and chroma axes, the
+// colour coefficients, the HDR scalars (m: null = SDR) and the tap capacities.
+void fy_setup(FyParams& p, int H, int W, int sub_x, int sub_y, int depth, int matrix, int full_range, int chroma_loc, const rv_hdr_map* m, int32_t orient, int32_t R,
+              int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image) {
+    p.R = R;
+    p.patch = patch;
+    p.g = R / patch;
+    // Resize(R) / CenterCrop(R) of the DISPLAY picture (W x H under transpose); each coded axis then takes what the display axis it serves got
+    const FrOrient ori = fr_orient(orient);
+    double dsy, dsx;
+    int dtop, dleft;
+    fr_resize_crop(ori.tr ? W : H, ori.tr ? H : W, R, dsy, dsx, dtop, dleft);
+    const double sy = ori.tr ? dsx : dsy, sx = ori.tr ? dsy : dsx;
+    p.top = ori.tr ? dleft : dtop;
+    p.left = ori.tr ? dtop : dleft;
+    p.mirx = ori.mx;
+    p.miry = ori.my;
+    p.ay = FrAxis{sy, 1.0, 0.0, H};
+    p.ax = FrAxis{sx, 1.0, 0.0, W};
+    // a subsampled axis whose chroma sample sits on the even luma sample lies a quarter of a chroma sample off: horizontally for left and top-left siting,
+    // vertically for top-left; an axis that is not subsampled is the luma axis.  The offset belongs to the CODED axis; where that axis is mirrored the sample
+    // sits on the other side of its luma pair on the display, so the offset changes sign
+    const double offy = sub_y == 2 && chroma_loc == 2 ? 0.25 : 0.0, offx = sub_x == 2 && chroma_loc != 1 ? 0.25 : 0.0;
+    p.cy = FrAxis{sy, (double)sub_y, ori.my ? -offy : offy, H / sub_y};
+    p.cx = FrAxis{sx, (double)sub_x, ori.mx ? -offx : offx, W / sub_x};
+    const double kr = matrix == 0 ? 0.299 : matrix == 1 ? 0.2126 : 0.2627, kb = matrix == 0 ? 0.114 : matrix == 1 ? 0.0722 : 0.0593, kg = 1.0 - kr - kb;
+    const double sc = (double)(1 << (depth - 8)), top = (double)((1 << depth) - 1);   // 2^(depth - 8); the largest code
+    const double cs = full_range ? 255.0 / top : 255.0 / (224.0 * sc);
+    p.yoff = full_range ? 0.0f : (float)(16.0 * sc);
+    p.cmid = (float)(128.0 * sc);
+    p.ky = (float)(full_range ? 255.0 / top : 255.0 / (219.0 * sc));
+    p.krcr = (float)(2.0 * (1.0 - kr) * cs);
+    p.kbcb = (float)(2.0 * (1.0 - kb) * cs);
+    p.kgcb = (float)(-(2.0 * kb * (1.0 - kb) / kg) * cs);
+    p.kgcr = (float)(-(2.0 * kr * (1.0 - kr) / kg) * cs);
+    for (int c = 0; c < 3; ++c) {
+        p.mean[c] = mean[c];
+        p.den[c] = std[c] + 1e-8f;
+    }
+    p.patches = (op16_t*)patches;
+    p.ldp = ldp;
+    p.image = image;
+    if (m) {
+        const double lw = m->peak_nits, lt = m->sdr_white_nits, max_lum = fy_pq_inv64(lt) / fy_pq_inv64(lw);
+        static const double to709[9] = {1.6605, -0.5876, -0.0728, -0.1246, 1.1329, -0.0083, -0.0182, -0.1006, 1.1187};   // BT.2087
+        p.Lw = m->peak_nits;
+        p.rLt = (float)(1.0 / lt);
+        p.pqLw = (float)fy_pq_inv64(lw);
+        p.maxLum = (float)max_lum;
+        p.KS = (float)(1.5 * max_lum - 0.5);
+        p.gm1 = (float)(0.2 + 0.42 * log10(lw / 1000.0));
+        for (int i = 0; i < 9; ++i) p.gam[i] = m->gamut ? (float)to709[i] : (i % 4 == 0 ? 1.0f : 0.0f);
+    }
+    p.NTX = fr_max_taps(p.ax, p.left, R);
+    p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
+    p.NTY = fr_max_taps(p.ay, p.top, R);
+    p.NCX = fr_max_taps(p.cx, p.left, R);
+    p.NCXp = p.NCX | 1;
+    p.NCY = fr_max_taps(p.cy, p.top, R);
+}
+
 // All entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m: the HDR entry's map (validated by it), else null;
 // orient: the oriented entry's code (validated by it), 0 for every other entry - the plan and the instances they always had.
 int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
@@ -488,61 +602,7 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t
         p.ocb = (int)(cb - p.c);
         p.ocr = (int)(cr - p.c);
     }
-    p.R = R;
-    p.patch = patch;
-    p.g = R / patch;
-    // Resize(R) / CenterCrop(R) of the DISPLAY picture (W x H under transpose); each coded axis then takes what the display axis it serves got
-    const FrOrient ori = fr_orient(orient);
-    double dsy, dsx;
-    int dtop, dleft;
-    fr_resize_crop(ori.tr ? W : H, ori.tr ? H : W, R, dsy, dsx, dtop, dleft);
-    const double sy = ori.tr ? dsx : dsy, sx = ori.tr ? dsy : dsx;
-    p.top = ori.tr ? dleft : dtop;
-    p.left = ori.tr ? dtop : dleft;
-    p.mirx = ori.mx;
-    p.miry = ori.my;
-    p.ay = FrAxis{sy, 1.0, 0.0, H};
-    p.ax = FrAxis{sx, 1.0, 0.0, W};
-    // a subsampled axis whose chroma sample sits on the even luma sample lies a quarter of a chroma sample off: horizontally for left and top-left siting,
-    // vertically for top-left; an axis that is not subsampled is the luma axis.  The offset belongs to the CODED axis; where that axis is mirrored the sample
-    // sits on the other side of its luma pair on the display, so the offset changes sign
-    const double offy = s.sub_y == 2 && s.chroma_loc == 2 ? 0.25 : 0.0, offx = s.sub_x == 2 && s.chroma_loc != 1 ? 0.25 : 0.0;
-    p.cy = FrAxis{sy, (double)s.sub_y, ori.my ? -offy : offy, H / s.sub_y};
-    p.cx = FrAxis{sx, (double)s.sub_x, ori.mx ? -offx : offx, W / s.sub_x};
-    const double kr = s.matrix == 0 ? 0.299 : s.matrix == 1 ? 0.2126 : 0.2627, kb = s.matrix == 0 ? 0.114 : s.matrix == 1 ? 0.0722 : 0.0593, kg = 1.0 - kr - kb;
-    const double sc = (double)(1 << (s.depth - 8)), top = (double)((1 << s.depth) - 1);   // 2^(depth - 8); the largest code
-    const double cs = s.full_range ? 255.0 / top : 255.0 / (224.0 * sc);
-    p.yoff = s.full_range ? 0.0f : (float)(16.0 * sc);
-    p.cmid = (float)(128.0 * sc);
-    p.ky = (float)(s.full_range ? 255.0 / top : 255.0 / (219.0 * sc));
-    p.krcr = (float)(2.0 * (1.0 - kr) * cs);
-    p.kbcb = (float)(2.0 * (1.0 - kb) * cs);
-    p.kgcb = (float)(-(2.0 * kb * (1.0 - kb) / kg) * cs);
-    p.kgcr = (float)(-(2.0 * kr * (1.0 - kr) / kg) * cs);
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean[c];
-        p.den[c] = std[c] + 1e-8f;
-    }
-    p.patches = (op16_t*)patches;
-    p.ldp = ldp;
-    p.image = image;
-    if (m) {
-        const double lw = m->peak_nits, lt = m->sdr_white_nits, max_lum = fy_pq_inv64(lt) / fy_pq_inv64(lw);
-        static const double to709[9] = {1.6605, -0.5876, -0.0728, -0.1246, 1.1329, -0.0083, -0.0182, -0.1006, 1.1187};   // BT.2087
-        p.Lw = m->peak_nits;
-        p.rLt = (float)(1.0 / lt);
-        p.pqLw = (float)fy_pq_inv64(lw);
-        p.maxLum = (float)max_lum;
-        p.KS = (float)(1.5 * max_lum - 0.5);
-        p.gm1 = (float)(0.2 + 0.42 * log10(lw / 1000.0));
-        for (int i = 0; i < 9; ++i) p.gam[i] = m->gamut ? (float)to709[i] : (i % 4 == 0 ? 1.0f : 0.0f);
-    }
-    p.NTX = fr_max_taps(p.ax, p.left, R);
-    p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
-    p.NTY = fr_max_taps(p.ay, p.top, R);
-    p.NCX = fr_max_taps(p.cx, p.left, R);
-    p.NCXp = p.NCX | 1;
-    p.NCY = fr_max_taps(p.cy, p.top, R);
+    fy_setup(p, H, W, s.sub_x, s.sub_y, s.depth, s.matrix, s.full_range, s.chroma_loc, m, orient, R, patch, mean, std, patches, ldp, image);
     FyParams best{};
     double best_cost = 0.0;
     bool have = false;
@@ -557,7 +617,7 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
     RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = best.o_stage + fy_stage_bytes(best);
-    const int oc = orient == 0 ? 0 : ori.tr ? 2 : 1;
+    const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
     if (!m) return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who);
     if (m->transfer == FY_TRC_PQ)
         return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who);
@@ -573,6 +633,279 @@ int fy_check_map(const rv_hdr_map* m, const char* who) {
     RV_CHECK_ARG(isfinite(m->sdr_white_nits) && m->sdr_white_nits >= 1.0f && m->sdr_white_nits <= 10000.0f, "%s: sdr_white_nits %g outside 1 .. 10000", who,
                  (double)m->sdr_white_nits);
     return RV_OK;
+}
+
+// ---- packed surfaces (rv_packed_to_patches): YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ... -------------------------------------------------------------
+// One base pointer; a row is a run of units of `unit` bytes that cover `ppu` pixels each.  Pixel x has its Y sample at byte x * (unit / ppu) + oy, chroma sample j
+// (one per unit) has Cb / Cr at j * unit + ocb / ocr.  The values are those of the planar surface that holds the same samples (sub_x = ppu, sub_y = 1), so the
+// luma and chroma ROW windows of a tile coincide: each source row segment - the units that hold the tile's luma and chroma column windows - is staged ONCE and
+// the Y, Cb and Cr horizontal passes run out of it, each with its own offset and sample step.  Tap tables, the fmaf chains per output and everything behind the
+// vertical pass are the planar kernel's, so the results are its bits.  FkParams wraps FyParams: the planar instances see the argument block they always saw.
+struct FkParams {
+    FyParams b;               // y: the surface; yfs / yrs: its strides; ocb / ocr: the chroma byte offsets in a unit; SEGY: bytes of a staged row; NRY: rows of inter
+    int unit, ppu, oy;        // bytes of a unit; pixels it covers; byte offset of its first Y sample
+    int shy, shcb, shcr;      // per component: 16-bit words: sample = word >> shift; 32-bit bit-field words: sample = (word >> shift) & 1023
+    int SPU;                  // units of a staged row segment
+};
+
+__device__ inline float fk_sample(uint8_t v, int) { return (float)v; }
+__device__ inline float fk_sample(uint16_t v, int shift) { return (float)(v >> shift); }
+__device__ inline float fk_sample(uint32_t v, int shift) { return (float)((v >> shift) & 1023u); }
+
+template <typename S, int TRC, int ORI>
+__global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkParams k) {
+    const FyParams& p = k.b;
+    extern __shared__ __attribute__((aligned(16))) char fy_smem[];
+    float* wx = (float*)fy_smem;                       // [TX][NTXp]
+    float* wy = (float*)(fy_smem + p.o_wy);            // [TY][NTY]
+    float* cwx = (float*)(fy_smem + p.o_cwx);          // [TX][NCXp]
+    int* xmin = (int*)(fy_smem + p.o_idx);             // [TX], then nx, cxmin, cnx [TX], ymin, ny [TY]
+    int* nx = xmin + p.TX;
+    int* cxmin = nx + p.TX;
+    int* cnx = cxmin + p.TX;
+    int* ymin = cnx + p.TX;
+    int* ny = ymin + p.TY;
+    float* inter = (float*)(fy_smem + p.o_iy);         // [NRY][Y | Cb | Cr][TX]
+    uint8_t* stage = (uint8_t*)(fy_smem + p.o_stage);  // [FR_SR][SEGY]
+    const int tid = threadIdx.x;
+    uint32_t b = blockIdx.x;
+    const int tile = b % p.tilesX;
+    b /= p.tilesX;
+    const int band = b % p.bands;
+    const int64_t f = b / p.bands;
+    const int y0 = band * p.TY, x0 = tile * p.TX;
+    const int ty = min(p.TY, p.R - y0), tx = min(p.TX, p.R - x0);
+
+    // ---- phase 0: tap tables (sub_y = 1: one row table serves luma and chroma) ---------------------------------------------------------
+    for (int i = tid; i < 2 * tx + ty; i += FR_THREADS) {
+        if constexpr (ORI == 0) {
+            if (i < tx) fy_tap_table(p.ax, x0 + p.left, p.NTX, p.NTXp, wx, xmin, nx, i);
+            else if (i < 2 * tx) fy_tap_table(p.cx, x0 + p.left, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
+            else fy_tap_table(p.ay, y0 + p.top, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
+        } else {
+            if (i < tx) fy_tap_table_m(p.ax, p.left, p.R, p.mirx, x0, p.NTX, p.NTXp, wx, xmin, nx, i);
+            else if (i < 2 * tx) fy_tap_table_m(p.cx, p.left, p.R, p.mirx, x0, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
+            else fy_tap_table_m(p.ay, p.top, p.R, p.miry, y0, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 1: stage each row's units once, three horizontal passes out of them ----------------------------------------------------
+    const int rmin = ymin[0];
+    const int nrows = min(ymin[ty - 1] + ny[ty - 1] - rmin, p.NRY);
+    const int u0 = min(xmin[0] / k.ppu, cxmin[0]);      // the units that hold the luma and the chroma column window
+    const int u1 = min(max((xmin[tx - 1] + nx[tx - 1] + k.ppu - 1) / k.ppu, cxmin[tx - 1] + cnx[tx - 1]), u0 + k.SPU);
+    constexpr int SB = (int)sizeof(S);
+    const int ystep = k.unit / k.ppu, ys = ystep / SB, cs = k.unit / SB;   // bytes / samples between neighbouring Y samples; samples between chroma neighbours
+    const uint8_t* src = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
+    for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
+        const int nr = min(FR_SR, nrows - r0);
+        const uint8_t* g0 = src + (int64_t)r0 * p.yrs;
+        __syncthreads();   // the previous chunk's readers are done with `stage`
+        fy_stage<S>(stage, g0, 0, p.yrs, 1, nr, (u1 - u0) * k.unit, p.SEGY, tid);
+        __syncthreads();
+        for (int it = tid; it < nr * tx; it += FR_THREADS) {
+            const int col = it % tx, r = it / tx;
+            const uint8_t* row = stage + r * p.SEGY + (int)((uintptr_t)(g0 + (int64_t)r * p.yrs) & 15);   // unit u0 of this row
+            float* q = inter + (r0 + r) * 3 * p.TX + col;
+            {
+                const S* s = (const S*)(row + (xmin[col] - u0 * k.ppu) * ystep + k.oy);
+                const float* w = wx + col * p.NTXp;
+                const int n = min(nx[col], u1 * k.ppu - xmin[col]);
+                float a = 0.f;
+                for (int t = 0; t < n; ++t) a = fmaf(w[t], fk_sample(s[t * ys], k.shy), a);
+                q[0] = a;
+            }
+            {
+                const uint8_t* b0 = row + (cxmin[col] - u0) * k.unit;
+                const S *sb = (const S*)(b0 + p.ocb), *sr = (const S*)(b0 + p.ocr);
+                const float* w = cwx + col * p.NCXp;
+                const int n = min(cnx[col], u1 - cxmin[col]);
+                float a0 = 0.f, a1 = 0.f;
+                for (int t = 0; t < n; ++t) {
+                    const float wt = w[t];
+                    const int o = t * cs;
+                    a0 = fmaf(wt, fk_sample(sb[o], k.shcb), a0);
+                    a1 = fmaf(wt, fk_sample(sr[o], k.shcr), a1);
+                }
+                q[p.TX] = a0;
+                q[2 * p.TX] = a1;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: vertical pass, then the planar kernel's colour matrix, normalisation and stores ---------------------------------------
+    for (int it = tid; it < ty * tx; it += FR_THREADS) {
+        const int col = it % tx, yy = it / tx;
+        const int rb = ymin[yy] - rmin;
+        const int n = min(ny[yy], nrows - rb);
+        const float* w = wy + yy * p.NTY;
+        const float* q = inter + rb * 3 * p.TX + col;
+        float yv = 0.f, cb = 0.f, cr = 0.f;
+        for (int t = 0; t < n; ++t) yv = fmaf(w[t], q[t * 3 * p.TX], yv);
+        for (int t = 0; t < n; ++t) {
+            cb = fmaf(w[t], q[(t * 3 + 1) * p.TX], cb);
+            cr = fmaf(w[t], q[(t * 3 + 2) * p.TX], cr);
+        }
+        fy_colour_store<TRC, ORI>(p, yv, cb, cr, f, y0, yy, x0, col);
+    }
+    fy_zero_pad<ORI>(p, f, y0, ty, x0, tx, tid);
+}
+
+// Largest number of units a tile of t coded outputs stages: those that hold its luma and its chroma column window.
+int fk_max_units(const FkParams& k, int t) {
+    const FyParams& p = k.b;
+    int span = 0;
+    for (int o0 = 0; o0 < p.R; o0 += t) {
+        const int o1 = (o0 + t < p.R ? o0 + t : p.R) - 1;
+        int lo, n0, hi, n1, clo, cn0, chi, cn1;
+        fr_axis_taps_m(p.ax, p.left, p.R, o0, p.mirx, lo, n0);
+        fr_axis_taps_m(p.ax, p.left, p.R, o1, p.mirx, hi, n1);
+        fr_axis_taps_m(p.cx, p.left, p.R, o0, p.mirx, clo, cn0);
+        fr_axis_taps_m(p.cx, p.left, p.R, o1, p.mirx, chi, cn1);
+        const int u0 = lo / k.ppu < clo ? lo / k.ppu : clo, ul = (hi + n1 + k.ppu - 1) / k.ppu, u1 = ul > chi + cn1 ? ul : chi + cn1;
+        if (u1 - u0 > span) span = u1 - u0;
+    }
+    return span;
+}
+
+// Tile plan of the packed kernel: one staged segment of whole units (up to 8 bytes per pixel), three `inter` planes; false = over the LDS budget.
+bool fk_plan(FkParams& k, int ty, int tx, double& cost, int& lds) {
+    FyParams& p = k.b;
+    p.TY = ty;
+    p.TX = tx;
+    p.tilesX = (p.R + tx - 1) / tx;
+    p.bands = (p.R + ty - 1) / ty;
+    p.NRY = fr_max_span(p.ay, p.top, p.R, ty, p.miry);
+    k.SPU = fk_max_units(k, tx);
+    p.SEGY = ((k.SPU * k.unit + 15) & ~15) + 16;
+    int64_t o = (int64_t)tx * p.NTXp * 4;
+    p.o_wy = (int)o;
+    o += (int64_t)ty * p.NTY * 4;
+    p.o_cwx = (int)o;
+    o += (int64_t)tx * p.NCXp * 4;
+    p.o_idx = (int)o;
+    o += (int64_t)(4 * tx + 2 * ty) * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_iy = (int)o;
+    o += (int64_t)p.NRY * 3 * tx * 4;
+    o = (o + 15) & ~(int64_t)15;
+    p.o_stage = (int)o;
+    o += (int64_t)FR_SR * p.SEGY;
+    if (o > FR_LDS_BUDGET) return false;
+    lds = (int)o;
+    // the planar planner's measure: source rows of the horizontal pass per output row (one luma and two chroma planes), plus the staged pixels per output pixel
+    const double fx = p.ax.scale > 1.0 ? p.ax.scale : 1.0;
+    cost = (double)p.NRY / ty * (3.0 + (double)k.SPU * k.ppu / (tx * fx));
+    return true;
+}
+
+template <typename S, int TRC, int ORI>
+int fk_launch(const FkParams& k, int64_t wgs, int lds, void* stream, const char* who) {
+    static std::atomic<uint64_t> have_lds{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
+        if (hipFuncSetAttribute((const void*)packed_to_patches_kernel<S, TRC, ORI>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+            rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
+            return RV_ERR_HIP;
+        }
+        have_lds.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL((packed_to_patches_kernel<S, TRC, ORI>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), k);
+    RV_CHECK_LAUNCH("packed_to_patches");
+    return RV_OK;
+}
+
+template <typename S, int TRC>
+int fk_launch_ori(int ori_class, const FkParams& k, int64_t wgs, int lds, void* stream, const char* who) {
+    if (ori_class == 0) return fk_launch<S, TRC, 0>(k, wgs, lds, stream, who);
+    return ori_class == 1 ? fk_launch<S, TRC, 1>(k, wgs, lds, stream, who) : fk_launch<S, TRC, 2>(k, wgs, lds, stream, who);
+}
+
+template <typename S>
+int fk_launch_trc(const rv_hdr_map* m, int ori_class, const FkParams& k, int64_t wgs, int lds, void* stream, const char* who) {
+    if (!m) return fk_launch_ori<S, FY_TRC_NONE>(ori_class, k, wgs, lds, stream, who);
+    return m->transfer == FY_TRC_PQ ? fk_launch_ori<S, FY_TRC_PQ>(ori_class, k, wgs, lds, stream, who) : fk_launch_ori<S, FY_TRC_HLG>(ori_class, k, wgs, lds, stream, who);
+}
+
+// The packed entry: validate the surface (the header has the list), plan, launch.  m and orient are validated by the caller.
+int fk_run(const rv_packed_surface& s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp,
+           float* image, void* stream, const char* who) {
+    const int sb = s.sample_bytes, unit = s.unit_bytes, ppu = s.pix_per_unit, H = s.H, W = s.W, n = s.n;
+    RV_CHECK_ARG(sb == 1 || sb == 2 || sb == 4, "%s: sample_bytes = %d (1, 2 = little-endian 16-bit words, 4 = one 32-bit word of three 10-bit fields)", who, sb);
+    RV_CHECK_ARG((ppu == 1 || ppu == 2) && unit == (sb == 4 ? 4 : 4 * sb) && (sb != 4 || ppu == 1),
+                 "%s: unit_bytes = %d, pix_per_unit = %d with sample_bytes = %d (a unit is 4 samples that cover 1 or 2 pixels, or one 32-bit word that covers 1)", who,
+                 unit, ppu, sb);
+    RV_CHECK_ARG(sb == 1 ? s.depth == 8 : sb == 2 ? (s.depth >= 9 && s.depth <= 16) : s.depth == 10,
+                 "%s: depth = %d does not go with sample_bytes = %d (8 with 1; 9 .. 16 with 2; 10 with 4)", who, s.depth, sb);
+    RV_CHECK_ARG(s.msb_aligned == 0 || (s.msb_aligned == 1 && sb == 2), "%s: msb_aligned = %d (0 or 1, and 1 with 16-bit words only)", who, s.msb_aligned);
+    const int oy = s.y_off, ocb = s.cb_off, ocr = s.cr_off;
+    if (sb == 4) {
+        RV_CHECK_ARG((oy == 0 || oy == 10 || oy == 20) && (ocb == 0 || ocb == 10 || ocb == 20) && (ocr == 0 || ocr == 10 || ocr == 20) && oy != ocb && oy != ocr &&
+                         ocb != ocr,
+                     "%s: y_off, cb_off, cr_off = %d, %d, %d (with sample_bytes 4: three distinct bit shifts out of 0, 10, 20)", who, oy, ocb, ocr);
+    } else {
+        // sample slots of a unit: Y0 (and Y1 half a unit on), Cb, Cr - inside the unit, on sample boundaries, no two the same
+        const int y1 = ppu == 2 ? oy + unit / 2 : oy;
+        RV_CHECK_ARG(oy >= 0 && ocb >= 0 && ocr >= 0 && y1 < unit && ocb < unit && ocr < unit && oy % sb == 0 && ocb % sb == 0 && ocr % sb == 0 && ocb != ocr &&
+                         ocb != oy && ocr != oy && ocb != y1 && ocr != y1,
+                     "%s: y_off, cb_off, cr_off = %d, %d, %d (distinct sample offsets inside the %d-byte unit%s)", who, oy, ocb, ocr, unit,
+                     ppu == 2 ? "; the second Y sample lies half a unit behind the first" : "");
+    }
+    RV_CHECK_ARG(s.matrix >= 0 && s.matrix <= 2, "%s: matrix %d (0 = BT.601, 1 = BT.709, 2 = BT.2020 non-constant luminance)", who, s.matrix);
+    RV_CHECK_ARG(s.full_range == 0 || s.full_range == 1, "%s: full_range %d (0 = studio, 1 = full)", who, s.full_range);
+    RV_CHECK_ARG(s.chroma_loc >= 0 && s.chroma_loc <= 2, "%s: chroma_loc %d (0 = left, 1 = centre, 2 = top-left)", who, s.chroma_loc);
+    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
+    RV_CHECK_ARG(H >= 1 && W >= ppu && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 x %d .. %d", who, H, W, ppu, FR_MAX_SIDE);
+    RV_CHECK_ARG(W % ppu == 0, "%s: frame width W = %d is odd (a unit covers %d pixels)", who, W, ppu);
+    RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
+    RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
+    if (n == 0) return RV_OK;
+    RV_CHECK_ARG(s.base, "%s: null base pointer", who);
+    RV_CHECK_ARG((((uintptr_t)s.base | (uintptr_t)s.frame_stride | (uintptr_t)s.row_stride) & (uintptr_t)(sb - 1)) == 0,
+                 "%s: %d-bit words: base and strides must be aligned to %d bytes (base %p, frame_stride %lld, row_stride %lld)", who, 8 * sb, sb, s.base,
+                 (long long)s.frame_stride, (long long)s.row_stride);
+    RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
+    RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
+    FkParams k{};
+    FyParams& p = k.b;
+    p.K = 3 * patch * patch;
+    p.Kp = (p.K + 127) / 128 * 128;
+    RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
+    p.y = (const uint8_t*)s.base;
+    p.yfs = s.frame_stride;
+    p.yrs = s.row_stride;
+    p.sbytes = sb;
+    k.unit = unit;
+    k.ppu = ppu;
+    if (sb == 4) {
+        k.shy = oy, k.shcb = ocb, k.shcr = ocr;
+    } else {
+        k.oy = oy, p.ocb = ocb, p.ocr = ocr;
+        k.shy = k.shcb = k.shcr = s.msb_aligned ? 16 - s.depth : 0;
+    }
+    fy_setup(p, H, W, ppu, 1, s.depth, s.matrix, s.full_range, s.chroma_loc, m, orient, R, patch, mean, std, patches, ldp, image);
+    FkParams best{};
+    double best_cost = 0.0;
+    int best_lds = 0;
+    bool have = false;
+    for (int ty = 16; ty >= 1; ty >>= 1)
+        for (int tx = 256; tx >= 1; tx >>= 1) {
+            const int tyc = ty < R ? ty : R, txc = tx < R ? tx : R;
+            double cost;
+            int lds;
+            FkParams q = k;
+            if (fk_plan(q, tyc, txc, cost, lds) && (!have || cost < best_cost)) best = q, best_cost = cost, best_lds = lds, have = true;
+        }
+    RV_CHECK_ARG(have, "%s: %d x %d -> %d at %d bytes per pixel needs more filter taps and staging than a workgroup's LDS holds", who, H, W, R, unit / ppu);
+    const int64_t wgs = (int64_t)n * best.b.bands * best.b.tilesX;
+    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
+    const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
+    if (sb == 1) return fk_launch_trc<uint8_t>(m, oc, best, wgs, best_lds, stream, who);
+    return sb == 2 ? fk_launch_trc<uint16_t>(m, oc, best, wgs, best_lds, stream, who) : fk_launch_trc<uint32_t>(m, oc, best, wgs, best_lds, stream, who);
 }
 
 }  // namespace
@@ -633,4 +966,16 @@ extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64
     s.full_range = full_range;
     s.chroma_loc = chroma_loc;
     return fy_run(s, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
+}
+
+// A packed surface (YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ...): one entry for SDR / HDR (m: NULL = SDR) and every orientation, shaped like the oriented
+// surface entry.  The values are those of the planar surface that holds the same samples.
+extern "C" int rv_packed_to_patches(const rv_packed_surface* s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3],
+                                    void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_packed_to_patches";
+    RV_CHECK_ARG(s, "%s: null surface", who);
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    if (m)
+        if (const int rc = fy_check_map(m, who)) return rc;
+    return fk_run(*s, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }

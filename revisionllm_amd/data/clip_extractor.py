@@ -47,15 +47,25 @@ class ClipFeatureExtractor:
         self.device = towers.device
 
     @torch.no_grad()
-    def encode_video(self, frames, bsz=60, layout=None, *, rotate=0, hflip=False, vflip=False):
+    def encode_video(self, frames, bsz=60, layout=None, *, rotate=0, hflip=False, vflip=False, pix_fmt=None):
         """-> f32 [T, d], ``bsz`` frames at a time (clip_extractor.py:22-37).  ``frames``: a tensor [T,3,R,R] (0..255, float or uint8) at the towers'
         resolution R - normalised here and handed to ``encode_image`` -, or DECODED uint8 frames of any size, [T,3,H,W] or [T,H,W,3] (``layout``
         "NCHW" / "NHWC" where the shape leaves it open), as one tensor or as an iterable of such chunks (what a decoder hands over): those go through
         ``encode_frames``, so no float copy at the source resolution ever exists.  ``rotate`` / ``hflip`` / ``vflip`` (``ops.orientation``: mp4's ``rotate``
         tag, then flips) say how decoded uint8 frames that are CODED turned or flipped are displayed; the front-end kernel turns them.  Float frames at the
-        towers' resolution are past the front end: a non-identity orientation is refused for them."""
+        towers' resolution are past the front end: a non-identity orientation is refused for them.  ``pix_fmt`` (``ops.RGB_PIX_FMTS``: "bgr24" from OpenCV,
+        "bgra" / "rgba" / "argb" ... from screen capture): the frames are decoded uint8 [T,H,W,3|4] frames in that byte order, whatever their size, and are
+        read as they lie."""
         tw, R = self.clip_extractor, self.clip_extractor.cfg["image_res"]
         orient = ops.orientation(rotate, hflip, vflip)
+        if pix_fmt is not None:
+            if pix_fmt not in ops.RGB_PIX_FMTS:
+                raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(ops.RGB_PIX_FMTS)} (packed 8-bit RGB)")
+            if layout not in (None, "NHWC"):
+                raise ValueError(f"pix_fmt {pix_fmt!r} names the byte order of packed pixels: layout {layout!r} does not go with it")
+            out = [tw.encode_frames(b, rotate=rotate, hflip=hflip, vflip=vflip, pix_fmt=pix_fmt)
+                   for b in self._batches((frames,) if torch.is_tensor(frames) else frames, bsz, shapes=f"[t,H,W,{ops.RGB_PIX_FMTS[pix_fmt][0]}]")]
+            return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
         if torch.is_tensor(frames):
             native = frames.dim() == 4 and tuple(frames.shape[1:]) == (3, R, R) and layout in (None, "NCHW")
             if orient and frames.dtype == torch.uint8:
@@ -96,16 +106,24 @@ class ClipFeatureExtractor:
         frame.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_surface_colour_defaults``; ``matrix="bt2020"`` says the stream is
         BT.2020 and brings top-left siting with it.  ``transfer="pq"`` | ``"hlg"`` says it is HDR10 / HLG: the BT.2020 tags become the defaults and the
         frames are converted to SDR inside the kernel (``ops.yuv_surface_to_patches``; ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` go through with it).
-        ``rotate`` / ``hflip`` / ``vflip`` (``ops.orientation``) say how the coded frames of a ``-noautorotate`` pipe are displayed; H, W: the CODED size."""
+        ``rotate`` / ``hflip`` / ``vflip`` (``ops.orientation``) say how the coded frames of a ``-noautorotate`` pipe are displayed; H, W: the CODED size.
+        The packed names of ``ops.PACKED_PIX_FMTS`` (yuyv422 / uyvy422 / y210le / ayuv / xv30le ...) are taken too: [t, ops.packed_frame_bytes(H, W, pix_fmt)]
+        buffers go, with the same colour defaults and the same batching, through ``encode_surfaces_packed`` (``ops.packed_to_patches``) as they lie."""
         tw = self.clip_extractor
+        packed = pix_fmt in ops.PACKED_PIX_FMTS                 # decided before anything else is computed
+        if not packed and pix_fmt not in ops.PIX_FMTS:
+            raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(ops.PIX_FMTS)} (planar / semi-planar) or of {sorted(ops.PACKED_PIX_FMTS)} (packed)")
         ops.orientation(colour.get("rotate", 0), colour.get("hflip", False), colour.get("vflip", False))     # refused before anything is read
-        fb = ops.yuv_frame_bytes(H, W, pix_fmt)
+        fb = ops.packed_frame_bytes(H, W, pix_fmt) if packed else ops.yuv_frame_bytes(H, W, pix_fmt)
         ops.hdr_map(colour.get("transfer"))                     # an unknown transfer is refused before anything is read
         colour = {**yuv_surface_colour_defaults(H, bt2020=colour.get("matrix") == "bt2020", transfer=colour.get("transfer")), **colour}
         if colour.get("transfer") is None:
             colour.pop("transfer", None)                        # transfer=None is the SDR call as it always was
         out = []
         for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=2, shapes=f"[t,{fb}]"):
+            if packed:
+                out.append(tw.encode_surfaces_packed(b, H=H, W=W, pix_fmt=pix_fmt, **colour))
+                continue
             planes, kw = ops.split_yuv(b, H, W, pix_fmt)
             out.append(tw.encode_surfaces_yuv(*planes, **kw, **colour))
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)

@@ -93,12 +93,14 @@ class ClipTowers:
         return self._encode_patches(_pad_k(patches).to(self.op_dtype), n)
 
     @torch.no_grad()
-    def encode_frames(self, frames_u8, layout=None, *, rotate=0, hflip=False, vflip=False):
+    def encode_frames(self, frames_u8, layout=None, *, rotate=0, hflip=False, vflip=False, pix_fmt=None):
         """Decoded uint8 frames [n,3,H,W] / [n,H,W,3] of any size (on the device) -> f32 [n, embed_dim]: resize, centre crop, normalise and unfold in one
         kernel (``ops.frames_to_patches``: the reference's Resize / CenterCrop / Normalize, inference.py:108-117), then what ``encode_image`` runs.
-        ``rotate`` / ``hflip`` / ``vflip``: the display orientation of frames that are coded turned or flipped (``ops.orientation``), applied in that kernel."""
+        ``rotate`` / ``hflip`` / ``vflip``: the display orientation of frames that are coded turned or flipped (``ops.orientation``), applied in that kernel.
+        ``pix_fmt`` (``ops.RGB_PIX_FMTS``: "bgr24", "bgra" ...): [n,H,W,3|4] frames in that byte order, read as they lie."""
         c = self.cfg
-        patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype, rotate=rotate, hflip=hflip, vflip=vflip)
+        patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype, rotate=rotate, hflip=hflip, vflip=vflip,
+                                           pix_fmt=pix_fmt)
         return self._encode_patches(patches, frames_u8.shape[0])
 
     @torch.no_grad()
@@ -118,6 +120,14 @@ class ClipTowers:
         c = self.cfg
         patches, _ = ops.yuv_surface_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
         return self._encode_patches(patches, y.shape[0])
+
+    @torch.no_grad()
+    def encode_surfaces_packed(self, buf, **surface):
+        """Frames of a packed YCbCr surface as ``ops.packed_to_patches`` takes them (``surface``: its ``H`` / ``W`` / ``pix_fmt``, colour tags, HDR arguments and
+        display orientation) -> f32 [n, embed_dim], as ``encode_surfaces_yuv``."""
+        c = self.cfg
+        patches, _ = ops.packed_to_patches(buf, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
+        return self._encode_patches(patches, buf.shape[0])
 
     def _encode_patches(self, patches, n):
         """patches [n*g*g, Kp] operand type (the unfolded, K-padded frames) -> f32 [n, embed_dim]: conv1 as a GEMM and everything behind it."""

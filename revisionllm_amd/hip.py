@@ -52,6 +52,14 @@ class RvHdrMap(C.Structure):
     _fields_ = [("transfer", C.c_int32), ("gamut", C.c_int32), ("peak_nits", C.c_float), ("sdr_white_nits", C.c_float)]
 
 
+class RvPackedSurface(C.Structure):
+    """``rv_packed_surface``: base pointer, strides (bytes), unit layout, component offsets, sample format and colour tags of a packed YCbCr surface
+    (rv_packed_to_patches)."""
+    _fields_ = [("base", C.c_void_p), ("frame_stride", C.c_int64), ("row_stride", C.c_int64), ("unit_bytes", C.c_int32), ("pix_per_unit", C.c_int32),
+                ("sample_bytes", C.c_int32), ("y_off", C.c_int32), ("cb_off", C.c_int32), ("cr_off", C.c_int32), ("depth", C.c_int32), ("msb_aligned", C.c_int32),
+                ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32), ("chroma_loc", C.c_int32)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -129,6 +137,9 @@ SIGNATURES = {
     "rv_frames_to_patches_oriented": (C.c_int, [_p, C.c_int, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
     "rv_yuv_surface_to_patches_oriented": (C.c_int, [C.POINTER(RvYuvSurface), C.POINTER(RvHdrMap), _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p,
                                                      _p]),
+    "rv_packed_to_patches": (C.c_int, [C.POINTER(RvPackedSurface), C.POINTER(RvHdrMap), _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
+    "rv_frames_to_patches_packed": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p,
+                                              _p]),
     "rv_project_dense": (C.c_int, [_p, _p, _p, C.c_int, _i64, _p]),
     "rv_clip_encoder_ws_bytes": (_sz, [_p, _i32, _i32, _i32, _i32]),
     "rv_clip_encoder": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),

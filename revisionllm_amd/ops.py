@@ -260,15 +260,28 @@ def orientation(rotate=0, hflip=False, vflip=False):
     return _ROTATIONS[rotate] ^ (2 if hflip else 0) ^ (4 if vflip else 0)      # the mirrors come last in the code and commute: a flip toggles its bit
 
 
-def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), *, rotate=0, hflip=False, vflip=False):
+#: ffmpeg's pix_fmt names of packed 8-bit RGB -> (bytes per pixel, byte offsets of R, G, B inside it); a fourth byte (alpha or padding) is never read
+RGB_PIX_FMTS = {
+    "rgb24": (3, 0, 1, 2), "bgr24": (3, 2, 1, 0), "rgba": (4, 0, 1, 2), "bgra": (4, 2, 1, 0), "argb": (4, 1, 2, 3), "abgr": (4, 3, 2, 1),
+    "rgb0": (4, 0, 1, 2), "bgr0": (4, 2, 1, 0), "0rgb": (4, 1, 2, 3), "0bgr": (4, 3, 2, 1),
+}
+
+
+def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), *, rotate=0, hflip=False, vflip=False,
+                      pix_fmt=None):
     """Decoded uint8 frames -> the CLIP front end in one launch (rv_frames_to_patches): Resize(R, antialiased bicubic) / CenterCrop(R) /
     (x / 255 - mean) / (std + 1e-8), then -> (patches, image): ``patches`` [n*g*g, Kp] of the operand type (the conv1 GEMM's A matrix: rows (frame, gy, gx),
     columns (channel, py, px), zero-padded from 3 * patch^2 to a multiple of 128), ``image`` f32 [n,3,R,R]; the one ``want`` does not name is None.
     frames: uint8 device tensor [n,3,H,W] ("NCHW") or [n,H,W,3] ("NHWC"); ``layout`` is inferred when only one reading fits.  A window of a larger buffer
     is passed by its strides (pixels of a row adjacent, NCHW channel planes a third of the frame stride apart); any other view is copied first.
     ``rotate`` / ``hflip`` / ``vflip`` (``orientation``): the frames are CODED sideways or upside down (a ``-noautorotate`` pipe, a hardware decoder) and are
-    turned and flipped inside the same launch (rv_frames_to_patches_oriented) - resize and crop are those of the displayed picture, no copy is made."""
+    turned and flipped inside the same launch (rv_frames_to_patches_oriented) - resize and crop are those of the displayed picture, no copy is made.
+    ``pix_fmt`` (one of ``RGB_PIX_FMTS``: "bgr24" is what ``cv2.VideoCapture`` hands over, "bgra" / "rgba" / "argb" ... what screen capture and colour converters
+    do): the frames are [n,H,W,3] or [n,H,W,4] in that byte order and are read as they lie (rv_frames_to_patches_packed) - the bits of the call on a contiguous
+    RGB copy, without the copy; a fourth byte is ignored.  ``None`` is the call as it always was."""
     orient = orientation(rotate, hflip, vflip)
+    if pix_fmt is not None:
+        return _frames_to_patches_packed(frames, R, patch, layout, mean, std, op_dtype, want, orient, pix_fmt)
     if not torch.is_tensor(frames) or not frames.is_cuda:
         raise hip.HipLibraryError("frames_to_patches needs a device tensor (got a CPU tensor); there is no CPU path")
     if frames.dtype != torch.uint8 or frames.dim() != 4:
@@ -303,6 +316,33 @@ def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_ST
         return patches, image
     hip.check(hip.lib(dt).rv_frames_to_patches(hip.ptr(frames), _LAYOUTS[layout], fs, rs, n, H, W, R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
                                                hip.ptr(image), hip.stream()), "rv_frames_to_patches")
+    return patches, image
+
+
+def _frames_to_patches_packed(frames, R, patch, layout, mean, std, op_dtype, want, orient, pix_fmt):
+    """``frames_to_patches(..., pix_fmt=...)``: every refusal comes before anything is read or launched."""
+    if pix_fmt not in RGB_PIX_FMTS:
+        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(RGB_PIX_FMTS)} (packed 8-bit RGB)")
+    pix, r, g, b = RGB_PIX_FMTS[pix_fmt]
+    if layout not in (None, "NHWC"):
+        raise ValueError(f"pix_fmt {pix_fmt!r} names the byte order of packed pixels [n,H,W,{pix}]: layout {layout!r} does not go with it")
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != pix:
+        raise ValueError(f"{pix_fmt} frames come as a uint8 tensor [n,H,W,{pix}], got "
+                         + (f"{frames.dtype} {tuple(frames.shape)}" if torch.is_tensor(frames) else type(frames).__name__))
+    if not frames.is_cuda:
+        raise hip.HipLibraryError("frames_to_patches needs a device tensor (got a CPU tensor); there is no CPU path")
+    n, H, W = frames.shape[:3]
+    ok = frames.stride(3) == 1 and frames.stride(2) == pix and frames.stride(1) >= pix * W and (n <= 1 or frames.stride(0) > 0)
+    frames = frames if ok else frames.contiguous()
+    fs, rs = (frames.stride(0) if n > 1 else frames.stride(1) * H), frames.stride(1)
+    dt = hip.op_dtype(op_dtype)
+    g_ = R // max(patch, 1)
+    kp = (3 * patch * patch + 127) // 128 * 128
+    patches = torch.empty(n * g_ * g_, kp, dtype=dt, device=frames.device) if "patches" in want else None
+    image = torch.empty(n, 3, R, R, dtype=torch.float32, device=frames.device) if "image" in want else None
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_frames_to_patches_packed(hip.ptr(frames), pix, r, g, b, fs, rs, n, H, W, orient, R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
+                                                      hip.ptr(image), hip.stream()), "rv_frames_to_patches_packed")
     return patches, image
 
 
@@ -551,6 +591,77 @@ def split_yuv(buf, H, W, pix_fmt):
         return (y, buf.as_strided((n, h, w), (fs, w, 1), at + H * W), buf.as_strided((n, h, w), (fs, w, 1), at + H * W + h * w)), kw
     pairs = buf.as_strided((n, h, w, 2), (fs, 2 * w, 2, 1), at + H * W)
     return ((y, pairs, None) if layout == "cbcr" else (y, pairs[..., 1], pairs[..., 0])), kw
+
+
+#: ffmpeg's pix_fmt names of PACKED YCbCr surfaces -> (unit bytes, pixels per unit, sample bytes, offset of Y / Cb / Cr inside the unit, depth, value in the high
+#: bits): the fields of rv_packed_surface (include/revision_hip.h has the layouts).  Offsets are bytes (the first Y sample's; with 2 pixels per unit the second one
+#: lies half a unit behind it), or bit shifts for the 32-bit word of three 10-bit fields (sample bytes 4).
+PACKED_PIX_FMTS = {
+    "yuyv422": (4, 2, 1, 0, 1, 3, 8, False), "uyvy422": (4, 2, 1, 1, 0, 2, 8, False), "yvyu422": (4, 2, 1, 0, 3, 1, 8, False),
+    "y210le": (8, 2, 2, 0, 2, 6, 10, True), "y212le": (8, 2, 2, 0, 2, 6, 12, True),
+    "ayuv": (4, 1, 1, 1, 2, 3, 8, False), "vuya": (4, 1, 1, 2, 1, 0, 8, False), "vuyx": (4, 1, 1, 2, 1, 0, 8, False), "uyva": (4, 1, 1, 1, 0, 2, 8, False),
+    "ayuv64le": (8, 1, 2, 2, 4, 6, 16, False), "xv36le": (8, 1, 2, 2, 0, 4, 12, True), "xv48le": (8, 1, 2, 2, 0, 4, 16, False),
+    "xv30le": (4, 1, 4, 10, 0, 20, 10, False),
+}
+
+
+def _packed_fmt(pix_fmt):
+    if pix_fmt not in PACKED_PIX_FMTS:
+        raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(PACKED_PIX_FMTS)} (packed) or of {sorted(PIX_FMTS)} (planar / semi-planar: split_yuv)")
+    return PACKED_PIX_FMTS[pix_fmt]
+
+
+def packed_frame_bytes(H, W, pix_fmt):
+    """Bytes of one ``H`` x ``W`` frame of a rawvideo pipe in a packed ``pix_fmt`` (one of ``PACKED_PIX_FMTS``)."""
+    unit, ppu = _packed_fmt(pix_fmt)[:2]
+    if isinstance(H, bool) or isinstance(W, bool) or not isinstance(H, int) or not isinstance(W, int) or H < 1 or W < ppu or W % ppu:
+        raise ValueError(f"{pix_fmt} frames have W a multiple of {ppu} (a unit of {unit} bytes covers {ppu} pixels) and H >= 1, got {H} x {W}")
+    return H * (W // ppu) * unit
+
+
+def packed_to_patches(buf, *, H, W, pix_fmt, R, patch, matrix="bt601", full_range=False, chroma_loc="left", transfer=None, peak_nits=1000.0, sdr_white_nits=203.0,
+                      gamut=None, rotate=0, hflip=False, vflip=False, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",)):
+    """Frames of a PACKED YCbCr surface (``PACKED_PIX_FMTS``: yuyv422 / uyvy422 from capture cards and webcams, y210le / ayuv / vuya / xv30le (Y410) / xv36le from
+    VAAPI / D3D11 / QSV decoders) -> the CLIP front end in one launch (rv_packed_to_patches) -> (patches, image) as ``frames_to_patches`` returns them.  The
+    values are the bits of ``yuv_surface_to_patches`` on the planar 4:2:2 / 4:4:4 surface that holds the same samples; no de-interleave pass is made and every
+    source row is read once.  A / X bytes, the top bits of xv30le and the low bits of y210le / xv36le words never matter.
+    buf: uint8 device tensor [n, H, row_bytes] with row_bytes = ``packed_frame_bytes(1, W, pix_fmt)``, passed by its strides - a padded pitch, or a window of a
+    larger surface that starts on a unit boundary, is passed as it lies - or [n, ``packed_frame_bytes(H, W, pix_fmt)``].  With 16 / 32-bit words the address and
+    the strides are multiples of the word size.  Colour tags, ``transfer`` / ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` and ``rotate`` / ``hflip`` / ``vflip``
+    as in ``yuv_surface_to_patches`` (``chroma_loc`` matters for the 4:2:2 formats only).  Every refusal comes before anything is read or launched."""
+    unit, ppu, sb, oy, ocb, ocr, depth, msb = _packed_fmt(pix_fmt)
+    orient = orientation(rotate, hflip, vflip)
+    hdr = hdr_map(transfer, matrix, gamut, peak_nits, sdr_white_nits)
+    if matrix not in _SURFACE_MATRICES or chroma_loc not in _SURFACE_LOCS:
+        raise ValueError(f"matrix {matrix!r} / chroma_loc {chroma_loc!r}: one of {sorted(_SURFACE_MATRICES)} / {sorted(_SURFACE_LOCS)}")
+    rb, fb = packed_frame_bytes(1, W, pix_fmt), packed_frame_bytes(H, W, pix_fmt)
+    if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or not ((buf.dim() == 3 and tuple(buf.shape[1:]) == (H, rb)) or (buf.dim() == 2 and buf.shape[1] == fb)):
+        raise ValueError(f"{pix_fmt} frames of {H} x {W} come as a uint8 tensor [n,{H},{rb}] or [n,{fb}], got "
+                         + (f"{buf.dtype} {tuple(buf.shape)}" if torch.is_tensor(buf) else type(buf).__name__))
+    n = buf.shape[0]
+    if buf.dim() == 2:
+        if buf.stride(1) != 1:
+            buf = buf.contiguous()
+        buf = buf.as_strided((n, H, rb), (buf.stride(0), rb, 1), buf.storage_offset())
+    elif not (buf.stride(2) == 1 and (H == 1 or buf.stride(1) >= rb) and (n <= 1 or buf.stride(0) > 0)):
+        buf = buf.contiguous()
+    rs = buf.stride(1) if H > 1 else rb
+    fs = buf.stride(0) if n > 1 else rs * H
+    if sb > 1 and (buf.storage_offset() % sb or rs % sb or fs % sb or (buf.is_cuda and buf.data_ptr() % sb)):
+        raise ValueError(f"{pix_fmt}: {8 * sb}-bit words must lie at multiples of {sb} bytes (offset {buf.storage_offset()}, row stride {rs}, frame stride {fs})")
+    if not buf.is_cuda:
+        raise hip.HipLibraryError("packed_to_patches needs a device tensor (got a CPU tensor); there is no CPU path")
+    dt = hip.op_dtype(op_dtype)
+    g = R // max(patch, 1)
+    kp = (3 * patch * patch + 127) // 128 * 128
+    patches = torch.empty(n * g * g, kp, dtype=dt, device=buf.device) if "patches" in want else None
+    image = torch.empty(n, 3, R, R, dtype=torch.float32, device=buf.device) if "image" in want else None
+    s = hip.RvPackedSurface(buf.data_ptr(), fs, rs, unit, ppu, sb, oy, ocb, ocr, depth, int(msb), n, H, W, _SURFACE_MATRICES[matrix], int(bool(full_range)),
+                            _SURFACE_LOCS[chroma_loc])
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_packed_to_patches(hip.C.byref(s), None if hdr is None else hip.C.byref(hdr), orient, R, patch, f3(*mean), f3(*std), hip.ptr(patches), kp,
+                                               hip.ptr(image), hip.stream()), "rv_packed_to_patches")
+    return patches, image
 
 
 def h2d(t, device, dtype=None):

@@ -24,7 +24,13 @@ difference is reported.  The goal: oriented <= two-step.  The run is ADDED to --
 
     python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME | --transfer pq|hlg | --rotate N [--hflip] [--vflip]]
                                       [--out FILE] [--once]
-    (--once: one launch, for a kernel trace)"""
+    (--once: one launch, for a kernel trace)
+
+--pix-fmt <packed name> (yuyv422 / y210le / xv30le / ayuv ...) and --rgb-order <bgra / bgr24 ...>: the packed entries (rv_packed_to_patches,
+rv_frames_to_patches_packed) against the planar / NHWC entry on the same samples and against the two-step path they replace (a torch de-interleave or channel
+swap over every full-resolution frame, then the existing entry), alternating on the same bytes.  The expectation: packed <= planar (each source row is staged
+once), and the two-step path costs the extra pass.  Each run is ADDED to --out (default profiles/frontend_packed.json) under its name.
+"""
 import argparse
 import json
 import os
@@ -199,6 +205,91 @@ def orient_run(a, dt):
     print(json.dumps(run))
 
 
+def deinterleave(buf, H, W, pix_fmt):
+    """What a caller does today with a packed surface: a torch pass over every frame into the planar planes ``ops.yuv_surface_to_patches`` takes."""
+    unit, ppu, sb, oy, ocb, ocr, depth, msb = ops.PACKED_PIX_FMTS[pix_fmt]
+    n = buf.shape[0]
+    if sb == 4:
+        w = buf.view(torch.int32).view(n, H, W)
+        planes = tuple(((w >> o) & 1023).to(torch.int16).view(torch.uint16) for o in (oy, ocb, ocr))
+        return planes, dict(depth=depth, msb_aligned=False, subsampling="444")
+    u = (buf if sb == 1 else buf.view(torch.int16)).view(n, H, W // ppu, 4)
+    y = torch.stack((u[..., oy // sb], u[..., oy // sb + 2]), -1).view(n, H, W) if ppu == 2 else u[..., oy // sb].contiguous()
+    planes = (y, u[..., ocb // sb].contiguous(), u[..., ocr // sb].contiguous())
+    planes = planes if sb == 1 else tuple(t.view(torch.uint16) for t in planes)
+    return planes, dict(depth=depth, msb_aligned=msb, subsampling="422" if ppu == 2 else "444")
+
+
+def alternate(forms, a):
+    """Median / min / max seconds per form, the forms alternating inside every iteration; the first outputs."""
+    t, first = {k: [] for k, _ in forms}, {}
+    for i in range(a.warmup + a.iters):
+        for name, fn in forms:
+            s, out = timed(fn)
+            if i >= a.warmup:
+                t[name].append(s)
+            if i == 0:
+                first[name] = out
+    med = {k: statistics.median(v) for k, v in t.items()}
+    return med, {k: dict(median=med[k] * 1e3, min=min(v) * 1e3, max=max(v) * 1e3) for k, v in t.items()}, first
+
+
+def add_to(out, key, run):
+    res = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            res = json.load(f)
+    res[key] = run
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(run))
+
+
+def packed_run(a, dt):
+    """--pix-fmt <a packed name>: rv_packed_to_patches against the planar entry on the same samples (already de-interleaved) and against the two-step path it
+    replaces (torch de-interleave + the planar entry), alternating on the same bytes.  The run is ADDED to --out under the format's name."""
+    n, H, W, R = a.frames, a.height, a.width, a.res
+    buf = torch.randint(0, 256, (n, ops.packed_frame_bytes(H, W, a.pix_fmt)), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).cuda()
+    colour = dict(matrix="bt709", full_range=False, chroma_loc="left")
+    planes, kw = deinterleave(buf, H, W, a.pix_fmt)
+    planar = lambda pl: ops.yuv_surface_to_patches(*pl, R=R, patch=a.patch, op_dtype=dt, **kw, **colour)[0]
+    forms = (("packed", lambda: ops.packed_to_patches(buf, H=H, W=W, pix_fmt=a.pix_fmt, R=R, patch=a.patch, op_dtype=dt, **colour)[0]),
+             ("planar", lambda: planar(planes)), ("two_step", lambda: planar(deinterleave(buf, H, W, a.pix_fmt)[0])))
+    if a.once:
+        forms[0][1]()
+        torch.cuda.synchronize()
+        return
+    med, ms, first = alternate(forms, a)
+    add_to(a.out, a.pix_fmt, dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), pix_fmt=a.pix_fmt, frames=n, height=H, width=W, res=R, patch=a.patch,
+                                  warmup=a.warmup, iters=a.iters, packed_ms=ms["packed"], planar_ms=ms["planar"], two_step_ms=ms["two_step"],
+                                  packed_over_planar=med["packed"] / med["planar"], packed_over_two_step=med["packed"] / med["two_step"],
+                                  packed_not_slower_than_planar=bool(med["packed"] <= med["planar"]),
+                                  same_bits_as_planar=bool(torch.equal(first["packed"].view(torch.int16), first["planar"].view(torch.int16)))))
+
+
+def rgb_order_run(a, dt):
+    """--rgb-order: rv_frames_to_patches_packed against the NHWC entry on an RGB copy and against channel-index ``.contiguous()`` + the NHWC entry."""
+    n, H, W, R = a.frames, a.height, a.width, a.res
+    pix, r, g, b = ops.RGB_PIX_FMTS[a.rgb_order]
+    src = torch.randint(0, 256, (n, H, W, pix), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).cuda()
+    swap = lambda: src[..., [r, g, b]].contiguous()
+    rgb = swap()
+    nhwc = lambda t: ops.frames_to_patches(t, R, a.patch, layout="NHWC", op_dtype=dt)[0]
+    forms = (("packed", lambda: ops.frames_to_patches(src, R, a.patch, op_dtype=dt, pix_fmt=a.rgb_order)[0]), ("rgb24", lambda: nhwc(rgb)),
+             ("two_step", lambda: nhwc(swap())))
+    if a.once:
+        forms[0][1]()
+        torch.cuda.synchronize()
+        return
+    med, ms, first = alternate(forms, a)
+    add_to(a.out, a.rgb_order, dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), rgb_order=a.rgb_order, frames=n, height=H, width=W, res=R,
+                                    patch=a.patch, warmup=a.warmup, iters=a.iters, packed_ms=ms["packed"], rgb24_ms=ms["rgb24"], two_step_ms=ms["two_step"],
+                                    packed_over_rgb24=med["packed"] / med["rgb24"], packed_over_two_step=med["packed"] / med["two_step"],
+                                    same_bits_as_rgb24=bool(torch.equal(first["packed"].view(torch.int16), first["rgb24"].view(torch.int16)))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
@@ -210,7 +301,10 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frontend_yuv_1080p.json"))
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--pix-fmt", default=None, help="time rv_yuv_surface_to_patches on this ffmpeg pix_fmt instead (ops.PIX_FMTS)")
+    ap.add_argument("--pix-fmt", default=None, help="time rv_yuv_surface_to_patches on this ffmpeg pix_fmt instead (ops.PIX_FMTS); a packed name "
+                    "(ops.PACKED_PIX_FMTS: yuyv422, y210le, xv30le, ayuv ...) times rv_packed_to_patches against the planar entry and the two-step path")
+    ap.add_argument("--rgb-order", default=None, help="time rv_frames_to_patches_packed on this byte order (ops.RGB_PIX_FMTS: bgra, bgr24 ...) against a channel "
+                    "swap + the NHWC entry")
     ap.add_argument("--transfer", default=None, choices=("pq", "hlg"), help="time rv_yuv_surface_to_patches_hdr on P010 at 1080p and 2160p against the SDR entry")
     ap.add_argument("--rotate", type=int, default=0, choices=(0, 90, 180, 270), help="time the oriented entry (clockwise degrees) against rot90 + the un-oriented entry")
     ap.add_argument("--hflip", action="store_true")
@@ -218,6 +312,10 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "frontend_yuv_prof needs the GPU: a CPU run says nothing about time"
     dt = hip.op_dtype()
+    if a.rgb_order is not None or a.pix_fmt in ops.PACKED_PIX_FMTS:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "frontend_packed.json")
+        return rgb_order_run(a, dt) if a.rgb_order is not None else packed_run(a, dt)
     if a.rotate or a.hflip or a.vflip:
         if a.out == ap.get_default("out"):
             a.out = os.path.join(ROOT, "profiles", "frontend_orient.json")
