@@ -460,6 +460,37 @@ int rv_frames_to_patches_packed(const uint8_t* frames, int32_t pix_bytes, int32_
                                 int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches,
                                 int64_t ldp, float* image, void* stream);
 
+/* The three front-end families on SEPARATELY ALLOCATED frames: a hardware decoder's surface pool hands out one device pointer per frame, in whatever order the
+ * pool recycles them; a capture ring buffer and the frames of several cameras of one resolution are scattered likewise.  Every entry above addresses frame f as
+ * base + f * frame_stride, which costs such a caller a device-to-device copy of every source frame into a staging batch.  These entries take the frames of a
+ * batch from a table of per-frame pointers in ONE launch per RV_FRAME_TABLE_MAX frames; everything else - size, pitches, sample format, colour tags, HDR map,
+ * orientation - is shared by the batch.  Each pointer is free: windows of larger surfaces keep working, frames need no slack around them (the kernels read
+ * exactly the row segments of the crop), and a frame may be listed twice.  No pass over the source is added, no device workspace is used.
+ * The pointer arrays (frames, planes, bases) are HOST arrays of n DEVICE pointers; they are read at the call (the table travels in the kernel arguments) and need
+ * not outlive it.  A batch longer than RV_FRAME_TABLE_MAX frames is cut into launches of at most that many by the entry; n = 60 is one launch.
+ *   rv_frames_to_patches_scattered   layout 0: frames[f] is an NCHW frame whose channel planes lie channel_stride bytes apart (pix_bytes 3 and offsets 0, 1, 2
+ *                                    are required); layout 1: packed pixels as rv_frames_to_patches_packed takes them (pix_bytes, r_off, g_off, b_off; rgb24 is
+ *                                    3 and 0, 1, 2).  row_stride in bytes.
+ *   rv_yuv_surfaces_to_patches       s gives n, the geometry, the row strides, the sample format and the tags; s->y / cb / cr and the two frame strides are NOT
+ *                                    read.  planes[f] holds the Y, Cb and Cr pointers of frame f; interleaved chroma (c_pix = 2 * sample_bytes) has cr = cb +-
+ *                                    sample_bytes, the same way round in every frame; planar chroma may lie anywhere, frame by frame.  m: NULL = SDR.
+ *   rv_packed_surfaces_to_patches    s as above (s->base and frame_stride are NOT read); bases[f] is the first unit of the first row of frame f.
+ * Values: EXACTLY what the contiguous entry of the family (rv_frames_to_patches_oriented / rv_frames_to_patches_packed, rv_yuv_surface_to_patches_oriented,
+ * rv_packed_to_patches) defines for frame f located at the f-th pointer(s): the same taps, weights and sums in the same order, so the outputs are the bits of that
+ * entry on a stacked copy of the frames.  Output rows of frame f are where they always were.
+ * Refused (RV_ERR_ARG, nothing launched - the whole table is validated before the first launch): everything the contiguous entry refuses; a null array with
+ * n > 0; a null pointer in any entry; a 16 / 32-bit surface with a pointer in any entry that is not a multiple of the word size; interleaved chroma where some
+ * frame's cr - cb is not that of frame 0; each of these messages names the frame.  n = 0 returns 0 and launches nothing. */
+#define RV_FRAME_TABLE_MAX 64
+typedef struct rv_surface_planes { const void *y, *cb, *cr; } rv_surface_planes;
+int rv_frames_to_patches_scattered(const uint8_t* const* frames, int layout, int32_t pix_bytes, int32_t r_off, int32_t g_off, int32_t b_off,
+                                   int64_t channel_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch,
+                                   const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+int rv_yuv_surfaces_to_patches(const rv_yuv_surface* s, const rv_surface_planes* planes, const rv_hdr_map* m /* NULL = SDR */, int32_t orient, int32_t R,
+                               int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+int rv_packed_surfaces_to_patches(const rv_packed_surface* s, const void* const* bases, const rv_hdr_map* m /* NULL = SDR */, int32_t orient, int32_t R,
+                                  int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream);
+
 /* ---- adapter ---------------------------------------------------------------------------- */
 /* nn.Linear(768, D) projector on [rows,768] bf16 -> [rows,D] (vtimellm_arch.py:42,125). out f32 or bf16. */
 int rv_project_dense(rv_ctx* ctx, const void* x_bf16, void* y, int out_dtype, int64_t rows, void* stream);

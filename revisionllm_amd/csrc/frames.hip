@@ -18,7 +18,13 @@
 // Packed RGB in any byte order (rv_frames_to_patches_packed: bgr24, bgra, argb ...): compiled per PK as well (0: the code it was).  The PK = 1 instances are the
 // NHWC path with a pixel of 3 or 4 bytes and R, G, B at their own byte offsets inside it; the staged row segment covers the whole pixels, a fourth byte is staged
 // and never read.
+//
+// Separately allocated frames (rv_frames_to_patches_scattered: a decoder's surface pool, a capture ring): compiled per TAB as well (0: the code it was, on the
+// argument block it always had).  A TAB = 1 instance takes FrTab - FrParams and, behind it, one base pointer per frame of the launch - and reads its frame's base
+// from that table in the argument segment (the frame number is uniform per workgroup: scalar loads) where the TAB = 0 instance computes src + f * fstride.  The
+// host cuts a batch into launches of at most RV_FRAME_TABLE_MAX frames.
 #include <atomic>
+#include <type_traits>
 
 #include "frames_taps.h"   // the tap definition, FR_* constants and capacity helpers (shared with frames_yuv.hip); fp contraction is off from there on
 
@@ -41,8 +47,15 @@ struct FrParams {
     int off[3];                          // PK = 1 instances only: byte offsets of R, G, B inside a pixel of `pix` bytes
 };
 
-template <int ORI, int PK>
-__global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrParams p) {
+// The argument block of the TAB = 1 instances: the frames of one launch lie where the table says (NCHW channel planes p.cstride apart; p.src / p.fstride unused).
+struct FrTab : FrParams {
+    const uint8_t* frame[RV_FRAME_TABLE_MAX];
+};
+template <int TAB>
+using FrArgs = std::conditional_t<TAB != 0, FrTab, FrParams>;
+
+template <int ORI, int PK, int TAB>
+__global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrArgs<TAB> p) {
     extern __shared__ __attribute__((aligned(16))) char fr_smem[];
     float* wh = (float*)fr_smem;                       // [TX][NTXp]
     float* wv = (float*)(fr_smem + p.o_wv);            // [TY][NTY]
@@ -91,7 +104,9 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrP
     const int segbytes = segpx * p.pix;
     const int planes = PK ? 1 : p.pix == 1 ? 3 : 1;
     const int nck = p.SEG >> 4;
-    const uint8_t* fsrc = p.src + f * p.fstride + (int64_t)cmin * p.pix;
+    const uint8_t* fsrc;
+    if constexpr (TAB != 0) fsrc = p.frame[f] + (int64_t)cmin * p.pix;
+    else fsrc = p.src + f * p.fstride + (int64_t)cmin * p.pix;
 
     // ---- phase 1: stage source bytes, horizontal pass ---------------------------------------------------------------------------
     for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
@@ -218,35 +233,38 @@ bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
 int fr_lds_bytes(const FrParams& p) { return p.o_stage + (p.pix == 1 ? 3 : 1) * FR_SR * p.SEG; }
 
 // One launch of the instance for orientation class ORI (PK: the packed-RGB instance); the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <int ORI, int PK>
-int fr_launch(const FrParams& p, int64_t wgs, int lds, void* stream, const char* who) {
+template <int ORI, int PK, int TAB = 0>
+int fr_launch(const FrArgs<TAB>& p, int64_t wgs, int lds, void* stream, const char* who) {
     static std::atomic<uint64_t> have_lds{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel<ORI, PK>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel<ORI, PK, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
             rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
             return RV_ERR_HIP;
         }
         have_lds.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((frames_to_patches_kernel<ORI, PK>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    hipLaunchKernelGGL((frames_to_patches_kernel<ORI, PK, TAB>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
     RV_CHECK_LAUNCH("frames_to_patches");
     return RV_OK;
 }
 
 // All entry points: validate, plan the tiles, launch.  `who` names the entry point in the messages; orient 0 is the un-oriented entry's plan and instance.  off:
-// null, or the packed entry's R, G, B byte offsets inside a pixel of pix_bytes bytes (layout is 1 then).
-int fr_run(const uint8_t* frames, int layout, int pix_bytes, const int32_t* off, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch,
-           const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream, const char* who) {
+// null, or the packed entry's R, G, B byte offsets inside a pixel of pix_bytes bytes (layout is 1 then).  tab: the scattered entry's host array of n frame
+// pointers (frames is null and frame_stride 3 * channel_stride then), else null - the plan and the instances the contiguous entries always had.
+int fr_run(const uint8_t* frames, const uint8_t* const* tab, int layout, int pix_bytes, const int32_t* off, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
+           int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream, const char* who) {
     RV_CHECK_ARG(layout == 0 || layout == 1, "%s: layout %d (0 = NCHW, 1 = NHWC)", who, layout);
     RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
     RV_CHECK_ARG(H >= 1 && W >= 1 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 .. %d", who, H, W, FR_MAX_SIDE);
     RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
     RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
     if (n == 0) return RV_OK;
-    RV_CHECK_ARG(frames, "%s: null frames", who);
+    RV_CHECK_ARG(frames || tab, "%s: null frames", who);
+    if (tab)   // the whole table before anything is launched
+        for (int32_t f = 0; f < n; ++f) RV_CHECK_ARG(tab[f], "%s: null pointer for frame %d of %d", who, f, n);
     RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
     RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
     FrParams p{};
@@ -298,9 +316,28 @@ int fr_run(const uint8_t* frames, int layout, int pix_bytes, const int32_t* off,
             if (fr_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
         }
     RV_CHECK_ARG(have, "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
+    const int lds = fr_lds_bytes(best);
+    if (tab) {   // launches of at most RV_FRAME_TABLE_MAX frames: the table and the output pointers move on, everything else is shared
+        const int oc = orient == 0 ? 0 : ori.tr ? 2 : 1;
+        const int64_t wmax = (int64_t)(n < RV_FRAME_TABLE_MAX ? n : RV_FRAME_TABLE_MAX) * best.bands * best.tilesX;
+        RV_CHECK_ARG(wmax < (1ll << 31), "%s: %lld workgroups per launch exceed one launch", who, (long long)wmax);
+        for (int32_t f0 = 0; f0 < n; f0 += RV_FRAME_TABLE_MAX) {
+            const int32_t nf = n - f0 < RV_FRAME_TABLE_MAX ? n - f0 : RV_FRAME_TABLE_MAX;
+            FrTab a{};
+            static_cast<FrParams&>(a) = best;
+            if (best.patches) a.patches = best.patches + (int64_t)f0 * best.g * best.g * ldp;
+            if (best.image) a.image = best.image + (int64_t)f0 * 3 * R * R;
+            for (int32_t f = 0; f < nf; ++f) a.frame[f] = tab[f0 + f];
+            const int64_t w = (int64_t)nf * best.bands * best.tilesX;
+            int rc;
+            if (off) rc = oc == 0 ? fr_launch<0, 1, 1>(a, w, lds, stream, who) : oc == 1 ? fr_launch<1, 1, 1>(a, w, lds, stream, who) : fr_launch<2, 1, 1>(a, w, lds, stream, who);
+            else rc = oc == 0 ? fr_launch<0, 0, 1>(a, w, lds, stream, who) : oc == 1 ? fr_launch<1, 0, 1>(a, w, lds, stream, who) : fr_launch<2, 0, 1>(a, w, lds, stream, who);
+            if (rc) return rc;
+        }
+        return RV_OK;
+    }
     const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
     RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
-    const int lds = fr_lds_bytes(best);
     if (off) {
         if (orient == 0) return fr_launch<0, 1>(best, wgs, lds, stream, who);
         return ori.tr ? fr_launch<2, 1>(best, wgs, lds, stream, who) : fr_launch<1, 1>(best, wgs, lds, stream, who);
@@ -314,7 +351,7 @@ int fr_run(const uint8_t* frames, int layout, int pix_bytes, const int32_t* off,
 extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
                                     int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp, float* image,
                                     void* stream) {
-    return fr_run(frames, layout, 3, nullptr, frame_stride, row_stride, n, H, W, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches");
+    return fr_run(frames, nullptr, layout, 3, nullptr, frame_stride, row_stride, n, H, W, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches");
 }
 
 // The same front end on the picture as it is displayed: H, W and the strides describe the coded frames, orient (0 .. 7) turns and flips them.
@@ -322,7 +359,7 @@ extern "C" int rv_frames_to_patches_oriented(const uint8_t* frames, int layout, 
                                              int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                                              float* image, void* stream) {
     RV_CHECK_ARG(orient >= 0 && orient <= 7, "rv_frames_to_patches_oriented: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", orient);
-    return fr_run(frames, layout, 3, nullptr, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches_oriented");
+    return fr_run(frames, nullptr, layout, 3, nullptr, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches_oriented");
 }
 
 // Packed 8-bit RGB in any byte order, 3 or 4 bytes per pixel: the oriented NHWC entry with the channels at their own offsets inside the pixel.
@@ -336,5 +373,25 @@ extern "C" int rv_frames_to_patches_packed(const uint8_t* frames, int32_t pix_by
                  "%s: r_off, g_off, b_off = %d, %d, %d (three distinct byte offsets inside the %d-byte pixel)", who, r_off, g_off, b_off, pix_bytes);
     RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
     const int32_t off[3] = {r_off, g_off, b_off};
-    return fr_run(frames, 1, pix_bytes, off, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+    return fr_run(frames, nullptr, 1, pix_bytes, off, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+}
+
+// The packed / oriented entries on separately allocated frames: frames[f] is where frame f lies; every other argument is shared (the header has the rules).
+extern "C" int rv_frames_to_patches_scattered(const uint8_t* const* frames, int layout, int32_t pix_bytes, int32_t r_off, int32_t g_off, int32_t b_off,
+                                              int64_t channel_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch,
+                                              const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_frames_to_patches_scattered";
+    RV_CHECK_ARG(layout == 0 || layout == 1, "%s: layout %d (0 = NCHW, 1 = packed pixels)", who, layout);
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    const int32_t off[3] = {r_off, g_off, b_off};
+    if (layout == 0) {
+        RV_CHECK_ARG(pix_bytes == 3 && r_off == 0 && g_off == 1 && b_off == 2, "%s: layout 0 (NCHW) takes pix_bytes 3 and offsets 0, 1, 2; got %d and %d, %d, %d", who,
+                     pix_bytes, r_off, g_off, b_off);
+        return fr_run(nullptr, frames, 0, 3, nullptr, 3 * channel_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+    }
+    RV_CHECK_ARG(pix_bytes == 3 || pix_bytes == 4, "%s: pix_bytes = %d (3, or 4 = a fourth byte that is never read)", who, pix_bytes);
+    RV_CHECK_ARG(r_off >= 0 && g_off >= 0 && b_off >= 0 && r_off < pix_bytes && g_off < pix_bytes && b_off < pix_bytes && r_off != g_off && r_off != b_off &&
+                     g_off != b_off,
+                 "%s: r_off, g_off, b_off = %d, %d, %d (three distinct byte offsets inside the %d-byte pixel)", who, r_off, g_off, b_off, pix_bytes);
+    return fr_run(nullptr, frames, 1, pix_bytes, off, 0, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }

@@ -60,7 +60,14 @@
 //
 // Packed surfaces (rv_packed_to_patches: YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ...) have a kernel of their own behind the planar one, packed_to_patches_kernel:
 // one staged segment per source row serves the Y, Cb and Cr passes; its section has the layout.  The planar instances are untouched by it.
+//
+// Separately allocated surfaces (rv_yuv_surfaces_to_patches, rv_packed_surfaces_to_patches: a decoder's surface pool): both kernels are compiled per TAB as well
+// (0: the code it was, on the argument block it always had).  A TAB = 1 instance takes FyTab / FkTab - FyParams / FkParams and, behind them, the plane pointers of every
+// frame of the launch - and reads its frame's base pointers from that table in the argument segment (the frame number is uniform per workgroup: scalar loads) where
+// the TAB = 0 instance computes base + f * frame stride.  Planar Cr - Cb comes from the table too: it may differ from frame to frame.  Everything behind the base
+// pointers is the same text.  The host cuts a batch into launches of at most RV_FRAME_TABLE_MAX frames.
 #include <atomic>
+#include <type_traits>
 
 #include "frames_taps.h"   // fp contraction is off from there on
 
@@ -242,8 +249,15 @@ __device__ inline void fy_zero_pad(const FyParams& p, int64_t f, int y0, int ty,
     }
 }
 
-template <typename S, int TRC, int ORI>
-__global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyParams p) {
+// The argument block of the TAB = 1 planar instances: the planes of frame f of one launch lie where fr[f] says (p.y / p.c / p.yfs / p.cfs / p.cdelta unused).
+struct FyTab : FyParams {
+    rv_surface_planes fr[RV_FRAME_TABLE_MAX];
+};
+template <int TAB>
+using FyArgs = std::conditional_t<TAB != 0, FyTab, FyParams>;
+
+template <typename S, int TRC, int ORI, int TAB>
+__global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs<TAB> p) {
     extern __shared__ __attribute__((aligned(16))) char fy_smem[];
     float* wx = (float*)fy_smem;                       // [TX][NTXp]
     float* wy = (float*)(fy_smem + p.o_wy);            // [TY][NTY]
@@ -290,7 +304,9 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
     const int nrows = min(ymin[ty - 1] + ny[ty - 1] - rmin, p.NRY);
     const int segpx = min(xmin[tx - 1] + nx[tx - 1] - cmin, p.SPY);
     constexpr int SB = (int)sizeof(S);
-    const uint8_t* ysrc = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
+    const uint8_t* ysrc;
+    if constexpr (TAB != 0) ysrc = (const uint8_t*)p.fr[f].y + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
+    else ysrc = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
     for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
         const int nr = min(FR_SR, nrows - r0);
         const uint8_t* g0 = ysrc + (int64_t)r0 * p.yrs;
@@ -314,12 +330,20 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
     const int cnrows = min(cymin[ty - 1] + cny[ty - 1] - crmin, p.NRC);
     const int csegpx = min(cxmin[tx - 1] + cnx[tx - 1] - ccmin, p.SPC);
     const int cplanes = p.cplanes, cstep = p.cpix / SB;   // cstep: samples between neighbours of one chroma plane
-    const uint8_t* csrc = p.c + f * p.cfs + (int64_t)crmin * p.crs + (int64_t)ccmin * p.cpix;
+    const uint8_t* csrc;
+    [[maybe_unused]] int64_t tdelta = 0;   // TAB = 1: this frame's Cr plane - Cb plane (planar), in the place of p.cdelta
+    if constexpr (TAB != 0) {   // interleaved: the lower of the two planes, with the shared ocb / ocr
+        const uint8_t *tcb = (const uint8_t*)p.fr[f].cb, *tcr = (const uint8_t*)p.fr[f].cr;
+        csrc = (cplanes == 1 && tcr < tcb ? tcr : tcb) + (int64_t)crmin * p.crs + (int64_t)ccmin * p.cpix;
+        tdelta = tcr - tcb;
+    } else {
+        csrc = p.c + f * p.cfs + (int64_t)crmin * p.crs + (int64_t)ccmin * p.cpix;
+    }
     for (int r0 = 0; r0 < cnrows; r0 += FR_SR) {
         const int nr = min(FR_SR, cnrows - r0);
         const uint8_t* g0 = csrc + (int64_t)r0 * p.crs;
         __syncthreads();
-        fy_stage<S>(stage, g0, p.cdelta, p.crs, cplanes, nr, csegpx * p.cpix, p.SEGC, tid);
+        fy_stage<S>(stage, g0, TAB != 0 ? tdelta : p.cdelta, p.crs, cplanes, nr, csegpx * p.cpix, p.SEGC, tid);
         __syncthreads();
         for (int it = tid; it < nr * tx; it += FR_THREADS) {
             const int col = it % tx, r = it / tx;
@@ -332,7 +356,7 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyPara
                 sr = (const S*)(b0 + p.ocr);
             } else {
                 sb = (const S*)b0;
-                sr = (const S*)(stage + (FR_SR + r) * p.SEGC + (int)((uintptr_t)(gs + p.cdelta) & 15) + xo * p.cpix);
+                sr = (const S*)(stage + (FR_SR + r) * p.SEGC + (int)((uintptr_t)(gs + (TAB != 0 ? tdelta : p.cdelta)) & 15) + xo * p.cpix);
             }
             const float* w = cwx + col * p.NCXp;
             const int n = min(cnx[col], csegpx - xo);
@@ -457,20 +481,20 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
 }
 
 // One launch of the instance for sample type S, transfer TRC and orientation class ORI; the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <typename S, int TRC, int ORI>
-int fy_launch(const FyParams& p, int64_t wgs, int lds, void* stream, const char* who) {
+template <typename S, int TRC, int ORI, int TAB = 0>
+int fy_launch(const FyArgs<TAB>& p, int64_t wgs, int lds, void* stream, const char* who) {
     static std::atomic<uint64_t> have_lds{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S, TRC, ORI>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S, TRC, ORI, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
             rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
             return RV_ERR_HIP;
         }
         have_lds.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((yuv_to_patches_kernel<S, TRC, ORI>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
+    hipLaunchKernelGGL((yuv_to_patches_kernel<S, TRC, ORI, TAB>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
     RV_CHECK_LAUNCH("yuv_to_patches");
     return RV_OK;
 }
@@ -481,10 +505,18 @@ double fy_pq_inv64(double nits) {
 }
 
 // The instance of an orientation class: 0 = none, 1 = mirrors, 2 = transpose.
-template <typename S, int TRC>
-int fy_launch_ori(int ori_class, const FyParams& p, int64_t wgs, int lds, void* stream, const char* who) {
-    if (ori_class == 0) return fy_launch<S, TRC, 0>(p, wgs, lds, stream, who);
-    return ori_class == 1 ? fy_launch<S, TRC, 1>(p, wgs, lds, stream, who) : fy_launch<S, TRC, 2>(p, wgs, lds, stream, who);
+template <typename S, int TRC, int TAB = 0>
+int fy_launch_ori(int ori_class, const FyArgs<TAB>& p, int64_t wgs, int lds, void* stream, const char* who) {
+    if (ori_class == 0) return fy_launch<S, TRC, 0, TAB>(p, wgs, lds, stream, who);
+    return ori_class == 1 ? fy_launch<S, TRC, 1, TAB>(p, wgs, lds, stream, who) : fy_launch<S, TRC, 2, TAB>(p, wgs, lds, stream, who);
+}
+
+// The TAB = 1 instance of a sample size, a transfer (m: null = SDR) and an orientation class.
+int fy_launch_any(int sb, const rv_hdr_map* m, int oc, const FyTab& a, int64_t wgs, int lds, void* stream, const char* who) {
+    if (!m) return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_NONE, 1>(oc, a, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_NONE, 1>(oc, a, wgs, lds, stream, who);
+    if (m->transfer == FY_TRC_PQ)
+        return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_PQ, 1>(oc, a, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_PQ, 1>(oc, a, wgs, lds, stream, who);
+    return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_HLG, 1>(oc, a, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_HLG, 1>(oc, a, wgs, lds, stream, who);
 }
 
 // What every entry point derives from the frame geometry, the subsampling and the colour tags: resize / crop per coded axis, the luma and chroma axes, the
@@ -549,8 +581,9 @@ void fy_setup(FyParams& p, int H, int W, int sub_x, int sub_y, int depth, int ma
 }
 
 // All entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m: the HDR entry's map (validated by it), else null;
-// orient: the oriented entry's code (validated by it), 0 for every other entry - the plan and the instances they always had.
-int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
+// orient: the oriented entry's code (validated by it), 0 for every other entry - the plan and the instances they always had.  tab: the scattered entry's host array
+// of s.n plane triples (s.y / cb / cr and the two frame strides are not read then), else null.
+int fy_run(const rv_yuv_surface& s, const rv_surface_planes* tab, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
            void* stream, const char* who) {
     const int sb = s.sample_bytes, H = s.H, W = s.W, n = s.n;
     RV_CHECK_ARG(sb == 1 || sb == 2, "%s: sample_bytes = %d (1, or 2 = little-endian 16-bit words)", who, sb);
@@ -570,24 +603,41 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t
     RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
     RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
     if (n == 0) return RV_OK;
-    const uint8_t *y = (const uint8_t*)s.y, *cb = (const uint8_t*)s.cb, *cr = (const uint8_t*)s.cr;
-    RV_CHECK_ARG(y && cb && cr, "%s: null plane (y %p, cb %p, cr %p)", who, s.y, s.cb, s.cr);
-    RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes)", who,
-                 s.c_pix, sb, sb);
-    RV_CHECK_ARG(sb == 1 || (((uintptr_t)y | (uintptr_t)cb | (uintptr_t)cr | (uintptr_t)s.y_frame_stride | (uintptr_t)s.y_row_stride |
-                               (uintptr_t)s.c_frame_stride | (uintptr_t)s.c_row_stride) & 1) == 0,
-                 "%s: 16-bit planes and strides must be aligned to 2 bytes (y %p, cb %p, cr %p, strides %lld %lld %lld %lld)", who, s.y, s.cb, s.cr,
-                 (long long)s.y_frame_stride, (long long)s.y_row_stride, (long long)s.c_frame_stride, (long long)s.c_row_stride);
+    const uint8_t *y, *cb, *cr;
+    if (tab) {   // the whole table before anything is launched; frame 0 then stands for the batch: the other frames have its interleave relation
+        y = (const uint8_t*)tab[0].y, cb = (const uint8_t*)tab[0].cb, cr = (const uint8_t*)tab[0].cr;
+        for (int32_t f = 0; f < n; ++f) {
+            const uint8_t *ty = (const uint8_t*)tab[f].y, *tb = (const uint8_t*)tab[f].cb, *tr = (const uint8_t*)tab[f].cr;
+            RV_CHECK_ARG(ty && tb && tr, "%s: null plane in frame %d of %d (y %p, cb %p, cr %p)", who, f, n, tab[f].y, tab[f].cb, tab[f].cr);
+            RV_CHECK_ARG(sb == 1 || (((uintptr_t)ty | (uintptr_t)tb | (uintptr_t)tr) & 1) == 0,
+                         "%s: 16-bit planes must be aligned to 2 bytes: frame %d of %d (y %p, cb %p, cr %p)", who, f, n, tab[f].y, tab[f].cb, tab[f].cr);
+            RV_CHECK_ARG(s.c_pix == sb || tr - tb == cr - cb, "%s: c_pix = %d takes interleaved planes: cr - cb = %lld bytes in frame %d of %d, %lld in frame 0", who,
+                         s.c_pix, (long long)(tr - tb), f, n, (long long)(cr - cb));
+        }
+        RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes): frame 0 of %d",
+                     who, s.c_pix, sb, sb, n);
+        RV_CHECK_ARG(sb == 1 || (((uintptr_t)s.y_row_stride | (uintptr_t)s.c_row_stride) & 1) == 0, "%s: 16-bit row strides must be aligned to 2 bytes (%lld %lld)", who,
+                     (long long)s.y_row_stride, (long long)s.c_row_stride);
+    } else {
+        y = (const uint8_t*)s.y, cb = (const uint8_t*)s.cb, cr = (const uint8_t*)s.cr;
+        RV_CHECK_ARG(y && cb && cr, "%s: null plane (y %p, cb %p, cr %p)", who, s.y, s.cb, s.cr);
+        RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes)", who,
+                     s.c_pix, sb, sb);
+        RV_CHECK_ARG(sb == 1 || (((uintptr_t)y | (uintptr_t)cb | (uintptr_t)cr | (uintptr_t)s.y_frame_stride | (uintptr_t)s.y_row_stride |
+                                   (uintptr_t)s.c_frame_stride | (uintptr_t)s.c_row_stride) & 1) == 0,
+                     "%s: 16-bit planes and strides must be aligned to 2 bytes (y %p, cb %p, cr %p, strides %lld %lld %lld %lld)", who, s.y, s.cb, s.cr,
+                     (long long)s.y_frame_stride, (long long)s.y_row_stride, (long long)s.c_frame_stride, (long long)s.c_row_stride);
+    }
     RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
     RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
     FyParams p{};
     p.K = 3 * patch * patch;
     p.Kp = (p.K + 127) / 128 * 128;
     RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
-    p.y = y;
-    p.yfs = s.y_frame_stride;
+    p.y = tab ? nullptr : y;
+    p.yfs = tab ? 0 : s.y_frame_stride;
     p.yrs = s.y_row_stride;
-    p.cfs = s.c_frame_stride;
+    p.cfs = tab ? 0 : s.c_frame_stride;
     p.crs = s.c_row_stride;
     p.cpix = s.c_pix;
     p.sbytes = sb;
@@ -614,10 +664,26 @@ int fy_run(const rv_yuv_surface& s, const rv_hdr_map* m, int32_t orient, int32_t
             if (fy_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
         }
     RV_CHECK_ARG(have, "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
-    const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
-    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     const int lds = best.o_stage + fy_stage_bytes(best);
     const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
+    if (tab) {   // launches of at most RV_FRAME_TABLE_MAX frames: the table and the output pointers move on, everything else is shared
+        best.y = best.c = nullptr;   // the kernel takes every base, and planar Cr - Cb, from the table
+        best.cdelta = 0;
+        const int64_t wmax = (int64_t)(n < RV_FRAME_TABLE_MAX ? n : RV_FRAME_TABLE_MAX) * best.bands * best.tilesX;
+        RV_CHECK_ARG(wmax < (1ll << 31), "%s: %lld workgroups per launch exceed one launch", who, (long long)wmax);
+        for (int32_t f0 = 0; f0 < n; f0 += RV_FRAME_TABLE_MAX) {
+            const int32_t nf = n - f0 < RV_FRAME_TABLE_MAX ? n - f0 : RV_FRAME_TABLE_MAX;
+            FyTab a{};
+            static_cast<FyParams&>(a) = best;
+            if (best.patches) a.patches = best.patches + (int64_t)f0 * best.g * best.g * ldp;
+            if (best.image) a.image = best.image + (int64_t)f0 * 3 * R * R;
+            for (int32_t f = 0; f < nf; ++f) a.fr[f] = tab[f0 + f];
+            if (const int rc = fy_launch_any(sb, m, oc, a, (int64_t)nf * best.bands * best.tilesX, lds, stream, who)) return rc;
+        }
+        return RV_OK;
+    }
+    const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
+    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
     if (!m) return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who);
     if (m->transfer == FY_TRC_PQ)
         return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who);
@@ -652,8 +718,15 @@ __device__ inline float fk_sample(uint8_t v, int) { return (float)v; }
 __device__ inline float fk_sample(uint16_t v, int shift) { return (float)(v >> shift); }
 __device__ inline float fk_sample(uint32_t v, int shift) { return (float)((v >> shift) & 1023u); }
 
-template <typename S, int TRC, int ORI>
-__global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkParams k) {
+// The argument block of the TAB = 1 packed instances: frame f of one launch starts where base[f] says (k.b.y / k.b.yfs unused).
+struct FkTab : FkParams {
+    const uint8_t* base[RV_FRAME_TABLE_MAX];
+};
+template <int TAB>
+using FkArgs = std::conditional_t<TAB != 0, FkTab, FkParams>;
+
+template <typename S, int TRC, int ORI, int TAB>
+__global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkArgs<TAB> k) {
     const FyParams& p = k.b;
     extern __shared__ __attribute__((aligned(16))) char fy_smem[];
     float* wx = (float*)fy_smem;                       // [TX][NTXp]
@@ -697,7 +770,9 @@ __global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkP
     const int u1 = min(max((xmin[tx - 1] + nx[tx - 1] + k.ppu - 1) / k.ppu, cxmin[tx - 1] + cnx[tx - 1]), u0 + k.SPU);
     constexpr int SB = (int)sizeof(S);
     const int ystep = k.unit / k.ppu, ys = ystep / SB, cs = k.unit / SB;   // bytes / samples between neighbouring Y samples; samples between chroma neighbours
-    const uint8_t* src = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
+    const uint8_t* src;
+    if constexpr (TAB != 0) src = k.base[f] + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
+    else src = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
     for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
         const int nr = min(FR_SR, nrows - r0);
         const uint8_t* g0 = src + (int64_t)r0 * p.yrs;
@@ -801,38 +876,40 @@ bool fk_plan(FkParams& k, int ty, int tx, double& cost, int& lds) {
     return true;
 }
 
-template <typename S, int TRC, int ORI>
-int fk_launch(const FkParams& k, int64_t wgs, int lds, void* stream, const char* who) {
+template <typename S, int TRC, int ORI, int TAB = 0>
+int fk_launch(const FkArgs<TAB>& k, int64_t wgs, int lds, void* stream, const char* who) {
     static std::atomic<uint64_t> have_lds{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const uint64_t bit = 1ull << (dev & 63);
     if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)packed_to_patches_kernel<S, TRC, ORI>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)packed_to_patches_kernel<S, TRC, ORI, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
             rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
             return RV_ERR_HIP;
         }
         have_lds.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((packed_to_patches_kernel<S, TRC, ORI>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), k);
+    hipLaunchKernelGGL((packed_to_patches_kernel<S, TRC, ORI, TAB>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), k);
     RV_CHECK_LAUNCH("packed_to_patches");
     return RV_OK;
 }
 
-template <typename S, int TRC>
-int fk_launch_ori(int ori_class, const FkParams& k, int64_t wgs, int lds, void* stream, const char* who) {
-    if (ori_class == 0) return fk_launch<S, TRC, 0>(k, wgs, lds, stream, who);
-    return ori_class == 1 ? fk_launch<S, TRC, 1>(k, wgs, lds, stream, who) : fk_launch<S, TRC, 2>(k, wgs, lds, stream, who);
+template <typename S, int TRC, int TAB = 0>
+int fk_launch_ori(int ori_class, const FkArgs<TAB>& k, int64_t wgs, int lds, void* stream, const char* who) {
+    if (ori_class == 0) return fk_launch<S, TRC, 0, TAB>(k, wgs, lds, stream, who);
+    return ori_class == 1 ? fk_launch<S, TRC, 1, TAB>(k, wgs, lds, stream, who) : fk_launch<S, TRC, 2, TAB>(k, wgs, lds, stream, who);
 }
 
-template <typename S>
-int fk_launch_trc(const rv_hdr_map* m, int ori_class, const FkParams& k, int64_t wgs, int lds, void* stream, const char* who) {
-    if (!m) return fk_launch_ori<S, FY_TRC_NONE>(ori_class, k, wgs, lds, stream, who);
-    return m->transfer == FY_TRC_PQ ? fk_launch_ori<S, FY_TRC_PQ>(ori_class, k, wgs, lds, stream, who) : fk_launch_ori<S, FY_TRC_HLG>(ori_class, k, wgs, lds, stream, who);
+template <typename S, int TAB = 0>
+int fk_launch_trc(const rv_hdr_map* m, int ori_class, const FkArgs<TAB>& k, int64_t wgs, int lds, void* stream, const char* who) {
+    if (!m) return fk_launch_ori<S, FY_TRC_NONE, TAB>(ori_class, k, wgs, lds, stream, who);
+    return m->transfer == FY_TRC_PQ ? fk_launch_ori<S, FY_TRC_PQ, TAB>(ori_class, k, wgs, lds, stream, who)
+                                    : fk_launch_ori<S, FY_TRC_HLG, TAB>(ori_class, k, wgs, lds, stream, who);
 }
 
-// The packed entry: validate the surface (the header has the list), plan, launch.  m and orient are validated by the caller.
-int fk_run(const rv_packed_surface& s, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp,
+// The packed entry: validate the surface (the header has the list), plan, launch.  m and orient are validated by the caller.  tab: the scattered entry's host array
+// of s.n base pointers (s.base and s.frame_stride are not read then), else null.
+int fk_run(const rv_packed_surface& s, const void* const* tab, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp,
            float* image, void* stream, const char* who) {
     const int sb = s.sample_bytes, unit = s.unit_bytes, ppu = s.pix_per_unit, H = s.H, W = s.W, n = s.n;
     RV_CHECK_ARG(sb == 1 || sb == 2 || sb == 4, "%s: sample_bytes = %d (1, 2 = little-endian 16-bit words, 4 = one 32-bit word of three 10-bit fields)", who, sb);
@@ -864,10 +941,20 @@ int fk_run(const rv_packed_surface& s, const rv_hdr_map* m, int32_t orient, int3
     RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
     RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
     if (n == 0) return RV_OK;
-    RV_CHECK_ARG(s.base, "%s: null base pointer", who);
-    RV_CHECK_ARG((((uintptr_t)s.base | (uintptr_t)s.frame_stride | (uintptr_t)s.row_stride) & (uintptr_t)(sb - 1)) == 0,
-                 "%s: %d-bit words: base and strides must be aligned to %d bytes (base %p, frame_stride %lld, row_stride %lld)", who, 8 * sb, sb, s.base,
-                 (long long)s.frame_stride, (long long)s.row_stride);
+    if (tab) {   // the whole table before anything is launched
+        for (int32_t f = 0; f < n; ++f) {
+            RV_CHECK_ARG(tab[f], "%s: null base pointer for frame %d of %d", who, f, n);
+            RV_CHECK_ARG(((uintptr_t)tab[f] & (uintptr_t)(sb - 1)) == 0, "%s: %d-bit words: the base of frame %d of %d must be aligned to %d bytes (%p)", who, 8 * sb, f,
+                         n, sb, tab[f]);
+        }
+        RV_CHECK_ARG(((uintptr_t)s.row_stride & (uintptr_t)(sb - 1)) == 0, "%s: %d-bit words: row_stride %lld must be aligned to %d bytes", who, 8 * sb,
+                     (long long)s.row_stride, sb);
+    } else {
+        RV_CHECK_ARG(s.base, "%s: null base pointer", who);
+        RV_CHECK_ARG((((uintptr_t)s.base | (uintptr_t)s.frame_stride | (uintptr_t)s.row_stride) & (uintptr_t)(sb - 1)) == 0,
+                     "%s: %d-bit words: base and strides must be aligned to %d bytes (base %p, frame_stride %lld, row_stride %lld)", who, 8 * sb, sb, s.base,
+                     (long long)s.frame_stride, (long long)s.row_stride);
+    }
     RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
     RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
     FkParams k{};
@@ -875,8 +962,8 @@ int fk_run(const rv_packed_surface& s, const rv_hdr_map* m, int32_t orient, int3
     p.K = 3 * patch * patch;
     p.Kp = (p.K + 127) / 128 * 128;
     RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
-    p.y = (const uint8_t*)s.base;
-    p.yfs = s.frame_stride;
+    p.y = tab ? nullptr : (const uint8_t*)s.base;
+    p.yfs = tab ? 0 : s.frame_stride;
     p.yrs = s.row_stride;
     p.sbytes = sb;
     k.unit = unit;
@@ -901,9 +988,27 @@ int fk_run(const rv_packed_surface& s, const rv_hdr_map* m, int32_t orient, int3
             if (fk_plan(q, tyc, txc, cost, lds) && (!have || cost < best_cost)) best = q, best_cost = cost, best_lds = lds, have = true;
         }
     RV_CHECK_ARG(have, "%s: %d x %d -> %d at %d bytes per pixel needs more filter taps and staging than a workgroup's LDS holds", who, H, W, R, unit / ppu);
+    const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
+    if (tab) {   // launches of at most RV_FRAME_TABLE_MAX frames: the table and the output pointers move on, everything else is shared
+        const int64_t wmax = (int64_t)(n < RV_FRAME_TABLE_MAX ? n : RV_FRAME_TABLE_MAX) * best.b.bands * best.b.tilesX;
+        RV_CHECK_ARG(wmax < (1ll << 31), "%s: %lld workgroups per launch exceed one launch", who, (long long)wmax);
+        for (int32_t f0 = 0; f0 < n; f0 += RV_FRAME_TABLE_MAX) {
+            const int32_t nf = n - f0 < RV_FRAME_TABLE_MAX ? n - f0 : RV_FRAME_TABLE_MAX;
+            FkTab a{};
+            static_cast<FkParams&>(a) = best;
+            if (best.b.patches) a.b.patches = best.b.patches + (int64_t)f0 * best.b.g * best.b.g * ldp;
+            if (best.b.image) a.b.image = best.b.image + (int64_t)f0 * 3 * R * R;
+            for (int32_t f = 0; f < nf; ++f) a.base[f] = (const uint8_t*)tab[f0 + f];
+            const int64_t w = (int64_t)nf * best.b.bands * best.b.tilesX;
+            const int rc = sb == 1   ? fk_launch_trc<uint8_t, 1>(m, oc, a, w, best_lds, stream, who)
+                           : sb == 2 ? fk_launch_trc<uint16_t, 1>(m, oc, a, w, best_lds, stream, who)
+                                     : fk_launch_trc<uint32_t, 1>(m, oc, a, w, best_lds, stream, who);
+            if (rc) return rc;
+        }
+        return RV_OK;
+    }
     const int64_t wgs = (int64_t)n * best.b.bands * best.b.tilesX;
     RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
-    const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
     if (sb == 1) return fk_launch_trc<uint8_t>(m, oc, best, wgs, best_lds, stream, who);
     return sb == 2 ? fk_launch_trc<uint16_t>(m, oc, best, wgs, best_lds, stream, who) : fk_launch_trc<uint32_t>(m, oc, best, wgs, best_lds, stream, who);
 }
@@ -913,7 +1018,7 @@ int fk_run(const rv_packed_surface& s, const rv_hdr_map* m, int32_t orient, int3
 extern "C" int rv_yuv_surface_to_patches(const rv_yuv_surface* s, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                                          float* image, void* stream) {
     RV_CHECK_ARG(s, "rv_yuv_surface_to_patches: null surface");
-    return fy_run(*s, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
+    return fy_run(*s, nullptr, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_surface_to_patches");
 }
 
 // The surface entry with the HDR -> SDR steps between the colour matrix and the normalisation: the map is validated here, everything else by fy_run.
@@ -923,7 +1028,7 @@ extern "C" int rv_yuv_surface_to_patches_hdr(const rv_yuv_surface* s, const rv_h
     RV_CHECK_ARG(s, "%s: null surface", who);
     RV_CHECK_ARG(m, "%s: null map", who);
     if (const int rc = fy_check_map(m, who)) return rc;
-    return fy_run(*s, m, 0, R, patch, mean, std, patches, ldp, image, stream, who);
+    return fy_run(*s, nullptr, m, 0, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
 // The surface entry on the picture as it is displayed: the struct describes the coded surface, orient (0 .. 7) turns and flips it; m: NULL = SDR, else the
@@ -935,7 +1040,7 @@ extern "C" int rv_yuv_surface_to_patches_oriented(const rv_yuv_surface* s, const
     RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
     if (m)
         if (const int rc = fy_check_map(m, who)) return rc;
-    return fy_run(*s, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+    return fy_run(*s, nullptr, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
 // The 8-bit 4:2:0 surface of the first entry point: its own two-valued matrix and chroma_loc, then the same code.
@@ -965,7 +1070,7 @@ extern "C" int rv_yuv_to_patches(const uint8_t* y, int64_t y_frame_stride, int64
     s.matrix = matrix;
     s.full_range = full_range;
     s.chroma_loc = chroma_loc;
-    return fy_run(s, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
+    return fy_run(s, nullptr, nullptr, 0, R, patch, mean, std, patches, ldp, image, stream, "rv_yuv_to_patches");
 }
 
 // A packed surface (YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ...): one entry for SDR / HDR (m: NULL = SDR) and every orientation, shaped like the oriented
@@ -977,5 +1082,30 @@ extern "C" int rv_packed_to_patches(const rv_packed_surface* s, const rv_hdr_map
     RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
     if (m)
         if (const int rc = fy_check_map(m, who)) return rc;
-    return fk_run(*s, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+    return fk_run(*s, nullptr, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+}
+
+// The oriented surface entry on separately allocated surfaces: planes[f] holds the Y, Cb and Cr pointers of frame f; the struct gives everything the frames share
+// (its own plane pointers and frame strides are not read).  The header has the rules.
+extern "C" int rv_yuv_surfaces_to_patches(const rv_yuv_surface* s, const rv_surface_planes* planes, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch,
+                                          const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_yuv_surfaces_to_patches";
+    RV_CHECK_ARG(s, "%s: null surface", who);
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    if (m)
+        if (const int rc = fy_check_map(m, who)) return rc;
+    RV_CHECK_ARG(planes || s->n <= 0, "%s: null array of plane pointers (n = %d)", who, s->n);
+    return fy_run(*s, planes, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
+}
+
+// The packed entry on separately allocated surfaces: bases[f] is the first unit of frame f.
+extern "C" int rv_packed_surfaces_to_patches(const rv_packed_surface* s, const void* const* bases, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch,
+                                             const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
+    const char* who = "rv_packed_surfaces_to_patches";
+    RV_CHECK_ARG(s, "%s: null surface", who);
+    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    if (m)
+        if (const int rc = fy_check_map(m, who)) return rc;
+    RV_CHECK_ARG(bases || s->n <= 0, "%s: null array of base pointers (n = %d)", who, s->n);
+    return fk_run(*s, bases, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }

@@ -40,6 +40,13 @@ def yuv_surface_colour_defaults(H, bt2020=False, transfer=None):
     return dict(matrix="bt2020", full_range=False, chroma_loc="topleft") if bt2020 else yuv_colour_defaults(H)
 
 
+def _split_each(frames, split):
+    """A list of per-frame buffers -> the lists of per-frame plane views (y, cb, cr or None) that the list forms of the YCbCr front end take; ``split``: the
+    batched splitter on a batch of one."""
+    per = [split(f.unsqueeze(0)) for f in frames]
+    return tuple(None if per[0][k] is None else [p[k][0] for p in per] for k in range(3))
+
+
 class ClipFeatureExtractor:
     def __init__(self, towers: ClipTowers, tokenizer=None):
         self.clip_extractor = towers
@@ -47,7 +54,7 @@ class ClipFeatureExtractor:
         self.device = towers.device
 
     @torch.no_grad()
-    def encode_video(self, frames, bsz=60, layout=None, *, rotate=0, hflip=False, vflip=False, pix_fmt=None):
+    def encode_video(self, frames, bsz=60, layout=None, *, rotate=0, hflip=False, vflip=False, pix_fmt=None, scattered=False):
         """-> f32 [T, d], ``bsz`` frames at a time (clip_extractor.py:22-37).  ``frames``: a tensor [T,3,R,R] (0..255, float or uint8) at the towers'
         resolution R - normalised here and handed to ``encode_image`` -, or DECODED uint8 frames of any size, [T,3,H,W] or [T,H,W,3] (``layout``
         "NCHW" / "NHWC" where the shape leaves it open), as one tensor or as an iterable of such chunks (what a decoder hands over): those go through
@@ -55,7 +62,9 @@ class ClipFeatureExtractor:
         tag, then flips) say how decoded uint8 frames that are CODED turned or flipped are displayed; the front-end kernel turns them.  Float frames at the
         towers' resolution are past the front end: a non-identity orientation is refused for them.  ``pix_fmt`` (``ops.RGB_PIX_FMTS``: "bgr24" from OpenCV,
         "bgra" / "rgba" / "argb" ... from screen capture): the frames are decoded uint8 [T,H,W,3|4] frames in that byte order, whatever their size, and are
-        read as they lie."""
+        read as they lie.  ``scattered=True`` (decoded uint8 frames only): a batch that spans several chunks is handed over as a list of per-frame views
+        and batched by a pointer table inside the front-end launch, in the place of the ``torch.cat`` that copies every such frame; the batches, and so the
+        features, are the same bit for bit."""
         tw, R = self.clip_extractor, self.clip_extractor.cfg["image_res"]
         orient = ops.orientation(rotate, hflip, vflip)
         if pix_fmt is not None:
@@ -64,7 +73,8 @@ class ClipFeatureExtractor:
             if layout not in (None, "NHWC"):
                 raise ValueError(f"pix_fmt {pix_fmt!r} names the byte order of packed pixels: layout {layout!r} does not go with it")
             out = [tw.encode_frames(b, rotate=rotate, hflip=hflip, vflip=vflip, pix_fmt=pix_fmt)
-                   for b in self._batches((frames,) if torch.is_tensor(frames) else frames, bsz, shapes=f"[t,H,W,{ops.RGB_PIX_FMTS[pix_fmt][0]}]")]
+                   for b in self._batches((frames,) if torch.is_tensor(frames) else frames, bsz, shapes=f"[t,H,W,{ops.RGB_PIX_FMTS[pix_fmt][0]}]",
+                                          scattered=scattered)]
             return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
         if torch.is_tensor(frames):
             native = frames.dim() == 4 and tuple(frames.shape[1:]) == (3, R, R) and layout in (None, "NCHW")
@@ -81,25 +91,26 @@ class ClipFeatureExtractor:
                 out = [tw.encode_image(x[i * bsz:(i + 1) * bsz]) for i in range(int(math.ceil(len(x) / bsz)))]
                 return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
             frames = (frames,)
-        out = [tw.encode_frames(b, layout=layout, rotate=rotate, hflip=hflip, vflip=vflip) for b in self._batches(frames, bsz)]
+        out = [tw.encode_frames(b, layout=layout, rotate=rotate, hflip=hflip, vflip=vflip) for b in self._batches(frames, bsz, scattered=scattered)]
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
 
     @torch.no_grad()
-    def encode_video_yuv(self, chunks, H, W, fmt, bsz=60, **colour):
+    def encode_video_yuv(self, chunks, H, W, fmt, bsz=60, scattered=False, **colour):
         """-> f32 [T, d] from the bytes of a rawvideo pipe (``ffmpeg -f rawvideo -pix_fmt nv12 | nv21 | yuv420p``; ``fmt`` "nv12" | "nv21" | "i420"): ``chunks``
         is one packed uint8 buffer [t, H*3//2, W] (``torch.frombuffer(data, dtype=torch.uint8).view(-1, H * 3 // 2, W)``) or an iterable of them, CPU or
         device.  They are regrouped into batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv420``) and go through
         ``encode_frames_yuv``: no RGB frame exists anywhere.  ``colour`` (``matrix`` / ``full_range`` / ``chroma_loc``) overrides ``yuv_colour_defaults(H)``;
-        ``rotate`` / ``hflip`` / ``vflip`` in it (``ops.orientation``) say how a ``-noautorotate`` pipe's coded frames are displayed.  H, W: the CODED size."""
+        ``rotate`` / ``hflip`` / ``vflip`` in it (``ops.orientation``) say how a ``-noautorotate`` pipe's coded frames are displayed.  H, W: the CODED size.
+        ``scattered=True``: no ``torch.cat`` where a batch spans chunks - per-frame plane views and a pointer table, as in ``encode_video``."""
         tw = self.clip_extractor
         ops.orientation(colour.get("rotate", 0), colour.get("hflip", False), colour.get("vflip", False))     # refused before anything is read
         colour = {**yuv_colour_defaults(H), **colour}
-        out = [tw.encode_frames_yuv(*ops.split_yuv420(b, H, W, fmt), **colour)
-               for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]")]
+        out = [tw.encode_frames_yuv(*(_split_each(b, lambda f: ops.split_yuv420(f, H, W, fmt)) if scattered else ops.split_yuv420(b, H, W, fmt)), **colour)
+               for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]", scattered=scattered)]
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
 
     @torch.no_grad()
-    def encode_video_pix_fmt(self, chunks, H, W, pix_fmt, bsz=60, **colour):
+    def encode_video_pix_fmt(self, chunks, H, W, pix_fmt, bsz=60, scattered=False, **colour):
         """-> f32 [T, d] from the bytes of a rawvideo pipe in any of ``ops.PIX_FMTS`` (``ffmpeg -f rawvideo -pix_fmt p010le | yuv420p10le | nv16 | yuv444p10le
         ...``): ``chunks`` is one uint8 buffer [t, ops.yuv_frame_bytes(H, W, pix_fmt)] or an iterable of them, CPU or device.  They are regrouped into
         batches of exactly ``bsz`` frames, split into plane views (``ops.split_yuv``) and go through ``encode_surfaces_yuv``: no conversion pass, no RGB
@@ -108,7 +119,8 @@ class ClipFeatureExtractor:
         frames are converted to SDR inside the kernel (``ops.yuv_surface_to_patches``; ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` go through with it).
         ``rotate`` / ``hflip`` / ``vflip`` (``ops.orientation``) say how the coded frames of a ``-noautorotate`` pipe are displayed; H, W: the CODED size.
         The packed names of ``ops.PACKED_PIX_FMTS`` (yuyv422 / uyvy422 / y210le / ayuv / xv30le ...) are taken too: [t, ops.packed_frame_bytes(H, W, pix_fmt)]
-        buffers go, with the same colour defaults and the same batching, through ``encode_surfaces_packed`` (``ops.packed_to_patches``) as they lie."""
+        buffers go, with the same colour defaults and the same batching, through ``encode_surfaces_packed`` (``ops.packed_to_patches``) as they lie.
+        ``scattered=True``: no ``torch.cat`` where a batch spans chunks - per-frame views and a pointer table, as in ``encode_video``; the same features."""
         tw = self.clip_extractor
         packed = pix_fmt in ops.PACKED_PIX_FMTS                 # decided before anything else is computed
         if not packed and pix_fmt not in ops.PIX_FMTS:
@@ -120,17 +132,36 @@ class ClipFeatureExtractor:
         if colour.get("transfer") is None:
             colour.pop("transfer", None)                        # transfer=None is the SDR call as it always was
         out = []
-        for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=2, shapes=f"[t,{fb}]"):
+        for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=2, shapes=f"[t,{fb}]", scattered=scattered):
             if packed:
                 out.append(tw.encode_surfaces_packed(b, H=H, W=W, pix_fmt=pix_fmt, **colour))
                 continue
-            planes, kw = ops.split_yuv(b, H, W, pix_fmt)
+            if scattered:
+                kw = ops.split_yuv(b[0].unsqueeze(0), H, W, pix_fmt)[1]
+                planes = _split_each(b, lambda f: ops.split_yuv(f, H, W, pix_fmt)[0])
+            else:
+                planes, kw = ops.split_yuv(b, H, W, pix_fmt)
             out.append(tw.encode_surfaces_yuv(*planes, **kw, **colour))
         return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
 
-    def _batches(self, chunks, bsz, ndim=4, shapes="[t,3,H,W] or [t,H,W,3]"):
+    def _batches(self, chunks, bsz, ndim=4, shapes="[t,3,H,W] or [t,H,W,3]", scattered=False):
         """Decoded uint8 chunks of any lengths -> device batches of exactly ``bsz`` frames (the last one shorter): the batching does not depend on
-        how the decoder cut the video."""
+        how the decoder cut the video.  ``scattered``: every batch is a LIST of per-frame views of the chunks, in the same order and with the same batch
+        boundaries, and nothing is copied (no ``torch.cat``): the list forms of the front end take the frames where they lie."""
+        if scattered:
+            held = []
+            for c in chunks:
+                if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != ndim:
+                    raise ValueError(f"decoded frames come as uint8 tensors {shapes}")
+                c = ops.h2d(c, self.device)
+                for i in range(len(c)):
+                    held.append(c[i])
+                    if len(held) == bsz:
+                        yield held
+                        held = []
+            if held:
+                yield held
+            return
         held, n = [], 0
         for c in chunks:
             if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != ndim:

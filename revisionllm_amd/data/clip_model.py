@@ -97,37 +97,40 @@ class ClipTowers:
         """Decoded uint8 frames [n,3,H,W] / [n,H,W,3] of any size (on the device) -> f32 [n, embed_dim]: resize, centre crop, normalise and unfold in one
         kernel (``ops.frames_to_patches``: the reference's Resize / CenterCrop / Normalize, inference.py:108-117), then what ``encode_image`` runs.
         ``rotate`` / ``hflip`` / ``vflip``: the display orientation of frames that are coded turned or flipped (``ops.orientation``), applied in that kernel.
-        ``pix_fmt`` (``ops.RGB_PIX_FMTS``: "bgr24", "bgra" ...): [n,H,W,3|4] frames in that byte order, read as they lie."""
+        ``pix_fmt`` (``ops.RGB_PIX_FMTS``: "bgr24", "bgra" ...): [n,H,W,3|4] frames in that byte order, read as they lie.
+        A list of per-frame tensors (separately allocated frames; ``ops.frames_to_patches`` has the rules) is taken in the place of the batched tensor."""
         c = self.cfg
         patches, _ = ops.frames_to_patches(frames_u8, c["image_res"], c["patch"], layout=layout, op_dtype=self.op_dtype, rotate=rotate, hflip=hflip, vflip=vflip,
                                            pix_fmt=pix_fmt)
-        return self._encode_patches(patches, frames_u8.shape[0])
+        return self._encode_patches(patches, len(frames_u8))
 
     @torch.no_grad()
     def encode_frames_yuv(self, y, cb, cr=None, **colour):
         """Decoded 8-bit 4:2:0 frames (Y [n,H,W] and the chroma planes as ``ops.yuv_to_patches`` takes them, on the device; ``colour``: its ``matrix`` /
         ``full_range`` / ``chroma_loc``, and the display orientation ``rotate`` / ``hflip`` / ``vflip`` of a surface coded turned or flipped) -> f32
-        [n, embed_dim]: resample, convert, crop, normalise and unfold in one kernel, then what ``encode_image`` runs."""
+        [n, embed_dim]: resample, convert, crop, normalise and unfold in one kernel, then what ``encode_image`` runs.  Lists of per-frame planes are passed
+        through (``ops.yuv_to_patches``)."""
         c = self.cfg
         patches, _ = ops.yuv_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **colour)
-        return self._encode_patches(patches, y.shape[0])
+        return self._encode_patches(patches, len(y))
 
     @torch.no_grad()
     def encode_surfaces_yuv(self, y, cb, cr=None, **surface):
         """Decoded frames of any surface ``ops.yuv_surface_to_patches`` takes (uint8 or uint16 planes on the device; ``surface``: its ``depth`` /
         ``msb_aligned`` / ``subsampling`` / ``matrix`` / ``full_range`` / ``chroma_loc``, and for an HDR surface its ``transfer`` / ``peak_nits`` /
-        ``sdr_white_nits`` / ``gamut``, and the display orientation ``rotate`` / ``hflip`` / ``vflip``) -> f32 [n, embed_dim], as ``encode_frames_yuv``."""
+        ``sdr_white_nits`` / ``gamut``, and the display orientation ``rotate`` / ``hflip`` / ``vflip``) -> f32 [n, embed_dim], as ``encode_frames_yuv``.
+        Lists of per-frame planes - the surfaces of a decoder's pool - are passed through and batched by a pointer table (``ops.yuv_surface_to_patches``)."""
         c = self.cfg
         patches, _ = ops.yuv_surface_to_patches(y, cb, cr, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
-        return self._encode_patches(patches, y.shape[0])
+        return self._encode_patches(patches, len(y))
 
     @torch.no_grad()
     def encode_surfaces_packed(self, buf, **surface):
         """Frames of a packed YCbCr surface as ``ops.packed_to_patches`` takes them (``surface``: its ``H`` / ``W`` / ``pix_fmt``, colour tags, HDR arguments and
-        display orientation) -> f32 [n, embed_dim], as ``encode_surfaces_yuv``."""
+        display orientation) -> f32 [n, embed_dim], as ``encode_surfaces_yuv``.  A list of per-frame tensors is passed through."""
         c = self.cfg
         patches, _ = ops.packed_to_patches(buf, R=c["image_res"], patch=c["patch"], op_dtype=self.op_dtype, **surface)
-        return self._encode_patches(patches, buf.shape[0])
+        return self._encode_patches(patches, len(buf))
 
     def _encode_patches(self, patches, n):
         """patches [n*g*g, Kp] operand type (the unfolded, K-padded frames) -> f32 [n, embed_dim]: conv1 as a GEMM and everything behind it."""

@@ -60,6 +60,15 @@ class RvPackedSurface(C.Structure):
                 ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32), ("chroma_loc", C.c_int32)]
 
 
+#: ``RV_FRAME_TABLE_MAX``: frames of one launch of the scattered entries (longer batches are cut by the library; callers need not)
+FRAME_TABLE_MAX = 64
+
+
+class RvSurfacePlanes(C.Structure):
+    """``rv_surface_planes``: the Y, Cb and Cr device pointers of ONE frame of a pool of separately allocated surfaces (rv_yuv_surfaces_to_patches)."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -140,6 +149,12 @@ SIGNATURES = {
     "rv_packed_to_patches": (C.c_int, [C.POINTER(RvPackedSurface), C.POINTER(RvHdrMap), _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p, _p]),
     "rv_frames_to_patches_packed": (C.c_int, [_p, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p, _i64, _p,
                                               _p]),
+    "rv_frames_to_patches_scattered": (C.c_int, [C.POINTER(_p), C.c_int, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_f),
+                                                 C.POINTER(_f), _p, _i64, _p, _p]),
+    "rv_yuv_surfaces_to_patches": (C.c_int, [C.POINTER(RvYuvSurface), C.POINTER(RvSurfacePlanes), C.POINTER(RvHdrMap), _i32, _i32, _i32, C.POINTER(_f),
+                                             C.POINTER(_f), _p, _i64, _p, _p]),
+    "rv_packed_surfaces_to_patches": (C.c_int, [C.POINTER(RvPackedSurface), C.POINTER(_p), C.POINTER(RvHdrMap), _i32, _i32, _i32, C.POINTER(_f), C.POINTER(_f), _p,
+                                                _i64, _p, _p]),
     "rv_project_dense": (C.c_int, [_p, _p, _p, C.c_int, _i64, _p]),
     "rv_clip_encoder_ws_bytes": (_sz, [_p, _i32, _i32, _i32, _i32]),
     "rv_clip_encoder": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _sz, _p]),

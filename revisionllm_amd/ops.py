@@ -267,6 +267,83 @@ RGB_PIX_FMTS = {
 }
 
 
+def _frame_list(frames, who, what="frames"):
+    """The checks every list form shares: a list / tuple of per-frame tensors (separately allocated surfaces, or views of larger ones) that agree in dtype,
+    device, shape and strides, so that one geometry and one set of pitches serve the whole batch.  ValueError otherwise, before the library is touched."""
+    if len(frames) == 0:
+        raise ValueError(f"{who}: an empty list of {what} has no frame to take the shape, the dtype and the device from")
+    for i, t in enumerate(frames):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {what}[{i}] is a {type(t).__name__}, not a tensor")
+    e = frames[0]
+    for i, t in enumerate(frames):
+        if t.dtype != e.dtype or t.device != e.device or t.shape != e.shape or t.stride() != e.stride():
+            raise ValueError(f"{who}: {what}[{i}] ({t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}) disagrees with {what}[0] ({e.dtype} {tuple(e.shape)} "
+                             f"strides {e.stride()} on {e.device}): the frames of a list share dtype, device, shape and strides")
+    return list(frames)
+
+
+def _require_device(tensors, who):
+    """The list forms' device check: the pointer tables hold device addresses, there is no CPU path."""
+    if not all(t.is_cuda for t in tensors):
+        raise hip.HipLibraryError(f"{who} needs device tensors (got a CPU tensor); there is no CPU path")
+
+
+def _frame_outputs(n, R, patch, op_dtype, want, device):
+    dt = hip.op_dtype(op_dtype)
+    g = R // max(patch, 1)
+    kp = (3 * patch * patch + 127) // 128 * 128
+    patches = torch.empty(n * g * g, kp, dtype=dt, device=device) if "patches" in want else None
+    image = torch.empty(n, 3, R, R, dtype=torch.float32, device=device) if "image" in want else None
+    return dt, kp, patches, image
+
+
+def _frames_to_patches_scattered(frames, R, patch, layout, mean, std, op_dtype, want, orient, pix_fmt):
+    """``frames_to_patches`` on a list of per-frame tensors [3,H,W] / [H,W,3] (with ``pix_fmt`` [H,W,3|4]): one pointer per frame, the strides of frame 0 for
+    all (rv_frames_to_patches_scattered).  Every ValueError comes before the library is touched."""
+    who = "frames_to_patches"
+    frames = _frame_list(frames, who)
+    e = frames[0]
+    if pix_fmt is not None:
+        if pix_fmt not in RGB_PIX_FMTS:
+            raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(RGB_PIX_FMTS)} (packed 8-bit RGB)")
+        pix, r, g, b = RGB_PIX_FMTS[pix_fmt]
+        if layout not in (None, "NHWC"):
+            raise ValueError(f"pix_fmt {pix_fmt!r} names the byte order of packed pixels [H,W,{pix}]: layout {layout!r} does not go with it")
+        if e.dtype != torch.uint8 or e.dim() != 3 or e.shape[2] != pix:
+            raise ValueError(f"{pix_fmt} frames in a list come as uint8 tensors [H,W,{pix}], got {e.dtype} {tuple(e.shape)}")
+        layout = "NHWC"
+    else:
+        pix, r, g, b = 3, 0, 1, 2
+        if e.dtype != torch.uint8 or e.dim() != 3:
+            raise ValueError(f"frames in a list come as uint8 tensors [3,H,W] or [H,W,3], got {e.dtype} {tuple(e.shape)}")
+        nchw, nhwc = e.shape[0] == 3, e.shape[2] == 3
+        if layout is None:
+            if nchw == nhwc:
+                raise ValueError(f"frames of shape {tuple(e.shape)} read as " + ("NCHW and as NHWC: pass layout=" if nchw else "neither NCHW nor NHWC"))
+            layout = "NCHW" if nchw else "NHWC"
+        if layout not in _LAYOUTS or not (nchw if layout == "NCHW" else nhwc):
+            raise ValueError(f"layout {layout!r} does not fit frames of shape {tuple(e.shape)}")
+    if layout == "NCHW":
+        H, W = e.shape[1], e.shape[2]
+        if not (e.stride(2) == 1 and e.stride(1) >= W and e.stride(0) > 0):
+            frames = [t.contiguous() for t in frames]
+        cs, rs = frames[0].stride(0), frames[0].stride(1)
+    else:
+        H, W = e.shape[0], e.shape[1]
+        if not (e.stride(2) == 1 and e.stride(1) == pix and e.stride(0) >= pix * W):
+            frames = [t.contiguous() for t in frames]
+        cs, rs = 0, frames[0].stride(0)
+    _require_device(frames, who)
+    n = len(frames)
+    dt, kp, patches, image = _frame_outputs(n, R, patch, op_dtype, want, e.device)
+    table = (hip.C.c_void_p * n)(*[t.data_ptr() for t in frames])
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_frames_to_patches_scattered(table, _LAYOUTS[layout], pix, r, g, b, cs, rs, n, H, W, orient, R, patch, f3(*mean), f3(*std),
+                                                         hip.ptr(patches), kp, hip.ptr(image), hip.stream()), "rv_frames_to_patches_scattered")
+    return patches, image
+
+
 def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",), *, rotate=0, hflip=False, vflip=False,
                       pix_fmt=None):
     """Decoded uint8 frames -> the CLIP front end in one launch (rv_frames_to_patches): Resize(R, antialiased bicubic) / CenterCrop(R) /
@@ -278,8 +355,13 @@ def frames_to_patches(frames, R, patch, layout=None, mean=CLIP_MEAN, std=CLIP_ST
     turned and flipped inside the same launch (rv_frames_to_patches_oriented) - resize and crop are those of the displayed picture, no copy is made.
     ``pix_fmt`` (one of ``RGB_PIX_FMTS``: "bgr24" is what ``cv2.VideoCapture`` hands over, "bgra" / "rgba" / "argb" ... what screen capture and colour converters
     do): the frames are [n,H,W,3] or [n,H,W,4] in that byte order and are read as they lie (rv_frames_to_patches_packed) - the bits of the call on a contiguous
-    RGB copy, without the copy; a fourth byte is ignored.  ``None`` is the call as it always was."""
+    RGB copy, without the copy; a fourth byte is ignored.  ``None`` is the call as it always was.
+    ``frames`` may also be a LIST (or tuple) of per-frame tensors [3,H,W] / [H,W,3] (with ``pix_fmt`` [H,W,3|4]) - the surfaces of a decoder's pool, the slots
+    of a capture ring, views of larger buffers: separately allocated frames that agree in dtype, device, shape and strides go through ONE launch per 64 frames
+    by a table of their pointers (rv_frames_to_patches_scattered), with no ``torch.stack`` in front; the bits are those of the call on the stacked tensor."""
     orient = orientation(rotate, hflip, vflip)
+    if isinstance(frames, (list, tuple)):
+        return _frames_to_patches_scattered(frames, R, patch, layout, mean, std, op_dtype, want, orient, pix_fmt)
     if pix_fmt is not None:
         return _frames_to_patches_packed(frames, R, patch, layout, mean, std, op_dtype, want, orient, pix_fmt)
     if not torch.is_tensor(frames) or not frames.is_cuda:
@@ -363,6 +445,62 @@ def _plane_strides(t, n, rows, cols, pix):
     return (t.stride(0) if n > 1 else rs * rows), rs
 
 
+def _yuv_surfaces_scattered(who, y, cb, cr, R, patch, depth, msb_aligned, subsampling, matrix, full_range, chroma_loc, hdr, orient, mean, std, op_dtype, want):
+    """The YCbCr wrappers on lists of per-frame planes (y [H,W]; cb [h,w,2] with cr None, or cb and cr [h,w] each): one pointer triple per frame, the row
+    strides of frame 0 for all (rv_yuv_surfaces_to_patches).  ``matrix`` / ``chroma_loc`` / ``subsampling`` arrive validated, as their codes.  Every
+    ValueError comes before the library is touched."""
+    lists = [("y", y), ("cb", cb)] + ([] if cr is None else [("cr", cr)])
+    for name, l in lists:
+        if not isinstance(l, (list, tuple)):
+            raise ValueError(f"{who}: y is a list of per-frame planes, so {name} must be one too (got a {type(l).__name__})")
+    y, cb = _frame_list(y, who, "y"), _frame_list(cb, who, "cb")
+    cr = None if cr is None else _frame_list(cr, who, "cr")
+    n, e = len(y), y[0]
+    if len(cb) != n or (cr is not None and len(cr) != n):
+        raise ValueError(f"{who}: {n} Y planes, {len(cb)} Cb planes" + ("" if cr is None else f", {len(cr)} Cr planes") + ": the lists name the same frames")
+    for name, l in lists[1:]:
+        if l[0].dtype != e.dtype or l[0].device != e.device:
+            raise ValueError(f"{who}: {name} planes are {l[0].dtype} on {l[0].device}, Y planes {e.dtype} on {e.device}: one dtype, one device")
+    if e.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError(f"{who} takes planes of one dtype, uint8 or uint16, got {e.dtype}")
+    sx, sy = subsampling
+    if e.dim() != 2 or e.shape[0] % sy or e.shape[1] % sx:
+        raise ValueError(f"{who}: Y planes in a list are [H,W] with H a multiple of {sy} and W of {sx}, got {tuple(e.shape)}")
+    H, W = e.shape
+    h, w, es = H // sy, W // sx, e.element_size()
+
+    def rows(t, r, c, pix):   # can a plane [r,c] be passed by its strides?  samples of a row ``pix`` apart, rows in ascending order
+        return (c == 1 or t.stride(1) == pix) and (r == 1 or t.stride(0) >= pix * c)
+
+    if cr is None:
+        if tuple(cb[0].shape) != (h, w, 2):
+            raise ValueError(f"{who}: interleaved CbCr of frames {H} x {W} is [{h},{w},2] per frame, got {tuple(cb[0].shape)}")
+        if not (cb[0].stride(2) == 1 and rows(cb[0], h, w, 2)):
+            cb = [t.contiguous() for t in cb]
+        cb, cr = [t[..., 0] for t in cb], [t[..., 1] for t in cb]
+    elif tuple(cb[0].shape) != (h, w) or tuple(cr[0].shape) != (h, w):
+        raise ValueError(f"{who}: Cb and Cr of frames {H} x {W} are [{h},{w}] per frame, got {tuple(cb[0].shape)} and {tuple(cr[0].shape)}")
+    if not rows(e, H, W, 1):
+        y = [t.contiguous() for t in y]
+    if abs(cb[0].data_ptr() - cr[0].data_ptr()) == es and cb[0].stride() == cr[0].stride() and rows(cb[0], h, w, 2):
+        c_pix = 2
+    else:
+        c_pix = 1
+        if not (cb[0].stride() == cr[0].stride() and rows(cb[0], h, w, 1)):
+            cb, cr = [t.contiguous() for t in cb], [t.contiguous() for t in cr]
+    yrs = y[0].stride(0) if H > 1 else W
+    crs = cb[0].stride(0) if h > 1 else c_pix * w
+    _require_device(y + cb + cr, who)
+    dt, kp, patches, image = _frame_outputs(n, R, patch, op_dtype, want, e.device)
+    table = (hip.RvSurfacePlanes * n)(*[(a.data_ptr(), b.data_ptr(), c.data_ptr()) for a, b, c in zip(y, cb, cr)])
+    s = hip.RvYuvSurface(None, None, None, 0, yrs * es, 0, crs * es, es, int(depth), int(bool(msb_aligned)), c_pix * es, sx, sy, n, H, W, matrix,
+                         int(bool(full_range)), chroma_loc)
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_yuv_surfaces_to_patches(hip.C.byref(s), table, None if hdr is None else hip.C.byref(hdr), orient, R, patch, f3(*mean), f3(*std),
+                                                     hip.ptr(patches), kp, hip.ptr(image), hip.stream()), "rv_yuv_surfaces_to_patches")
+    return patches, image
+
+
 def yuv_to_patches(y, cb, cr=None, *, R, patch, matrix="bt601", full_range=False, chroma_loc="left", mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None,
                    want=("patches",), rotate=0, hflip=False, vflip=False):
     """Decoded 8-bit 4:2:0 YCbCr frames -> the CLIP front end in one launch (rv_yuv_to_patches; the header has the definition of the values): Y resampled at
@@ -374,8 +512,17 @@ def yuv_to_patches(y, cb, cr=None, *, R, patch, matrix="bt601", full_range=False
     Planes are passed by their strides when each row's bytes are adjacent (a window of a larger decode surface, a padded pitch); any other view is copied first.
     matrix "bt601" | "bt709"; full_range False = studio; chroma_loc "left" (MPEG-2 / H.264) | "centre" (JPEG / MPEG-1).
     ``rotate`` / ``hflip`` / ``vflip`` (``orientation``): the planes are the CODED surface of a stream that is displayed turned or flipped; they go through
-    rv_yuv_surface_to_patches_oriented as the 8-bit 4:2:0 surface they are (``yuv_surface_to_patches`` says what orientation does to the siting)."""
+    rv_yuv_surface_to_patches_oriented as the 8-bit 4:2:0 surface they are (``yuv_surface_to_patches`` says what orientation does to the siting).
+    ``y`` / ``cb`` / ``cr`` may also be LISTS of per-frame planes (y [H,W]; cb [H/2,W/2,2], or cb and cr [H/2,W/2]) of equal length, as
+    ``yuv_surface_to_patches`` takes them: separately allocated surfaces in one launch, without a stacking copy."""
     orient = orientation(rotate, hflip, vflip)
+    if isinstance(y, (list, tuple)):
+        if matrix not in _MATRICES or chroma_loc not in _CHROMA_LOCS:
+            raise ValueError(f"matrix {matrix!r} / chroma_loc {chroma_loc!r}: one of {sorted(_MATRICES)} / {sorted(_CHROMA_LOCS)}")
+        if y and torch.is_tensor(y[0]) and y[0].dtype != torch.uint8:
+            raise ValueError(f"yuv_to_patches takes uint8 planes, got {y[0].dtype}")
+        return _yuv_surfaces_scattered("yuv_to_patches", y, cb, cr, R, patch, 8, False, (2, 2), _MATRICES[matrix], full_range, _CHROMA_LOCS[chroma_loc], None, orient,
+                                       mean, std, op_dtype, want)
     for t in (y, cb) + (() if cr is None else (cr,)):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise hip.HipLibraryError("yuv_to_patches needs device tensors (got a CPU tensor); there is no CPU path")
@@ -499,9 +646,19 @@ def yuv_surface_to_patches(y, cb, cr=None, *, R, patch, depth=8, msb_aligned=Fal
     Orientation: ``rotate`` 0 | 90 | 180 | 270 (clockwise degrees to display: mp4's ``rotate`` tag), then ``hflip`` / ``vflip`` (``orientation``).  The planes,
     ``subsampling`` and ``chroma_loc`` describe the CODED surface; it is turned and flipped inside the same kernel (rv_yuv_surface_to_patches_oriented), SDR or
     HDR: resize and crop are those of the displayed picture, the siting follows its axis and changes side where that axis is mirrored, and a turned 4:2:2
-    surface (4:4:0 on the display) is taken as the 4:2:2 surface it is.  The identity is the un-oriented entry."""
+    surface (4:4:0 on the display) is taken as the 4:2:2 surface it is.  The identity is the un-oriented entry.
+    Surface pools: ``y`` / ``cb`` / ``cr`` may also be LISTS (or tuples) of per-frame planes of equal length - y [H,W]; cb [h,w,2] with ``cr=None``, or cb and
+    cr [h,w] each, which may be three unrelated allocations per frame.  The frames of a list agree in dtype, device, shape and strides (one pitch for the
+    pool); each may be a view of a larger surface.  They go through one launch per 64 frames by a table of their pointers (rv_yuv_surfaces_to_patches): no
+    ``torch.stack``, and the bits of the call on the stacked planes.  Every other keyword behaves as it does for tensors."""
     orient = orientation(rotate, hflip, vflip)
     hdr = hdr_map(transfer, matrix, gamut, peak_nits, sdr_white_nits)
+    if isinstance(y, (list, tuple)):
+        if matrix not in _SURFACE_MATRICES or chroma_loc not in _SURFACE_LOCS or subsampling not in _SUBSAMPLINGS:
+            raise ValueError(f"matrix {matrix!r} / chroma_loc {chroma_loc!r} / subsampling {subsampling!r}: one of {sorted(_SURFACE_MATRICES)} / "
+                             f"{sorted(_SURFACE_LOCS)} / {sorted(_SUBSAMPLINGS)}")
+        return _yuv_surfaces_scattered("yuv_surface_to_patches", y, cb, cr, R, patch, depth, msb_aligned, _SUBSAMPLINGS[subsampling], _SURFACE_MATRICES[matrix],
+                                       full_range, _SURFACE_LOCS[chroma_loc], hdr, orient, mean, std, op_dtype, want)
     for t in (y, cb) + (() if cr is None else (cr,)):
         if not torch.is_tensor(t) or not t.is_cuda:
             raise hip.HipLibraryError("yuv_surface_to_patches needs device tensors (got a CPU tensor); there is no CPU path")
@@ -619,6 +776,36 @@ def packed_frame_bytes(H, W, pix_fmt):
     return H * (W // ppu) * unit
 
 
+def _packed_to_patches_scattered(bufs, H, W, pix_fmt, R, patch, matrix, full_range, chroma_loc, hdr, orient, mean, std, op_dtype, want):
+    """``packed_to_patches`` on a list of per-frame tensors: one base pointer per frame, the row stride of frame 0 for all (rv_packed_surfaces_to_patches)."""
+    who = "packed_to_patches"
+    unit, ppu, sb, oy, ocb, ocr, depth, msb = _packed_fmt(pix_fmt)
+    rb, fb = packed_frame_bytes(1, W, pix_fmt), packed_frame_bytes(H, W, pix_fmt)
+    bufs = _frame_list(bufs, who)
+    e = bufs[0]
+    if e.dtype != torch.uint8 or not ((e.dim() == 2 and tuple(e.shape) == (H, rb)) or (e.dim() == 1 and e.shape[0] == fb)):
+        raise ValueError(f"{pix_fmt} frames of {H} x {W} in a list come as uint8 tensors [{H},{rb}] or [{fb}], got {e.dtype} {tuple(e.shape)}")
+    if e.dim() == 1:
+        if e.stride(0) != 1:
+            bufs = [t.contiguous() for t in bufs]
+        bufs = [t.as_strided((H, rb), (rb, 1), t.storage_offset()) for t in bufs]
+    elif not (e.stride(1) == 1 and (H == 1 or e.stride(0) >= rb)):
+        bufs = [t.contiguous() for t in bufs]
+    rs = bufs[0].stride(0) if H > 1 else rb
+    for i, t in enumerate(bufs):
+        if sb > 1 and (t.storage_offset() % sb or rs % sb or (t.is_cuda and t.data_ptr() % sb)):
+            raise ValueError(f"{pix_fmt}: {8 * sb}-bit words must lie at multiples of {sb} bytes (frame {i}: offset {t.storage_offset()}, row stride {rs})")
+    _require_device(bufs, who)
+    n = len(bufs)
+    dt, kp, patches, image = _frame_outputs(n, R, patch, op_dtype, want, e.device)
+    table = (hip.C.c_void_p * n)(*[t.data_ptr() for t in bufs])
+    s = hip.RvPackedSurface(None, 0, rs, unit, ppu, sb, oy, ocb, ocr, depth, int(msb), n, H, W, matrix, int(bool(full_range)), chroma_loc)
+    f3 = hip.C.c_float * 3
+    hip.check(hip.lib(dt).rv_packed_surfaces_to_patches(hip.C.byref(s), table, None if hdr is None else hip.C.byref(hdr), orient, R, patch, f3(*mean), f3(*std),
+                                                        hip.ptr(patches), kp, hip.ptr(image), hip.stream()), "rv_packed_surfaces_to_patches")
+    return patches, image
+
+
 def packed_to_patches(buf, *, H, W, pix_fmt, R, patch, matrix="bt601", full_range=False, chroma_loc="left", transfer=None, peak_nits=1000.0, sdr_white_nits=203.0,
                       gamut=None, rotate=0, hflip=False, vflip=False, mean=CLIP_MEAN, std=CLIP_STD, op_dtype=None, want=("patches",)):
     """Frames of a PACKED YCbCr surface (``PACKED_PIX_FMTS``: yuyv422 / uyvy422 from capture cards and webcams, y210le / ayuv / vuya / xv30le (Y410) / xv36le from
@@ -628,13 +815,18 @@ def packed_to_patches(buf, *, H, W, pix_fmt, R, patch, matrix="bt601", full_rang
     buf: uint8 device tensor [n, H, row_bytes] with row_bytes = ``packed_frame_bytes(1, W, pix_fmt)``, passed by its strides - a padded pitch, or a window of a
     larger surface that starts on a unit boundary, is passed as it lies - or [n, ``packed_frame_bytes(H, W, pix_fmt)``].  With 16 / 32-bit words the address and
     the strides are multiples of the word size.  Colour tags, ``transfer`` / ``peak_nits`` / ``sdr_white_nits`` / ``gamut`` and ``rotate`` / ``hflip`` / ``vflip``
-    as in ``yuv_surface_to_patches`` (``chroma_loc`` matters for the 4:2:2 formats only).  Every refusal comes before anything is read or launched."""
+    as in ``yuv_surface_to_patches`` (``chroma_loc`` matters for the 4:2:2 formats only).  Every refusal comes before anything is read or launched.
+    ``buf`` may also be a LIST (or tuple) of per-frame tensors [H, row_bytes] or [frame bytes] that agree in dtype, device, shape and strides: separately
+    allocated surfaces in one launch per 64 frames by a table of their base pointers (rv_packed_surfaces_to_patches), without a stacking copy."""
     unit, ppu, sb, oy, ocb, ocr, depth, msb = _packed_fmt(pix_fmt)
     orient = orientation(rotate, hflip, vflip)
     hdr = hdr_map(transfer, matrix, gamut, peak_nits, sdr_white_nits)
     if matrix not in _SURFACE_MATRICES or chroma_loc not in _SURFACE_LOCS:
         raise ValueError(f"matrix {matrix!r} / chroma_loc {chroma_loc!r}: one of {sorted(_SURFACE_MATRICES)} / {sorted(_SURFACE_LOCS)}")
     rb, fb = packed_frame_bytes(1, W, pix_fmt), packed_frame_bytes(H, W, pix_fmt)
+    if isinstance(buf, (list, tuple)):
+        return _packed_to_patches_scattered(buf, H, W, pix_fmt, R, patch, _SURFACE_MATRICES[matrix], full_range, _SURFACE_LOCS[chroma_loc], hdr, orient, mean, std,
+                                            op_dtype, want)
     if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or not ((buf.dim() == 3 and tuple(buf.shape[1:]) == (H, rb)) or (buf.dim() == 2 and buf.shape[1] == fb)):
         raise ValueError(f"{pix_fmt} frames of {H} x {W} come as a uint8 tensor [n,{H},{rb}] or [n,{fb}], got "
                          + (f"{buf.dtype} {tuple(buf.shape)}" if torch.is_tensor(buf) else type(buf).__name__))

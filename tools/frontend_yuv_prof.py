@@ -22,14 +22,20 @@ against the un-oriented entry alone (another picture, the same bytes): three for
 siting, so that the one-call and the two-step form compute the same picture (a flip cannot carry left siting through the two-step form); their largest patch
 difference is reported.  The goal: oriented <= two-step.  The run is ADDED to --out (default profiles/frontend_orient.json) under its orientation.
 
-    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME | --transfer pq|hlg | --rotate N [--hflip] [--vflip]]
-                                      [--out FILE] [--once]
+    python tools/frontend_yuv_prof.py [--frames 60] [--height 1080] [--width 1920] [--pix-fmt NAME | --transfer pq|hlg | --rotate N [--hflip] [--vflip] |
+                                      --scattered] [--out FILE] [--once]
     (--once: one launch, for a kernel trace)
 
 --pix-fmt <packed name> (yuyv422 / y210le / xv30le / ayuv ...) and --rgb-order <bgra / bgr24 ...>: the packed entries (rv_packed_to_patches,
 rv_frames_to_patches_packed) against the planar / NHWC entry on the same samples and against the two-step path they replace (a torch de-interleave or channel
 swap over every full-resolution frame, then the existing entry), alternating on the same bytes.  The expectation: packed <= planar (each source row is staged
 once), and the two-step path costs the extra pass.  Each run is ADDED to --out (default profiles/frontend_packed.json) under its name.
+
+--scattered: the list forms (rv_yuv_surfaces_to_patches, rv_frames_to_patches_scattered: one pointer per frame in the kernel arguments) on --frames separately
+allocated 1080p surfaces, for NV12, P010 + PQ and bgra, against the contiguous entry on a pre-stacked copy of the same bytes and against the two-step path a
+surface pool forces without them (torch.stack of every plane, then the contiguous entry): three forms alternating in one process, each launch between two device
+events, the same warm-up and launch counts.  No ratio is fixed in advance; the expectation is list / contiguous about 1 and list / two-step below 1 by about the
+cost of the copy.  Writes the three runs to --out (default profiles/frontend_scattered.json).
 """
 import argparse
 import json
@@ -290,6 +296,57 @@ def rgb_order_run(a, dt):
                                     same_bits_as_rgb24=bool(torch.equal(first["packed"].view(torch.int16), first["rgb24"].view(torch.int16)))))
 
 
+def scattered_run(a, dt):
+    """--scattered: the list entry on separately allocated surfaces against the contiguous entry on a stacked copy and against torch.stack + that entry."""
+    n, H, W, R = a.frames, a.height, a.width, a.res
+    gen = torch.Generator().manual_seed(0)
+
+    def surfaces(*shape):
+        """n separate allocations of one plane, with another allocation between two of them so that they are not neighbours."""
+        out, spacers = [], []
+        for i in range(n):
+            t = torch.randint(0, 256, shape, dtype=torch.uint8, generator=gen).cuda()
+            out.append(t)
+            spacers.append(torch.empty(4096 * (1 + i % 3), dtype=torch.uint8, device="cuda"))
+        return out, spacers
+
+    res = {}
+    for name in ("nv12", "p010le_pq", "bgra"):
+        if name == "bgra":
+            frames, keep = surfaces(H, W, 4)
+            call = lambda f: ops.frames_to_patches(f, R, a.patch, op_dtype=dt, pix_fmt="bgra")[0]
+            stack = lambda: torch.stack(frames)
+        else:
+            wide = name != "nv12"
+            es, dtype = (2, torch.uint16) if wide else (1, torch.uint8)
+            yb, keep = surfaces(H, W * es)                       # bytes: the stack below is a plain byte copy
+            cb, keep2 = surfaces(H // 2, W * es)
+            y, c = [t.view(dtype) for t in yb], [t.view(dtype).view(H // 2, W // 2, 2) for t in cb]
+            kw = dict(depth=10, msb_aligned=True, matrix="bt2020", chroma_loc="topleft", transfer="pq") if wide else dict(matrix="bt709")
+            frames = (y, c)
+            call = lambda f: ops.yuv_surface_to_patches(f[0], f[1], R=R, patch=a.patch, op_dtype=dt, **kw)[0]
+            stack = lambda: (torch.stack(yb).view(dtype), torch.stack(cb).view(dtype).view(n, H // 2, W // 2, 2))
+        stacked = stack()
+        forms = (("list", lambda: call(frames)), ("contiguous", lambda: call(stacked)), ("two_step", lambda: call(stack())))
+        if a.once:
+            forms[0][1]()
+            torch.cuda.synchronize()
+            continue
+        med, ms, first = alternate(forms, a)
+        res[name] = dict(frames=n, height=H, width=W, res=R, patch=a.patch, warmup=a.warmup, iters=a.iters, list_ms=ms["list"], contiguous_ms=ms["contiguous"],
+                         two_step_ms=ms["two_step"], list_over_contiguous=med["list"] / med["contiguous"], list_over_two_step=med["list"] / med["two_step"],
+                         same_bits_as_contiguous=bool(torch.equal(first["list"].view(torch.int16), first["contiguous"].view(torch.int16))))
+        del keep
+    if a.once:
+        return
+    res = dict(device=torch.cuda.get_device_name(0), operand=hip.flavour(), **res)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
@@ -309,9 +366,15 @@ def main():
     ap.add_argument("--rotate", type=int, default=0, choices=(0, 90, 180, 270), help="time the oriented entry (clockwise degrees) against rot90 + the un-oriented entry")
     ap.add_argument("--hflip", action="store_true")
     ap.add_argument("--vflip", action="store_true")
+    ap.add_argument("--scattered", action="store_true", help="time the list entries on separately allocated surfaces (NV12, P010 + PQ, bgra) against the contiguous "
+                    "entry on a stacked copy and against torch.stack + that entry")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "frontend_yuv_prof needs the GPU: a CPU run says nothing about time"
     dt = hip.op_dtype()
+    if a.scattered:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "frontend_scattered.json")
+        return scattered_run(a, dt)
     if a.rgb_order is not None or a.pix_fmt in ops.PACKED_PIX_FMTS:
         if a.out == ap.get_default("out"):
             a.out = os.path.join(ROOT, "profiles", "frontend_packed.json")
