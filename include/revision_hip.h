@@ -608,13 +608,18 @@ int rv_sample(const rv_ctx* ctx /* optional: tunables */, const float* logits, i
 /* get_entropy_statistics (funs_get_feature_X.py:120-146): logits f32 [B,G,V] -> [B,4] = max,min,mean,std. */
 int rv_entropy_stats(const float* logits, int32_t B, int32_t G, int32_t V, float* out, void* stream);
 /* Stage-2 cosine score (eval_nlq_retrieval_e2e2.py:380-386): feat bf16/f32 [n,T,768]; per segment:
- * column-normalise over frames, top-k frames by <f,q>, sum, dot q.  out f32 [n]. */
+ * column-normalise over frames, top-k frames by <f,q>, sum, dot q.  out f32 [n]; k <= 0: the mean over the frames.
+ * Non-finite input: the frames are ranked in torch.topk's order (a NaN similarity before every number, ties: smaller frame index), so out[i] is
+ * NaN whenever a similarity of segment i is NaN, for every k, as the reference's is - a NaN feature, or a column that is zero in every frame
+ * (0 / 0 in its norm), makes every similarity of the segment NaN.  The other segments of the launch are unaffected. */
 int rv_topk_cosine(const void* feat, int feat_dtype, const float* q_cls, int32_t n, int32_t T, int32_t d, int32_t k,
                    float* out, void* stream);
 
 /* _topk_pooling (revisionllm/eval/similarity.py:71-94): video bf16/f32 [Nv,T,d], text f32 [Nt,d] -> out f32 [Nv,Nt,d] = SUM of
  * the k frames of video v with the largest <f_t, text_j> (ties: smaller frame index), added in descending-similarity order;
- * out_idx i32 [Nv,Nt,k] (the selected frames, optional).  1 <= k <= min(64, T). */
+ * out_idx i32 [Nv,Nt,k] (the selected frames, optional).  1 <= k <= min(64, T).
+ * Non-finite input: torch.topk's order - a frame whose similarity is NaN ranks before every number (among NaN frames the smaller index first), is
+ * selected, and its columns come out NaN where the frame holds NaN, as the reference's do; out_idx always holds k distinct indices in [0, T). */
 int rv_topk_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, int32_t k,
                  float* out, int32_t* out_idx, void* stream);
 

@@ -27,6 +27,29 @@ __device__ __forceinline__ ArgMax wave_argmax(ArgMax a) {
     return a;
 }
 
+// The order of the score kernels (torch.topk's): NaN before every number, then the larger value, then the smaller frame index.  A strict total
+// order over (value, index) pairs with distinct indices, so "the first entry strictly after the previous pick" walks the frames in rank order
+// without marking the picked ones: no round can return a frame twice or, while rounds <= frames, none at all.  (sample_kernel keeps better():
+// its candidates are keys, never NaN.)
+__device__ __forceinline__ bool rank_before(ArgMax a, ArgMax b) {  // a ranks strictly before b
+    const bool an = a.v != a.v, bn = b.v != b.v;
+    if (an != bn) return an;
+    return (an || a.v == b.v) ? a.i < b.i : a.v > b.v;
+}
+__device__ __forceinline__ ArgMax rank_none() { return ArgMax{-INFINITY, 0x7fffffff}; }                  // after every frame's entry
+__device__ __forceinline__ ArgMax rank_start() { return ArgMax{__int_as_float(0x7fc00000), -1}; }       // before every frame's entry
+__device__ __forceinline__ ArgMax rank_next(ArgMax best, ArgMax prev, ArgMax c) {  // the earlier of best and c among the entries after prev
+    return (rank_before(prev, c) && rank_before(c, best)) ? c : best;
+}
+__device__ __forceinline__ ArgMax wave_rank_first(ArgMax a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ArgMax b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
+        a = rank_before(b, a) ? b : a;
+    }
+    return a;
+}
+
 __device__ __forceinline__ float block_sum(float v, float* sh) {  // sh: 16 floats; all threads get the result
     v = wave_sum(v);
     __syncthreads();
@@ -688,16 +711,12 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __re
             for (int t = 0; t < Tn; ++t) acc += sims[t];
             acc /= (float)Tn;
         } else {
-            for (int r = 0; r < k && r < Tn; ++r) {
-                int bi = 0;
-                float bv = -INFINITY;
-                for (int t = 0; t < Tn; ++t)
-                    if (sims[t] > bv) {
-                        bv = sims[t];
-                        bi = t;
-                    }
-                acc += bv;
-                sims[bi] = -INFINITY;
+            ArgMax prev = rank_start();
+            for (int r = 0; r < k && r < Tn; ++r) {   // rank order: a NaN similarity comes first and makes the sum NaN, as the reference's does
+                ArgMax best = rank_none();
+                for (int t = 0; t < Tn; ++t) best = rank_next(best, prev, ArgMax{sims[t], t});
+                acc += best.v;
+                prev = best;
             }
         }
         out[blockIdx.x] = acc;
@@ -708,7 +727,7 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __re
 // The same with 16-byte loads (d a multiple of the vector width VEC = 16 B / sizeof(T)): thread t owns column chunk t % (d / VEC)
 // and walks the frames of group t / (d / VEC), so a wave reads whole 1 KiB row segments; the per-group partial sums meet in LDS
 // and are added in group order (deterministic).  The scores take one wave per frame with the same 16-byte loads, and the
-// top-k is k wave-argmax rounds (largest value, then smallest frame index: the serial scan's choice).  39 MB of bf16 features
+// top-k is k wave-wide rank rounds (rank_before: NaN, then largest value, then smallest frame index: the serial scan's choice).  39 MB of bf16 features
 // for 100 segments: 157 -> ~25 us.
 template <typename T>
 __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__ feat, const float* __restrict__ q, int Tn, int d,
@@ -771,20 +790,20 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__
         for (int t = lane; t < Tn; t += 64) acc += sims[t];
         acc = wave_sum(acc) / (float)Tn;
     } else {
-        for (int r = 0; r < k && r < Tn; ++r) {
-            ArgMax best{-INFINITY, 0x7fffffff};
-            for (int t = lane; t < Tn; t += 64) best = better(best, ArgMax{sims[t], t});
-            best = wave_argmax(best);
+        ArgMax prev = rank_start();
+        for (int r = 0; r < k && r < Tn; ++r) {   // rank order: a NaN similarity comes first and makes the sum NaN, as the reference's does
+            ArgMax best = rank_none();
+            for (int t = lane; t < Tn; t += 64) best = rank_next(best, prev, ArgMax{sims[t], t});
+            best = wave_rank_first(best);
             acc += best.v;
-            if (lane == 0 && best.i < Tn) sims[best.i] = -INFINITY;
-            __builtin_amdgcn_s_waitcnt(0);   // the LDS write lands before the next round's reads (one wave: program order)
+            prev = best;
         }
     }
     if (lane == 0) out[blockIdx.x] = acc;
 }
 
 // _topk_pooling (similarity.py:71-94) for one (video, text) pair per block: sims[t] = <f_t, q>, the k frames with the largest
-// sims (ties: smaller frame index), pooled[c] = sum over the selected frames of f[t][c], added in descending-sims order.
+// sims (torch.topk's order: a NaN similarity first, ties: smaller frame index), pooled[c] = sum over the selected frames of f[t][c], added in descending-sims order.
 // 256 threads: one wave per frame for the scores, the whole block over the columns for the sum.
 template <typename T>
 __global__ __launch_bounds__(256) void topk_pool_kernel(const T* __restrict__ video, const float* __restrict__ text, int Tn, int d,
@@ -806,15 +825,13 @@ __global__ __launch_bounds__(256) void topk_pool_kernel(const T* __restrict__ vi
     }
     __syncthreads();
     if (wave == 0) {
-        for (int r = 0; r < k; ++r) {
-            ArgMax best{-INFINITY, 0x7fffffff};
-            for (int t = lane; t < Tn; t += 64) best = better(best, ArgMax{sims[t], t});
-            best = wave_argmax(best);
-            if (lane == 0) {
-                sel[r] = best.i;
-                sims[best.i] = -INFINITY;
-            }
-            __builtin_amdgcn_s_waitcnt(0);
+        ArgMax prev = rank_start();
+        for (int r = 0; r < k; ++r) {   // k <= Tn (checked at the entry): every round finds a frame; sims is only read
+            ArgMax best = rank_none();
+            for (int t = lane; t < Tn; t += 64) best = rank_next(best, prev, ArgMax{sims[t], t});
+            best = wave_rank_first(best);
+            if (lane == 0) sel[r] = best.i < Tn ? best.i : Tn - 1;   // (never the second: no index outside the video can be stored or used)
+            prev = best;
         }
     }
     __syncthreads();

@@ -162,11 +162,17 @@ def pack_fragments_fp8_prefill(w):
     return pack_fp8_prefill(q), scale
 
 
-def quant_rows_fp8(x):
-    """fp16 / bf16 activations [M,K] -> (e4m3fn bytes uint8 [M,K], f32 [M] row scales) on the device (rv_quant_rows_fp8)."""
+def quant_rows_fp8(x, out=None):
+    """fp16 / bf16 activations [M,K] -> (e4m3fn bytes uint8 [M,K], f32 [M] row scales) on the device (rv_quant_rows_fp8).  ``x`` and ``out`` (uint8
+    [M,K], written in place and returned) may be column windows of wider tensors: rows with unit column stride, a row stride that is a multiple of 8 and
+    at least K, and a 16-byte aligned start are passed with their row strides; any other ``x`` is copied first.  ``out`` is never copied: the entry point
+    refuses a row stride that is no multiple of 8."""
     M, K = x.shape
-    x = _c(x)
-    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    if x.stride(1) != 1 or x.stride(0) < K or x.stride(0) % 8 != 0 or x.data_ptr() % 16 != 0:
+        x = x.contiguous()          # what the kernel's 16-byte loads cannot take is copied, as before
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device) if out is None else out
+    assert q.dtype == torch.uint8 and tuple(q.shape) == (M, K) and q.device == x.device, "quant_rows_fp8: out must be uint8 [M,K] on x's device"
+    assert q.stride(1) == 1 and (M <= 1 or q.stride(0) >= K), "quant_rows_fp8: out needs unit column stride and rows that do not overlap"
     sc = torch.empty(M, dtype=torch.float32, device=x.device)
     hip.check(hip.lib(x).rv_quant_rows_fp8(hip.ptr(x), x.stride(0), hip.ptr(q), q.stride(0), hip.ptr(sc), M, K, hip.stream()), "rv_quant_rows_fp8")
     return q, sc
@@ -203,6 +209,8 @@ def layernorm(x, w, b, pos=None, period=0, want=("f32", "op16"), op_dtype=None):
     y32 = torch.empty_like(x) if "f32" in want else None
     y16 = torch.empty(rows, d, dtype=dt, device=x.device) if ("op16" in want or "bf16" in want) else None
     yp = torch.empty(rows, d, dtype=dt, device=x.device) if pos is not None else None
+    if rows == 0:          # (an empty tensor has no pointer to pass)
+        return y32, y16, yp
     hip.check(hip.lib(dt).rv_layernorm(hip.ptr(_c(x)), hip.ptr(w), hip.ptr(b), hip.ptr(y32), hip.ptr(y16), hip.ptr(yp),
                                      hip.ptr(pos), period, rows, d, hip.stream()), "rv_layernorm")
     return y32, y16, yp
