@@ -623,6 +623,38 @@ int rv_topk_cosine(const void* feat, int feat_dtype, const float* q_cls, int32_t
 int rv_topk_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, int32_t k,
                  float* out, int32_t* out_idx, void* stream);
 
+/* ---- proposal-query matching (revisionllm/eval/similarity.py:24-69) and attention pooling (:96-113) ----
+ * The reference scores a proposal by slicing its window out of the video, normalising each frame of the slice, _topk_pooling the k = min(3, len)
+ * frames most similar to the normalised text CLS and taking the pooled row's dot product with the text: the SUM of the window's top-k cosines.
+ * Two launches do it for all proposals: the features are read ONCE into a per-frame cosine row, then every span works on that row.  Durations and
+ * windows stay on the device (the reference converts both to int32 on the host).
+ * Arithmetic: 16-bit features are read as stored and every operation is f32, as in the other score kernels; the reference run in bf16 does bf16
+ * arithmetic instead (its f32 run is what the tests compare to).  Not taken: several texts per video, per-frame masking (the mask only gives the duration,
+ * as in the reference). */
+
+/* video f32 / 16-bit operands [B,L,d] contiguous, text f32 [B,d] -> out f32 [B,L]: out[b,l] = <f_l, t_b> / (|f_l| |t_b|)  (similarity.py:36, :61-64 for
+ * every frame).  One pass over the features; 16-byte loads when d is a multiple of 16 B / element size and the base is 16-byte aligned.  A zero frame
+ * or a zero text gives NaN (0 / 0, as the reference's divisions do).  d <= 8192 (the text row staged in LDS); no limit on L. */
+int rv_frame_cosine(const void* video, int dtype, const float* text, int32_t B, int32_t L, int32_t d, float* out, void* stream);
+
+/* sims f32 [B,L] (rv_frame_cosine's row), spans f32 [B,N,2] as (centre, width), mask f32 [B,L] -> scores f32 [B,N], windows i32 [B,N,2] (optional, may
+ * be NULL).  The window rule is similarity.py:52-60 in f32, each operation rounded on its own: duration = sum of the mask row, x1 = c - 0.5 w,
+ * x2 = c + 0.5 w, p = x * duration, start = max(0, int32(floor(p1))), end = int32(ceil(p2)); the window is Python's range(L)[start:end] over the
+ * ARRAY length L: lo = min(start, L), hi = end < 0 ? max(end + L, 0) : min(end, L), empty when hi <= lo.  windows holds (lo, hi).
+ * mode 0: the sum of the min(k, hi - lo) largest sims of the window in torch.topk's order (NaN first, larger value, smaller index); 1 <= k <= 64.
+ * mode 1: sum_t softmax_t(s / temperature) s_t over the window (the alternative at similarity.py:63); temperature finite and not 0.
+ * An empty window scores 0 (the reference sums zero frames); a NaN similarity inside the window gives NaN in both modes.
+ * Build-defined (the reference's int conversion is undefined there): a non-finite p1 or p2 gives score NaN and window (-1, -1); finite values
+ * outside int32 saturate.  No read of sims lies outside [b L + lo, b L + hi). */
+int rv_span_scores(const float* sims, const float* spans, const float* mask, int32_t B, int32_t L, int32_t N, int32_t mode, int32_t k,
+                   float temperature, float* scores, int32_t* windows, void* stream);
+
+/* _attention_pooling (similarity.py:96-113): video f32 / 16-bit operands [Nv,T,d], text f32 [Nt,d] -> out f32 [Nv,Nt,d] =
+ * sum_t softmax_t(<f_t, text_j> / temperature) f_t.  temperature finite and not 0 (negative values are taken as given); (d + T) * 4 + 256 bytes of LDS
+ * <= 64 KB.  A NaN similarity makes that (video, text) row NaN in every column, as torch.softmax does; other videos are unaffected. */
+int rv_attn_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, float temperature,
+                 float* out, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

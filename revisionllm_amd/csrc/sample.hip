@@ -3,6 +3,9 @@
 //                     entropy of the processed and of the raw next-token distribution
 //   rv_entropy_stats  get_entropy_statistics (funs_get_feature_X.py:120-146) over stacked per-step scores
 //   rv_topk_cosine    column-normalised top-k pooled cosine score (eval_nlq_retrieval_e2e2.py:380-386)
+//   rv_frame_cosine   per-frame cosine row of a whole video against its text CLS   } forward_clip_matching / _get_predicted_proposal_feat
+//   rv_span_scores    (centre, width) proposals -> windows -> top-k / softmax score  } (eval/similarity.py:24-69) without a host round trip
+//   rv_attn_pool      _attention_pooling (eval/similarity.py:96-113)
 #include "kernels.h"
 
 namespace {
@@ -844,6 +847,243 @@ __global__ __launch_bounds__(256) void topk_pool_kernel(const T* __restrict__ vi
     if (out_idx && tid < k) out_idx[((int64_t)v * Nt + tx) * k + tid] = sel[tid];
 }
 
+// ---- proposal-query matching (eval/similarity.py:24-69) --------------------------------------------------------------------------------------
+// The reference scores a proposal by slicing its window out of the video, normalising every frame of the slice, pooling the top-k frames by
+// <frame / |frame|, text / |text|> and taking the pooled row's dot product with the text: the SUM of the top-k cosines of the window.  So the features
+// are read once into a cosine row (frame_cosine_kernel) and every span works on that row (span_scores_kernel).
+
+constexpr int FC_TPB = 256;        // 4 waves
+constexpr int FC_FRAMES = 32;      // frames of one block (8 per wave): the text row is normalised once per 32 frames
+constexpr int FC_FLIGHT = 4;       // frames a wave of the 16-byte-load path reads at a time
+constexpr int FC_DMAX = 8192;      // the staged text row: 32 KB of LDS
+
+// out[b, l] = <f_l, t_b> / (|f_l| |t_b|): the text row goes to LDS as t / |t| (a zero text: 0 / 0 = NaN in every column), a wave takes a frame, the dot
+// product and the sum of squares come from the same loads, and the division by |f_l| is the reference's (a zero frame: 0 / 0 = NaN).
+// VECTOR: 16-byte loads (d a multiple of 16 B / sizeof(T), 16-byte aligned rows), FC_FLIGHT frames of a wave in flight; else one element per lane and step.
+template <typename T, bool VECTOR>
+__global__ __launch_bounds__(FC_TPB) void frame_cosine_kernel(const T* __restrict__ video, const float* __restrict__ text, int L, int d,
+                                                              float* __restrict__ out) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // [d] t / |t|
+    __shared__ float red[FC_TPB / 64];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* t = text + (int64_t)b * d;
+    float ss = 0.f;
+    for (int c = tid; c < d; c += FC_TPB) {
+        const float v = t[c];
+        smem[c] = v;
+        ss += v * v;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) red[wave] = ss;
+    __syncthreads();
+    const float tnorm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    for (int c = tid; c < d; c += FC_TPB) smem[c] = smem[c] / tnorm;    // (each thread rewrites the elements it wrote)
+    __syncthreads();
+    const int l0 = blockIdx.x * FC_FRAMES + wave * (FC_FRAMES / 4);
+    const int l1 = l0 + FC_FRAMES / 4 < L ? l0 + FC_FRAMES / 4 : L;
+    const T* f = video + (int64_t)b * L * d;
+    float* o = out + (int64_t)b * L;
+    if constexpr (VECTOR) {
+        const int chunks = d / VEC;
+        auto load = [&](const T* p, float (&v)[VEC]) {
+            if constexpr (sizeof(T) == 2) {
+                const op16x8 r = *(const op16x8*)p;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) v[e] = op16_to_f32((op16_t)r[e]);
+            } else {
+                const f32x4 r = *(const f32x4*)p;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) v[e] = r[e];
+            }
+        };
+        for (int l = l0; l < l1; l += FC_FLIGHT) {
+            const T* fr[FC_FLIGHT];
+            float dot[FC_FLIGHT], sq[FC_FLIGHT];
+#pragma unroll
+            for (int j = 0; j < FC_FLIGHT; ++j) {
+                fr[j] = f + (int64_t)(l + j < l1 ? l + j : l1 - 1) * d;     // (past the wave's last frame: that frame again, never a row outside the video)
+                dot[j] = sq[j] = 0.f;
+            }
+            for (int cc = lane; cc < chunks; cc += 64) {
+                float v[FC_FLIGHT][VEC];
+#pragma unroll
+                for (int j = 0; j < FC_FLIGHT; ++j) load(fr[j] + cc * VEC, v[j]);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const float tn = smem[cc * VEC + e];
+#pragma unroll
+                    for (int j = 0; j < FC_FLIGHT; ++j) {
+                        dot[j] += v[j][e] * tn;
+                        sq[j] += v[j][e] * v[j][e];
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < FC_FLIGHT; ++j) {
+                const float dj = wave_sum(dot[j]), qj = wave_sum(sq[j]);
+                if (lane == 0 && l + j < l1) o[l + j] = dj / sqrtf(qj);
+            }
+        }
+    } else {
+        for (int l = l0; l < l1; ++l) {
+            const T* fa = f + (int64_t)l * d;
+            float da = 0.f, qa = 0.f;
+            for (int c = lane; c < d; c += 64) {
+                const float v = ld<T>(fa + c);
+                da += v * smem[c];
+                qa += v * v;
+            }
+            da = wave_sum(da);
+            qa = wave_sum(qa);
+            if (lane == 0) o[l] = da / sqrtf(qa);
+        }
+    }
+}
+
+// f32 -> int32 as torch's .to(torch.int32) gives it for the values the reference meets; outside int32's range (undefined there) the value saturates
+__device__ __forceinline__ int sat_i32(float v) {
+    return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
+}
+
+// One wave per span (4 spans per block, all of video blockIdx.y).  The block adds the video's mask row up first (duration; 0 / 1 masks: exact in any
+// order up to 2^24 frames; every block of a video repeats that sum - N / 4 reads of an L2-resident row of 4 L bytes - which is the price of keeping the
+// matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row:
+//   x1 = c - 0.5 w, x2 = c + 0.5 w, p = x * duration (every operation rounded to f32 on its own: no contraction), start = max(0, int(floor(p1))),
+//   end = int(ceil(p2)), and Python's range(L)[start:end] over the ARRAY length L: lo = min(start, L), hi = end < 0 ? max(end + L, 0) : min(end, L).
+// Every read of sims lies in [b L + lo, b L + hi).  MODE 0: the sum of the min(k, hi - lo) first entries in rank order (NaN, larger value, smaller
+// index: k wave-wide rank rounds over a lane-strided window, no LDS); MODE 1: sum_t softmax_t(s / tau) s_t in two lane-strided passes - the maximum, then both sums - (a NaN in
+// the window is carried next to the running maximum, which fmaxf would drop).  An empty window scores 0; a non-finite p1 / p2 gives NaN and the
+// window (-1, -1).
+template <int MODE>
+__global__ __launch_bounds__(256) void span_scores_kernel(const float* __restrict__ sims, const float* __restrict__ spans, const float* __restrict__ mask,
+                                                          int L, int N, int k, float tau, float* __restrict__ scores, int32_t* __restrict__ windows) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    {
+        const float* m = mask + (int64_t)b * L;
+        float s = 0.f;
+        for (int l = tid; l < L; l += 256) s += m[l];
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+    }
+    __syncthreads();
+    const float duration = (red[0] + red[1]) + (red[2] + red[3]);
+    const int n = blockIdx.x * 4 + wave;
+    if (n >= N) return;
+    const int64_t sp = (int64_t)b * N + n;
+    const float c = spans[sp * 2], w = spans[sp * 2 + 1];
+    const float hw = __fmul_rn(0.5f, w);
+    const float p1 = __fmul_rn(__fsub_rn(c, hw), duration), p2 = __fmul_rn(__fadd_rn(c, hw), duration);
+    if (!(fabsf(p1) < INFINITY) || !(fabsf(p2) < INFINITY)) {      // NaN or +-inf
+        if (lane == 0) {
+            scores[sp] = __int_as_float(0x7fc00000);
+            if (windows) windows[sp * 2] = windows[sp * 2 + 1] = -1;
+        }
+        return;
+    }
+    int start = sat_i32(floorf(p1));
+    start = start < 0 ? 0 : start;
+    const int end = sat_i32(ceilf(p2));
+    const int lo = start < L ? start : L;
+    int hi;
+    if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
+    else hi = end < L ? end : L;
+    if (lane == 0 && windows) {
+        windows[sp * 2] = lo;
+        windows[sp * 2 + 1] = hi;
+    }
+    const float* s = sims + (int64_t)b * L;
+    float acc = 0.f;
+    if (hi > lo) {
+        if constexpr (MODE == 0) {
+            ArgMax prev = rank_start();
+            const int rounds = k < hi - lo ? k : hi - lo;
+            for (int r = 0; r < rounds; ++r) {
+                ArgMax best = rank_none();
+                for (int t = lo + lane; t < hi; t += 64) best = rank_next(best, prev, ArgMax{s[t], t});
+                best = wave_rank_first(best);
+                acc += best.v;
+                prev = best;
+            }
+        } else {
+            float mx = -INFINITY;
+            bool nan = false;
+            for (int t = lo + lane; t < hi; t += 64) {
+                const float x = s[t] / tau;
+                nan |= x != x;
+                mx = fmaxf(mx, x);
+            }
+            mx = wave_max(mx);
+            if (__ballot(nan) != 0ull) mx = __int_as_float(0x7fc00000);
+            float z = 0.f, zs = 0.f;
+            for (int t = lo + lane; t < hi; t += 64) {
+                const float v = s[t];
+                const float e = expf(v / tau - mx);
+                z += e;
+                zs += e * v;
+            }
+            acc = wave_sum(zs) / wave_sum(z);
+        }
+    }
+    if (lane == 0) scores[sp] = acc;
+}
+
+// _attention_pooling (similarity.py:96-113) for one (video, text) pair per block, laid out as topk_pool_kernel: x[t] = <f_t, q> / tau to LDS (one wave per
+// frame), the softmax over the frames with the maximum subtracted (a NaN x is carried into the maximum: the whole row is NaN then, as torch.softmax's
+// is), then out[c] = sum_t p[t] f[t][c] with the threads over the columns, frames in ascending order.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ video, const float* __restrict__ text, int Tn, int d, int Nt, float tau,
+                                                        float* __restrict__ out) {
+    extern __shared__ float smem[];
+    float* qs = smem;          // [d]
+    float* xs = smem + d;      // [Tn] x, then p
+    __shared__ float red[64];
+    const int v = blockIdx.x, tx = blockIdx.y;
+    const T* f = video + (int64_t)v * Tn * d;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int c = tid; c < d; c += 256) qs[c] = text[(int64_t)tx * d + c];
+    __syncthreads();
+    for (int t = wave; t < Tn; t += 4) {
+        float s = 0.f;
+        for (int c = lane; c < d; c += 64) s += ld<T>(f + (int64_t)t * d + c) * qs[c];
+        s = wave_sum(s);
+        if (lane == 0) xs[t] = s / tau;
+    }
+    __syncthreads();
+    float mx = -INFINITY;
+    bool nan = false;
+    for (int t = tid; t < Tn; t += 256) {
+        const float x = xs[t];
+        nan |= x != x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if (__ballot(nan) != 0ull) mx = __int_as_float(0x7fc00000);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (red[0] != red[0] || red[1] != red[1] || red[2] != red[2] || red[3] != red[3]) mx = __int_as_float(0x7fc00000);
+    float z = 0.f;
+    for (int t = tid; t < Tn; t += 256) {
+        const float e = expf(xs[t] - mx);
+        xs[t] = e;                                  // (each thread rewrites the elements it read)
+        z += e;
+    }
+    z = wave_sum(z);
+    if (lane == 0) red[4 + wave] = z;
+    __syncthreads();
+    z = (red[4] + red[5]) + (red[6] + red[7]);
+    for (int t = tid; t < Tn; t += 256) xs[t] = xs[t] / z;
+    __syncthreads();
+    float* o = out + ((int64_t)v * Nt + tx) * d;
+    for (int c = tid; c < d; c += 256) {
+        float a = 0.f;
+        for (int t = 0; t < Tn; ++t) a += xs[t] * ld<T>(f + (int64_t)t * d + c);
+        o[c] = a;
+    }
+}
+
 }  // namespace
 
 extern "C" int rv_sample(const rv_ctx* ctx, const float* logits, int32_t B, int32_t V, const float* uniforms, int32_t do_sample, float temperature,
@@ -909,5 +1149,59 @@ extern "C" int rv_topk_pool(const void* video, int dtype, const float* text, int
     else
         hipLaunchKernelGGL(topk_pool_kernel<float>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const float*)video, text, T, d, Nt, k, out, out_idx);
     RV_CHECK_LAUNCH("rv_topk_pool");
+    return RV_OK;
+}
+
+extern "C" int rv_frame_cosine(const void* video, int dtype, const float* text, int32_t B, int32_t L, int32_t d, float* out, void* stream) {
+    RV_CHECK_ARG(video && text && out && B > 0 && L > 0 && d > 0, "rv_frame_cosine: bad arguments");
+    RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_frame_cosine: dtype must be f32 or %s", RV_OP16_NAME);
+    RV_CHECK_ARG(d <= FC_DMAX, "rv_frame_cosine: d=%d exceeds the %d columns of the staged text row", d, FC_DMAX);
+    RV_CHECK_ARG(B <= 65535, "rv_frame_cosine: at most 65535 videos per launch");
+    const int vec = dtype == RV_OP16 ? 8 : 4;
+    const bool vector = d % vec == 0 && ((uintptr_t)video & 15u) == 0;
+    const dim3 grid((unsigned)cdiv(L, FC_FRAMES), B);
+    const size_t sm = (size_t)d * sizeof(float);
+    hipStream_t st = as_stream(stream);
+    if (dtype == RV_OP16) {
+        if (vector) hipLaunchKernelGGL((frame_cosine_kernel<op16_t, true>), grid, dim3(FC_TPB), sm, st, (const op16_t*)video, text, L, d, out);
+        else hipLaunchKernelGGL((frame_cosine_kernel<op16_t, false>), grid, dim3(FC_TPB), sm, st, (const op16_t*)video, text, L, d, out);
+    } else {
+        if (vector) hipLaunchKernelGGL((frame_cosine_kernel<float, true>), grid, dim3(FC_TPB), sm, st, (const float*)video, text, L, d, out);
+        else hipLaunchKernelGGL((frame_cosine_kernel<float, false>), grid, dim3(FC_TPB), sm, st, (const float*)video, text, L, d, out);
+    }
+    RV_CHECK_LAUNCH("rv_frame_cosine");
+    return RV_OK;
+}
+
+extern "C" int rv_span_scores(const float* sims, const float* spans, const float* mask, int32_t B, int32_t L, int32_t N, int32_t mode, int32_t k,
+                              float temperature, float* scores, int32_t* windows, void* stream) {
+    RV_CHECK_ARG(sims && spans && mask && scores && B > 0 && L > 0 && N > 0, "rv_span_scores: bad arguments");
+    RV_CHECK_ARG(mode == 0 || mode == 1, "rv_span_scores: mode=%d must be 0 (top-k) or 1 (attention)", mode);
+    RV_CHECK_ARG(B <= 65535, "rv_span_scores: at most 65535 videos per launch");
+    const dim3 grid((unsigned)cdiv(N, 4), B);
+    if (mode == 0) {
+        RV_CHECK_ARG(k >= 1 && k <= KCAP, "rv_span_scores: k=%d must be in [1, %d]", k, KCAP);
+        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, L, N, k, 1.0f, scores, windows);
+    } else {
+        RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_span_scores: temperature must be finite and not 0");
+        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, L, N, k, temperature, scores, windows);
+    }
+    RV_CHECK_LAUNCH("rv_span_scores");
+    return RV_OK;
+}
+
+extern "C" int rv_attn_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, float temperature,
+                            float* out, void* stream) {
+    RV_CHECK_ARG(video && text && out && Nv > 0 && T > 0 && d > 0 && Nt > 0, "rv_attn_pool: bad arguments");
+    RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_attn_pool: dtype must be f32 or %s", RV_OP16_NAME);
+    RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_attn_pool: temperature must be finite and not 0");
+    RV_CHECK_ARG(Nt <= 65535, "rv_attn_pool: at most 65535 texts per launch");
+    const size_t sm = (size_t)(d + T) * sizeof(float);
+    RV_CHECK_ARG(sm + 64 * sizeof(float) <= 64 * 1024, "rv_attn_pool: d + T too large for LDS (dynamic %zu B + 256 B static)", sm);
+    if (dtype == RV_OP16)
+        hipLaunchKernelGGL(attn_pool_kernel<op16_t>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const op16_t*)video, text, T, d, Nt, temperature, out);
+    else
+        hipLaunchKernelGGL(attn_pool_kernel<float>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const float*)video, text, T, d, Nt, temperature, out);
+    RV_CHECK_LAUNCH("rv_attn_pool");
     return RV_OK;
 }

@@ -1,10 +1,45 @@
-"""``_topk_pooling`` under the reference's module name (revisionllm/eval/similarity.py:71-94), imported by the drivers at
-eval_nlq_retrieval_e2e2.py:22 / eval_nlq_negative.py:21 and called at e2e2.py:384, negative.py:313.  The arithmetic is the
-HIP kernel behind ``rv_topk_pool``; there is no CPU path (host tensors are staged to the device and the result comes back on
-the caller's device, in the dtype of ``video_embeds`` like the reference's gather + sum)."""
+"""The reference's ``revisionllm/eval/similarity.py`` under its module name: ``span_cxw_to_xx`` (:5-21), ``forward_clip_matching`` (:24-41),
+``_get_predicted_proposal_feat`` (:44-69), ``_topk_pooling`` (:71-94, imported by the drivers at eval_nlq_retrieval_e2e2.py:22 / eval_nlq_negative.py:21 and
+called at e2e2.py:384, negative.py:313) and ``_attention_pooling`` (:96-113), with the reference's positional signatures.  The arithmetic is the HIP
+kernels behind ``rv_topk_pool``, ``rv_frame_cosine`` + ``rv_span_scores`` and ``rv_attn_pool``; there is no CPU path (host tensors are staged to the
+device and the result comes back on the caller's device, in the float dtype of the video features like the reference's result).  Only
+``span_cxw_to_xx`` is plain torch on whatever device its input lives.
+
+Proposal-query matching: the reference walks the proposals in a Python double loop (slice, per-frame norm, topk, gather, einsum per proposal, after two
+device -> host copies of the window bounds).  A proposal's score is the sum of the top-k cosines of its window, so here the features are read once into a
+per-frame cosine row and one more launch scores every span on that row; durations and windows never leave the device.  Keywords after ``is_groundtruth``
+are this build's: ``k`` (the reference's 3), ``pooling`` ("topk", or "attention" = the alternative commented out at similarity.py:63 with ``temperature``),
+``return_windows``.  Not taken: the reference's bf16 arithmetic (16-bit features are read as stored, all arithmetic is f32), several texts per video, per-frame
+masking (as in the reference the mask only gives each video's duration)."""
+import math
+
 import torch
 
 from .. import ops
+
+_FLOATS = (torch.float16, torch.bfloat16, torch.float32)
+
+
+def span_cxw_to_xx(cxw_spans):
+    """(..., 2) rows of (centre, width) -> (..., 2) rows of (start, end) = (centre - width / 2, centre + width / 2), in the input's type and on its device."""
+    centre, width = cxw_spans.unbind(dim=-1)
+    half = 0.5 * width                       # exact: the two bounds carry one rounding each, as the reference's do
+    return torch.stack((centre - half, centre + half), dim=-1)
+
+
+def _device_of(t, who):
+    if t.is_cuda:
+        return t.device
+    if not torch.cuda.is_available():
+        from ..hip import HipLibraryError
+        raise HipLibraryError(f"{who} runs on the HIP device path only (no GPU visible)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _features_up(video, dev):
+    """The features on the device in a type the kernels read (16-bit floats and f32 as they are, anything else as f32)."""
+    video = video if video.is_cuda else ops.h2d(video, dev)
+    return video if video.dtype in _FLOATS else video.float()
 
 
 def _topk_pooling(text_embeds, video_embeds, k):
@@ -23,3 +58,71 @@ def _topk_pooling(text_embeds, video_embeds, k):
         video_embeds = video_embeds.float()
     text = text_embeds.to(video_embeds.device).float()
     return ops.topk_pool(text, video_embeds, k).to(device=home, dtype=dt)
+
+
+def _attention_pooling(text_embeds, video_embeds, temperature):
+    """text_embeds [num_texts, d], video_embeds [num_vids, num_frames, d] -> [num_vids, num_texts, d]: for every (video, text)
+    ``sum_t softmax_t(<frame_t, text> / temperature) frame_t`` (similarity.py:96-113)."""
+    if text_embeds.dim() != 2 or video_embeds.dim() != 3 or text_embeds.shape[1] != video_embeds.shape[2]:
+        raise ValueError(f"_attention_pooling: text {tuple(text_embeds.shape)} / video {tuple(video_embeds.shape)}")
+    temperature = float(temperature)
+    if temperature == 0.0 or not math.isfinite(temperature):
+        raise ValueError(f"_attention_pooling: temperature={temperature} must be finite and not 0")
+    home, dt = video_embeds.device, video_embeds.dtype
+    dev = _device_of(video_embeds, "_attention_pooling")
+    video = _features_up(video_embeds, dev)
+    text = ops.h2d(text_embeds, dev).float()
+    return ops.attn_pool(text, video, temperature).to(device=home, dtype=dt if dt.is_floating_point else torch.float32)
+
+
+def _match(who, text, video, mask, proposal, k, pooling, temperature, return_windows):
+    if proposal is None:
+        raise TypeError(f"{who}: proposal is None (the reference fails there too: it has no default proposals)")
+    for name, t in (("text", text), ("video", video), ("mask", mask), ("proposal", proposal)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
+    if video.dim() != 3 or text.dim() != 2 or text.shape != (video.shape[0], video.shape[2]):
+        raise ValueError(f"{who}: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, d] and [B, L, d])")
+    if mask.shape != video.shape[:2]:
+        raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected [B, L])")
+    if proposal.dim() != 3 or proposal.shape[0] != video.shape[0] or proposal.shape[2] != 2:
+        raise ValueError(f"{who}: proposal {tuple(proposal.shape)} (expected [B={video.shape[0]}, N, 2] rows of (centre, width))")
+    if min(video.shape) == 0:
+        raise ValueError(f"{who}: empty video {tuple(video.shape)}")
+    for name, t in (("text", text), ("video", video), ("proposal", proposal)):
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{who}: {name} must be a floating-point tensor (got {t.dtype})")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    if pooling not in ops.SPAN_POOLINGS:
+        raise ValueError(f"{who}: pooling={pooling!r} (expected one of {sorted(ops.SPAN_POOLINGS)})")
+    if pooling == "topk" and not (isinstance(k, int) and 1 <= k <= 64):
+        raise ValueError(f"{who}: k={k!r} must be an integer in [1, 64]")
+    if pooling == "attention" and (float(temperature) == 0.0 or not math.isfinite(float(temperature))):
+        raise ValueError(f"{who}: temperature={temperature} must be finite and not 0")
+    home, dt = video.device, video.dtype
+    dev = _device_of(video, who)
+    video = _features_up(video, dev)
+    sims = ops.frame_cosine(ops.h2d(text, dev).float(), video)
+    out = ops.span_scores(sims, ops.h2d(proposal, dev).float(), ops.h2d(mask, dev).float(), k=k, pooling=pooling, temperature=temperature,
+                          return_windows=return_windows)
+    if return_windows:
+        return out[0].to(device=home, dtype=dt), out[1].to(device=home)
+    return out.to(device=home, dtype=dt)
+
+
+def forward_clip_matching(src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal=None, is_groundtruth=False, *, k=3, pooling="topk",
+                          temperature=0.01, return_windows=False):
+    """src_cls_txt [B, d], src_vid_appear [B, L, d], src_vid_appear_mask [B, L] (0 on padding: its row sum is the video's duration), proposal [B, N, 2]
+    rows of (centre, width) as fractions of the duration -> the proposal-query similarity matrix [B, N] (similarity.py:24-41): the sum of the
+    min(k, len) largest cosines between the text CLS and the frames of ``range(L)[floor(x1 * duration) : ceil(x2 * duration)]``; an empty window scores 0.
+    Two launches (plus one small cast kernel for each of: a mask or proposals that are not f32, a 16-bit result), no device -> host copy and no synchronisation
+    when the inputs live on the device.  ``return_windows``: also the i32 [B, N, 2] windows
+    (lo, hi) the scores were taken over.  ``is_groundtruth`` is accepted and unused, as in the reference."""
+    return _match("forward_clip_matching", src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, k, pooling, temperature, return_windows)
+
+
+def _get_predicted_proposal_feat(src_vid_appear, src_vid_appear_mask, pred_proposal, text_cls_features):
+    """similarity.py:44-69 with the reference's argument order.  ``text_cls_features`` are the unit-norm rows ``forward_clip_matching`` hands over
+    there; the cosine kernel normalises them (again), so rows of another length give the same scores as their unit-norm versions."""
+    return _match("_get_predicted_proposal_feat", text_cls_features, src_vid_appear, src_vid_appear_mask, pred_proposal, 3, "topk", 0.01, False)

@@ -922,3 +922,55 @@ def topk_pool(text_embeds, video_embeds, k, return_index=False):
     hip.check(hip.lib(None if video_embeds.dtype == torch.float32 else video_embeds).rv_topk_pool(hip.ptr(_c(video_embeds)), hip.dtype_code(video_embeds), hip.ptr(_c(text_embeds.float())), Nv, T, d,
                                      Nt, int(k), hip.ptr(out), hip.ptr(idx), hip.stream()), "rv_topk_pool")
     return (out, idx) if return_index else out
+
+
+def _score_lib(t):
+    return hip.lib(None if t.dtype == torch.float32 else t)
+
+
+def frame_cosine(text, video):
+    """The per-frame cosine row of ``forward_clip_matching`` (similarity.py:36, :61-64): text f32 [B,d], video [B,L,d] (16-bit operands or f32) -> f32 [B,L],
+    ``<f_l, t_b> / (|f_l| |t_b|)``; a zero frame or a zero text gives NaN as the reference's divisions do."""
+    if video.dim() != 3 or text.dim() != 2 or text.shape != (video.shape[0], video.shape[2]):
+        raise ValueError(f"frame_cosine: text {tuple(text.shape)} / video {tuple(video.shape)}")
+    B, L, d = video.shape
+    out = torch.empty(B, L, dtype=torch.float32, device=video.device)
+    hip.check(_score_lib(video).rv_frame_cosine(hip.ptr(_c(video)), hip.dtype_code(video), hip.ptr(_c(text.float())), B, L, d, hip.ptr(out), hip.stream()),
+              "rv_frame_cosine")
+    return out
+
+
+SPAN_POOLINGS = {"topk": 0, "attention": 1}
+
+
+def span_scores(sims, spans, mask, k=3, pooling="topk", temperature=0.01, return_windows=False):
+    """sims f32 [B,L], spans [B,N,2] as (centre, width), mask [B,L] -> scores f32 [B,N] (and the windows i32 [B,N,2] as (lo, hi) of ``range(L)[start:end]``):
+    the reference's window rule (similarity.py:52-60) and, per window, the sum of its min(k, len) largest sims (``pooling="topk"``) or
+    ``sum softmax(s / temperature) s`` (``"attention"``).  Nothing comes back to the host."""
+    if pooling not in SPAN_POOLINGS:
+        raise ValueError(f"span_scores: pooling={pooling!r} (expected one of {sorted(SPAN_POOLINGS)})")
+    if sims.dim() != 2 or spans.dim() != 3 or spans.shape[0] != sims.shape[0] or spans.shape[2] != 2 or mask.shape != sims.shape:
+        raise ValueError(f"span_scores: sims {tuple(sims.shape)} / spans {tuple(spans.shape)} / mask {tuple(mask.shape)}")
+    if sims.dtype != torch.float32:
+        raise ValueError(f"span_scores: sims must be float32 (got {sims.dtype})")
+    B, L = sims.shape
+    N = spans.shape[1]
+    scores = torch.empty(B, N, dtype=torch.float32, device=sims.device)
+    win = torch.empty(B, N, 2, dtype=torch.int32, device=sims.device) if return_windows else None
+    if N > 0:
+        hip.check(hip.lib().rv_span_scores(hip.ptr(_c(sims)), hip.ptr(_c(spans.float())), hip.ptr(_c(mask.float())), B, L, N, SPAN_POOLINGS[pooling], int(k),
+                                           float(temperature), hip.ptr(scores), hip.ptr(win), hip.stream()), "rv_span_scores")
+    return (scores, win) if return_windows else scores
+
+
+def attn_pool(text_embeds, video_embeds, temperature):
+    """``_attention_pooling`` (similarity.py:96-113) on the device: text [Nt,d], video [Nv,T,d] (16-bit operands or f32) -> f32 [Nv,Nt,d] =
+    ``sum_t softmax_t(<f_t, text_j> / temperature) f_t``."""
+    if text_embeds.dim() != 2 or video_embeds.dim() != 3 or text_embeds.shape[1] != video_embeds.shape[2]:
+        raise ValueError(f"attn_pool: text {tuple(text_embeds.shape)} / video {tuple(video_embeds.shape)}")
+    Nv, T, d = video_embeds.shape
+    Nt = text_embeds.shape[0]
+    out = torch.empty(Nv, Nt, d, dtype=torch.float32, device=video_embeds.device)
+    hip.check(_score_lib(video_embeds).rv_attn_pool(hip.ptr(_c(video_embeds)), hip.dtype_code(video_embeds), hip.ptr(_c(text_embeds.float())), Nv, T, d, Nt,
+                                                    float(temperature), hip.ptr(out), hip.stream()), "rv_attn_pool")
+    return out
