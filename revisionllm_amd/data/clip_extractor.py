@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .. import ops
+from .. import frontend, ops
 from ..ops import CLIP_MEAN, CLIP_STD  # noqa: F401  (the constants' home is next to the kernel wrapper that defaults to them)
 from .clip_model import ClipTowers
 
@@ -68,14 +68,9 @@ class ClipFeatureExtractor:
         tw, R = self.clip_extractor, self.clip_extractor.cfg["image_res"]
         orient = ops.orientation(rotate, hflip, vflip)
         if pix_fmt is not None:
-            if pix_fmt not in ops.RGB_PIX_FMTS:
-                raise ValueError(f"pix_fmt {pix_fmt!r}: one of {sorted(ops.RGB_PIX_FMTS)} (packed 8-bit RGB)")
-            if layout not in (None, "NHWC"):
-                raise ValueError(f"pix_fmt {pix_fmt!r} names the byte order of packed pixels: layout {layout!r} does not go with it")
-            out = [tw.encode_frames(b, rotate=rotate, hflip=hflip, vflip=vflip, pix_fmt=pix_fmt)
-                   for b in self._batches((frames,) if torch.is_tensor(frames) else frames, bsz, shapes=f"[t,H,W,{ops.RGB_PIX_FMTS[pix_fmt][0]}]",
-                                          scattered=scattered)]
-            return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+            pix = frontend._rgb_format(pix_fmt, layout)[0]      # an unknown name, or a layout that does not go with it, is refused before anything is read
+            return self._features(tw.encode_frames(b, rotate=rotate, hflip=hflip, vflip=vflip, pix_fmt=pix_fmt)
+                                  for b in self._batches((frames,) if torch.is_tensor(frames) else frames, bsz, shapes=f"[t,H,W,{pix}]", scattered=scattered))
         if torch.is_tensor(frames):
             native = frames.dim() == 4 and tuple(frames.shape[1:]) == (3, R, R) and layout in (None, "NCHW")
             if orient and frames.dtype == torch.uint8:
@@ -88,11 +83,9 @@ class ClipFeatureExtractor:
                     raise ValueError(f"rotate={rotate} / hflip={hflip} / vflip={vflip}: float frames at the towers' resolution are past the front end; turn "
                                      "them before the call, or hand over the decoded uint8 frames")
                 x = preprocess(frames)
-                out = [tw.encode_image(x[i * bsz:(i + 1) * bsz]) for i in range(int(math.ceil(len(x) / bsz)))]
-                return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+                return self._features(tw.encode_image(x[i * bsz:(i + 1) * bsz]) for i in range(int(math.ceil(len(x) / bsz))))
             frames = (frames,)
-        out = [tw.encode_frames(b, layout=layout, rotate=rotate, hflip=hflip, vflip=vflip) for b in self._batches(frames, bsz, scattered=scattered)]
-        return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+        return self._features(tw.encode_frames(b, layout=layout, rotate=rotate, hflip=hflip, vflip=vflip) for b in self._batches(frames, bsz, scattered=scattered))
 
     @torch.no_grad()
     def encode_video_yuv(self, chunks, H, W, fmt, bsz=60, scattered=False, **colour):
@@ -105,9 +98,9 @@ class ClipFeatureExtractor:
         tw = self.clip_extractor
         ops.orientation(colour.get("rotate", 0), colour.get("hflip", False), colour.get("vflip", False))     # refused before anything is read
         colour = {**yuv_colour_defaults(H), **colour}
-        out = [tw.encode_frames_yuv(*(_split_each(b, lambda f: ops.split_yuv420(f, H, W, fmt)) if scattered else ops.split_yuv420(b, H, W, fmt)), **colour)
-               for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]", scattered=scattered)]
-        return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+        return self._features(
+            tw.encode_frames_yuv(*(_split_each(b, lambda f: ops.split_yuv420(f, H, W, fmt)) if scattered else ops.split_yuv420(b, H, W, fmt)), **colour)
+            for b in self._batches((chunks,) if torch.is_tensor(chunks) else chunks, bsz, ndim=3, shapes=f"[t,{H * 3 // 2},{W}]", scattered=scattered))
 
     @torch.no_grad()
     def encode_video_pix_fmt(self, chunks, H, W, pix_fmt, bsz=60, scattered=False, **colour):
@@ -142,26 +135,18 @@ class ClipFeatureExtractor:
             else:
                 planes, kw = ops.split_yuv(b, H, W, pix_fmt)
             out.append(tw.encode_surfaces_yuv(*planes, **kw, **colour))
-        return torch.cat(out, 0) if out else torch.empty(0, tw.cfg["embed_dim"], device=self.device)
+        return self._features(out)
+
+    def _features(self, batches):
+        """The features of the batches, joined: f32 [T, d] (T = 0 for a video without frames)."""
+        out = list(batches)
+        return torch.cat(out, 0) if out else torch.empty(0, self.clip_extractor.cfg["embed_dim"], device=self.device)
 
     def _batches(self, chunks, bsz, ndim=4, shapes="[t,3,H,W] or [t,H,W,3]", scattered=False):
         """Decoded uint8 chunks of any lengths -> device batches of exactly ``bsz`` frames (the last one shorter): the batching does not depend on
         how the decoder cut the video.  ``scattered``: every batch is a LIST of per-frame views of the chunks, in the same order and with the same batch
         boundaries, and nothing is copied (no ``torch.cat``): the list forms of the front end take the frames where they lie."""
-        if scattered:
-            held = []
-            for c in chunks:
-                if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != ndim:
-                    raise ValueError(f"decoded frames come as uint8 tensors {shapes}")
-                c = ops.h2d(c, self.device)
-                for i in range(len(c)):
-                    held.append(c[i])
-                    if len(held) == bsz:
-                        yield held
-                        held = []
-            if held:
-                yield held
-            return
+        join = (lambda held: held) if scattered else (lambda held: held[0] if len(held) == 1 else torch.cat(held, 0))
         held, n = [], 0
         for c in chunks:
             if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != ndim:
@@ -169,13 +154,16 @@ class ClipFeatureExtractor:
             c = ops.h2d(c, self.device)
             while len(c):
                 take = c[:bsz - n]
-                held.append(take)
+                if scattered:
+                    held.extend(take)                           # per-frame views
+                else:
+                    held.append(take)
                 n, c = n + len(take), c[len(take):]
                 if n == bsz:
-                    yield held[0] if len(held) == 1 else torch.cat(held, 0)
+                    yield join(held)
                     held, n = [], 0
         if n:
-            yield held[0] if len(held) == 1 else torch.cat(held, 0)
+            yield join(held)
 
     @torch.no_grad()
     def encode_text(self, text_list, bsz=60, tokens=None):

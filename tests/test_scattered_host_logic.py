@@ -77,7 +77,7 @@ def rec(monkeypatch):
     monkeypatch.setattr(hip, "lib", lambda f=None: r)
     monkeypatch.setattr(hip, "ptr", lambda t: None if t is None else t.data_ptr())
     monkeypatch.setattr(hip, "stream", lambda: None)
-    monkeypatch.setattr(ops, "_require_device", lambda tensors, who: None)
+    monkeypatch.setattr("revisionllm_amd.frontend._require_device", lambda tensors, who: None)
     return r
 
 
