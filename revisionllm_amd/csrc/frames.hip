@@ -7,26 +7,23 @@
 //   phase 0  the tile's tap tables (first tap, count, normalised f32 weights; computed in f64) for its TX columns and TY rows into LDS
 //   phase 1  per chunk of FR_SR source rows: stage the bytes the tile needs in LDS (16-byte loads where the address allows, single bytes at the
 //            ends of a row segment), then the horizontal pass into f32 LDS rows  inter[source row][channel][column]
-//   phase 2  vertical pass over inter, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
+//   phase 2  vertical pass over inter, normalise, then the tail all front-end kernels share (frames_common.h): store f32 image and / or op16 patch rows, zero
+//            the pad columns of the patch rows the tile starts
 // Tap counts depend on the geometry (4 * scale + 1 per axis): every tap loop is a runtime loop over LDS-resident weights.  The host picks TY / TX so that
 // a workgroup stays under FR_LDS_BUDGET bytes (two workgroups per CU) and refuses a geometry that does not fit with TY = TX = 1.
 //
-// Display orientation (rv_frames_to_patches_oriented): the kernel is compiled per ORI (0 = none: the code it was; 1 = mirrors; 2 = transpose, with or without
-// mirrors).  Loads, staging and the LDS plan stay in CODED orientation: a coded axis takes the scale, crop offset and mirror flag of the display axis it
-// serves, its tap table holds the display window reflected into coded sample indices, and only the store is permuted to image[f, c, yd, xd].
+// Display orientation (rv_frames_to_patches_oriented): the kernel is compiled per ORI (0 = none; 1 = mirrors; 2 = transpose, with or without mirrors).  Loads,
+// staging and the LDS plan stay in CODED orientation: a coded axis takes the scale, crop offset and mirror flag of the display axis it serves, its tap table
+// holds the display window reflected into coded sample indices, and only the store is permuted to image[f, c, yd, xd].
 //
-// Packed RGB in any byte order (rv_frames_to_patches_packed: bgr24, bgra, argb ...): compiled per PK as well (0: the code it was).  The PK = 1 instances are the
-// NHWC path with a pixel of 3 or 4 bytes and R, G, B at their own byte offsets inside it; the staged row segment covers the whole pixels, a fourth byte is staged
-// and never read.
+// Packed RGB in any byte order (rv_frames_to_patches_packed: bgr24, bgra, argb ...): compiled per PK as well.  The PK = 1 instances are the NHWC path with a
+// pixel of 3 or 4 bytes and R, G, B at their own byte offsets inside it; the staged row segment covers the whole pixels, a fourth byte is staged and never read.
 //
-// Separately allocated frames (rv_frames_to_patches_scattered: a decoder's surface pool, a capture ring): compiled per TAB as well (0: the code it was, on the
-// argument block it always had).  A TAB = 1 instance takes FrTab - FrParams and, behind it, one base pointer per frame of the launch - and reads its frame's base
-// from that table in the argument segment (the frame number is uniform per workgroup: scalar loads) where the TAB = 0 instance computes src + f * fstride.  The
-// host cuts a batch into launches of at most RV_FRAME_TABLE_MAX frames.
-#include <atomic>
-#include <type_traits>
-
-#include "frames_taps.h"   // the tap definition, FR_* constants and capacity helpers (shared with frames_yuv.hip); fp contraction is off from there on
+// Separately allocated frames (rv_frames_to_patches_scattered: a decoder's surface pool, a capture ring): compiled per TAB as well.  A TAB = 1 instance takes
+// FrTab - FrParams and, behind it, one base pointer per frame of the launch - and reads its frame's base from that table in the argument segment (the frame
+// number is uniform per workgroup: scalar loads) where the TAB = 0 instance computes src + f * fstride.  The host cuts a batch into launches of at most
+// RV_FRAME_TABLE_MAX frames.
+#include "frames_common.h"   // fp contraction is off from there on
 
 namespace {
 
@@ -43,13 +40,13 @@ struct FrParams {
     op16_t* patches;
     int64_t ldp;
     float* image;
-    int mirx, miry;                      // oriented instances only (behind everything the ORI = 0 instance reads): the coded x / y axis is mirrored
+    int mirx, miry;                      // the coded x / y axis is mirrored (read by the oriented instances only)
     int off[3];                          // PK = 1 instances only: byte offsets of R, G, B inside a pixel of `pix` bytes
 };
 
 // The argument block of the TAB = 1 instances: the frames of one launch lie where the table says (NCHW channel planes p.cstride apart; p.src / p.fstride unused).
 struct FrTab : FrParams {
-    const uint8_t* frame[RV_FRAME_TABLE_MAX];
+    const uint8_t* tab[RV_FRAME_TABLE_MAX];
 };
 template <int TAB>
 using FrArgs = std::conditional_t<TAB != 0, FrTab, FrParams>;
@@ -78,24 +75,9 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrA
     for (int i = tid; i < tx + ty; i += FR_THREADS) {
         const bool isx = i < tx;
         const int o = isx ? i : i - tx;
-        const double scale = isx ? p.sx : p.sy;
-        const int idx = isx ? x0 + o + p.left : y0 + o + p.top;
-        int t0, nt;
-        if constexpr (ORI == 0) {
-            fr_taps(scale, isx ? p.W : p.H, idx, t0, nt);
-            nt = min(nt, isx ? p.NTX : p.NTY);
-            float* w = isx ? wh + o * p.NTXp : wv + o * p.NTY;
-            const double inv = scale >= 1.0 ? 1.0 / scale : 1.0, centre = scale * (idx + 0.5);
-            double tot = 0.0;
-            for (int t = 0; t < nt; ++t) tot += fr_cubic((t0 + t - centre + 0.5) * inv);
-            const double rt = tot != 0.0 ? 1.0 / tot : 1.0;
-            for (int t = 0; t < nt; ++t) w[t] = (float)(fr_cubic((t0 + t - centre + 0.5) * inv) * rt);
-        } else {
-            fr_tap_table_m(FrAxis{scale, 1.0, 0.0, isx ? p.W : p.H}, isx ? p.left : p.top, p.R, isx ? p.mirx : p.miry, (isx ? x0 : y0) + o,
-                           isx ? p.NTX : p.NTY, isx ? wh + o * p.NTXp : wv + o * p.NTY, t0, nt);
-        }
-        (isx ? xmin : ymin)[o] = t0;
-        (isx ? nx : ny)[o] = nt;
+        const int mir = ORI == 0 ? 0 : isx ? p.mirx : p.miry;
+        fr_tap_table(FrAxis{isx ? p.sx : p.sy, 1.0, 0.0, isx ? p.W : p.H}, isx ? p.left : p.top, p.R, mir, (isx ? x0 : y0) + o, isx ? p.NTX : p.NTY,
+                     isx ? wh + o * p.NTXp : wv + o * p.NTY, (isx ? xmin : ymin)[o], (isx ? nx : ny)[o]);
     }
     __syncthreads();
     const int rmin = ymin[0], cmin = xmin[0];
@@ -105,7 +87,7 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrA
     const int planes = PK ? 1 : p.pix == 1 ? 3 : 1;
     const int nck = p.SEG >> 4;
     const uint8_t* fsrc;
-    if constexpr (TAB != 0) fsrc = p.frame[f] + (int64_t)cmin * p.pix;
+    if constexpr (TAB != 0) fsrc = p.tab[f] + (int64_t)cmin * p.pix;
     else fsrc = p.src + f * p.fstride + (int64_t)cmin * p.pix;
 
     // ---- phase 1: stage source bytes, horizontal pass ---------------------------------------------------------------------------
@@ -174,35 +156,12 @@ __global__ __launch_bounds__(FR_THREADS) void frames_to_patches_kernel(const FrA
         float acc = 0.f;
         for (int t = 0; t < n; ++t) acc = fmaf(w[t], q[t * 3 * p.TX], acc);
         const float v = (acc / 255.0f - (c == 0 ? p.mean[0] : c == 1 ? p.mean[1] : p.mean[2])) / (c == 0 ? p.den[0] : c == 1 ? p.den[1] : p.den[2]);
-        int y = y0 + yy, x = x0 + col;
-        if constexpr (ORI != 0) {   // the display pixel this coded output is
-            const int dy = fr_disp_index(0, p.R, y, p.miry), dx = fr_disp_index(0, p.R, x, p.mirx);
-            y = ORI == 2 ? dx : dy;
-            x = ORI == 2 ? dy : dx;
-        }
-        if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = v;
-        if (p.patches)
-            p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(v);
+        fr_store<ORI>(p, f, c, y0 + yy, x0 + col, v);
     }
-    // pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile
-    if (p.patches && p.Kp > p.K) {
-        int py0 = y0, pty = ty, px0 = x0, ptx = tx;   // the tile's rectangle of the display image
-        if constexpr (ORI != 0) {
-            const int cy0 = p.miry ? p.R - y0 - ty : y0, cx0 = p.mirx ? p.R - x0 - tx : x0;
-            py0 = ORI == 2 ? cx0 : cy0;
-            pty = ORI == 2 ? tx : ty;
-            px0 = ORI == 2 ? cy0 : cx0;
-            ptx = ORI == 2 ? ty : tx;
-        }
-        const int gy0 = (py0 + p.patch - 1) / p.patch, gy1 = (py0 + pty + p.patch - 1) / p.patch;
-        const int gx0 = (px0 + p.patch - 1) / p.patch, gx1 = (px0 + ptx + p.patch - 1) / p.patch;
-        const int pad = p.Kp - p.K, ngx = gx1 - gx0;
-        for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
-            const int j = it % pad, pr = it / pad;
-            p.patches[((f * p.g + gy0 + pr / ngx) * p.g + gx0 + pr % ngx) * p.ldp + p.K + j] = 0;
-        }
-    }
+    fr_zero_pad<ORI>(p, f, y0, ty, x0, tx, tid);
 }
+
+int fr_stage_bytes(const FrParams& p) { return (p.pix == 1 ? 3 : 1) * FR_SR * p.SEG; }
 
 // Tile plan: capacities from the exact tap placement of the crop's rows and columns (the kernel clamps to them all the same); false = over the LDS budget.
 bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
@@ -223,55 +182,53 @@ bool fr_plan(FrParams& p, int ty, int tx, double& cost) {
     o += (int64_t)p.NR * 3 * tx * 4;
     o = (o + 15) & ~(int64_t)15;
     p.o_stage = (int)o;
-    o += (int64_t)(p.pix == 1 ? 3 : 1) * FR_SR * p.SEG;
+    o += fr_stage_bytes(p);
     if (o > FR_LDS_BUDGET) return false;
     // source rows the horizontal pass computes per output row, plus the (cheaper) bytes staged per output pixel
     cost = (double)p.NR / ty * (3.0 + (double)p.SEGPX / (tx * (p.sx > 1.0 ? p.sx : 1.0)));
     return true;
 }
 
-int fr_lds_bytes(const FrParams& p) { return p.o_stage + (p.pix == 1 ? 3 : 1) * FR_SR * p.SEG; }
+// One launch of the instance for orientation class oc and pixel form pk (1: packed RGB), on the contiguous block (FrParams) or the table form (FrTab).
+template <class Args>
+int fr_dispatch(int oc, int pk, const Args& a, int64_t wgs, int lds, void* stream, const char* who) {
+    return fr_pick<3>(oc, [&](auto ORI) {
+        return fr_pick<2>(pk, [&](auto PK) {
+            return fr_launch<frames_to_patches_kernel<decltype(ORI)::value, decltype(PK)::value, std::is_same_v<Args, FrTab>>>(a, wgs, lds, stream, who, "frames_to_patches");
+        });
+    });
+}
 
-// One launch of the instance for orientation class ORI (PK: the packed-RGB instance); the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <int ORI, int PK, int TAB = 0>
-int fr_launch(const FrArgs<TAB>& p, int64_t wgs, int lds, void* stream, const char* who) {
-    static std::atomic<uint64_t> have_lds{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)frames_to_patches_kernel<ORI, PK, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
-            rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
-            return RV_ERR_HIP;
-        }
-        have_lds.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((frames_to_patches_kernel<ORI, PK, TAB>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
-    RV_CHECK_LAUNCH("frames_to_patches");
+// The packed entries' pixel: 3 or 4 bytes, R, G, B at distinct byte offsets inside it.
+int fr_check_pixel(int32_t pix_bytes, int32_t r_off, int32_t g_off, int32_t b_off, const char* who) {
+    RV_CHECK_ARG(pix_bytes == 3 || pix_bytes == 4, "%s: pix_bytes = %d (3, or 4 = a fourth byte that is never read)", who, pix_bytes);
+    RV_CHECK_ARG(r_off >= 0 && g_off >= 0 && b_off >= 0 && r_off < pix_bytes && g_off < pix_bytes && b_off < pix_bytes && r_off != g_off && r_off != b_off &&
+                     g_off != b_off,
+                 "%s: r_off, g_off, b_off = %d, %d, %d (three distinct byte offsets inside the %d-byte pixel)", who, r_off, g_off, b_off, pix_bytes);
     return RV_OK;
 }
 
-// All entry points: validate, plan the tiles, launch.  `who` names the entry point in the messages; orient 0 is the un-oriented entry's plan and instance.  off:
-// null, or the packed entry's R, G, B byte offsets inside a pixel of pix_bytes bytes (layout is 1 then).  tab: the scattered entry's host array of n frame
-// pointers (frames is null and frame_stride 3 * channel_stride then), else null - the plan and the instances the contiguous entries always had.
+// All entry points: validate, plan the tiles, launch.  `who` names the entry point in the messages; orient is validated by the caller (0 for the un-oriented
+// entry).  off: null, or the packed entry's R, G, B byte offsets inside a pixel of pix_bytes bytes (layout is 1 then).  tab: the scattered entry's host array of n
+// frame pointers (frames is null and frame_stride 3 * channel_stride then), else null.
 int fr_run(const uint8_t* frames, const uint8_t* const* tab, int layout, int pix_bytes, const int32_t* off, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
            int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image, void* stream, const char* who) {
     RV_CHECK_ARG(layout == 0 || layout == 1, "%s: layout %d (0 = NCHW, 1 = NHWC)", who, layout);
-    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
-    RV_CHECK_ARG(H >= 1 && W >= 1 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 .. %d", who, H, W, FR_MAX_SIDE);
-    RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
-    RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
-    if (n == 0) return RV_OK;
-    RV_CHECK_ARG(frames || tab, "%s: null frames", who);
-    if (tab)   // the whole table before anything is launched
-        for (int32_t f = 0; f < n; ++f) RV_CHECK_ARG(tab[f], "%s: null pointer for frame %d of %d", who, f, n);
-    RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
-    RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
-    FrParams p{};
-    p.K = 3 * patch * patch;
-    p.Kp = (p.K + 127) / 128 * 128;
-    RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
+    const int rc = fr_check_common(
+        R, patch, n, mean, std, patches, ldp, image, who,
+        [&]() -> int {
+            RV_CHECK_ARG(H >= 1 && W >= 1 && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 .. %d", who, H, W, FR_MAX_SIDE);
+            return RV_OK;
+        },
+        [&]() -> int {
+            RV_CHECK_ARG(frames || tab, "%s: null frames", who);
+            if (tab)   // the whole table before anything is launched
+                for (int32_t f = 0; f < n; ++f) RV_CHECK_ARG(tab[f], "%s: null pointer for frame %d of %d", who, f, n);
+            return RV_OK;
+        });
+    if (rc || n == 0) return rc;
     RV_CHECK_ARG(layout == 1 || frame_stride % 3 == 0, "%s: NCHW channel planes lie frame_stride / 3 apart; frame_stride = %lld", who, (long long)frame_stride);
+    FrParams p{};
     p.src = frames;
     p.fstride = frame_stride;
     p.rstride = row_stride;
@@ -281,69 +238,15 @@ int fr_run(const uint8_t* frames, const uint8_t* const* tab, int layout, int pix
         for (int c = 0; c < 3; ++c) p.off[c] = off[c];
     p.H = H;
     p.W = W;
-    p.R = R;
-    p.patch = patch;
-    p.g = R / patch;
-    // Resize(R) / CenterCrop(R) of the DISPLAY picture (W x H under transpose); each coded axis then takes what the display axis it serves got
-    const FrOrient ori = fr_orient(orient);
-    double sy, sx;
-    int top, left;
-    fr_resize_crop(ori.tr ? W : H, ori.tr ? H : W, R, sy, sx, top, left);
-    p.sy = ori.tr ? sx : sy;
-    p.sx = ori.tr ? sy : sx;
-    p.top = ori.tr ? left : top;
-    p.left = ori.tr ? top : left;
-    p.mirx = ori.mx;
-    p.miry = ori.my;
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean[c];
-        p.den[c] = std[c] + 1e-8f;
-    }
-    p.patches = (op16_t*)patches;
-    p.ldp = ldp;
-    p.image = image;
+    fr_setup(p, H, W, orient, R, patch, mean, std, patches, ldp, image, p.sy, p.sx);
     p.NTX = fr_max_taps(FrAxis{p.sx, 1.0, 0.0, W}, p.left, R);
     p.NTXp = p.NTX | 1;   // odd row pitch: the columns' weight rows start in different banks
     p.NTY = fr_max_taps(FrAxis{p.sy, 1.0, 0.0, H}, p.top, R);
     FrParams best{};
-    double best_cost = 0.0;
-    bool have = false;
-    for (int ty = 16; ty >= 1; ty >>= 1)
-        for (int tx = 256; tx >= 1; tx >>= 1) {
-            const int tyc = ty < R ? ty : R, txc = tx < R ? tx : R;
-            double cost;
-            FrParams q = p;
-            if (fr_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
-        }
-    RV_CHECK_ARG(have, "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
-    const int lds = fr_lds_bytes(best);
-    if (tab) {   // launches of at most RV_FRAME_TABLE_MAX frames: the table and the output pointers move on, everything else is shared
-        const int oc = orient == 0 ? 0 : ori.tr ? 2 : 1;
-        const int64_t wmax = (int64_t)(n < RV_FRAME_TABLE_MAX ? n : RV_FRAME_TABLE_MAX) * best.bands * best.tilesX;
-        RV_CHECK_ARG(wmax < (1ll << 31), "%s: %lld workgroups per launch exceed one launch", who, (long long)wmax);
-        for (int32_t f0 = 0; f0 < n; f0 += RV_FRAME_TABLE_MAX) {
-            const int32_t nf = n - f0 < RV_FRAME_TABLE_MAX ? n - f0 : RV_FRAME_TABLE_MAX;
-            FrTab a{};
-            static_cast<FrParams&>(a) = best;
-            if (best.patches) a.patches = best.patches + (int64_t)f0 * best.g * best.g * ldp;
-            if (best.image) a.image = best.image + (int64_t)f0 * 3 * R * R;
-            for (int32_t f = 0; f < nf; ++f) a.frame[f] = tab[f0 + f];
-            const int64_t w = (int64_t)nf * best.bands * best.tilesX;
-            int rc;
-            if (off) rc = oc == 0 ? fr_launch<0, 1, 1>(a, w, lds, stream, who) : oc == 1 ? fr_launch<1, 1, 1>(a, w, lds, stream, who) : fr_launch<2, 1, 1>(a, w, lds, stream, who);
-            else rc = oc == 0 ? fr_launch<0, 0, 1>(a, w, lds, stream, who) : oc == 1 ? fr_launch<1, 0, 1>(a, w, lds, stream, who) : fr_launch<2, 0, 1>(a, w, lds, stream, who);
-            if (rc) return rc;
-        }
-        return RV_OK;
-    }
-    const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
-    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
-    if (off) {
-        if (orient == 0) return fr_launch<0, 1>(best, wgs, lds, stream, who);
-        return ori.tr ? fr_launch<2, 1>(best, wgs, lds, stream, who) : fr_launch<1, 1>(best, wgs, lds, stream, who);
-    }
-    if (orient == 0) return fr_launch<0, 0>(best, wgs, lds, stream, who);
-    return ori.tr ? fr_launch<2, 0>(best, wgs, lds, stream, who) : fr_launch<1, 0>(best, wgs, lds, stream, who);
+    RV_CHECK_ARG(fr_best_plan(p, R, fr_plan, best), "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
+    const int lds = best.o_stage + fr_stage_bytes(best), oc = fr_orient_class(orient);
+    return fr_launch_all<FrTab>(
+        best, [](auto& a) -> auto& { return a; }, tab, n, [&](const auto& a, int64_t wgs) { return fr_dispatch(oc, off != nullptr, a, wgs, lds, stream, who); }, who);
 }
 
 }  // namespace
@@ -358,8 +261,9 @@ extern "C" int rv_frames_to_patches(const uint8_t* frames, int layout, int64_t f
 extern "C" int rv_frames_to_patches_oriented(const uint8_t* frames, int layout, int64_t frame_stride, int64_t row_stride, int32_t n, int32_t H, int32_t W,
                                              int32_t orient, int32_t R, int32_t patch, const float mean[3], const float std[3], void* patches, int64_t ldp,
                                              float* image, void* stream) {
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "rv_frames_to_patches_oriented: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", orient);
-    return fr_run(frames, nullptr, layout, 3, nullptr, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, "rv_frames_to_patches_oriented");
+    const char* who = "rv_frames_to_patches_oriented";
+    if (const int rc = fr_check_orient(orient, who)) return rc;
+    return fr_run(frames, nullptr, layout, 3, nullptr, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
 // Packed 8-bit RGB in any byte order, 3 or 4 bytes per pixel: the oriented NHWC entry with the channels at their own offsets inside the pixel.
@@ -367,11 +271,8 @@ extern "C" int rv_frames_to_patches_packed(const uint8_t* frames, int32_t pix_by
                                            int64_t row_stride, int32_t n, int32_t H, int32_t W, int32_t orient, int32_t R, int32_t patch, const float mean[3],
                                            const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
     const char* who = "rv_frames_to_patches_packed";
-    RV_CHECK_ARG(pix_bytes == 3 || pix_bytes == 4, "%s: pix_bytes = %d (3, or 4 = a fourth byte that is never read)", who, pix_bytes);
-    RV_CHECK_ARG(r_off >= 0 && g_off >= 0 && b_off >= 0 && r_off < pix_bytes && g_off < pix_bytes && b_off < pix_bytes && r_off != g_off && r_off != b_off &&
-                     g_off != b_off,
-                 "%s: r_off, g_off, b_off = %d, %d, %d (three distinct byte offsets inside the %d-byte pixel)", who, r_off, g_off, b_off, pix_bytes);
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    if (const int rc = fr_check_pixel(pix_bytes, r_off, g_off, b_off, who)) return rc;
+    if (const int rc = fr_check_orient(orient, who)) return rc;
     const int32_t off[3] = {r_off, g_off, b_off};
     return fr_run(frames, nullptr, 1, pix_bytes, off, frame_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
@@ -382,16 +283,13 @@ extern "C" int rv_frames_to_patches_scattered(const uint8_t* const* frames, int 
                                               const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
     const char* who = "rv_frames_to_patches_scattered";
     RV_CHECK_ARG(layout == 0 || layout == 1, "%s: layout %d (0 = NCHW, 1 = packed pixels)", who, layout);
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
+    if (const int rc = fr_check_orient(orient, who)) return rc;
     const int32_t off[3] = {r_off, g_off, b_off};
     if (layout == 0) {
         RV_CHECK_ARG(pix_bytes == 3 && r_off == 0 && g_off == 1 && b_off == 2, "%s: layout 0 (NCHW) takes pix_bytes 3 and offsets 0, 1, 2; got %d and %d, %d, %d", who,
                      pix_bytes, r_off, g_off, b_off);
         return fr_run(nullptr, frames, 0, 3, nullptr, 3 * channel_stride, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
     }
-    RV_CHECK_ARG(pix_bytes == 3 || pix_bytes == 4, "%s: pix_bytes = %d (3, or 4 = a fourth byte that is never read)", who, pix_bytes);
-    RV_CHECK_ARG(r_off >= 0 && g_off >= 0 && b_off >= 0 && r_off < pix_bytes && g_off < pix_bytes && b_off < pix_bytes && r_off != g_off && r_off != b_off &&
-                     g_off != b_off,
-                 "%s: r_off, g_off, b_off = %d, %d, %d (three distinct byte offsets inside the %d-byte pixel)", who, r_off, g_off, b_off, pix_bytes);
+    if (const int rc = fr_check_pixel(pix_bytes, r_off, g_off, b_off, who)) return rc;
     return fr_run(nullptr, frames, 1, pix_bytes, off, 0, row_stride, n, H, W, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }

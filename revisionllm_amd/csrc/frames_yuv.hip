@@ -47,29 +47,27 @@
 //   phase 1  per chunk of FR_SR source rows, first of the Y plane, then of the chroma planes: stage the bytes the tile needs in LDS (16-byte loads where the
 //            address allows, single samples at the ends of a row segment; an interleaved chroma segment holds both planes), then the horizontal pass into
 //            f32 LDS rows  interY[source row][column],  interC[chroma row][Cb | Cr][column]
-//   phase 2  vertical pass over both, colour matrix, normalise, store f32 image and / or op16 patch rows; zero the pad columns of the patch rows the tile starts
+//   phase 2  vertical pass over both, then fy_colour_store: colour matrix, HDR steps, normalise, and the tail all front-end kernels share (frames_common.h) -
+//            store f32 image and / or op16 patch rows, zero the pad columns of the patch rows the tile starts
 // At 4:2:0: half the horizontal-pass work of three RGB planes (one full plane + two quarter planes filtered with half the taps), and two thirds of its
-// `inter` rows.  The kernel is compiled per sample type (uint8_t; uint16_t with a run-time shift), so the 8-bit instance is the 8-bit kernel it was, and per
-// transfer (TRC: 0 = none, 1 = PQ, 2 = HLG): the HDR steps exist in the HDR instances only, the TRC = 0 instances are the code they were.
+// `inter` rows.  The kernel is compiled per sample type (uint8_t; uint16_t with a run-time shift) and per transfer (TRC: 0 = none, 1 = PQ, 2 = HLG): the HDR
+// steps exist in the HDR instances only.
 //
-// Display orientation (rv_yuv_surface_to_patches_oriented; include/revision_hip.h has the definition): compiled per ORI as well (0 = none: the code it was;
-// 1 = mirrors; 2 = transpose, with or without mirrors).  Loads, staging and the LDS plan stay in CODED orientation.  Every coded axis takes the scale and
+// Display orientation (rv_yuv_surface_to_patches_oriented; include/revision_hip.h has the definition): compiled per ORI as well (0 = none; 1 = mirrors;
+// 2 = transpose, with or without mirrors).  Loads, staging and the LDS plan stay in CODED orientation.  Every coded axis takes the scale and
 // crop offset of the display axis it serves and a mirror flag; the chroma siting offset stays with its coded axis and changes sign where that axis is
 // mirrored; a tap table holds the display window reflected into coded sample indices; only the store is permuted to image[f, c, yd, xd].  So a 4:2:2
 // surface turned by 90 degrees (4:4:0 on the display) is still the 2,1 surface it was coded as.
 //
 // Packed surfaces (rv_packed_to_patches: YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ...) have a kernel of their own behind the planar one, packed_to_patches_kernel:
-// one staged segment per source row serves the Y, Cb and Cr passes; its section has the layout.  The planar instances are untouched by it.
+// one staged segment per source row serves the Y, Cb and Cr passes; its section has the layout.  Phases 0 and 2 are the planar kernel's routines.
 //
-// Separately allocated surfaces (rv_yuv_surfaces_to_patches, rv_packed_surfaces_to_patches: a decoder's surface pool): both kernels are compiled per TAB as well
-// (0: the code it was, on the argument block it always had).  A TAB = 1 instance takes FyTab / FkTab - FyParams / FkParams and, behind them, the plane pointers of every
-// frame of the launch - and reads its frame's base pointers from that table in the argument segment (the frame number is uniform per workgroup: scalar loads) where
-// the TAB = 0 instance computes base + f * frame stride.  Planar Cr - Cb comes from the table too: it may differ from frame to frame.  Everything behind the base
-// pointers is the same text.  The host cuts a batch into launches of at most RV_FRAME_TABLE_MAX frames.
-#include <atomic>
-#include <type_traits>
-
-#include "frames_taps.h"   // fp contraction is off from there on
+// Separately allocated surfaces (rv_yuv_surfaces_to_patches, rv_packed_surfaces_to_patches: a decoder's surface pool): both kernels are compiled per TAB as well.
+// A TAB = 1 instance takes FyTab / FkTab - FyParams / FkParams and, behind them, the plane pointers of every frame of the launch - and reads its frame's base
+// pointers from that table in the argument segment (the frame number is uniform per workgroup: scalar loads) where the TAB = 0 instance computes base + f *
+// frame stride.  Planar Cr - Cb comes from the table too: it may differ from frame to frame.  The host cuts a batch into launches of at most RV_FRAME_TABLE_MAX
+// frames.
+#include "frames_common.h"   // fp contraction is off from there on
 
 namespace {
 
@@ -89,9 +87,9 @@ struct FyParams {
     op16_t* patches;
     int64_t ldp;
     float* image;
-    // HDR instances only (behind everything the TRC = 0 instances read): Lw, 1 / Lt, PQinv(Lw), maxLum, KS, gamma - 1, the gamut matrix by rows (or the identity)
+    // HDR instances only: Lw, 1 / Lt, PQinv(Lw), maxLum, KS, gamma - 1, the gamut matrix by rows (or the identity)
     float Lw, rLt, pqLw, maxLum, KS, gm1, gam[9];
-    int mirx, miry;   // oriented instances only: the coded x / y axis is mirrored
+    int mirx, miry;   // the coded x / y axis is mirrored (read by the oriented instances only)
 };
 
 // ---- HDR -> SDR per output pixel (the head of the file has the definition) ---------------------------------------------------------------------------
@@ -153,26 +151,6 @@ __device__ inline void fy_hdr_to_sdr(float v[3], const FyParams& p) {
     }
 }
 
-// Entry o of the tile's tap table of one axis (output index first + o): first tap, count (clamped to the host's capacity) and normalised f32 weights.
-__device__ inline void fy_tap_table(const FrAxis& a, int first, int cap, int pitch, float* w, int* t0s, int* nts, int o) {
-    const double fscale = a.scale / a.div, centre = fr_axis_centre(a, first + o);
-    int t0, nt;
-    fr_taps_at(centre, fscale, a.in, t0, nt);
-    nt = min(nt, cap);
-    const double inv = fscale >= 1.0 ? 1.0 / fscale : 1.0;
-    double tot = 0.0;
-    for (int t = 0; t < nt; ++t) tot += fr_cubic((t0 + t - centre + 0.5) * inv);
-    const double rt = tot != 0.0 ? 1.0 / tot : 1.0;
-    for (int t = 0; t < nt; ++t) w[o * pitch + t] = (float)(fr_cubic((t0 + t - centre + 0.5) * inv) * rt);
-    t0s[o] = t0;
-    nts[o] = nt;
-}
-
-// The same entry of an oriented axis (coded output o0 + o of the R cropped outputs, mirrored or not): fr_tap_table_m has the reflection.
-__device__ inline void fy_tap_table_m(const FrAxis& a, int first, int R, int mir, int o0, int cap, int pitch, float* w, int* t0s, int* nts, int o) {
-    fr_tap_table_m(a, first, R, mir, o0 + o, cap, w + o * pitch, t0s[o], nts[o]);
-}
-
 // Stage `nr` rows of `planes` planes: the `segbytes` bytes from `g0` on (row r of plane pl: g0 + pl * pdelta + r * rstride) into stage[(pl * FR_SR + r) * SEG ..],
 // each segment keeping its position inside a 16-byte line.  Reads [segment start, segment end) and nothing else: whole 16-byte lines inside it, single
 // samples of type S (segments start and end on a sample) at its two ends.
@@ -195,15 +173,10 @@ __device__ inline void fy_stage(uint8_t* stage, const uint8_t* g0, int64_t pdelt
     }
 }
 
-// A staged sample as f32: the 16-bit instance drops the low bits of a word whose value sits in the high bits (shift = 0 otherwise).
-__device__ inline float fy_sample(uint8_t v, int) { return (float)v; }
-__device__ inline float fy_sample(uint16_t v, int shift) { return (float)(v >> shift); }
-
-// The packed kernel's copy of what yuv_to_patches_kernel does behind its vertical pass (that kernel keeps its own text, so that its instances stay the code they
-// were): the resampled Y', Cb', Cr' of coded output (y0 + yy, x0 + col) of frame f -> colour matrix, the HDR steps of the HDR instances, normalise, store the f32
-// image and / or op16 patch element at the display pixel this coded output is.
+// Phase 2 of both kernels, behind the vertical pass: the resampled Y', Cb', Cr' of coded output (y, x) of frame f -> colour matrix, the HDR steps of the HDR
+// instances, normalise, store (fr_store has the display permutation).
 template <int TRC, int ORI>
-__device__ inline void fy_colour_store(const FyParams& p, float yv, float cb, float cr, int64_t f, int y0, int yy, int x0, int col) {
+__device__ inline void fy_colour_store(const FyParams& p, float yv, float cb, float cr, int64_t f, int y, int x) {
     const float yl = (yv - p.yoff) * p.ky;
     cb -= p.cmid;
     cr -= p.cmid;
@@ -212,46 +185,13 @@ __device__ inline void fy_colour_store(const FyParams& p, float yv, float cb, fl
     v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
     v[2] = fmaf(p.kbcb, cb, yl);
     if constexpr (TRC != FY_TRC_NONE) fy_hdr_to_sdr<TRC>(v, p);
-    int y = y0 + yy, x = x0 + col;
-    if constexpr (ORI != 0) {   // the display pixel this coded output is
-        const int dy = fr_disp_index(0, p.R, y, p.miry), dx = fr_disp_index(0, p.R, x, p.mirx);
-        y = ORI == 2 ? dx : dy;
-        x = ORI == 2 ? dy : dx;
-    }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float o = (v[c] / 255.0f - p.mean[c]) / p.den[c];
-        if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = o;
-        if (p.patches)
-            p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(o);
-    }
+    for (int c = 0; c < 3; ++c) fr_store<ORI>(p, f, c, y, x, (v[c] / 255.0f - p.mean[c]) / p.den[c]);
 }
 
-// ... and its zero fill of the pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile.
-template <int ORI>
-__device__ inline void fy_zero_pad(const FyParams& p, int64_t f, int y0, int ty, int x0, int tx, int tid) {
-    if (p.patches && p.Kp > p.K) {
-        int py0 = y0, pty = ty, px0 = x0, ptx = tx;   // the tile's rectangle of the display image
-        if constexpr (ORI != 0) {
-            const int cy0 = p.miry ? p.R - y0 - ty : y0, cx0 = p.mirx ? p.R - x0 - tx : x0;
-            py0 = ORI == 2 ? cx0 : cy0;
-            pty = ORI == 2 ? tx : ty;
-            px0 = ORI == 2 ? cy0 : cx0;
-            ptx = ORI == 2 ? ty : tx;
-        }
-        const int gy0 = (py0 + p.patch - 1) / p.patch, gy1 = (py0 + pty + p.patch - 1) / p.patch;
-        const int gx0 = (px0 + p.patch - 1) / p.patch, gx1 = (px0 + ptx + p.patch - 1) / p.patch;
-        const int pad = p.Kp - p.K, ngx = gx1 - gx0;
-        for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
-            const int j = it % pad, pr = it / pad;
-            p.patches[((f * p.g + gy0 + pr / ngx) * p.g + gx0 + pr % ngx) * p.ldp + p.K + j] = 0;
-        }
-    }
-}
-
-// The argument block of the TAB = 1 planar instances: the planes of frame f of one launch lie where fr[f] says (p.y / p.c / p.yfs / p.cfs / p.cdelta unused).
+// The argument block of the TAB = 1 planar instances: the planes of frame f of one launch lie where tab[f] says (p.y / p.c / p.yfs / p.cfs / p.cdelta unused).
 struct FyTab : FyParams {
-    rv_surface_planes fr[RV_FRAME_TABLE_MAX];
+    rv_surface_planes tab[RV_FRAME_TABLE_MAX];
 };
 template <int TAB>
 using FyArgs = std::conditional_t<TAB != 0, FyTab, FyParams>;
@@ -284,18 +224,13 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs
     const int ty = min(p.TY, p.R - y0), tx = min(p.TX, p.R - x0);
 
     // ---- phase 0: tap tables --------------------------------------------------------------------------------------------------
+    const int mirx = ORI == 0 ? 0 : p.mirx, miry = ORI == 0 ? 0 : p.miry;
     for (int i = tid; i < 2 * (tx + ty); i += FR_THREADS) {
-        if constexpr (ORI == 0) {
-            if (i < tx) fy_tap_table(p.ax, x0 + p.left, p.NTX, p.NTXp, wx, xmin, nx, i);
-            else if (i < 2 * tx) fy_tap_table(p.cx, x0 + p.left, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
-            else if (i < 2 * tx + ty) fy_tap_table(p.ay, y0 + p.top, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
-            else fy_tap_table(p.cy, y0 + p.top, p.NCY, p.NCY, cwy, cymin, cny, i - 2 * tx - ty);
-        } else {
-            if (i < tx) fy_tap_table_m(p.ax, p.left, p.R, p.mirx, x0, p.NTX, p.NTXp, wx, xmin, nx, i);
-            else if (i < 2 * tx) fy_tap_table_m(p.cx, p.left, p.R, p.mirx, x0, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
-            else if (i < 2 * tx + ty) fy_tap_table_m(p.ay, p.top, p.R, p.miry, y0, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
-            else fy_tap_table_m(p.cy, p.top, p.R, p.miry, y0, p.NCY, p.NCY, cwy, cymin, cny, i - 2 * tx - ty);
-        }
+        int o = i;
+        if (o < tx) fr_tap_table(p.ax, p.left, p.R, mirx, x0 + o, p.NTX, wx + o * p.NTXp, xmin[o], nx[o]);
+        else if ((o -= tx) < tx) fr_tap_table(p.cx, p.left, p.R, mirx, x0 + o, p.NCX, cwx + o * p.NCXp, cxmin[o], cnx[o]);
+        else if ((o -= tx) < ty) fr_tap_table(p.ay, p.top, p.R, miry, y0 + o, p.NTY, wy + o * p.NTY, ymin[o], ny[o]);
+        else o -= ty, fr_tap_table(p.cy, p.top, p.R, miry, y0 + o, p.NCY, cwy + o * p.NCY, cymin[o], cny[o]);
     }
     __syncthreads();
 
@@ -305,7 +240,7 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs
     const int segpx = min(xmin[tx - 1] + nx[tx - 1] - cmin, p.SPY);
     constexpr int SB = (int)sizeof(S);
     const uint8_t* ysrc;
-    if constexpr (TAB != 0) ysrc = (const uint8_t*)p.fr[f].y + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
+    if constexpr (TAB != 0) ysrc = (const uint8_t*)p.tab[f].y + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
     else ysrc = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)cmin * SB;
     for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
         const int nr = min(FR_SR, nrows - r0);
@@ -320,7 +255,7 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs
             const float* w = wx + col * p.NTXp;
             const int n = min(nx[col], segpx - xo);
             float a = 0.f;
-            for (int t = 0; t < n; ++t) a = fmaf(w[t], fy_sample(s[t], p.shift), a);
+            for (int t = 0; t < n; ++t) a = fmaf(w[t], fr_sample(s[t], p.shift), a);
             iy[(r0 + r) * p.TX + col] = a;
         }
     }
@@ -333,7 +268,7 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs
     const uint8_t* csrc;
     [[maybe_unused]] int64_t tdelta = 0;   // TAB = 1: this frame's Cr plane - Cb plane (planar), in the place of p.cdelta
     if constexpr (TAB != 0) {   // interleaved: the lower of the two planes, with the shared ocb / ocr
-        const uint8_t *tcb = (const uint8_t*)p.fr[f].cb, *tcr = (const uint8_t*)p.fr[f].cr;
+        const uint8_t *tcb = (const uint8_t*)p.tab[f].cb, *tcr = (const uint8_t*)p.tab[f].cr;
         csrc = (cplanes == 1 && tcr < tcb ? tcr : tcb) + (int64_t)crmin * p.crs + (int64_t)ccmin * p.cpix;
         tdelta = tcr - tcb;
     } else {
@@ -364,8 +299,8 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs
             for (int t = 0; t < n; ++t) {
                 const float wt = w[t];
                 const int o = t * cstep;
-                a0 = fmaf(wt, fy_sample(sb[o], p.shift), a0);
-                a1 = fmaf(wt, fy_sample(sr[o], p.shift), a1);
+                a0 = fmaf(wt, fr_sample(sb[o], p.shift), a0);
+                a1 = fmaf(wt, fr_sample(sr[o], p.shift), a1);
             }
             float* q = ic + (r0 + r) * 2 * p.TX + col;
             q[0] = a0;
@@ -395,46 +330,9 @@ __global__ __launch_bounds__(FR_THREADS) void yuv_to_patches_kernel(const FyArgs
                 cr = fmaf(w[t], q[(t * 2 + 1) * p.TX], cr);
             }
         }
-        const float yl = (yv - p.yoff) * p.ky;
-        cb -= p.cmid;
-        cr -= p.cmid;
-        float v[3];
-        v[0] = fmaf(p.krcr, cr, yl);
-        v[1] = fmaf(p.kgcr, cr, fmaf(p.kgcb, cb, yl));
-        v[2] = fmaf(p.kbcb, cb, yl);
-        if constexpr (TRC != FY_TRC_NONE) fy_hdr_to_sdr<TRC>(v, p);
-        int y = y0 + yy, x = x0 + col;
-        if constexpr (ORI != 0) {   // the display pixel this coded output is
-            const int dy = fr_disp_index(0, p.R, y, p.miry), dx = fr_disp_index(0, p.R, x, p.mirx);
-            y = ORI == 2 ? dx : dy;
-            x = ORI == 2 ? dy : dx;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float o = (v[c] / 255.0f - p.mean[c]) / p.den[c];
-            if (p.image) p.image[((f * 3 + c) * p.R + y) * p.R + x] = o;
-            if (p.patches)
-                p.patches[((f * p.g + y / p.patch) * p.g + x / p.patch) * p.ldp + (c * p.patch + y % p.patch) * p.patch + x % p.patch] = f32_to_op16(o);
-        }
+        fy_colour_store<TRC, ORI>(p, yv, cb, cr, f, y0 + yy, x0 + col);
     }
-    // pad columns K .. Kp - 1 of the patch rows whose first pixel lies in this tile
-    if (p.patches && p.Kp > p.K) {
-        int py0 = y0, pty = ty, px0 = x0, ptx = tx;   // the tile's rectangle of the display image
-        if constexpr (ORI != 0) {
-            const int cy0 = p.miry ? p.R - y0 - ty : y0, cx0 = p.mirx ? p.R - x0 - tx : x0;
-            py0 = ORI == 2 ? cx0 : cy0;
-            pty = ORI == 2 ? tx : ty;
-            px0 = ORI == 2 ? cy0 : cx0;
-            ptx = ORI == 2 ? ty : tx;
-        }
-        const int gy0 = (py0 + p.patch - 1) / p.patch, gy1 = (py0 + pty + p.patch - 1) / p.patch;
-        const int gx0 = (px0 + p.patch - 1) / p.patch, gx1 = (px0 + ptx + p.patch - 1) / p.patch;
-        const int pad = p.Kp - p.K, ngx = gx1 - gx0;
-        for (int it = tid; it < (gy1 - gy0) * ngx * pad; it += FR_THREADS) {
-            const int j = it % pad, pr = it / pad;
-            p.patches[((f * p.g + gy0 + pr / ngx) * p.g + gx0 + pr % ngx) * p.ldp + p.K + j] = 0;
-        }
-    }
+    fr_zero_pad<ORI>(p, f, y0, ty, x0, tx, tid);
 }
 
 int fy_stage_bytes(const FyParams& p) {
@@ -480,70 +378,38 @@ bool fy_plan(FyParams& p, int ty, int tx, double& cost) {
     return true;
 }
 
-// One launch of the instance for sample type S, transfer TRC and orientation class ORI; the dynamic-LDS opt-in is a per-device attribute of each instance.
-template <typename S, int TRC, int ORI, int TAB = 0>
-int fy_launch(const FyArgs<TAB>& p, int64_t wgs, int lds, void* stream, const char* who) {
-    static std::atomic<uint64_t> have_lds{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)yuv_to_patches_kernel<S, TRC, ORI, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
-            rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
-            return RV_ERR_HIP;
-        }
-        have_lds.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((yuv_to_patches_kernel<S, TRC, ORI, TAB>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), p);
-    RV_CHECK_LAUNCH("yuv_to_patches");
-    return RV_OK;
-}
-
 double fy_pq_inv64(double nits) {
     const double y = pow(nits / 10000.0, PQ_M1_D);
     return pow((PQ_C1_D + PQ_C2_D * y) / (1.0 + PQ_C3_D * y), PQ_M2_D);
 }
 
-// The instance of an orientation class: 0 = none, 1 = mirrors, 2 = transpose.
-template <typename S, int TRC, int TAB = 0>
-int fy_launch_ori(int ori_class, const FyArgs<TAB>& p, int64_t wgs, int lds, void* stream, const char* who) {
-    if (ori_class == 0) return fy_launch<S, TRC, 0, TAB>(p, wgs, lds, stream, who);
-    return ori_class == 1 ? fy_launch<S, TRC, 1, TAB>(p, wgs, lds, stream, who) : fy_launch<S, TRC, 2, TAB>(p, wgs, lds, stream, who);
+// One launch of the planar instance for a sample size, a transfer (m: null = SDR) and an orientation class, on the contiguous block (FyParams) or the table form (FyTab).
+template <class Args>
+int fy_dispatch(int sb, const rv_hdr_map* m, int oc, const Args& a, int64_t wgs, int lds, void* stream, const char* who) {
+    return fr_pick<2>(sb >> 1, [&](auto S) {
+        return fr_pick<3>(m ? m->transfer : FY_TRC_NONE, [&](auto TRC) {
+            return fr_pick<3>(oc, [&](auto ORI) {
+                return fr_launch<yuv_to_patches_kernel<FrSample<decltype(S)::value>, decltype(TRC)::value, decltype(ORI)::value, std::is_same_v<Args, FyTab>>>(
+                    a, wgs, lds, stream, who, "yuv_to_patches");
+            });
+        });
+    });
 }
 
-// The TAB = 1 instance of a sample size, a transfer (m: null = SDR) and an orientation class.
-int fy_launch_any(int sb, const rv_hdr_map* m, int oc, const FyTab& a, int64_t wgs, int lds, void* stream, const char* who) {
-    if (!m) return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_NONE, 1>(oc, a, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_NONE, 1>(oc, a, wgs, lds, stream, who);
-    if (m->transfer == FY_TRC_PQ)
-        return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_PQ, 1>(oc, a, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_PQ, 1>(oc, a, wgs, lds, stream, who);
-    return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_HLG, 1>(oc, a, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_HLG, 1>(oc, a, wgs, lds, stream, who);
-}
-
-// What every entry point derives from the frame geometry, the subsampling and the colour tags: resize / crop per coded axis, the luma and chroma axes, the
+// What every entry point derives from the frame geometry, the subsampling and the colour tags: fr_setup's share, the luma and chroma axes, the
 // colour coefficients, the HDR scalars (m: null = SDR) and the tap capacities.
 void fy_setup(FyParams& p, int H, int W, int sub_x, int sub_y, int depth, int matrix, int full_range, int chroma_loc, const rv_hdr_map* m, int32_t orient, int32_t R,
               int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image) {
-    p.R = R;
-    p.patch = patch;
-    p.g = R / patch;
-    // Resize(R) / CenterCrop(R) of the DISPLAY picture (W x H under transpose); each coded axis then takes what the display axis it serves got
-    const FrOrient ori = fr_orient(orient);
-    double dsy, dsx;
-    int dtop, dleft;
-    fr_resize_crop(ori.tr ? W : H, ori.tr ? H : W, R, dsy, dsx, dtop, dleft);
-    const double sy = ori.tr ? dsx : dsy, sx = ori.tr ? dsy : dsx;
-    p.top = ori.tr ? dleft : dtop;
-    p.left = ori.tr ? dtop : dleft;
-    p.mirx = ori.mx;
-    p.miry = ori.my;
+    double sy, sx;
+    fr_setup(p, H, W, orient, R, patch, mean, std, patches, ldp, image, sy, sx);
     p.ay = FrAxis{sy, 1.0, 0.0, H};
     p.ax = FrAxis{sx, 1.0, 0.0, W};
     // a subsampled axis whose chroma sample sits on the even luma sample lies a quarter of a chroma sample off: horizontally for left and top-left siting,
     // vertically for top-left; an axis that is not subsampled is the luma axis.  The offset belongs to the CODED axis; where that axis is mirrored the sample
     // sits on the other side of its luma pair on the display, so the offset changes sign
     const double offy = sub_y == 2 && chroma_loc == 2 ? 0.25 : 0.0, offx = sub_x == 2 && chroma_loc != 1 ? 0.25 : 0.0;
-    p.cy = FrAxis{sy, (double)sub_y, ori.my ? -offy : offy, H / sub_y};
-    p.cx = FrAxis{sx, (double)sub_x, ori.mx ? -offx : offx, W / sub_x};
+    p.cy = FrAxis{sy, (double)sub_y, p.miry ? -offy : offy, H / sub_y};
+    p.cx = FrAxis{sx, (double)sub_x, p.mirx ? -offx : offx, W / sub_x};
     const double kr = matrix == 0 ? 0.299 : matrix == 1 ? 0.2126 : 0.2627, kb = matrix == 0 ? 0.114 : matrix == 1 ? 0.0722 : 0.0593, kg = 1.0 - kr - kb;
     const double sc = (double)(1 << (depth - 8)), top = (double)((1 << depth) - 1);   // 2^(depth - 8); the largest code
     const double cs = full_range ? 255.0 / top : 255.0 / (224.0 * sc);
@@ -554,13 +420,6 @@ void fy_setup(FyParams& p, int H, int W, int sub_x, int sub_y, int depth, int ma
     p.kbcb = (float)(2.0 * (1.0 - kb) * cs);
     p.kgcb = (float)(-(2.0 * kb * (1.0 - kb) / kg) * cs);
     p.kgcr = (float)(-(2.0 * kr * (1.0 - kr) / kg) * cs);
-    for (int c = 0; c < 3; ++c) {
-        p.mean[c] = mean[c];
-        p.den[c] = std[c] + 1e-8f;
-    }
-    p.patches = (op16_t*)patches;
-    p.ldp = ldp;
-    p.image = image;
     if (m) {
         const double lw = m->peak_nits, lt = m->sdr_white_nits, max_lum = fy_pq_inv64(lt) / fy_pq_inv64(lw);
         static const double to709[9] = {1.6605, -0.5876, -0.0728, -0.1246, 1.1329, -0.0083, -0.0182, -0.1006, 1.1187};   // BT.2087
@@ -580,9 +439,30 @@ void fy_setup(FyParams& p, int H, int W, int sub_x, int sub_y, int depth, int ma
     p.NCY = fr_max_taps(p.cy, p.top, R);
 }
 
-// All entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m: the HDR entry's map (validated by it), else null;
-// orient: the oriented entry's code (validated by it), 0 for every other entry - the plan and the instances they always had.  tab: the scattered entry's host array
-// of s.n plane triples (s.y / cb / cr and the two frame strides are not read then), else null.
+// The colour tags of a planar or packed surface.
+int fy_check_colour(int matrix, int full_range, int chroma_loc, const char* who) {
+    RV_CHECK_ARG(matrix >= 0 && matrix <= 2, "%s: matrix %d (0 = BT.601, 1 = BT.709, 2 = BT.2020 non-constant luminance)", who, matrix);
+    RV_CHECK_ARG(full_range == 0 || full_range == 1, "%s: full_range %d (0 = studio, 1 = full)", who, full_range);
+    RV_CHECK_ARG(chroma_loc >= 0 && chroma_loc <= 2, "%s: chroma_loc %d (0 = left, 1 = centre, 2 = top-left)", who, chroma_loc);
+    return RV_OK;
+}
+
+// What an entry point checks before fy_run / fk_run: its orientation code (0 where it takes none) and its HDR map (m: null = SDR).
+int fy_check_orient_map(int32_t orient, const rv_hdr_map* m, const char* who) {
+    if (const int rc = fr_check_orient(orient, who)) return rc;
+    if (!m) return RV_OK;
+    RV_CHECK_ARG(m->transfer == FY_TRC_PQ || m->transfer == FY_TRC_HLG, "%s: transfer %d (1 = PQ, 2 = HLG)", who, m->transfer);
+    RV_CHECK_ARG(m->gamut == 0 || m->gamut == 1, "%s: gamut %d (0 = none, 1 = BT.2020 -> BT.709)", who, m->gamut);
+    RV_CHECK_ARG(isfinite(m->peak_nits) && m->peak_nits >= 1.0f && m->peak_nits <= 10000.0f, "%s: peak_nits %g outside 1 .. 10000", who,
+                 (double)m->peak_nits);
+    RV_CHECK_ARG(isfinite(m->sdr_white_nits) && m->sdr_white_nits >= 1.0f && m->sdr_white_nits <= 10000.0f, "%s: sdr_white_nits %g outside 1 .. 10000", who,
+                 (double)m->sdr_white_nits);
+    return RV_OK;
+}
+
+// All planar entry points: validate the surface, plan the tiles, launch.  `who` names the entry point in the messages; m (null = SDR) and orient (0 where the entry
+// takes none) are validated by the caller.  tab: the scattered entry's host array of s.n plane triples (s.y / cb / cr and the two frame strides are not read
+// then), else null.
 int fy_run(const rv_yuv_surface& s, const rv_surface_planes* tab, const rv_hdr_map* m, int32_t orient, int32_t R, int32_t patch, const float* mean, const float* std, void* patches, int64_t ldp, float* image,
            void* stream, const char* who) {
     const int sb = s.sample_bytes, H = s.H, W = s.W, n = s.n;
@@ -593,112 +473,72 @@ int fy_run(const rv_yuv_surface& s, const rv_surface_planes* tab, const rv_hdr_m
     RV_CHECK_ARG((s.sub_x == 2 && s.sub_y == 2) || (s.sub_x == 2 && s.sub_y == 1) || (s.sub_x == 1 && s.sub_y == 1),
                  "%s: sub_x, sub_y = %d, %d (2,2 = 4:2:0; 2,1 = 4:2:2; 1,1 = 4:4:4)", who, s.sub_x, s.sub_y);
     RV_CHECK_ARG(s.c_pix == sb || s.c_pix == 2 * sb, "%s: c_pix = %d (%d = planar, %d = interleaved)", who, s.c_pix, sb, 2 * sb);
-    RV_CHECK_ARG(s.matrix >= 0 && s.matrix <= 2, "%s: matrix %d (0 = BT.601, 1 = BT.709, 2 = BT.2020 non-constant luminance)", who, s.matrix);
-    RV_CHECK_ARG(s.full_range == 0 || s.full_range == 1, "%s: full_range %d (0 = studio, 1 = full)", who, s.full_range);
-    RV_CHECK_ARG(s.chroma_loc >= 0 && s.chroma_loc <= 2, "%s: chroma_loc %d (0 = left, 1 = centre, 2 = top-left)", who, s.chroma_loc);
-    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
-    RV_CHECK_ARG(H >= s.sub_y && W >= s.sub_x && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside %d x %d .. %d", who, H, W, s.sub_y,
-                 s.sub_x, FR_MAX_SIDE);
-    RV_CHECK_ARG(H % s.sub_y == 0 && W % s.sub_x == 0, "%s: frame size %d x %d is odd (a chroma sample covers %d x %d luma samples)", who, H, W, s.sub_y, s.sub_x);
-    RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
-    RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
-    if (n == 0) return RV_OK;
-    const uint8_t *y, *cb, *cr;
-    if (tab) {   // the whole table before anything is launched; frame 0 then stands for the batch: the other frames have its interleave relation
-        y = (const uint8_t*)tab[0].y, cb = (const uint8_t*)tab[0].cb, cr = (const uint8_t*)tab[0].cr;
-        for (int32_t f = 0; f < n; ++f) {
-            const uint8_t *ty = (const uint8_t*)tab[f].y, *tb = (const uint8_t*)tab[f].cb, *tr = (const uint8_t*)tab[f].cr;
-            RV_CHECK_ARG(ty && tb && tr, "%s: null plane in frame %d of %d (y %p, cb %p, cr %p)", who, f, n, tab[f].y, tab[f].cb, tab[f].cr);
-            RV_CHECK_ARG(sb == 1 || (((uintptr_t)ty | (uintptr_t)tb | (uintptr_t)tr) & 1) == 0,
-                         "%s: 16-bit planes must be aligned to 2 bytes: frame %d of %d (y %p, cb %p, cr %p)", who, f, n, tab[f].y, tab[f].cb, tab[f].cr);
-            RV_CHECK_ARG(s.c_pix == sb || tr - tb == cr - cb, "%s: c_pix = %d takes interleaved planes: cr - cb = %lld bytes in frame %d of %d, %lld in frame 0", who,
-                         s.c_pix, (long long)(tr - tb), f, n, (long long)(cr - cb));
-        }
-        RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes): frame 0 of %d",
-                     who, s.c_pix, sb, sb, n);
-        RV_CHECK_ARG(sb == 1 || (((uintptr_t)s.y_row_stride | (uintptr_t)s.c_row_stride) & 1) == 0, "%s: 16-bit row strides must be aligned to 2 bytes (%lld %lld)", who,
-                     (long long)s.y_row_stride, (long long)s.c_row_stride);
-    } else {
-        y = (const uint8_t*)s.y, cb = (const uint8_t*)s.cb, cr = (const uint8_t*)s.cr;
-        RV_CHECK_ARG(y && cb && cr, "%s: null plane (y %p, cb %p, cr %p)", who, s.y, s.cb, s.cr);
-        RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes)", who,
-                     s.c_pix, sb, sb);
-        RV_CHECK_ARG(sb == 1 || (((uintptr_t)y | (uintptr_t)cb | (uintptr_t)cr | (uintptr_t)s.y_frame_stride | (uintptr_t)s.y_row_stride |
-                                   (uintptr_t)s.c_frame_stride | (uintptr_t)s.c_row_stride) & 1) == 0,
-                     "%s: 16-bit planes and strides must be aligned to 2 bytes (y %p, cb %p, cr %p, strides %lld %lld %lld %lld)", who, s.y, s.cb, s.cr,
-                     (long long)s.y_frame_stride, (long long)s.y_row_stride, (long long)s.c_frame_stride, (long long)s.c_row_stride);
-    }
-    RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
-    RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
+    if (const int rc = fy_check_colour(s.matrix, s.full_range, s.chroma_loc, who)) return rc;
+    const uint8_t *y = nullptr, *cb = nullptr, *cr = nullptr;
+    const int rc = fr_check_common(
+        R, patch, n, mean, std, patches, ldp, image, who,
+        [&]() -> int {
+            RV_CHECK_ARG(H >= s.sub_y && W >= s.sub_x && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside %d x %d .. %d", who, H, W, s.sub_y,
+                         s.sub_x, FR_MAX_SIDE);
+            RV_CHECK_ARG(H % s.sub_y == 0 && W % s.sub_x == 0, "%s: frame size %d x %d is odd (a chroma sample covers %d x %d luma samples)", who, H, W, s.sub_y, s.sub_x);
+            return RV_OK;
+        },
+        [&]() -> int {
+            if (tab) {   // the whole table before anything is launched; frame 0 then stands for the batch: the other frames have its interleave relation
+                y = (const uint8_t*)tab[0].y, cb = (const uint8_t*)tab[0].cb, cr = (const uint8_t*)tab[0].cr;
+                for (int32_t f = 0; f < n; ++f) {
+                    const uint8_t *ty = (const uint8_t*)tab[f].y, *tb = (const uint8_t*)tab[f].cb, *tr = (const uint8_t*)tab[f].cr;
+                    RV_CHECK_ARG(ty && tb && tr, "%s: null plane in frame %d of %d (y %p, cb %p, cr %p)", who, f, n, tab[f].y, tab[f].cb, tab[f].cr);
+                    RV_CHECK_ARG(sb == 1 || (((uintptr_t)ty | (uintptr_t)tb | (uintptr_t)tr) & 1) == 0,
+                                 "%s: 16-bit planes must be aligned to 2 bytes: frame %d of %d (y %p, cb %p, cr %p)", who, f, n, tab[f].y, tab[f].cb, tab[f].cr);
+                    RV_CHECK_ARG(s.c_pix == sb || tr - tb == cr - cb, "%s: c_pix = %d takes interleaved planes: cr - cb = %lld bytes in frame %d of %d, %lld in frame 0", who,
+                                 s.c_pix, (long long)(tr - tb), f, n, (long long)(cr - cb));
+                }
+                RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes): frame 0 of %d",
+                             who, s.c_pix, sb, sb, n);
+                RV_CHECK_ARG(sb == 1 || (((uintptr_t)s.y_row_stride | (uintptr_t)s.c_row_stride) & 1) == 0, "%s: 16-bit row strides must be aligned to 2 bytes (%lld %lld)", who,
+                             (long long)s.y_row_stride, (long long)s.c_row_stride);
+            } else {
+                y = (const uint8_t*)s.y, cb = (const uint8_t*)s.cb, cr = (const uint8_t*)s.cr;
+                RV_CHECK_ARG(y && cb && cr, "%s: null plane (y %p, cb %p, cr %p)", who, s.y, s.cb, s.cr);
+                RV_CHECK_ARG(s.c_pix == sb || cr - cb == sb || cb - cr == sb, "%s: c_pix = %d takes interleaved planes (cr = cb + %d bytes or cb = cr + %d bytes)", who,
+                             s.c_pix, sb, sb);
+                RV_CHECK_ARG(sb == 1 || (((uintptr_t)y | (uintptr_t)cb | (uintptr_t)cr | (uintptr_t)s.y_frame_stride | (uintptr_t)s.y_row_stride |
+                                           (uintptr_t)s.c_frame_stride | (uintptr_t)s.c_row_stride) & 1) == 0,
+                             "%s: 16-bit planes and strides must be aligned to 2 bytes (y %p, cb %p, cr %p, strides %lld %lld %lld %lld)", who, s.y, s.cb, s.cr,
+                             (long long)s.y_frame_stride, (long long)s.y_row_stride, (long long)s.c_frame_stride, (long long)s.c_row_stride);
+            }
+            return RV_OK;
+        });
+    if (rc || n == 0) return rc;
     FyParams p{};
-    p.K = 3 * patch * patch;
-    p.Kp = (p.K + 127) / 128 * 128;
-    RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
-    p.y = tab ? nullptr : y;
-    p.yfs = tab ? 0 : s.y_frame_stride;
     p.yrs = s.y_row_stride;
-    p.cfs = tab ? 0 : s.c_frame_stride;
     p.crs = s.c_row_stride;
     p.cpix = s.c_pix;
     p.sbytes = sb;
     p.shift = s.msb_aligned ? 16 - s.depth : 0;
+    const uint8_t* c = cb;   // the Cb plane (planar) or the lower of the two interleaved planes
     if (s.c_pix == sb) {
         p.cplanes = 2;
-        p.c = cb;
-        p.cdelta = cr - cb;
     } else {
         p.cplanes = 1;
-        p.c = cb < cr ? cb : cr;
-        p.ocb = (int)(cb - p.c);
-        p.ocr = (int)(cr - p.c);
+        c = cb < cr ? cb : cr;
+        p.ocb = (int)(cb - c);
+        p.ocr = (int)(cr - c);
+    }
+    if (!tab) {   // a TAB = 1 instance takes every base, and planar Cr - Cb, from the table
+        p.y = y;
+        p.c = c;
+        p.yfs = s.y_frame_stride;
+        p.cfs = s.c_frame_stride;
+        p.cdelta = s.c_pix == sb ? cr - cb : 0;
     }
     fy_setup(p, H, W, s.sub_x, s.sub_y, s.depth, s.matrix, s.full_range, s.chroma_loc, m, orient, R, patch, mean, std, patches, ldp, image);
     FyParams best{};
-    double best_cost = 0.0;
-    bool have = false;
-    for (int ty = 16; ty >= 1; ty >>= 1)
-        for (int tx = 256; tx >= 1; tx >>= 1) {
-            const int tyc = ty < R ? ty : R, txc = tx < R ? tx : R;
-            double cost;
-            FyParams q = p;
-            if (fy_plan(q, tyc, txc, cost) && (!have || cost < best_cost)) best = q, best_cost = cost, have = true;
-        }
-    RV_CHECK_ARG(have, "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
-    const int lds = best.o_stage + fy_stage_bytes(best);
-    const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
-    if (tab) {   // launches of at most RV_FRAME_TABLE_MAX frames: the table and the output pointers move on, everything else is shared
-        best.y = best.c = nullptr;   // the kernel takes every base, and planar Cr - Cb, from the table
-        best.cdelta = 0;
-        const int64_t wmax = (int64_t)(n < RV_FRAME_TABLE_MAX ? n : RV_FRAME_TABLE_MAX) * best.bands * best.tilesX;
-        RV_CHECK_ARG(wmax < (1ll << 31), "%s: %lld workgroups per launch exceed one launch", who, (long long)wmax);
-        for (int32_t f0 = 0; f0 < n; f0 += RV_FRAME_TABLE_MAX) {
-            const int32_t nf = n - f0 < RV_FRAME_TABLE_MAX ? n - f0 : RV_FRAME_TABLE_MAX;
-            FyTab a{};
-            static_cast<FyParams&>(a) = best;
-            if (best.patches) a.patches = best.patches + (int64_t)f0 * best.g * best.g * ldp;
-            if (best.image) a.image = best.image + (int64_t)f0 * 3 * R * R;
-            for (int32_t f = 0; f < nf; ++f) a.fr[f] = tab[f0 + f];
-            if (const int rc = fy_launch_any(sb, m, oc, a, (int64_t)nf * best.bands * best.tilesX, lds, stream, who)) return rc;
-        }
-        return RV_OK;
-    }
-    const int64_t wgs = (int64_t)n * best.bands * best.tilesX;
-    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
-    if (!m) return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_NONE>(oc, best, wgs, lds, stream, who);
-    if (m->transfer == FY_TRC_PQ)
-        return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_PQ>(oc, best, wgs, lds, stream, who);
-    return sb == 1 ? fy_launch_ori<uint8_t, FY_TRC_HLG>(oc, best, wgs, lds, stream, who) : fy_launch_ori<uint16_t, FY_TRC_HLG>(oc, best, wgs, lds, stream, who);
-}
-
-// The HDR entry's checks of its map.
-int fy_check_map(const rv_hdr_map* m, const char* who) {
-    RV_CHECK_ARG(m->transfer == FY_TRC_PQ || m->transfer == FY_TRC_HLG, "%s: transfer %d (1 = PQ, 2 = HLG)", who, m->transfer);
-    RV_CHECK_ARG(m->gamut == 0 || m->gamut == 1, "%s: gamut %d (0 = none, 1 = BT.2020 -> BT.709)", who, m->gamut);
-    RV_CHECK_ARG(isfinite(m->peak_nits) && m->peak_nits >= 1.0f && m->peak_nits <= 10000.0f, "%s: peak_nits %g outside 1 .. 10000", who,
-                 (double)m->peak_nits);
-    RV_CHECK_ARG(isfinite(m->sdr_white_nits) && m->sdr_white_nits >= 1.0f && m->sdr_white_nits <= 10000.0f, "%s: sdr_white_nits %g outside 1 .. 10000", who,
-                 (double)m->sdr_white_nits);
-    return RV_OK;
+    RV_CHECK_ARG(fr_best_plan(p, R, fy_plan, best), "%s: %d x %d -> %d needs more filter taps than a workgroup's LDS holds", who, H, W, R);
+    const int lds = best.o_stage + fy_stage_bytes(best), oc = fr_orient_class(orient);
+    return fr_launch_all<FyTab>(
+        best, [](auto& a) -> auto& { return a; }, tab, n, [&](const auto& a, int64_t wgs) { return fy_dispatch(sb, m, oc, a, wgs, lds, stream, who); }, who);
 }
 
 // ---- packed surfaces (rv_packed_to_patches): YUY2 / UYVY / Y210, AYUV / VUYA / Y410 / XV36 ... -------------------------------------------------------------
@@ -714,13 +554,9 @@ struct FkParams {
     int SPU;                  // units of a staged row segment
 };
 
-__device__ inline float fk_sample(uint8_t v, int) { return (float)v; }
-__device__ inline float fk_sample(uint16_t v, int shift) { return (float)(v >> shift); }
-__device__ inline float fk_sample(uint32_t v, int shift) { return (float)((v >> shift) & 1023u); }
-
-// The argument block of the TAB = 1 packed instances: frame f of one launch starts where base[f] says (k.b.y / k.b.yfs unused).
+// The argument block of the TAB = 1 packed instances: frame f of one launch starts where tab[f] says (k.b.y / k.b.yfs unused).
 struct FkTab : FkParams {
-    const uint8_t* base[RV_FRAME_TABLE_MAX];
+    const void* tab[RV_FRAME_TABLE_MAX];
 };
 template <int TAB>
 using FkArgs = std::conditional_t<TAB != 0, FkTab, FkParams>;
@@ -750,16 +586,12 @@ __global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkA
     const int ty = min(p.TY, p.R - y0), tx = min(p.TX, p.R - x0);
 
     // ---- phase 0: tap tables (sub_y = 1: one row table serves luma and chroma) ---------------------------------------------------------
+    const int mirx = ORI == 0 ? 0 : p.mirx, miry = ORI == 0 ? 0 : p.miry;
     for (int i = tid; i < 2 * tx + ty; i += FR_THREADS) {
-        if constexpr (ORI == 0) {
-            if (i < tx) fy_tap_table(p.ax, x0 + p.left, p.NTX, p.NTXp, wx, xmin, nx, i);
-            else if (i < 2 * tx) fy_tap_table(p.cx, x0 + p.left, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
-            else fy_tap_table(p.ay, y0 + p.top, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
-        } else {
-            if (i < tx) fy_tap_table_m(p.ax, p.left, p.R, p.mirx, x0, p.NTX, p.NTXp, wx, xmin, nx, i);
-            else if (i < 2 * tx) fy_tap_table_m(p.cx, p.left, p.R, p.mirx, x0, p.NCX, p.NCXp, cwx, cxmin, cnx, i - tx);
-            else fy_tap_table_m(p.ay, p.top, p.R, p.miry, y0, p.NTY, p.NTY, wy, ymin, ny, i - 2 * tx);
-        }
+        int o = i;
+        if (o < tx) fr_tap_table(p.ax, p.left, p.R, mirx, x0 + o, p.NTX, wx + o * p.NTXp, xmin[o], nx[o]);
+        else if ((o -= tx) < tx) fr_tap_table(p.cx, p.left, p.R, mirx, x0 + o, p.NCX, cwx + o * p.NCXp, cxmin[o], cnx[o]);
+        else o -= tx, fr_tap_table(p.ay, p.top, p.R, miry, y0 + o, p.NTY, wy + o * p.NTY, ymin[o], ny[o]);
     }
     __syncthreads();
 
@@ -771,7 +603,7 @@ __global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkA
     constexpr int SB = (int)sizeof(S);
     const int ystep = k.unit / k.ppu, ys = ystep / SB, cs = k.unit / SB;   // bytes / samples between neighbouring Y samples; samples between chroma neighbours
     const uint8_t* src;
-    if constexpr (TAB != 0) src = k.base[f] + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
+    if constexpr (TAB != 0) src = (const uint8_t*)k.tab[f] + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
     else src = p.y + f * p.yfs + (int64_t)rmin * p.yrs + (int64_t)u0 * k.unit;
     for (int r0 = 0; r0 < nrows; r0 += FR_SR) {
         const int nr = min(FR_SR, nrows - r0);
@@ -788,7 +620,7 @@ __global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkA
                 const float* w = wx + col * p.NTXp;
                 const int n = min(nx[col], u1 * k.ppu - xmin[col]);
                 float a = 0.f;
-                for (int t = 0; t < n; ++t) a = fmaf(w[t], fk_sample(s[t * ys], k.shy), a);
+                for (int t = 0; t < n; ++t) a = fmaf(w[t], fr_sample(s[t * ys], k.shy), a);
                 q[0] = a;
             }
             {
@@ -800,8 +632,8 @@ __global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkA
                 for (int t = 0; t < n; ++t) {
                     const float wt = w[t];
                     const int o = t * cs;
-                    a0 = fmaf(wt, fk_sample(sb[o], k.shcb), a0);
-                    a1 = fmaf(wt, fk_sample(sr[o], k.shcr), a1);
+                    a0 = fmaf(wt, fr_sample(sb[o], k.shcb), a0);
+                    a1 = fmaf(wt, fr_sample(sr[o], k.shcr), a1);
                 }
                 q[p.TX] = a0;
                 q[2 * p.TX] = a1;
@@ -823,9 +655,9 @@ __global__ __launch_bounds__(FR_THREADS) void packed_to_patches_kernel(const FkA
             cb = fmaf(w[t], q[(t * 3 + 1) * p.TX], cb);
             cr = fmaf(w[t], q[(t * 3 + 2) * p.TX], cr);
         }
-        fy_colour_store<TRC, ORI>(p, yv, cb, cr, f, y0, yy, x0, col);
+        fy_colour_store<TRC, ORI>(p, yv, cb, cr, f, y0 + yy, x0 + col);
     }
-    fy_zero_pad<ORI>(p, f, y0, ty, x0, tx, tid);
+    fr_zero_pad<ORI>(p, f, y0, ty, x0, tx, tid);
 }
 
 // Largest number of units a tile of t coded outputs stages: those that hold its luma and its chroma column window.
@@ -846,7 +678,7 @@ int fk_max_units(const FkParams& k, int t) {
 }
 
 // Tile plan of the packed kernel: one staged segment of whole units (up to 8 bytes per pixel), three `inter` planes; false = over the LDS budget.
-bool fk_plan(FkParams& k, int ty, int tx, double& cost, int& lds) {
+bool fk_plan(FkParams& k, int ty, int tx, double& cost) {
     FyParams& p = k.b;
     p.TY = ty;
     p.TX = tx;
@@ -869,42 +701,23 @@ bool fk_plan(FkParams& k, int ty, int tx, double& cost, int& lds) {
     p.o_stage = (int)o;
     o += (int64_t)FR_SR * p.SEGY;
     if (o > FR_LDS_BUDGET) return false;
-    lds = (int)o;
     // the planar planner's measure: source rows of the horizontal pass per output row (one luma and two chroma planes), plus the staged pixels per output pixel
     const double fx = p.ax.scale > 1.0 ? p.ax.scale : 1.0;
     cost = (double)p.NRY / ty * (3.0 + (double)k.SPU * k.ppu / (tx * fx));
     return true;
 }
 
-template <typename S, int TRC, int ORI, int TAB = 0>
-int fk_launch(const FkArgs<TAB>& k, int64_t wgs, int lds, void* stream, const char* who) {
-    static std::atomic<uint64_t> have_lds{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(have_lds.load(std::memory_order_relaxed) & bit)) {
-        if (hipFuncSetAttribute((const void*)packed_to_patches_kernel<S, TRC, ORI, TAB>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_LDS_BUDGET) != hipSuccess) {
-            rv_set_error("%s: cannot reserve %d bytes of LDS", who, FR_LDS_BUDGET);
-            return RV_ERR_HIP;
-        }
-        have_lds.fetch_or(bit, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((packed_to_patches_kernel<S, TRC, ORI, TAB>), dim3((unsigned)wgs), dim3(FR_THREADS), lds, as_stream(stream), k);
-    RV_CHECK_LAUNCH("packed_to_patches");
-    return RV_OK;
-}
-
-template <typename S, int TRC, int TAB = 0>
-int fk_launch_ori(int ori_class, const FkArgs<TAB>& k, int64_t wgs, int lds, void* stream, const char* who) {
-    if (ori_class == 0) return fk_launch<S, TRC, 0, TAB>(k, wgs, lds, stream, who);
-    return ori_class == 1 ? fk_launch<S, TRC, 1, TAB>(k, wgs, lds, stream, who) : fk_launch<S, TRC, 2, TAB>(k, wgs, lds, stream, who);
-}
-
-template <typename S, int TAB = 0>
-int fk_launch_trc(const rv_hdr_map* m, int ori_class, const FkArgs<TAB>& k, int64_t wgs, int lds, void* stream, const char* who) {
-    if (!m) return fk_launch_ori<S, FY_TRC_NONE, TAB>(ori_class, k, wgs, lds, stream, who);
-    return m->transfer == FY_TRC_PQ ? fk_launch_ori<S, FY_TRC_PQ, TAB>(ori_class, k, wgs, lds, stream, who)
-                                    : fk_launch_ori<S, FY_TRC_HLG, TAB>(ori_class, k, wgs, lds, stream, who);
+// One launch of the packed instance for a sample size, a transfer (m: null = SDR) and an orientation class, on the contiguous block (FkParams) or the table form (FkTab).
+template <class Args>
+int fk_dispatch(int sb, const rv_hdr_map* m, int oc, const Args& a, int64_t wgs, int lds, void* stream, const char* who) {
+    return fr_pick<3>(sb >> 1, [&](auto S) {
+        return fr_pick<3>(m ? m->transfer : FY_TRC_NONE, [&](auto TRC) {
+            return fr_pick<3>(oc, [&](auto ORI) {
+                return fr_launch<packed_to_patches_kernel<FrSample<decltype(S)::value>, decltype(TRC)::value, decltype(ORI)::value, std::is_same_v<Args, FkTab>>>(
+                    a, wgs, lds, stream, who, "packed_to_patches");
+            });
+        });
+    });
 }
 
 // The packed entry: validate the surface (the header has the list), plan, launch.  m and orient are validated by the caller.  tab: the scattered entry's host array
@@ -932,36 +745,34 @@ int fk_run(const rv_packed_surface& s, const void* const* tab, const rv_hdr_map*
                      "%s: y_off, cb_off, cr_off = %d, %d, %d (distinct sample offsets inside the %d-byte unit%s)", who, oy, ocb, ocr, unit,
                      ppu == 2 ? "; the second Y sample lies half a unit behind the first" : "");
     }
-    RV_CHECK_ARG(s.matrix >= 0 && s.matrix <= 2, "%s: matrix %d (0 = BT.601, 1 = BT.709, 2 = BT.2020 non-constant luminance)", who, s.matrix);
-    RV_CHECK_ARG(s.full_range == 0 || s.full_range == 1, "%s: full_range %d (0 = studio, 1 = full)", who, s.full_range);
-    RV_CHECK_ARG(s.chroma_loc >= 0 && s.chroma_loc <= 2, "%s: chroma_loc %d (0 = left, 1 = centre, 2 = top-left)", who, s.chroma_loc);
-    RV_CHECK_ARG(R >= 1 && patch >= 1 && R % patch == 0, "%s: R = %d is not a multiple of patch = %d", who, R, patch);
-    RV_CHECK_ARG(H >= 1 && W >= ppu && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 x %d .. %d", who, H, W, ppu, FR_MAX_SIDE);
-    RV_CHECK_ARG(W % ppu == 0, "%s: frame width W = %d is odd (a unit covers %d pixels)", who, W, ppu);
-    RV_CHECK_ARG(R <= FR_MAX_SIDE, "%s: R = %d above %d", who, R, FR_MAX_SIDE);
-    RV_CHECK_ARG(n >= 0, "%s: n = %d", who, n);
-    if (n == 0) return RV_OK;
-    if (tab) {   // the whole table before anything is launched
-        for (int32_t f = 0; f < n; ++f) {
-            RV_CHECK_ARG(tab[f], "%s: null base pointer for frame %d of %d", who, f, n);
-            RV_CHECK_ARG(((uintptr_t)tab[f] & (uintptr_t)(sb - 1)) == 0, "%s: %d-bit words: the base of frame %d of %d must be aligned to %d bytes (%p)", who, 8 * sb, f,
-                         n, sb, tab[f]);
-        }
-        RV_CHECK_ARG(((uintptr_t)s.row_stride & (uintptr_t)(sb - 1)) == 0, "%s: %d-bit words: row_stride %lld must be aligned to %d bytes", who, 8 * sb,
-                     (long long)s.row_stride, sb);
-    } else {
-        RV_CHECK_ARG(s.base, "%s: null base pointer", who);
-        RV_CHECK_ARG((((uintptr_t)s.base | (uintptr_t)s.frame_stride | (uintptr_t)s.row_stride) & (uintptr_t)(sb - 1)) == 0,
-                     "%s: %d-bit words: base and strides must be aligned to %d bytes (base %p, frame_stride %lld, row_stride %lld)", who, 8 * sb, sb, s.base,
-                     (long long)s.frame_stride, (long long)s.row_stride);
-    }
-    RV_CHECK_ARG(patches || image, "%s: both outputs null", who);
-    RV_CHECK_ARG(mean && std, "%s: null mean / std", who);
+    if (const int rc = fy_check_colour(s.matrix, s.full_range, s.chroma_loc, who)) return rc;
+    const int rc = fr_check_common(
+        R, patch, n, mean, std, patches, ldp, image, who,
+        [&]() -> int {
+            RV_CHECK_ARG(H >= 1 && W >= ppu && H <= FR_MAX_SIDE && W <= FR_MAX_SIDE, "%s: frame size %d x %d outside 1 x %d .. %d", who, H, W, ppu, FR_MAX_SIDE);
+            RV_CHECK_ARG(W % ppu == 0, "%s: frame width W = %d is odd (a unit covers %d pixels)", who, W, ppu);
+            return RV_OK;
+        },
+        [&]() -> int {
+            if (tab) {   // the whole table before anything is launched
+                for (int32_t f = 0; f < n; ++f) {
+                    RV_CHECK_ARG(tab[f], "%s: null base pointer for frame %d of %d", who, f, n);
+                    RV_CHECK_ARG(((uintptr_t)tab[f] & (uintptr_t)(sb - 1)) == 0, "%s: %d-bit words: the base of frame %d of %d must be aligned to %d bytes (%p)", who, 8 * sb, f,
+                                 n, sb, tab[f]);
+                }
+                RV_CHECK_ARG(((uintptr_t)s.row_stride & (uintptr_t)(sb - 1)) == 0, "%s: %d-bit words: row_stride %lld must be aligned to %d bytes", who, 8 * sb,
+                             (long long)s.row_stride, sb);
+            } else {
+                RV_CHECK_ARG(s.base, "%s: null base pointer", who);
+                RV_CHECK_ARG((((uintptr_t)s.base | (uintptr_t)s.frame_stride | (uintptr_t)s.row_stride) & (uintptr_t)(sb - 1)) == 0,
+                             "%s: %d-bit words: base and strides must be aligned to %d bytes (base %p, frame_stride %lld, row_stride %lld)", who, 8 * sb, sb, s.base,
+                             (long long)s.frame_stride, (long long)s.row_stride);
+            }
+            return RV_OK;
+        });
+    if (rc || n == 0) return rc;
     FkParams k{};
     FyParams& p = k.b;
-    p.K = 3 * patch * patch;
-    p.Kp = (p.K + 127) / 128 * 128;
-    RV_CHECK_ARG(!patches || ldp >= p.Kp, "%s: ldp = %lld below Kp = %d", who, (long long)ldp, p.Kp);
     p.y = tab ? nullptr : (const uint8_t*)s.base;
     p.yfs = tab ? 0 : s.frame_stride;
     p.yrs = s.row_stride;
@@ -976,41 +787,11 @@ int fk_run(const rv_packed_surface& s, const void* const* tab, const rv_hdr_map*
     }
     fy_setup(p, H, W, ppu, 1, s.depth, s.matrix, s.full_range, s.chroma_loc, m, orient, R, patch, mean, std, patches, ldp, image);
     FkParams best{};
-    double best_cost = 0.0;
-    int best_lds = 0;
-    bool have = false;
-    for (int ty = 16; ty >= 1; ty >>= 1)
-        for (int tx = 256; tx >= 1; tx >>= 1) {
-            const int tyc = ty < R ? ty : R, txc = tx < R ? tx : R;
-            double cost;
-            int lds;
-            FkParams q = k;
-            if (fk_plan(q, tyc, txc, cost, lds) && (!have || cost < best_cost)) best = q, best_cost = cost, best_lds = lds, have = true;
-        }
-    RV_CHECK_ARG(have, "%s: %d x %d -> %d at %d bytes per pixel needs more filter taps and staging than a workgroup's LDS holds", who, H, W, R, unit / ppu);
-    const int oc = orient == 0 ? 0 : fr_orient(orient).tr ? 2 : 1;
-    if (tab) {   // launches of at most RV_FRAME_TABLE_MAX frames: the table and the output pointers move on, everything else is shared
-        const int64_t wmax = (int64_t)(n < RV_FRAME_TABLE_MAX ? n : RV_FRAME_TABLE_MAX) * best.b.bands * best.b.tilesX;
-        RV_CHECK_ARG(wmax < (1ll << 31), "%s: %lld workgroups per launch exceed one launch", who, (long long)wmax);
-        for (int32_t f0 = 0; f0 < n; f0 += RV_FRAME_TABLE_MAX) {
-            const int32_t nf = n - f0 < RV_FRAME_TABLE_MAX ? n - f0 : RV_FRAME_TABLE_MAX;
-            FkTab a{};
-            static_cast<FkParams&>(a) = best;
-            if (best.b.patches) a.b.patches = best.b.patches + (int64_t)f0 * best.b.g * best.b.g * ldp;
-            if (best.b.image) a.b.image = best.b.image + (int64_t)f0 * 3 * R * R;
-            for (int32_t f = 0; f < nf; ++f) a.base[f] = (const uint8_t*)tab[f0 + f];
-            const int64_t w = (int64_t)nf * best.b.bands * best.b.tilesX;
-            const int rc = sb == 1   ? fk_launch_trc<uint8_t, 1>(m, oc, a, w, best_lds, stream, who)
-                           : sb == 2 ? fk_launch_trc<uint16_t, 1>(m, oc, a, w, best_lds, stream, who)
-                                     : fk_launch_trc<uint32_t, 1>(m, oc, a, w, best_lds, stream, who);
-            if (rc) return rc;
-        }
-        return RV_OK;
-    }
-    const int64_t wgs = (int64_t)n * best.b.bands * best.b.tilesX;
-    RV_CHECK_ARG(wgs < (1ll << 31), "%s: %lld workgroups (n = %d) exceed one launch", who, (long long)wgs, n);
-    if (sb == 1) return fk_launch_trc<uint8_t>(m, oc, best, wgs, best_lds, stream, who);
-    return sb == 2 ? fk_launch_trc<uint16_t>(m, oc, best, wgs, best_lds, stream, who) : fk_launch_trc<uint32_t>(m, oc, best, wgs, best_lds, stream, who);
+    RV_CHECK_ARG(fr_best_plan(k, R, fk_plan, best), "%s: %d x %d -> %d at %d bytes per pixel needs more filter taps and staging than a workgroup's LDS holds", who, H, W, R,
+                 unit / ppu);
+    const int lds = best.b.o_stage + FR_SR * best.b.SEGY, oc = fr_orient_class(orient);
+    return fr_launch_all<FkTab>(
+        best, [](auto& a) -> auto& { return a.b; }, tab, n, [&](const auto& a, int64_t wgs) { return fk_dispatch(sb, m, oc, a, wgs, lds, stream, who); }, who);
 }
 
 }  // namespace
@@ -1027,7 +808,7 @@ extern "C" int rv_yuv_surface_to_patches_hdr(const rv_yuv_surface* s, const rv_h
     const char* who = "rv_yuv_surface_to_patches_hdr";
     RV_CHECK_ARG(s, "%s: null surface", who);
     RV_CHECK_ARG(m, "%s: null map", who);
-    if (const int rc = fy_check_map(m, who)) return rc;
+    if (const int rc = fy_check_orient_map(0, m, who)) return rc;
     return fy_run(*s, nullptr, m, 0, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
@@ -1037,9 +818,7 @@ extern "C" int rv_yuv_surface_to_patches_oriented(const rv_yuv_surface* s, const
                                                   const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
     const char* who = "rv_yuv_surface_to_patches_oriented";
     RV_CHECK_ARG(s, "%s: null surface", who);
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
-    if (m)
-        if (const int rc = fy_check_map(m, who)) return rc;
+    if (const int rc = fy_check_orient_map(orient, m, who)) return rc;
     return fy_run(*s, nullptr, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
@@ -1079,9 +858,7 @@ extern "C" int rv_packed_to_patches(const rv_packed_surface* s, const rv_hdr_map
                                     void* patches, int64_t ldp, float* image, void* stream) {
     const char* who = "rv_packed_to_patches";
     RV_CHECK_ARG(s, "%s: null surface", who);
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
-    if (m)
-        if (const int rc = fy_check_map(m, who)) return rc;
+    if (const int rc = fy_check_orient_map(orient, m, who)) return rc;
     return fk_run(*s, nullptr, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
 
@@ -1091,9 +868,7 @@ extern "C" int rv_yuv_surfaces_to_patches(const rv_yuv_surface* s, const rv_surf
                                           const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
     const char* who = "rv_yuv_surfaces_to_patches";
     RV_CHECK_ARG(s, "%s: null surface", who);
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
-    if (m)
-        if (const int rc = fy_check_map(m, who)) return rc;
+    if (const int rc = fy_check_orient_map(orient, m, who)) return rc;
     RV_CHECK_ARG(planes || s->n <= 0, "%s: null array of plane pointers (n = %d)", who, s->n);
     return fy_run(*s, planes, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
@@ -1103,9 +878,7 @@ extern "C" int rv_packed_surfaces_to_patches(const rv_packed_surface* s, const v
                                              const float mean[3], const float std[3], void* patches, int64_t ldp, float* image, void* stream) {
     const char* who = "rv_packed_surfaces_to_patches";
     RV_CHECK_ARG(s, "%s: null surface", who);
-    RV_CHECK_ARG(orient >= 0 && orient <= 7, "%s: orient %d (0 .. 7: bit 0 transpose, bit 1 mirror x, bit 2 mirror y)", who, orient);
-    if (m)
-        if (const int rc = fy_check_map(m, who)) return rc;
+    if (const int rc = fy_check_orient_map(orient, m, who)) return rc;
     RV_CHECK_ARG(bases || s->n <= 0, "%s: null array of base pointers (n = %d)", who, s->n);
     return fk_run(*s, bases, m, orient, R, patch, mean, std, patches, ldp, image, stream, who);
 }
