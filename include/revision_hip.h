@@ -230,9 +230,11 @@ int rv_sine_pos(float* pos, int32_t T, int32_t d, void* stream);
  * q [B,Lq,H,dh] bf16 (q_row_stride, q_batch_stride in elements; heads contiguous dh chunks);
  * k [.. Lk ..] bf16 (k_row_stride, k_batch_stride, k_head_stride); vt = V^T [dh, Lk] per (b,h)
  * (vt_batch_stride, vt_head_stride, vt_d_stride); out [B,Lq,H*dh] bf16 (o_row_stride, o_batch_stride).
- * causal: query i (absolute position q_pos0 + i) sees keys <= its position.
+ * causal: query i (absolute position q_pos0 + i) sees keys <= its position; q_pos0 >= 0 (a negative one - query 0 in front of
+ * key 0, a row without any key - is refused with RV_ERR_ARG).
  * key_pad: u8 [B/kv_batch_div,Lk] (1 = ignore) or NULL (nn.MultiheadAttention key_padding_mask,
- * transformer.py:293-294).  Query batch b reads K/V batch b / kv_batch_div (one text for v segments).
+ * transformer.py:293-294).  Query batch b reads K/V batch b / kv_batch_div (one text for v segments): B must be a multiple of
+ * kv_batch_div (a remainder would read a key batch that does not exist: refused with RV_ERR_ARG).
  * A key batch whose keys are ALL padded has no key: its query rows come out as zeros (nn.MultiheadAttention yields NaN there).
  * V^T rows (vt_d_stride) must be padded with finite values to a multiple of 32 keys. */
 int rv_attention(const void* q, int64_t q_row_stride, int64_t q_batch_stride, const void* k, int64_t k_row_stride,

@@ -876,5 +876,8 @@ extern "C" int rv_attention(const void* q, int64_t q_row_stride, int64_t q_batch
     AttnArgs a{q, q_row_stride, q_batch_stride, k, k_row_stride, k_batch_stride, k_head_stride, vt, vt_batch_stride,
                vt_head_stride, vt_d_stride, out, o_row_stride, o_batch_stride, key_pad, B, H, dh, Lq, Lk, causal, q_pos0,
                kv_batch_div, scale};
+    // (the internal callers never ask for either; a remainder batch would read a key batch that does not exist, a query in front of key 0 has no key)
+    RV_CHECK_ARG(kv_batch_div <= 0 || B % kv_batch_div == 0, "attention: B = %d is not a multiple of kv_batch_div = %d", B, kv_batch_div);
+    RV_CHECK_ARG(!causal || q_pos0 >= 0, "attention: causal with q_pos0 = %d < 0 (query 0 would see no key)", q_pos0);
     return k_attention(a, as_stream(stream));
 }
