@@ -631,8 +631,8 @@ int rv_topk_pool(const void* video, int dtype, const float* text, int32_t Nv, in
  * Two launches do it for all proposals: the features are read ONCE into a per-frame cosine row, then every span works on that row.  Durations and
  * windows stay on the device (the reference converts both to int32 on the host).
  * Arithmetic: 16-bit features are read as stored and every operation is f32, as in the other score kernels; the reference run in bf16 does bf16
- * arithmetic instead (its f32 run is what the tests compare to).  Not taken: several texts per video, per-frame masking (the mask only gives the duration,
- * as in the reference). */
+ * arithmetic instead (its f32 run is what the tests compare to).  Not taken: per-frame masking (the mask only gives the duration, as in the
+ * reference).  Several texts per video: the two _multi entries below. */
 
 /* video f32 / 16-bit operands [B,L,d] contiguous, text f32 [B,d] -> out f32 [B,L]: out[b,l] = <f_l, t_b> / (|f_l| |t_b|)  (similarity.py:36, :61-64 for
  * every frame).  One pass over the features; 16-byte loads when d is a multiple of 16 B / element size and the base is 16-byte aligned.  A zero frame
@@ -650,6 +650,25 @@ int rv_frame_cosine(const void* video, int dtype, const float* text, int32_t B, 
  * outside int32 saturate.  No read of sims lies outside [b L + lo, b L + hi). */
 int rv_span_scores(const float* sims, const float* spans, const float* mask, int32_t B, int32_t L, int32_t N, int32_t mode, int32_t k,
                    float temperature, float* scores, int32_t* windows, void* stream);
+
+/* Q texts per video (similarity.py:24-69 for every query of a video in one pass over its features).
+ * video f32 / 16-bit operands [B,L,d] contiguous, text f32 [B,Q,d], text_unit f32 [B,Q,d] (workspace: receives text / |text|) -> out f32 [B,Q,L]:
+ * out[b,q,l] = <f_bl, t_bq> / (|f_bl| |t_bq|), each query's row contiguous for rv_span_scores_multi.  Order of operations: the texts are normalised
+ * (a small launch of its own), then the dot products on the f32-input MFMA (16-bit features converted in registers, which is exact; per element a
+ * k-ordered fmaf chain, no wider accumulation), then the division by |f|, whose square comes from the same loads.  The features are read from global
+ * memory once per call for up to 128 queries (once per 128 beyond).  16-byte loads when d is a multiple of 16 B / element size and video and text_unit
+ * are 16-byte aligned, an element-wise path otherwise.  A query's row does not depend on Q, on its slot or on the other texts, bit for bit.
+ * A zero text gives a NaN row for that query only; a zero frame NaN in column l of every query; a NaN feature of frame l NaN in column l only.
+ * B * Q <= 65535; no limit on L or d. */
+int rv_frame_cosine_multi(const void* video, int dtype, const float* text, int32_t B, int32_t Q, int32_t L, int32_t d, float* text_unit, float* out,
+                          void* stream);
+
+/* rv_span_scores for Q queries per video: sims f32 [B,Q,L] (rv_frame_cosine_multi's rows), spans f32 [B,Q,N,2] (each query's own proposals),
+ * mask f32 [B,L] (one row, hence one duration, per video) -> scores f32 [B,Q,N], windows i32 [B,Q,N,2] (optional, may be NULL).  The same kernel
+ * body as rv_span_scores, so every rule above holds per (b, q) row and a row's result equals rv_span_scores' on that row bit for bit.
+ * B * Q <= 65535. */
+int rv_span_scores_multi(const float* sims, const float* spans, const float* mask, int32_t B, int32_t Q, int32_t L, int32_t N, int32_t mode, int32_t k,
+                         float temperature, float* scores, int32_t* windows, void* stream);
 
 /* _attention_pooling (similarity.py:96-113): video f32 / 16-bit operands [Nv,T,d], text f32 [Nt,d] -> out f32 [Nv,Nt,d] =
  * sum_t softmax_t(<f_t, text_j> / temperature) f_t.  temperature finite and not 0 (negative values are taken as given); (d + T) * 4 + 256 bytes of LDS

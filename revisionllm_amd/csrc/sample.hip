@@ -5,6 +5,7 @@
 //   rv_topk_cosine    column-normalised top-k pooled cosine score (eval_nlq_retrieval_e2e2.py:380-386)
 //   rv_frame_cosine   per-frame cosine row of a whole video against its text CLS   } forward_clip_matching / _get_predicted_proposal_feat
 //   rv_span_scores    (centre, width) proposals -> windows -> top-k / softmax score  } (eval/similarity.py:24-69) without a host round trip
+//   rv_span_scores_multi  the same kernel over [B,Q] rows of similarities and proposals that share their video's mask row (after rv_frame_cosine_multi of similarity.hip)
 //   rv_attn_pool      _attention_pooling (eval/similarity.py:96-113)
 #include "kernels.h"
 
@@ -946,7 +947,9 @@ __device__ __forceinline__ int sat_i32(float v) {
     return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
 }
 
-// One wave per span (4 spans per block, all of video blockIdx.y).  The block adds the video's mask row up first (duration; 0 / 1 masks: exact in any
+// One wave per span (4 spans per block, all of row blockIdx.y).  A row is a video (rpm = 1, rv_span_scores) or one of a video's rpm queries
+// (rv_span_scores_multi): similarities, spans and outputs are indexed by the row, the mask - and hence the duration - by row / rpm ("rows per mask").
+// The block adds the row's mask row up first (duration; 0 / 1 masks: exact in any
 // order up to 2^24 frames; every block of a video repeats that sum - N / 4 reads of an L2-resident row of 4 L bytes - which is the price of keeping the
 // matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row:
 //   x1 = c - 0.5 w, x2 = c + 0.5 w, p = x * duration (every operation rounded to f32 on its own: no contraction), start = max(0, int(floor(p1))),
@@ -957,11 +960,12 @@ __device__ __forceinline__ int sat_i32(float v) {
 // window (-1, -1).
 template <int MODE>
 __global__ __launch_bounds__(256) void span_scores_kernel(const float* __restrict__ sims, const float* __restrict__ spans, const float* __restrict__ mask,
-                                                          int L, int N, int k, float tau, float* __restrict__ scores, int32_t* __restrict__ windows) {
+                                                          int rpm, int L, int N, int k, float tau, float* __restrict__ scores,
+                                                          int32_t* __restrict__ windows) {
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     {
-        const float* m = mask + (int64_t)b * L;
+        const float* m = mask + (int64_t)(b / rpm) * L;
         float s = 0.f;
         for (int l = tid; l < L; l += 256) s += m[l];
         s = wave_sum(s);
@@ -1181,12 +1185,29 @@ extern "C" int rv_span_scores(const float* sims, const float* spans, const float
     const dim3 grid((unsigned)cdiv(N, 4), B);
     if (mode == 0) {
         RV_CHECK_ARG(k >= 1 && k <= KCAP, "rv_span_scores: k=%d must be in [1, %d]", k, KCAP);
-        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, L, N, k, 1.0f, scores, windows);
+        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, 1, L, N, k, 1.0f, scores, windows);
     } else {
         RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_span_scores: temperature must be finite and not 0");
-        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, L, N, k, temperature, scores, windows);
+        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, 1, L, N, k, temperature, scores, windows);
     }
     RV_CHECK_LAUNCH("rv_span_scores");
+    return RV_OK;
+}
+
+extern "C" int rv_span_scores_multi(const float* sims, const float* spans, const float* mask, int32_t B, int32_t Q, int32_t L, int32_t N, int32_t mode,
+                                    int32_t k, float temperature, float* scores, int32_t* windows, void* stream) {
+    RV_CHECK_ARG(sims && spans && mask && scores && B > 0 && Q > 0 && L > 0 && N > 0, "rv_span_scores_multi: bad arguments");
+    RV_CHECK_ARG(mode == 0 || mode == 1, "rv_span_scores_multi: mode=%d must be 0 (top-k) or 1 (attention)", mode);
+    RV_CHECK_ARG((int64_t)B * Q <= 65535, "rv_span_scores_multi: at most 65535 (video, query) rows per launch (B=%d, Q=%d)", B, Q);
+    const dim3 grid((unsigned)cdiv(N, 4), (unsigned)(B * Q));
+    if (mode == 0) {
+        RV_CHECK_ARG(k >= 1 && k <= KCAP, "rv_span_scores_multi: k=%d must be in [1, %d]", k, KCAP);
+        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, Q, L, N, k, 1.0f, scores, windows);
+    } else {
+        RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_span_scores_multi: temperature must be finite and not 0");
+        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, Q, L, N, k, temperature, scores, windows);
+    }
+    RV_CHECK_LAUNCH("rv_span_scores_multi");
     return RV_OK;
 }
 

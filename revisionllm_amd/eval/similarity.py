@@ -9,8 +9,11 @@ Proposal-query matching: the reference walks the proposals in a Python double lo
 device -> host copies of the window bounds).  A proposal's score is the sum of the top-k cosines of its window, so here the features are read once into a
 per-frame cosine row and one more launch scores every span on that row; durations and windows never leave the device.  Keywords after ``is_groundtruth``
 are this build's: ``k`` (the reference's 3), ``pooling`` ("topk", or "attention" = the alternative commented out at similarity.py:63 with ``temperature``),
-``return_windows``.  Not taken: the reference's bf16 arithmetic (16-bit features are read as stored, all arithmetic is f32), several texts per video, per-frame
-masking (as in the reference the mask only gives each video's duration)."""
+``return_windows``.  Not taken: the reference's bf16 arithmetic (16-bit features are read as stored, all arithmetic is f32), per-frame
+masking (as in the reference the mask only gives each video's duration).
+
+Several texts per video (this build's addition, no counterpart in the reference): ``forward_clip_matching_multi`` scores Q queries, each with its own
+proposals, against one pass over their video's features (``rv_frame_cosine_multi`` on the f32-input MFMA + ``rv_span_scores_multi``)."""
 import math
 
 import torch
@@ -75,17 +78,25 @@ def _attention_pooling(text_embeds, video_embeds, temperature):
     return ops.attn_pool(text, video, temperature).to(device=home, dtype=dt if dt.is_floating_point else torch.float32)
 
 
-def _match(who, text, video, mask, proposal, k, pooling, temperature, return_windows):
+def _match(who, text, video, mask, proposal, k, pooling, temperature, return_windows, multi=False):
     if proposal is None:
         raise TypeError(f"{who}: proposal is None (the reference fails there too: it has no default proposals)")
     for name, t in (("text", text), ("video", video), ("mask", mask), ("proposal", proposal)):
         if not torch.is_tensor(t):
             raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
-    if video.dim() != 3 or text.dim() != 2 or text.shape != (video.shape[0], video.shape[2]):
+    if multi:
+        if video.dim() != 3 or text.dim() != 3 or text.shape[0] != video.shape[0] or text.shape[2] != video.shape[2]:
+            raise ValueError(f"{who}: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, Q, d] and [B, L, d])")
+        if text.shape[1] == 0:
+            raise ValueError(f"{who}: no text in {tuple(text.shape)}")
+    elif video.dim() != 3 or text.dim() != 2 or text.shape != (video.shape[0], video.shape[2]):
         raise ValueError(f"{who}: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, d] and [B, L, d])")
     if mask.shape != video.shape[:2]:
         raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected [B, L])")
-    if proposal.dim() != 3 or proposal.shape[0] != video.shape[0] or proposal.shape[2] != 2:
+    if multi:
+        if proposal.dim() != 4 or proposal.shape[:2] != text.shape[:2] or proposal.shape[3] != 2:
+            raise ValueError(f"{who}: proposal {tuple(proposal.shape)} (expected [B={text.shape[0]}, Q={text.shape[1]}, N, 2] rows of (centre, width))")
+    elif proposal.dim() != 3 or proposal.shape[0] != video.shape[0] or proposal.shape[2] != 2:
         raise ValueError(f"{who}: proposal {tuple(proposal.shape)} (expected [B={video.shape[0]}, N, 2] rows of (centre, width))")
     if min(video.shape) == 0:
         raise ValueError(f"{who}: empty video {tuple(video.shape)}")
@@ -103,9 +114,10 @@ def _match(who, text, video, mask, proposal, k, pooling, temperature, return_win
     home, dt = video.device, video.dtype
     dev = _device_of(video, who)
     video = _features_up(video, dev)
-    sims = ops.frame_cosine(ops.h2d(text, dev).float(), video)
-    out = ops.span_scores(sims, ops.h2d(proposal, dev).float(), ops.h2d(mask, dev).float(), k=k, pooling=pooling, temperature=temperature,
-                          return_windows=return_windows)
+    cosine, scores = (ops.frame_cosine_multi, ops.span_scores_multi) if multi else (ops.frame_cosine, ops.span_scores)
+    sims = cosine(ops.h2d(text, dev).float(), video)
+    out = scores(sims, ops.h2d(proposal, dev).float(), ops.h2d(mask, dev).float(), k=k, pooling=pooling, temperature=temperature,
+                 return_windows=return_windows)
     if return_windows:
         return out[0].to(device=home, dtype=dt), out[1].to(device=home)
     return out.to(device=home, dtype=dt)
@@ -120,6 +132,18 @@ def forward_clip_matching(src_cls_txt, src_vid_appear, src_vid_appear_mask, prop
     when the inputs live on the device.  ``return_windows``: also the i32 [B, N, 2] windows
     (lo, hi) the scores were taken over.  ``is_groundtruth`` is accepted and unused, as in the reference."""
     return _match("forward_clip_matching", src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, k, pooling, temperature, return_windows)
+
+
+def forward_clip_matching_multi(src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal=None, is_groundtruth=False, *, k=3, pooling="topk",
+                                temperature=0.01, return_windows=False):
+    """``forward_clip_matching`` for Q queries per video: src_cls_txt [B, Q, d], src_vid_appear [B, L, d], src_vid_appear_mask [B, L], proposal
+    [B, Q, N, 2] (each query's own (centre, width) rows) -> [B, Q, N], with ``return_windows`` also the i32 [B, Q, N, 2] windows.  ``out[:, q]`` is
+    ``forward_clip_matching(src_cls_txt[:, q], src_vid_appear, src_vid_appear_mask, proposal[:, q])`` within the cosine bound (the windows exactly),
+    but the features are read once for all Q texts: three launches (text norms, cosine rows on the f32-input MFMA, spans), no synchronisation, and the
+    video is not copied.  A query's scores do not depend on Q, on its slot or on the other texts, bit for bit; Q = 1 takes the same kernels (callers
+    with one text per video keep ``forward_clip_matching``).  Dtype and device handling, keywords and refusals are ``forward_clip_matching``'s."""
+    return _match("forward_clip_matching_multi", src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, k, pooling, temperature, return_windows,
+                  multi=True)
 
 
 def _get_predicted_proposal_feat(src_vid_appear, src_vid_appear_mask, pred_proposal, text_cls_features):

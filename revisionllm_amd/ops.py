@@ -349,6 +349,44 @@ def span_scores(sims, spans, mask, k=3, pooling="topk", temperature=0.01, return
     return (scores, win) if return_windows else scores
 
 
+def frame_cosine_multi(text, video):
+    """``frame_cosine`` for Q texts per video: text f32 [B,Q,d], video [B,L,d] (16-bit operands or f32, passed as it is when contiguous) -> f32 [B,Q,L],
+    ``<f_bl, t_bq> / (|f_bl| |t_bq|)`` with the features read once for all Q texts (``rv_frame_cosine_multi``: f32-input MFMA).  A query's row does not
+    depend on Q, on its slot or on the other texts.  A zero text gives a NaN row, a zero frame a NaN column.  No synchronisation."""
+    if video.dim() != 3 or text.dim() != 3 or text.shape[0] != video.shape[0] or text.shape[2] != video.shape[2]:
+        raise ValueError(f"frame_cosine_multi: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, Q, d] and [B, L, d])")
+    B, L, d = video.shape
+    Q = text.shape[1]
+    text = _c(text.float())
+    unit = torch.empty_like(text)                       # the kernel's workspace: text / |text|
+    out = torch.empty(B, Q, L, dtype=torch.float32, device=video.device)
+    hip.check(_score_lib(video).rv_frame_cosine_multi(hip.ptr(_c(video)), hip.dtype_code(video), hip.ptr(text), B, Q, L, d, hip.ptr(unit), hip.ptr(out),
+                                                      hip.stream()), "rv_frame_cosine_multi")
+    return out
+
+
+def span_scores_multi(sims, spans, mask, k=3, pooling="topk", temperature=0.01, return_windows=False):
+    """``span_scores`` for Q queries per video: sims f32 [B,Q,L], spans [B,Q,N,2] (each query's own (centre, width) proposals), mask [B,L] (one duration
+    per video) -> scores f32 [B,Q,N] (and the windows i32 [B,Q,N,2]).  The kernel of ``span_scores``: each (b, q) row equals ``span_scores`` on that
+    row bit for bit.  No synchronisation."""
+    if pooling not in SPAN_POOLINGS:
+        raise ValueError(f"span_scores_multi: pooling={pooling!r} (expected one of {sorted(SPAN_POOLINGS)})")
+    if (sims.dim() != 3 or spans.dim() != 4 or spans.shape[:2] != sims.shape[:2] or spans.shape[3] != 2
+            or mask.shape != (sims.shape[0], sims.shape[2])):
+        raise ValueError(f"span_scores_multi: sims {tuple(sims.shape)} / spans {tuple(spans.shape)} / mask {tuple(mask.shape)}")
+    if sims.dtype != torch.float32:
+        raise ValueError(f"span_scores_multi: sims must be float32 (got {sims.dtype})")
+    B, Q, L = sims.shape
+    N = spans.shape[2]
+    scores = torch.empty(B, Q, N, dtype=torch.float32, device=sims.device)
+    win = torch.empty(B, Q, N, 2, dtype=torch.int32, device=sims.device) if return_windows else None
+    if N > 0:
+        hip.check(hip.lib().rv_span_scores_multi(hip.ptr(_c(sims)), hip.ptr(_c(spans.float())), hip.ptr(_c(mask.float())), B, Q, L, N,
+                                                 SPAN_POOLINGS[pooling], int(k), float(temperature), hip.ptr(scores), hip.ptr(win), hip.stream()),
+                  "rv_span_scores_multi")
+    return (scores, win) if return_windows else scores
+
+
 def attn_pool(text_embeds, video_embeds, temperature):
     """``_attention_pooling`` (similarity.py:96-113) on the device: text [Nt,d], video [Nv,T,d] (16-bit operands or f32) -> f32 [Nv,Nt,d] =
     ``sum_t softmax_t(<f_t, text_j> / temperature) f_t``."""
