@@ -676,6 +676,35 @@ int rv_span_scores_multi(const float* sims, const float* spans, const float* mas
 int rv_attn_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, float temperature,
                  float* out, void* stream);
 
+/* ---- ranking scored proposals: sort, greedy temporal NMS, top-M, hits against a ground-truth span (no counterpart kernel in the reference: its
+ * eval/metrics.py grounding_metrics_stream ranks on the host from JSON logs, one Python sort per query) ----
+ * scores f32 [R,N] (a row = one video, or one (video, query): rv_span_scores[_multi]'s rows with R = B or B Q), spans f32 [R,N,2], gt f32 [R,2] as
+ * (start, end) or NULL, hit_iou f32 [T] thresholds in DEVICE memory (NULL exactly when T = 0) ->
+ *   order     i32 [R,N]    (optional) the rank order, a permutation of 0 .. N-1
+ *   keep      i32 [R,top]  the indices that survive NMS, in rank order, at most `top` of them, then -1
+ *   n_keep    i32 [R]      how many
+ *   keep_iou  f32 [R,top]  (optional, needs gt) IoU of each kept proposal with gt[r]; 0 in the padding
+ *   first_hit i32 [R,T]    (optional, needs gt) the smallest p with keep_iou[r,p] > hit_iou[t], or -1
+ * Every f32 operation is rounded on its own (no contraction, no fast-math), so the result is a function of the row alone: it does not depend on R, on
+ * the row's place or on which of the two kernel forms ran.
+ * Bounds: form 0 reads (start, end); form 1 reads (centre, width): s = c - 0.5 w, e = c + 0.5 w (span_cxw_to_xx's rule).  A span is VOID when a bound
+ * is not finite or e <= s.
+ * Overlap: inter(a,b) = max(0, min(ea,eb) - max(sa,sb)), union = ((ea - sa) + (eb - sb)) - inter.  With a void span inter = 0 and the IoU is 0: a void
+ * span neither suppresses nor is suppressed (it is still ranked and kept in its turn).
+ * Order: descending score; ties - -0 against +0 included - go to the smaller index; a NaN score ranks AFTER every number, -inf included, and among NaNs the
+ * smaller index comes first.  This differs ON PURPOSE from the torch.topk order of the score kernels above (NaN first): rv_span_scores gives NaN to a
+ * proposal with non-finite bounds, and a ranked list must not open with it.
+ * Greedy NMS: walk the order; a proposal still alive is kept, and every LATER proposal j with inter(i,j) > nms_iou * union(i,j) dies (one multiplication,
+ * one comparison, no division; a proposal that has died suppresses nothing).  Stop after `top` kept.  nms_iou >= 1 suppresses nothing (inter <= union).
+ * With gt: keep_iou = union > 0 ? inter / union : 0 (one correctly rounded division) against gt[r]; a void gt gives 0 everywhere and no hit.  The hit
+ * test is a strict > in f32.
+ * Refused with RV_ERR_ARG, outputs untouched: a null scores / spans / keep / n_keep; R < 1; N < 1 or N > 2048; top outside [1, N]; form not 0 or 1;
+ * nms_iou negative or not finite; T outside [0, 16]; hit_iou, T > 0, keep_iou or first_hit without gt; T > 0 without hit_iou; gt with T = 0 and no keep_iou.
+ * N <= 64: one wave per row (registers and cross-lane operations only); N <= 2048: one workgroup per row (bitonic sort in 38 KB of LDS).  Rows ride on
+ * the grid's x dimension: no limit of 65535 on R. */
+int rv_span_rank(const float* scores, const float* spans, int32_t form, int32_t R, int32_t N, int32_t top, float nms_iou, const float* gt,
+                 const float* hit_iou, int32_t T, int32_t* order, int32_t* keep, int32_t* n_keep, float* keep_iou, int32_t* first_hit, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

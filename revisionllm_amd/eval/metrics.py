@@ -37,6 +37,39 @@ def grounding_metrics_stream(all_logs):
     return metrics
 
 
+def grounding_metrics_ranked(keep_iou, first_hit, hit_iou=(0.1, 0.3, 0.5, 0.7, 0.9)):
+    """``grounding_metrics_stream`` from the device ranking (``eval.similarity.rank_proposals`` with a ground truth): keep_iou [..., top] and
+    first_hit [..., T] (torch tensors on any device, or numpy arrays), ``hit_iou`` the T thresholds they were made with -> the same dict: mIoU from
+    ``keep_iou[..., 0]``, R{r}@{m} from ``0 <= first_hit < r``.  One reduction on the inputs' device and one copy of 1 + 4 T numbers.  (The stream
+    version compares float64 IoUs with float64 thresholds, the ranking f32 with f32: a row differs only where an IoU equals float32(m) exactly.)"""
+    hit_iou = tuple(hit_iou)
+    ranks = (1, 5, 10, 50)
+    if hasattr(keep_iou, "detach"):
+        import torch
+        iou0 = keep_iou.reshape(-1, keep_iou.shape[-1])[:, 0].double()
+        fh = first_hit.reshape(-1, first_hit.shape[-1])
+        n = iou0.shape[0]
+        if n == 0:
+            return None
+        counts = torch.stack([((fh >= 0) & (fh < r)).sum(dim=0) for r in ranks]).double()           # [4, T]
+        flat = torch.cat([iou0.sum().reshape(1), counts.reshape(-1)]).tolist()
+    else:
+        iou0 = np.asarray(keep_iou).reshape(-1, np.shape(keep_iou)[-1])[:, 0].astype(np.float64)
+        fh = np.asarray(first_hit).reshape(-1, np.shape(first_hit)[-1])
+        n = iou0.shape[0]
+        if n == 0:
+            return None
+        flat = [float(iou0.sum())] + [float(((fh >= 0) & (fh < r))[:, t].sum()) for r in ranks for t in range(fh.shape[1])]
+    if fh.shape[-1] != len(hit_iou):
+        raise ValueError(f"grounding_metrics_ranked: first_hit has {fh.shape[-1]} thresholds, hit_iou {len(hit_iou)}")
+    metrics = collections.defaultdict(int)
+    metrics["mIoU"] = flat[0] / n * 100
+    for t, m in enumerate(hit_iou):
+        for i, r in enumerate(ranks):
+            metrics[f"R{r}@{m}"] = flat[1 + i * len(hit_iou) + t] / n * 100
+    return metrics
+
+
 def load_predictions(path, distributed=16):
     """Concatenate the per-shard JSONL files of a run (:59-79)."""
     if distributed > 0:

@@ -13,7 +13,11 @@ are this build's: ``k`` (the reference's 3), ``pooling`` ("topk", or "attention"
 masking (as in the reference the mask only gives each video's duration).
 
 Several texts per video (this build's addition, no counterpart in the reference): ``forward_clip_matching_multi`` scores Q queries, each with its own
-proposals, against one pass over their video's features (``rv_frame_cosine_multi`` on the f32-input MFMA + ``rv_span_scores_multi``)."""
+proposals, against one pass over their video's features (``rv_frame_cosine_multi`` on the f32-input MFMA + ``rv_span_scores_multi``).
+
+Ranking (this build's addition; the reference ranks on the host from JSON logs, metric_retrieval_forward.py:35-56): ``rank_proposals`` takes the score
+rows of either matching call with their proposals and returns, per row, the best proposals in order with near-duplicates removed and - given a ground
+truth - their IoUs and first hits (``rv_span_rank``, one launch); ``eval.metrics.grounding_metrics_ranked`` reduces those to mIoU / R{r}@{m}."""
 import math
 
 import torch
@@ -144,6 +148,35 @@ def forward_clip_matching_multi(src_cls_txt, src_vid_appear, src_vid_appear_mask
     with one text per video keep ``forward_clip_matching``).  Dtype and device handling, keywords and refusals are ``forward_clip_matching``'s."""
     return _match("forward_clip_matching_multi", src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, k, pooling, temperature, return_windows,
                   multi=True)
+
+
+def rank_proposals(scores, proposal, *, top=None, nms_iou=1.0, gt=None, hit_iou=ops.HIT_IOU, return_order=False):
+    """scores [B, N] or [B, Q, N] (``forward_clip_matching`` / ``_multi``'s result), proposal [..., N, 2] rows of (centre, width) as those calls take them,
+    gt [..., 2] rows of (start, end) or None -> ``ops.SpanRank(keep, n_keep, keep_iou, first_hit, order)``: per row the indices of the proposals that
+    survive greedy NMS (``inter > nms_iou * union`` against an earlier kept one; 1.0 = none) in descending score order, at most ``top`` (None: all), padded
+    with -1; how many; with ``gt`` their IoUs with it and, per threshold of ``hit_iou``, the first kept place whose IoU exceeds it (-1: none); with
+    ``return_order`` the full rank order.  Ties go to the smaller index and a NaN score ranks last.  One launch, no synchronisation and no device -> host
+    copy when the inputs live on the device; host tensors are staged and the results come back on the device ``scores`` lives on.  16-bit scores are
+    read as f32 (exact)."""
+    who = "rank_proposals"
+    for name, t in (("scores", scores), ("proposal", proposal)) + ((("gt", gt),) if gt is not None else ()):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{who}: {name} must be a floating-point tensor (got {t.dtype})")
+    if scores.dim() not in (2, 3) or proposal.shape != scores.shape + (2,):
+        raise ValueError(f"{who}: scores {tuple(scores.shape)} / proposal {tuple(proposal.shape)} (expected [B, N] or [B, Q, N] and [..., N, 2] rows of "
+                         f"(centre, width))")
+    if gt is not None and gt.shape != scores.shape[:-1] + (2,):
+        raise ValueError(f"{who}: gt {tuple(gt.shape)} for scores {tuple(scores.shape)} (expected [..., 2] rows of (start, end))")
+    if scores.shape[-1] > ops.SPAN_RANK_MAX:
+        raise ValueError(f"{who}: N={scores.shape[-1]} proposals per row (at most {ops.SPAN_RANK_MAX})")
+    ops.span_rank_keywords(who, top, nms_iou, hit_iou)
+    home = scores.device
+    dev = _device_of(scores, who)
+    out = ops.span_rank(ops.h2d(scores, dev).float(), ops.h2d(proposal, dev).float(), top=top, nms_iou=nms_iou, form="cxw",
+                        gt=None if gt is None else ops.h2d(gt, dev).float(), hit_iou=hit_iou, return_order=return_order)
+    return ops.SpanRank(*(None if t is None else t.to(home) for t in out))
 
 
 def _get_predicted_proposal_feat(src_vid_appear, src_vid_appear_mask, pred_proposal, text_cls_features):

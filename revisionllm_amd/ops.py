@@ -2,7 +2,9 @@
 
 Every function takes / returns torch DEVICE tensors and enqueues on torch's current stream.
 """
+import collections
 import math
+import numbers
 
 import torch
 
@@ -385,6 +387,87 @@ def span_scores_multi(sims, spans, mask, k=3, pooling="topk", temperature=0.01, 
                                                  SPAN_POOLINGS[pooling], int(k), float(temperature), hip.ptr(scores), hip.ptr(win), hip.stream()),
                   "rv_span_scores_multi")
     return (scores, win) if return_windows else scores
+
+
+SPAN_FORMS = {"xx": 0, "cxw": 1}
+SPAN_RANK_MAX = 2048
+HIT_IOU = (0.1, 0.3, 0.5, 0.7, 0.9)
+SpanRank = collections.namedtuple("SpanRank", "keep n_keep keep_iou first_hit order")
+_hit_tables = collections.OrderedDict()
+_HIT_TABLES_MAX = 16
+
+
+def _hit_table(hit_iou, device):
+    """The thresholds as an f32 device vector, uploaded once per (values, device, stream) and kept for the last 16 such keys: a ranking call then queues no
+    copy.  The stream is part of the key because the upload is ordered on the stream that was current when it was queued: a call on another stream gets a
+    table of its own, uploaded on that stream, instead of reading this one without ordering."""
+    key = (hit_iou, str(device), torch.cuda.current_stream(device).cuda_stream)
+    table = _hit_tables.get(key)
+    if table is None:
+        table = _hit_tables[key] = h2d(torch.tensor(hit_iou, dtype=torch.float32), device)
+        while len(_hit_tables) > _HIT_TABLES_MAX:
+            _hit_tables.popitem(last=False)        # (the allocator keeps a freed block ordered behind the work queued on its stream)
+    else:
+        _hit_tables.move_to_end(key)
+    return table
+
+
+def span_rank_keywords(who, top, nms_iou, hit_iou):
+    """The keyword refusals of ``span_rank`` (raised before any device is looked for) -> (nms_iou as float, hit_iou as a tuple of floats)."""
+    if top is not None and not (isinstance(top, numbers.Integral) and not isinstance(top, bool) and top >= 1):
+        raise ValueError(f"{who}: top={top!r} must be a positive integer or None")
+    try:
+        nms_iou, hit_iou = float(nms_iou), tuple(float(h) for h in hit_iou)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: nms_iou={nms_iou!r} must be a number and hit_iou={hit_iou!r} a sequence of numbers") from None
+    if not (math.isfinite(nms_iou) and nms_iou >= 0.0):
+        raise ValueError(f"{who}: nms_iou={nms_iou} must be finite and >= 0")
+    if len(hit_iou) > 16:
+        raise ValueError(f"{who}: {len(hit_iou)} thresholds in hit_iou (at most 16)")
+    return nms_iou, hit_iou
+
+
+def span_rank(scores, spans, top=None, nms_iou=1.0, form="cxw", gt=None, hit_iou=HIT_IOU, return_order=False):
+    """Rank scored proposals on the device (``rv_span_rank``): scores [R,N] or [B,Q,N], spans [...,N,2] as (centre, width) (``form="cxw"``) or (start, end)
+    (``"xx"``), gt [...,2] as (start, end) or None -> SpanRank(keep i32 [...,top], n_keep i32 [...], keep_iou f32 [...,top], first_hit i32 [...,T], order
+    i32 [...,N]); parts not asked for are None (keep_iou and first_hit need ``gt``, order ``return_order``).  Descending score, ties to the smaller index,
+    NaN last; greedy NMS at ``inter > nms_iou * union`` (1.0: none); ``keep`` is padded with -1, ``keep_iou`` with 0; ``first_hit[..., t]`` is the first
+    kept place whose IoU with gt exceeds ``hit_iou[t]``, or -1.  ``top=None`` means N, a larger ``top`` is N.  One launch, no synchronisation, no host copy."""
+    if form not in SPAN_FORMS:
+        raise ValueError(f"span_rank: form={form!r} (expected one of {sorted(SPAN_FORMS)})")
+    if not torch.is_tensor(scores) or not torch.is_tensor(spans) or (gt is not None and not torch.is_tensor(gt)):
+        raise ValueError("span_rank: scores, spans and gt must be tensors")
+    if scores.dim() not in (2, 3) or spans.shape != scores.shape + (2,):
+        raise ValueError(f"span_rank: scores {tuple(scores.shape)} / spans {tuple(spans.shape)} (expected [R, N] or [B, Q, N] and [..., N, 2])")
+    if gt is not None and gt.shape != scores.shape[:-1] + (2,):
+        raise ValueError(f"span_rank: gt {tuple(gt.shape)} for scores {tuple(scores.shape)} (expected [..., 2] rows of (start, end))")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"span_rank: scores must be float32 (got {scores.dtype})")
+    for name, t in (("spans", spans), ("gt", gt)):
+        if t is not None and not t.dtype.is_floating_point:
+            raise ValueError(f"span_rank: {name} must be a floating-point tensor (got {t.dtype})")
+    lead, N = tuple(scores.shape[:-1]), scores.shape[-1]
+    if N > SPAN_RANK_MAX:
+        raise ValueError(f"span_rank: N={N} proposals per row (at most {SPAN_RANK_MAX})")
+    nms_iou, hit_iou = span_rank_keywords("span_rank", top, nms_iou, hit_iou if gt is not None else ())
+    top = N if top is None else min(int(top), N)
+    T, dev = len(hit_iou), scores.device
+    R = math.prod(lead)
+    keep = torch.empty(lead + (top,), dtype=torch.int32, device=dev)
+    n_keep = torch.empty(lead, dtype=torch.int32, device=dev)
+    keep_iou = torch.empty(lead + (top,), dtype=torch.float32, device=dev) if gt is not None else None
+    first_hit = torch.empty(lead + (T,), dtype=torch.int32, device=dev) if gt is not None else None
+    order = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_order else None
+    if N > 0 and R > 0:
+        hip.check(hip.lib().rv_span_rank(hip.ptr(_c(scores)), hip.ptr(_c(spans.float())), SPAN_FORMS[form], R, N, top, nms_iou,
+                                         hip.ptr(_c(gt.float())) if gt is not None else None, hip.ptr(_hit_table(hit_iou, dev)) if T else None, T,
+                                         hip.ptr(order), hip.ptr(keep), hip.ptr(n_keep), hip.ptr(keep_iou), hip.ptr(first_hit if T else None), hip.stream()),
+                  "rv_span_rank")
+    elif R > 0:                                          # no proposals: nothing kept, no hit (no launch)
+        n_keep.zero_()
+        if first_hit is not None:
+            first_hit.fill_(-1)
+    return SpanRank(keep, n_keep, keep_iou, first_hit, order)
 
 
 def attn_pool(text_embeds, video_embeds, temperature):
