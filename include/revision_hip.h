@@ -705,6 +705,44 @@ int rv_attn_pool(const void* video, int dtype, const float* text, int32_t Nv, in
 int rv_span_rank(const float* scores, const float* spans, int32_t form, int32_t R, int32_t N, int32_t top, float nms_iou, const float* gt,
                  const float* hit_iou, int32_t T, int32_t* order, int32_t* keep, int32_t* n_keep, float* keep_iou, int32_t* first_hit, void* stream);
 
+/* ---- span proposals from a similarity row: temporal grouping of the thresholded row at several levels, in the manner of TAG / watershed proposals
+ * (this project's own definition; the reference takes its proposals from the LLM and has no counterpart) ----
+ * sims f32 [R,L] (a row = one video, or one (video, query): rv_frame_cosine[_multi]'s rows), mask f32 [R / rpm, L] (rpm = "rows per mask", as in
+ * rv_span_scores_multi; R a multiple of rpm), levels: T floats in HOST memory (copied into the kernel arguments), 1 <= T <= 8 ->
+ *   spans    f32 [R,N,2]  (centre, width) as fractions of the duration, the form rv_span_scores and rv_span_rank read; NaN (0x7fc00000) in the padding
+ *   n_spans  i32 [R]      min(found, N)
+ *   n_found  i32 [R]      (optional) found, the number of surviving runs: n_found > n_spans shows an overflow
+ *   windows  i32 [R,N,2]  (optional) (lo, hi) of each span, (-1, -1) in the padding
+ *   smoothed f32 [R,L]    (optional) s' in [0, D); the rest of it is untouched
+ * Every f32 operation is rounded on its own (no contraction), so a row's result is a function of that row alone: it does not depend on R, on the
+ * row's place or on the tiling.
+ * Duration: dur = the f32 sum of the row's mask row, D = min(L, max(0, int(floor(dur)))), D = 0 for a non-finite dur.  Only frames [0, D) exist for the
+ * row; the mask gives the duration only, as everywhere in this library, and no frame of sims at or past D is read.  The result is defined for masks
+ * whose sum is exact in any order (0 / 1 masks); for other masks it is build-defined (the order of the sum is the kernel's).
+ * Smoothing (smooth odd, h = smooth / 2): for t in [0, D), a = max(0, t - h), b = min(D - 1, t + h),
+ * s'[t] = (((s[a] + s[a+1]) + ...) + s[b]) / float(b - a + 1): the adds in ascending order, then one division (no sliding sum: its roundings differ).
+ * A NaN inside the window gives a NaN s'[t].
+ * Thresholds: mx / mn = the largest / smallest non-NaN s' of the row.  relative = 1: theta_l = mn + level_l * (mx - mn) (three operations in that
+ * order); relative = 0: theta_l = level_l.
+ * Runs: frame t is ABOVE at level l when s'[t] > theta_l (strict; a NaN is never above).  A run [lo, hi) of level l begins and ends on an above frame,
+ * holds no more than `gap` consecutive frames that are not above, and is preceded and followed by more than `gap` such frames or by the row's ends.
+ * A flat row, an all-NaN row and D = 0 give no run.
+ * Filter: a run goes when hi - lo < min_len, or when max_len > 0 and hi - lo > max_len (max_len = 0: no limit).  Duplicates: a run of level l < T - 1
+ * goes when level l + 1 has a run with the same (lo, hi).  (That covers every higher level: thresholds ascend, so the above sets are nested, closing
+ * gaps is monotone, so the runs are nested, and a run shared with level l + 2 is level l + 1's as well.)
+ * Order: levels T - 1 down to 0, ascending lo inside a level - the sharpest peaks first, and a full list drops the loosest threshold's spans.
+ * Encoding: c = ((float(lo) + float(hi)) * 0.5f) / dur, w = ((float(hi) - float(lo)) - 0.5f) / dur.  rv_span_scores' window rule then computes
+ * p1 / p2 near lo + 0.25 / hi - 0.25 and its floor / ceil give back exactly (lo, hi) - for every L up to the limit below.  A padding span (NaN) gets
+ * the score NaN and the window (-1, -1) from rv_span_scores, ranks last in rv_span_rank and is void there.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null sims / mask / levels / spans / n_spans; R < 1; rpm < 1; R not a multiple of
+ * rpm; L < 1 or L > 1048576; T outside [1, 8]; relative not 0 / 1; a level that is not finite, not strictly ascending, or outside [0, 1) with
+ * relative = 1; smooth even or outside [1, 65]; gap outside [0, 63]; min_len < 1; max_len < 0; 0 < max_len < min_len; N outside [1, 2048] (2048 is
+ * rv_span_rank's limit, so the output feeds it as it is).
+ * One 256-thread workgroup per row, rows on the grid's x dimension with 64-bit offsets (no limit of 65535 on R); 2.6 KB of LDS whatever L. */
+int rv_span_propose(const float* sims, const float* mask, int32_t R, int32_t rpm, int32_t L, const float* levels, int32_t T, int32_t relative,
+                    int32_t smooth, int32_t gap, int32_t min_len, int32_t max_len, int32_t N, float* spans, int32_t* n_spans, int32_t* n_found,
+                    int32_t* windows, float* smoothed, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

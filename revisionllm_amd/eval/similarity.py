@@ -17,7 +17,13 @@ proposals, against one pass over their video's features (``rv_frame_cosine_multi
 
 Ranking (this build's addition; the reference ranks on the host from JSON logs, metric_retrieval_forward.py:35-56): ``rank_proposals`` takes the score
 rows of either matching call with their proposals and returns, per row, the best proposals in order with near-duplicates removed and - given a ground
-truth - their IoUs and first hits (``rv_span_rank``, one launch); ``eval.metrics.grounding_metrics_ranked`` reduces those to mIoU / R{r}@{m}."""
+truth - their IoUs and first hits (``rv_span_rank``, one launch); ``eval.metrics.grounding_metrics_ranked`` reduces those to mIoU / R{r}@{m}.
+
+Proposals (this build's addition; the reference's proposals come from the LLM): ``propose_spans`` turns the per-frame cosine rows themselves into
+candidate spans - the row smoothed, thresholded at several levels, stretches above a threshold with short gaps closed (``rv_span_propose``, one
+launch) - in the (centre, width) form every call above takes.  ``ground_queries`` chains the four device stages - cosine rows, proposals, span scores,
+ranking - into a grounder that needs no proposals from outside and never synchronises: ``Grounding(spans, scores, n_keep, proposals, rank)``."""
+import collections
 import math
 
 import torch
@@ -177,6 +183,85 @@ def rank_proposals(scores, proposal, *, top=None, nms_iou=1.0, gt=None, hit_iou=
     out = ops.span_rank(ops.h2d(scores, dev).float(), ops.h2d(proposal, dev).float(), top=top, nms_iou=nms_iou, form="cxw",
                         gt=None if gt is None else ops.h2d(gt, dev).float(), hit_iou=hit_iou, return_order=return_order)
     return ops.SpanRank(*(None if t is None else t.to(home) for t in out))
+
+
+def propose_spans(sims, mask, *, levels=ops.SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None, max_spans=256,
+                  return_windows=False, return_smoothed=False):
+    """``ops.span_propose`` with the device handling of the matching calls: sims [R, L] or [B, Q, L] (the cosine rows; 16-bit rows are read as f32, which
+    is exact), mask [R, L] / [B, L] of any bool, integer or float dtype -> ``ops.SpanProposals(spans, n_spans, n_found, windows, smoothed)``: per row
+    up to ``max_spans`` candidate spans as (centre, width) fractions of the duration (NaN in the padding), how many, how many there were before
+    ``max_spans`` cut the list, and on request their (lo, hi) frame windows and the smoothed row.  One launch, no synchronisation and no device -> host
+    copy when the inputs live on the device; host tensors are staged and the results come back on the device ``sims`` lives on."""
+    who = "propose_spans"
+    ops.span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    ops.span_propose_shapes(who, sims, mask)
+    home = sims.device
+    dev = _device_of(sims, who)
+    out = ops.span_propose(ops.h2d(sims, dev).float(), ops.h2d(mask, dev), levels=levels, relative=relative, smooth=smooth, gap=gap, min_len=min_len,
+                           max_len=max_len, max_spans=max_spans, return_windows=return_windows, return_smoothed=return_smoothed)
+    return ops.SpanProposals(*(None if t is None else t.to(home) for t in out))
+
+
+Grounding = collections.namedtuple("Grounding", "spans scores n_keep proposals rank")
+
+
+def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk", temperature=0.01, gt=None, hit_iou=ops.HIT_IOU, **propose_keywords):
+    """Ground queries in their videos with the matching stage alone: text [B, d] or [B, Q, d], video [B, L, d], mask [B, L], gt [..., 2] rows of
+    (start, end) or None -> ``Grounding(spans, scores, n_keep, proposals, rank)``.  Four device stages: the cosine rows (``ops.frame_cosine[_multi]``),
+    candidate spans from those rows (``ops.span_propose`` with ``propose_keywords``: levels, relative, smooth, gap, min_len, max_len, max_spans,
+    return_windows, return_smoothed), their scores (``ops.span_scores[_multi]`` with ``k``, ``pooling``, ``temperature``) and the ranking
+    (``ops.span_rank`` with ``top``, ``nms_iou``, ``gt``, ``hit_iou``).  ``spans`` f32 [..., top, 2] are the kept proposals as (centre, width) in rank
+    order and ``scores`` f32 [..., top] their scores, both gathered by ``rank.keep`` with NaN in the padding; ``n_keep`` i32 [...] counts the kept
+    places that hold a proposal (``rank.n_keep`` also counts padding spans, which rank last); ``proposals`` and ``rank`` are the ``SpanProposals`` and
+    ``SpanRank`` they came from.  ``top`` above ``max_spans`` is ``max_spans``.  No synchronisation and no device -> host copy when the inputs live on
+    the device; host tensors are staged and every result comes back on the device ``video`` lives on."""
+    who = "ground_queries"
+    for name, t in (("text", text), ("video", video), ("mask", mask)) + ((("gt", gt),) if gt is not None else ()):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
+    multi = text.dim() == 3
+    if video.dim() != 3 or text.dim() not in (2, 3) or text.shape[0] != video.shape[0] or text.shape[-1] != video.shape[2] or min(text.shape) == 0:
+        raise ValueError(f"{who}: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, d] or [B, Q, d] and [B, L, d])")
+    if mask.shape != video.shape[:2]:
+        raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected [B, L])")
+    if min(video.shape) == 0:
+        raise ValueError(f"{who}: empty video {tuple(video.shape)}")
+    for name, t in (("text", text), ("video", video)) + ((("gt", gt),) if gt is not None else ()):
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{who}: {name} must be a floating-point tensor (got {t.dtype})")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    if gt is not None and gt.shape != text.shape[:-1] + (2,):
+        raise ValueError(f"{who}: gt {tuple(gt.shape)} for text {tuple(text.shape)} (expected [..., 2] rows of (start, end))")
+    if video.shape[1] > ops.SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={video.shape[1]} frames (at most {ops.SPAN_PROPOSE_MAX_FRAMES})")
+    if pooling not in ops.SPAN_POOLINGS:
+        raise ValueError(f"{who}: pooling={pooling!r} (expected one of {sorted(ops.SPAN_POOLINGS)})")
+    if pooling == "topk" and not (isinstance(k, int) and 1 <= k <= 64):
+        raise ValueError(f"{who}: k={k!r} must be an integer in [1, 64]")
+    if pooling == "attention" and (float(temperature) == 0.0 or not math.isfinite(float(temperature))):
+        raise ValueError(f"{who}: temperature={temperature} must be finite and not 0")
+    ops.span_rank_keywords(who, top, nms_iou, hit_iou)
+    unknown = set(propose_keywords) - {"levels", "relative", "smooth", "gap", "min_len", "max_len", "max_spans", "return_windows", "return_smoothed"}
+    if unknown:
+        raise TypeError(f"{who}: unexpected keyword(s) {sorted(unknown)}")
+    ops.span_propose_keywords(who, **{n: v for n, v in propose_keywords.items() if not n.startswith("return_")})
+    home = video.device
+    dev = _device_of(video, who)
+    video = _features_up(video, dev)
+    mask = ops.h2d(mask, dev).float()
+    cosine, score = (ops.frame_cosine_multi, ops.span_scores_multi) if multi else (ops.frame_cosine, ops.span_scores)
+    sims = cosine(ops.h2d(text, dev).float(), video)
+    proposals = ops.span_propose(sims, mask, **propose_keywords)
+    scores = score(sims, proposals.spans, mask, k=k, pooling=pooling, temperature=temperature)
+    rank = ops.span_rank(scores, proposals.spans, top=top, nms_iou=nms_iou, form="cxw", gt=None if gt is None else ops.h2d(gt, dev).float(), hit_iou=hit_iou)
+    held = (rank.keep >= 0) & (rank.keep < proposals.n_spans.unsqueeze(-1))                 # kept places that hold a proposal: a prefix (NaN ranks last)
+    at = rank.keep.clamp(min=0).long()
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    spans = torch.where(held.unsqueeze(-1), torch.gather(proposals.spans, -2, at.unsqueeze(-1).expand(at.shape + (2,))), nan)
+    kept_scores = torch.where(held, torch.gather(scores, -1, at), nan)
+    back = lambda tup: type(tup)(*(None if t is None else t.to(home) for t in tup))                 # noqa: E731
+    return Grounding(spans.to(home), kept_scores.to(home), held.sum(-1, dtype=torch.int32).to(home), back(proposals), back(rank))
 
 
 def _get_predicted_proposal_feat(src_vid_appear, src_vid_appear_mask, pred_proposal, text_cls_features):

@@ -5,6 +5,7 @@ Every function takes / returns torch DEVICE tensors and enqueues on torch's curr
 import collections
 import math
 import numbers
+import struct
 
 import torch
 
@@ -468,6 +469,105 @@ def span_rank(scores, spans, top=None, nms_iou=1.0, form="cxw", gt=None, hit_iou
         if first_hit is not None:
             first_hit.fill_(-1)
     return SpanRank(keep, n_keep, keep_iou, first_hit, order)
+
+
+SPAN_PROPOSE_MAX_LEVELS = 8
+SPAN_PROPOSE_MAX_FRAMES = 1 << 20
+SPAN_PROPOSE_LEVELS = (0.5, 0.6, 0.7, 0.8, 0.9)
+SpanProposals = collections.namedtuple("SpanProposals", "spans n_spans n_found windows smoothed")
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _f32(v):
+    """A Python float rounded to float32 (inf when it is out of range)."""
+    try:
+        return struct.unpack("f", struct.pack("f", v))[0]
+    except OverflowError:
+        return math.copysign(math.inf, v)
+
+
+def span_propose_keywords(who, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None, max_spans=256):
+    """The keyword refusals of ``span_propose`` (raised before any device is looked for) -> (levels as a tuple of floats, relative as 0 / 1, smooth, gap,
+    min_len, max_len with None as 0, max_spans) as ``rv_span_propose`` takes them."""
+    try:
+        levels = tuple(float(v) for v in levels)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: levels={levels!r} must be a sequence of numbers") from None
+    if not 1 <= len(levels) <= SPAN_PROPOSE_MAX_LEVELS:
+        raise ValueError(f"{who}: {len(levels)} levels (1 to {SPAN_PROPOSE_MAX_LEVELS})")
+    if not (isinstance(relative, (bool, numbers.Integral)) and relative in (0, 1)):
+        raise ValueError(f"{who}: relative={relative!r} must be True or False")
+    as_f32 = [_f32(v) for v in levels]                   # what the kernel compares
+    for i, v in enumerate(as_f32):
+        if not math.isfinite(v):
+            raise ValueError(f"{who}: level {levels[i]} is not a finite float32")
+        if i and not v > as_f32[i - 1]:
+            raise ValueError(f"{who}: levels={levels} must be strictly ascending (as float32)")
+        if relative and not 0.0 <= v < 1.0:
+            raise ValueError(f"{who}: relative level {levels[i]} outside [0, 1)")
+    if not (_is_int(smooth) and 1 <= smooth <= 65 and smooth % 2 == 1):
+        raise ValueError(f"{who}: smooth={smooth!r} must be an odd integer in [1, 65]")
+    if not (_is_int(gap) and 0 <= gap <= 63):
+        raise ValueError(f"{who}: gap={gap!r} must be an integer in [0, 63]")
+    if not (_is_int(min_len) and 1 <= min_len < 2 ** 31):
+        raise ValueError(f"{who}: min_len={min_len!r} must be a positive integer")
+    if max_len is not None and not (_is_int(max_len) and min_len <= max_len < 2 ** 31):
+        raise ValueError(f"{who}: max_len={max_len!r} must be None or an integer >= min_len={min_len}")
+    if not (_is_int(max_spans) and 1 <= max_spans <= SPAN_RANK_MAX):
+        raise ValueError(f"{who}: max_spans={max_spans!r} must be an integer in [1, {SPAN_RANK_MAX}]")
+    return tuple(as_f32), int(bool(relative)), int(smooth), int(gap), int(min_len), 0 if max_len is None else int(max_len), int(max_spans)
+
+
+def span_propose_shapes(who, sims, mask):
+    """The tensor refusals of ``span_propose`` -> (leading shape, R, rows per mask row, L)."""
+    if not torch.is_tensor(sims) or not torch.is_tensor(mask):
+        raise ValueError(f"{who}: sims and mask must be tensors")
+    if sims.dim() not in (2, 3) or mask.dim() != 2 or mask.shape[-1] != sims.shape[-1]:
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / mask {tuple(mask.shape)} (expected [R, L] or [B, Q, L] and [R, L] / [B, L])")
+    lead, L = tuple(sims.shape[:-1]), sims.shape[-1]
+    R, M = math.prod(lead), mask.shape[0]
+    if min(R, L, M) < 1 or (sims.dim() == 3 and M != lead[0]) or R % M != 0:
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / mask {tuple(mask.shape)} (one mask row per video: a whole number of rows of sims for each)")
+    if L > SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={L} frames (at most {SPAN_PROPOSE_MAX_FRAMES})")
+    if not sims.dtype.is_floating_point:
+        raise ValueError(f"{who}: sims must be a floating-point tensor (got {sims.dtype})")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    return lead, R, R // M, L
+
+
+def span_propose(sims, mask, *, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None, max_spans=256, return_windows=False,
+                 return_smoothed=False):
+    """Candidate spans from similarity rows on the device (``rv_span_propose``): sims f32 [R,L] or [B,Q,L] (``frame_cosine`` / ``frame_cosine_multi``'s
+    rows), mask [R,L] / [B,L] of any bool, integer or float dtype (its row sum is the duration; with fewer rows than sims each serves a whole number of
+    consecutive rows) -> SpanProposals(spans f32 [...,max_spans,2] as (centre, width) with NaN padding, n_spans i32 [...], n_found i32 [...], windows i32
+    [...,max_spans,2] with (-1, -1) padding, smoothed f32 [...,L]); ``windows`` and ``smoothed`` are None unless asked for, and ``smoothed`` is written
+    inside each row's duration only (NaN elsewhere).  The row is box-smoothed over ``smooth`` frames and thresholded at every level (``relative``: a
+    fraction of the way from the row's smallest to its largest value); a maximal stretch above a threshold, gaps of at most ``gap`` frames closed, is a
+    span if its length lies in [min_len, max_len] and the next level has no identical one.  Highest level first, then ascending start;
+    ``n_found > n_spans`` shows that ``max_spans`` cut the list.  One launch (a mask that is not f32 adds a cast kernel, ``return_smoothed`` a fill), no
+    synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
+    who = "span_propose"
+    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    lv, relative, smooth, gap, min_len, max_len, N = kw
+    dev = sims.device
+    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
+    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
+    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
+    table = (hip.C.c_float * len(lv))(*lv)
+    hip.check(hip.lib().rv_span_propose(hip.ptr(_c(sims)), hip.ptr(_c(mask.float())), R, rpm, L, table, len(lv), relative, smooth, gap, min_len, max_len, N,
+                                        hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows), hip.ptr(smoothed), hip.stream()),
+              "rv_span_propose")
+    return SpanProposals(spans, n_spans, n_found, windows, smoothed)
 
 
 def attn_pool(text_embeds, video_embeds, temperature):
