@@ -743,6 +743,45 @@ int rv_span_propose(const float* sims, const float* mask, int32_t R, int32_t rpm
                     int32_t smooth, int32_t gap, int32_t min_len, int32_t max_len, int32_t N, float* spans, int32_t* n_spans, int32_t* n_found,
                     int32_t* windows, float* smoothed, void* stream);
 
+/* ---- coarse window selection for the stage-2 recursion: which windows of stage2.cut_windows' geometry a query should see, chosen from its per-frame
+ * cosine row (the stage the reference evaluates in eval/evaluate_pre_filtered_window.py and feeds from a stage-1 LLM log, e2e2.py:278-294; scoring
+ * the windows by their top-k cosines is this project's own definition) ----
+ * sims f32 [R,L] (a row = one video, or one (video, query): rv_frame_cosine[_multi]'s rows), mask f32 [R / rpm, L] (rpm = "rows per mask", as in
+ * rv_span_propose; R a multiple of rpm), gt f32 [R,2] (start, end) in frames, or NULL ->
+ *   select     i32 [R,keep]          the chosen windows' indices ASCENDING (the form of run_query's grounding_windows: a sorted list that also
+ *                                    indexes cut_windows' frame_idx), then -1
+ *   n_select   i32 [R]               min(keep, W_r)
+ *   n_windows  i32 [R]               W_r
+ *   win_scores f32 [R,Wcap]          (optional) the score of every window, NaN (0x7fc00000) in the padding
+ *   bounds     i32 [R / rpm,Wcap,2]  (optional) (lo, hi) of every window, (-1, -1) in the padding; written by the first row of each mask row
+ *   order      i32 [R,Wcap]          (optional) the selection sequence seq, -1 in the padding
+ *   hit_rank   i32 [R]               (optional, needs gt) the smallest place p with window seq[p] covering the ground truth, or -1
+ * Duration (rv_span_propose's rule): dur = the f32 sum of the row's mask row, D = min(L, max(0, int(floor(dur)))), D = 0 for a non-finite dur.  Only
+ * frames [0, D) exist for the row; no frame of sims at or past D is read.  The result is defined for masks whose sum is exact in any order (0 / 1
+ * masks); for other masks it is build-defined (the order of the sum is the kernel's).
+ * Windows (stage2.cut_windows' rule in integers, 64-bit intermediate products): hop = win / stride (integer division), W_r = max(0, ceil(D / hop) - 1);
+ * for i in [0, W_r): s = (i * win) / stride, e = min(s + win, D - 1), and if e - s < win then s = e - win; the window is frames
+ * [lo, hi) = [max(s, 0), e + 1).  (s, e) are cut_windows' `times` for clip_length = win; every window is non-empty and inside [0, D).  The clamp
+ * at 0 is this library's own (cut_windows lets a negative start wrap; the driver skips such videos).
+ * Score of a window: the sum of its min(k, hi - lo) largest sims in rv_span_scores' mode-0 order - NaN first, then the larger value, then the
+ * smaller index - accumulated from 0 in that order, each add rounded: a NaN frame gives a NaN window, and the score equals rv_span_scores' on a span
+ * whose window is [lo, hi) bit for bit.
+ * Rank order (rv_span_rank's): descending score, ties (-0 against +0 included) to the smaller index, NaN after every number, NaNs among themselves
+ * by index.
+ * Selection sequence seq, a permutation of the W_r windows.  Pass 1 walks the rank order: a window still alive is taken, and every window j with
+ * |i - j| < min_sep dies; a dead window is skipped and kills nothing; min_sep = 1 kills nothing.  Pass 2 appends the windows not yet taken in rank
+ * order (the "top up to batch" of the reference's pre-filter).  n_select = min(keep, W_r); select = the first n_select entries of seq sorted
+ * ascending.  (The first entries of pass 1 do not depend on how far the walk goes, so select needs no more of seq than n_select entries.)
+ * Ground truth: a window covers it when float(lo) < ge && float(hi) > gs (both strict); a gt that is not finite or has ge <= gs is void and gives
+ * hit_rank = -1.  Rank@K of the reference's windows_selection is 0 <= hit_rank < K; with min_sep = 1 the place is the score rank.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null sims / mask / select / n_select / n_windows; R < 1; rpm < 1; R not a
+ * multiple of rpm; L < 1 or L > 1048576; stride < 1; win < stride; win > L; k outside [1, 64]; Wcap != max(1, ceil(L / hop) - 1) or Wcap > 2048;
+ * keep outside [1, Wcap]; min_sep outside [1, Wcap]; hit_rank without gt.
+ * One 1024-thread workgroup per row, rows on the grid's x dimension with 64-bit offsets (no limit of 65535 on R); 24 KB of LDS whatever L. */
+int rv_window_select(const float* sims, const float* mask, int32_t R, int32_t rpm, int32_t L, int32_t win, int32_t stride, int32_t k, int32_t keep,
+                     int32_t min_sep, int32_t Wcap, const float* gt, int32_t* select, int32_t* n_select, int32_t* n_windows, float* win_scores,
+                     int32_t* bounds, int32_t* order, int32_t* hit_rank, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

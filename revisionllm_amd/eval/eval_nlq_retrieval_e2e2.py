@@ -93,6 +93,9 @@ def parse_args(argv=None):
     p.add_argument("--mixed_prefill", action="store_true",
                    help="(build-defined; --in_flight > 1) prefills of different geometry (query length, window count) share a pass, adapter calls of different query "
                         "lengths a call (serve.DecodeServer(mixed_prefill=True)); default off")
+    p.add_argument("--clip_prefilter", action="store_true",
+                   help="a query without a stage-1 record in --grounding_path gets its --batch windows from its CLS feature's per-frame cosines "
+                        "(stage2.clip_grounding_windows) instead of running every window; off: every code path is what it was")
     p.add_argument("--pool_rows", type=int, default=56, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per call at most (--in_flight > 1; answers are a dozen tokens)")
     return p.parse_args(argv)
@@ -212,6 +215,10 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
             if id_ in grounding_dict:
                 grounding_windows = prefilter_windows(grounding_dict[id_]["answer"], frame_idx.shape[0], batch, args.stride)
                 frame_idx = frame_idx[grounding_windows]
+            elif getattr(args, "clip_prefilter", False) and query_cls is not None:
+                grounding_windows = stage2.clip_grounding_windows(features, query_cls, debug_window=args.debug_window, feature_fps=args.feature_fps,
+                                                                  stride=args.stride, batch=batch)
+                frame_idx = frame_idx[grounding_windows]
             else:
                 grounding_windows = list(range(frame_idx.shape[0]))
             staged = stager.stage_windows(features, frame_idx)
@@ -281,6 +288,10 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, groundin
             _, frame_idx = stage2.cut_windows(len(features), args.debug_window, args.feature_fps, args.stride, args.num_frames)
             if id_ in grounding_dict:
                 grounding_windows = prefilter_windows(grounding_dict[id_]["answer"], frame_idx.shape[0], args.batch, args.stride)
+                frame_idx = frame_idx[grounding_windows]
+            elif getattr(args, "clip_prefilter", False) and query_cls is not None:
+                grounding_windows = stage2.clip_grounding_windows(features, query_cls, debug_window=args.debug_window, feature_fps=args.feature_fps,
+                                                                  stride=args.stride, batch=args.batch)
                 frame_idx = frame_idx[grounding_windows]
             else:
                 grounding_windows = list(range(frame_idx.shape[0]))

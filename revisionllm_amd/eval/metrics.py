@@ -70,6 +70,33 @@ def grounding_metrics_ranked(keep_iou, first_hit, hit_iou=(0.1, 0.3, 0.5, 0.7, 0
     return metrics
 
 
+def window_recall(hit_rank, topk=(1, 5, 10, 50, 100)):
+    """Rank@K of the coarse window selection (``windows_selection`` of the reference's eval/evaluate_pre_filtered_window.py:31-74) from the device
+    selection: hit_rank [...] (``eval.similarity.select_windows`` with a ground truth: the first place of the selection sequence whose window overlaps
+    it, or -1; a torch tensor on any device, or a numpy array) -> a list of ``len(topk)`` fractions in [0, 1], the share of rows with
+    ``0 <= hit_rank < K`` for each K, as that function returns them.  One reduction on the input's device and one copy of ``len(topk)`` numbers."""
+    try:
+        topk = tuple(int(kk) for kk in topk)
+    except (TypeError, ValueError):
+        raise ValueError(f"window_recall: topk={topk!r} must be a sequence of integers") from None
+    if not topk or min(topk) < 1:
+        raise ValueError(f"window_recall: topk={topk} must hold positive integers")
+    if hasattr(hit_rank, "detach"):
+        import torch
+        hr = hit_rank.reshape(-1)
+        n = hr.shape[0]
+        if n == 0:
+            return None
+        counts = torch.stack([((hr >= 0) & (hr < kk)).sum() for kk in topk]).tolist()
+    else:
+        hr = np.asarray(hit_rank).reshape(-1)
+        n = hr.shape[0]
+        if n == 0:
+            return None
+        counts = [int(((hr >= 0) & (hr < kk)).sum()) for kk in topk]
+    return [c / n for c in counts]
+
+
 def load_predictions(path, distributed=16):
     """Concatenate the per-shard JSONL files of a run (:59-79)."""
     if distributed > 0:

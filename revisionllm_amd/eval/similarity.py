@@ -22,7 +22,12 @@ truth - their IoUs and first hits (``rv_span_rank``, one launch); ``eval.metrics
 Proposals (this build's addition; the reference's proposals come from the LLM): ``propose_spans`` turns the per-frame cosine rows themselves into
 candidate spans - the row smoothed, thresholded at several levels, stretches above a threshold with short gaps closed (``rv_span_propose``, one
 launch) - in the (centre, width) form every call above takes.  ``ground_queries`` chains the four device stages - cosine rows, proposals, span scores,
-ranking - into a grounder that needs no proposals from outside and never synchronises: ``Grounding(spans, scores, n_keep, proposals, rank)``."""
+ranking - into a grounder that needs no proposals from outside and never synchronises: ``Grounding(spans, scores, n_keep, proposals, rank)``.
+
+Window selection (the reference evaluates this stage in evaluate_pre_filtered_window.py and feeds it from a stage-1 LLM log, e2e2.py:278-294):
+``select_windows`` turns the cosine rows into the sorted window list ``run_query(grounding_windows=)`` takes - every window of ``cut_windows``'
+geometry scored by its top-k cosines, the best ``keep`` spread at least ``min_sep`` apart (``rv_window_select``, one launch) - and, given a ground
+truth, the place of the first window that overlaps it (``eval.metrics.window_recall``)."""
 import collections
 import math
 
@@ -262,6 +267,44 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     kept_scores = torch.where(held, torch.gather(scores, -1, at), nan)
     back = lambda tup: type(tup)(*(None if t is None else t.to(home) for t in tup))                 # noqa: E731
     return Grounding(spans.to(home), kept_scores.to(home), held.sum(-1, dtype=torch.int32).to(home), back(proposals), back(rank))
+
+
+def select_windows(text, video, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):
+    """Choose the stage-2 recursion's windows from the CLIP features alone: text [B, d] or [B, Q, d], video [B, L, d], mask [B, L], gt [..., 2] rows of
+    (start, end) in frames or None -> ``ops.WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)``.  Two device stages: the
+    cosine rows (``ops.frame_cosine[_multi]``) and ``ops.window_select`` on them with the same keywords (``rv_window_select``: the windows of
+    ``stage2.cut_windows`` for ``clip_length = win``, each scored by its ``k`` largest cosines, taken in rank order at least ``min_sep`` indices apart,
+    topped up in rank order, the first ``keep`` handed back ascending - the form of ``run_query(grounding_windows=)``).  ``hit_rank`` feeds
+    ``eval.metrics.window_recall``.  No synchronisation and no device -> host copy when the inputs live on the device; host tensors are staged and
+    every result comes back on the device ``video`` lives on."""
+    who = "select_windows"
+    for name, t in (("text", text), ("video", video), ("mask", mask)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
+    multi = text.dim() == 3
+    if video.dim() != 3 or text.dim() not in (2, 3) or text.shape[0] != video.shape[0] or text.shape[-1] != video.shape[2] or min(text.shape) == 0:
+        raise ValueError(f"{who}: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, d] or [B, Q, d] and [B, L, d])")
+    if mask.shape != video.shape[:2]:
+        raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected [B, L])")
+    if min(video.shape) == 0:
+        raise ValueError(f"{who}: empty video {tuple(video.shape)}")
+    for name, t in (("text", text), ("video", video)):
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{who}: {name} must be a floating-point tensor (got {t.dtype})")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    if video.shape[1] > ops.SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={video.shape[1]} frames (at most {ops.SPAN_PROPOSE_MAX_FRAMES})")
+    kw = ops.window_select_keywords(who, win, stride, keep, k, min_sep)
+    ops.window_select_capacity(who, video.shape[1], kw[0], kw[1], kw[4])
+    ops.window_select_gt(who, gt, tuple(text.shape[:-1]))
+    home = video.device
+    dev = _device_of(video, who)
+    sims = (ops.frame_cosine_multi if multi else ops.frame_cosine)(ops.h2d(text, dev).float(), _features_up(video, dev))
+    out = ops.window_select(sims, ops.h2d(mask, dev), win=win, stride=stride, keep=keep, k=k, min_sep=min_sep,
+                            gt=None if gt is None else ops.h2d(gt, dev).float(), return_scores=return_scores, return_bounds=return_bounds,
+                            return_order=return_order)
+    return ops.WindowSelection(*(None if t is None else t.to(home) for t in out))
 
 
 def _get_predicted_proposal_feat(src_vid_appear, src_vid_appear_mask, pred_proposal, text_cls_features):

@@ -15,6 +15,7 @@ the reference's own functions (tests/golden/g9_driver.json).
 """
 import json
 import math
+import numbers
 import re
 
 import numpy as np
@@ -41,6 +42,34 @@ def cut_windows(ctx_l, debug_window=125, feature_fps=5, stride=5, num_frames=250
         times.append((start, end))
         idx.append(np.linspace(start, end, num_frames, dtype=np.int32))
     return times, (np.stack(idx) if idx else np.zeros((0, num_frames), np.int32))
+
+
+def clip_grounding_windows(features, query_cls, *, debug_window=125, feature_fps=5, stride=5, batch=100, k=3, min_sep=1):
+    """The windows the recursion should see for one query, chosen from the CLIP features alone: features [ctx_l, d] (numpy array or tensor, on the host
+    or the device), query_cls [d] -> a sorted Python list of at most ``batch`` distinct window indices of ``cut_windows(ctx_l, debug_window,
+    feature_fps, stride)``.  A drop-in for the stage-1 pre-filter's result (``prefilter_windows`` of the stage-2 driver, which needs the log of a
+    stage-1 LLM pass): it indexes ``frame_idx`` and is what ``run_query(grounding_windows=)`` takes.  Every window is scored by the sum of its ``k``
+    largest per-frame cosines with the query; the best are taken at least ``min_sep`` window indices apart and topped up in rank order
+    (``eval.similarity.select_windows``: two launches).  The ``.tolist()`` of the selected row at the end is the ONE device -> host copy of the
+    chain (and its only synchronisation).  ``debug_window * feature_fps`` must be a whole number of frames."""
+    who = "clip_grounding_windows"
+    from . import similarity
+    clip_length = debug_window * feature_fps
+    if not (isinstance(clip_length, numbers.Real) and not isinstance(clip_length, bool) and math.isfinite(clip_length) and clip_length == int(clip_length)
+            and clip_length >= 1):
+        raise ValueError(f"{who}: debug_window * feature_fps = {clip_length!r} must be a positive whole number of frames")
+    if not (isinstance(batch, numbers.Integral) and not isinstance(batch, bool) and batch >= 1):
+        raise ValueError(f"{who}: batch={batch!r} must be a positive integer")
+    as_tensor = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))               # noqa: E731
+    features, query_cls = as_tensor(features), as_tensor(query_cls)
+    if features.dim() != 2 or query_cls.dim() != 1 or query_cls.shape[0] != features.shape[1] or min(features.shape) == 0:
+        raise ValueError(f"{who}: features {tuple(features.shape)} / query_cls {tuple(query_cls.shape)} (expected [ctx_l, d] and [d])")
+    if not features.dtype.is_floating_point or not query_cls.dtype.is_floating_point:
+        raise ValueError(f"{who}: features and query_cls must be floating point (got {features.dtype}, {query_cls.dtype})")
+    ctx_l = features.shape[0]
+    sel = similarity.select_windows(query_cls[None].to(features.device), features[None], torch.ones(1, ctx_l, device=features.device),
+                                    win=int(clip_length), stride=stride, keep=batch, k=k, min_sep=min_sep)
+    return [i for i in sel.select[0].tolist() if i >= 0]
 
 
 def plan_groups(W, batch, zooms=(4, 2, 1)):

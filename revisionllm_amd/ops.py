@@ -570,6 +570,78 @@ def span_propose(sims, mask, *, levels=SPAN_PROPOSE_LEVELS, relative=True, smoot
     return SpanProposals(spans, n_spans, n_found, windows, smoothed)
 
 
+WINDOW_SELECT_MAX = 2048
+WindowSelection = collections.namedtuple("WindowSelection", "select n_select n_windows scores bounds order hit_rank")
+
+
+def window_select_keywords(who, win, stride, keep, k=3, min_sep=1):
+    """The keyword refusals of ``window_select`` that need no tensor (raised before any device is looked for) -> the five as ints."""
+    for name, v in (("win", win), ("stride", stride), ("keep", keep), ("k", k), ("min_sep", min_sep)):
+        if not (_is_int(v) and 1 <= v < 2 ** 31):
+            raise ValueError(f"{who}: {name}={v!r} must be a positive integer")
+    if win < stride:
+        raise ValueError(f"{who}: win={win} frames with stride={stride} (stride <= win)")
+    if k > 64:
+        raise ValueError(f"{who}: k={k} must be in [1, 64]")
+    return int(win), int(stride), int(keep), int(k), int(min_sep)
+
+
+def window_select_capacity(who, L, win, stride, min_sep=1):
+    """Wcap = max(1, ceil(L / (win // stride)) - 1), the most windows a row of L frames can have; refuses win > L, more than 2048 windows and
+    min_sep > Wcap."""
+    if win > L:
+        raise ValueError(f"{who}: win={win} frames for rows of L={L}")
+    hop = win // stride
+    cap = max(1, -(-L // hop) - 1)
+    if cap > WINDOW_SELECT_MAX:
+        raise ValueError(f"{who}: L={L}, win={win}, stride={stride} give up to {cap} windows (at most {WINDOW_SELECT_MAX})")
+    if min_sep > cap:
+        raise ValueError(f"{who}: min_sep={min_sep} must be in [1, {cap}] (the most windows a row of L={L} can have)")
+    return cap
+
+
+def window_select_gt(who, gt, lead):
+    if gt is None:
+        return
+    if not torch.is_tensor(gt) or gt.shape != lead + (2,):
+        raise ValueError(f"{who}: gt {tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__} (expected {lead + (2,)}: rows of (start, end) in frames)")
+    if not gt.dtype.is_floating_point:
+        raise ValueError(f"{who}: gt must be a floating-point tensor (got {gt.dtype})")
+
+
+def window_select(sims, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):
+    """Choose the recursion's windows from similarity rows on the device (``rv_window_select``): sims f32 [R,L] or [B,Q,L] (``frame_cosine`` /
+    ``frame_cosine_multi``'s rows), mask [R,L] / [B,L] of any bool, integer or float dtype (its row sum is the duration; with fewer rows than sims each
+    serves a whole number of consecutive rows), gt [...,2] rows of (start, end) in frames or None -> WindowSelection(select i32 [...,keep] ascending
+    with -1 padding, n_select i32 [...], n_windows i32 [...], scores f32 [...,Wcap] with NaN padding, bounds i32 [mask rows,Wcap,2] as (lo, hi) with
+    (-1, -1) padding, order i32 [...,Wcap] with -1 padding, hit_rank i32 [...]); ``scores``, ``bounds`` and ``order`` are None unless asked for,
+    ``hit_rank`` unless ``gt`` is given.  The windows are ``stage2.cut_windows``' for ``clip_length = win``; a window's score is the sum of its ``k``
+    largest sims; the windows are taken in rank order, a taken one removing the others within ``min_sep`` indices of it, then topped up in rank order;
+    ``select`` is the first ``min(keep, n_windows)`` of that sequence sorted, ``hit_rank`` the first place of the sequence whose window overlaps gt.
+    ``Wcap = max(1, ceil(L / (win // stride)) - 1)``; a ``keep`` above it is Wcap.  One launch (a mask that is not f32 adds a cast kernel), no
+    synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
+    who = "window_select"
+    win, stride, keep, k, min_sep = window_select_keywords(who, win, stride, keep, k, min_sep)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    Wcap = window_select_capacity(who, L, win, stride, min_sep)
+    window_select_gt(who, gt, lead)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    keep = min(keep, Wcap)
+    dev = sims.device
+    select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
+    n_select = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
+    scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
+    bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
+    order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
+    hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
+    hip.check(hip.lib().rv_window_select(hip.ptr(_c(sims)), hip.ptr(_c(mask.float())), R, rpm, L, win, stride, k, keep, min_sep, Wcap,
+                                         hip.ptr(_c(gt.float())) if gt is not None else None, hip.ptr(select), hip.ptr(n_select), hip.ptr(n_windows),
+                                         hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()), "rv_window_select")
+    return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
+
+
 def attn_pool(text_embeds, video_embeds, temperature):
     """``_attention_pooling`` (similarity.py:96-113) on the device: text [Nt,d], video [Nv,T,d] (16-bit operands or f32) -> f32 [Nv,Nt,d] =
     ``sum_t softmax_t(<f_t, text_j> / temperature) f_t``."""
