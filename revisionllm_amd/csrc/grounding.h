@@ -1,0 +1,119 @@
+// What the stages of the CLIP grounding chain share, one definition each: the frame order of the score kernels, the rank key of a score, the bitonic
+// sort of (key, index) pairs, the duration rule and the small helpers around them.  Included by the chain's translation units only (sample.hip for
+// rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip): two stages that have to agree bit for bit call the same code.
+#pragma once
+#include "kernels.h"
+
+namespace {
+
+constexpr int TOPK_FRAMES_MAX = 64;   // the most frames a top-k score adds up: k of rv_span_scores(_multi), rv_topk_pool and rv_window_select
+
+__device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
+__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
+__device__ __forceinline__ int top_bit(uint64_t w) { return 63 - __clzll((long long)w); }   // w != 0
+__device__ __forceinline__ bool span_solid(float s, float e) { return fabsf(s) < INFINITY && fabsf(e) < INFINITY && e > s; }   // not void
+
+template <typename T>
+__device__ __forceinline__ float ld(const T* p);
+template <>
+__device__ __forceinline__ float ld<float>(const float* p) { return *p; }
+template <>
+__device__ __forceinline__ float ld<op16_t>(const op16_t* p) { return op16_to_f32(*p); }
+
+// VEC features from p as f32: one element, or one 16-byte load (VEC = 16 B / sizeof(T), p 16-byte aligned)
+template <typename T, int VEC>
+__device__ __forceinline__ void load_features(const T* p, float (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = ld<T>(p);
+    } else if constexpr (sizeof(T) == 2) {
+        const op16x8 r = *(const op16x8*)p;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = op16_to_f32((op16_t)r[e]);
+    } else {
+        const f32x4 r = *(const f32x4*)p;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = r[e];
+    }
+}
+
+// ---- frame order ----
+// The order of the score kernels (torch.topk's): NaN before every number, then the larger value, then the smaller frame index.  A strict total
+// order over (value, index) pairs with distinct indices, so "the first entry strictly after the previous pick" walks the frames in rank order
+// without marking the picked ones: no round can return a frame twice or, while rounds <= frames, none at all.
+struct ArgMax {
+    float v;
+    int i;
+};
+__device__ __forceinline__ bool rank_before(ArgMax a, ArgMax b) {  // a ranks strictly before b
+    const bool an = a.v != a.v, bn = b.v != b.v;
+    if (an != bn) return an;
+    return (an || a.v == b.v) ? a.i < b.i : a.v > b.v;
+}
+__device__ __forceinline__ ArgMax rank_none() { return ArgMax{-INFINITY, 0x7fffffff}; }   // after every frame's entry
+__device__ __forceinline__ ArgMax rank_start() { return ArgMax{qnan(), -1}; }             // before every frame's entry
+__device__ __forceinline__ ArgMax rank_next(ArgMax best, ArgMax prev, ArgMax c) {  // the earlier of best and c among the entries after prev
+    return (rank_before(prev, c) && rank_before(c, best)) ? c : best;
+}
+__device__ __forceinline__ ArgMax wave_rank_first(ArgMax a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ArgMax b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
+        a = rank_before(b, a) ? b : a;
+    }
+    return a;
+}
+
+// ---- score key ----
+// Rank key of a score: an unsigned number that is SMALLER for what ranks earlier.  Numbers in descending order (-0 counts as +0, so the index decides
+// between them), every NaN behind -inf with the largest key.  Ties go to the smaller index: the pair (key, index) is compared, and a padding entry
+// carries the NaN key with an index past the row's entries, so it lands behind all of them.
+__device__ __forceinline__ uint32_t rank_key(float x) {
+    if (x != x) return 0xffffffffu;
+    uint32_t b = (uint32_t)__float_as_int(x);
+    if (b == 0x80000000u) b = 0u;
+    const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // ascending with the value
+    return ~asc;                                                         // (-inf: 0xff800000, below the NaN key)
+}
+
+// ---- sort ----
+// Bitonic sort of keys[0, P) in LDS, ascending, by the TPB threads of the block (all call; P a power of two; the caller's stores to keys lie behind a
+// barrier, and one ends every step here)
+template <int TPB>
+__device__ __forceinline__ void bitonic_sort_u64(uint64_t* keys, int P) {
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += TPB) {
+                const int i = 2 * t - (t & (j - 1)), l = i + j;      // the pair (i, i + j), bit j of i clear
+                const uint64_t a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0)) {
+                    keys[i] = b;
+                    keys[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- duration ----
+// The sum of a mask row, the same bits in every thread of the block (all call; red: TPB / 64 floats of LDS): per-thread partials over the frames
+// tid, tid + TPB, .., the wave's sum, then the waves' sums from left to right, every add rounded on its own.  One barrier, behind the stores to red.
+template <int TPB>
+__device__ __forceinline__ float block_mask_sum(const float* __restrict__ m, int L, float* red) {
+    float part = 0.f;
+    for (int i = threadIdx.x; i < L; i += TPB) part = __fadd_rn(part, m[i]);
+    part = wave_sum(part);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
+    __syncthreads();
+    float dur = red[0];
+#pragma unroll
+    for (int w = 1; w < TPB / 64; ++w) dur = __fadd_rn(dur, red[w]);
+    return dur;
+}
+// D = min(L, floor(dur)) frames; none for a sum that is not finite or below 1
+__device__ __forceinline__ int duration_frames(float dur, int L) {
+    if (!(fabsf(dur) < INFINITY && dur >= 1.f)) return 0;
+    return dur >= (float)L ? L : (int)floorf(dur);
+}
+
+}  // namespace

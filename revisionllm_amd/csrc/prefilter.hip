@@ -2,9 +2,9 @@
 // stage-1 LLM log, e2e2.py:278-294; here the choice comes from the per-frame cosine row):
 //   rv_window_select   per row: duration from the mask, every window of stage2.cut_windows' geometry scored by the sum of its top-k sims, rank order,
 //                      greedy selection with a minimum separation, top up in rank order, the first `keep` handed back ascending - one launch
-// The definition stands in include/revision_hip.h.  A window's score is accumulated add by add in rank order, as span_scores_kernel (sample.hip) does
+// The definition stands in include/revision_hip.h.  A window's score is accumulated add by add in rank order, as span_scores_kernel (similarity.hip) does
 // it, and everything after the scores is integer work, so a row's result does not depend on R, on the row's place or on any tiling.
-#include "kernels.h"
+#include "grounding.h"
 
 namespace {
 
@@ -29,38 +29,10 @@ struct WindowArgs {
     int L, rpm, win, stride, k, keep, min_sep, Wcap;
 };
 
-// The order of the score kernels (sample.hip): NaN before every number, then the larger value, then the smaller frame index
-struct Pick {
-    float v;
-    int i;
-};
-__device__ __forceinline__ bool pick_before(Pick a, Pick b) {
-    const bool an = a.v != a.v, bn = b.v != b.v;
-    if (an != bn) return an;
-    return (an || a.v == b.v) ? a.i < b.i : a.v > b.v;
-}
-__device__ __forceinline__ Pick wave_pick_first(Pick a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const Pick b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
-        a = pick_before(b, a) ? b : a;
-    }
-    return a;
-}
-
-// rv_span_rank's key map (similarity.hip): SMALLER for what ranks earlier; -0 counts as +0, every NaN behind -inf
-__device__ __forceinline__ uint32_t ws_rank_key(float x) {
-    if (x != x) return 0xffffffffu;
-    uint32_t b = (uint32_t)__float_as_int(x);
-    if (b == 0x80000000u) b = 0u;
-    const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ~asc;
-}
-
-// The same order as one unsigned number per frame, for a window held in registers: (frame key << 32 | frame index), SMALLER for what ranks earlier.
-// A NaN has the key 0, a number rv_span_rank's key (from 0x007fffff for +inf to 0xff800000 for -inf; -0 as +0, so the index decides between them as
-// a.v == b.v does above); 0xffffffff marks a slot behind the window's end.
-__device__ __forceinline__ uint32_t ws_frame_key(float x) { return x != x ? 0u : ws_rank_key(x); }
+// The frame order (grounding.h) as one unsigned number per frame, for a window held in registers: (frame key << 32 | frame index), SMALLER for what ranks earlier.
+// A NaN has the key 0, a number its rank_key (from 0x007fffff for +inf to 0xff800000 for -inf; -0 as +0, so the index decides between them as
+// rank_before()'s a.v == b.v does); 0xffffffff marks a slot behind the window's end.
+__device__ __forceinline__ uint32_t ws_frame_key(float x) { return x != x ? 0u : rank_key(x); }
 // the number behind a frame key != 0 (-0 comes back as +0: added to a sum that started at +0 it gives the same bits)
 __device__ __forceinline__ float ws_key_value(uint32_t key) {
     const uint32_t asc = ~key;
@@ -124,17 +96,8 @@ __global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs 
     const float* __restrict__ s = a.sims + r * L;
     const float* __restrict__ m = a.mask + (r / a.rpm) * L;
 
-    float part = 0.f;
-    for (int i = tid; i < L; i += WS_TPB) part = __fadd_rn(part, m[i]);
-    part = wave_sum(part);
-    if (lane == 0) red[wave] = part;
-    if (tid == 0) first = 0x7fffffff;
-    __syncthreads();
-    float dur = red[0];
-#pragma unroll
-    for (int w = 1; w < WS_WAVES; ++w) dur = __fadd_rn(dur, red[w]);
-    int D = 0;
-    if (fabsf(dur) < INFINITY && dur >= 1.f) D = dur >= (float)L ? L : (int)floorf(dur);
+    if (tid == 0) first = 0x7fffffff;           // (in front of the sum: its barrier covers this store)
+    const int D = duration_frames(block_mask_sum<WS_TPB>(m, L, red), L);
     const int hop = win / stride;
     int W = (D + hop - 1) / hop - 1;
     W = W < 0 ? 0 : W;                       // (W <= Wcap: D <= L)
@@ -169,20 +132,17 @@ __global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs 
                 from = best + 1ull;
             }
         } else {
-            Pick prev{__int_as_float(0x7fc00000), -1};                  // before every frame's entry
+            ArgMax prev = rank_start();
             for (int q = 0; q < rounds; ++q) {
-                Pick best{-INFINITY, 0x7fffffff};                       // after every frame's entry
-                for (int t = lo + lane; t < hi; t += 64) {
-                    const Pick c{s[t], t};
-                    if (pick_before(prev, c) && pick_before(c, best)) best = c;
-                }
-                best = wave_pick_first(best);
+                ArgMax best = rank_none();
+                for (int t = lo + lane; t < hi; t += 64) best = rank_next(best, prev, ArgMax{s[t], t});
+                best = wave_rank_first(best);
                 acc = __fadd_rn(acc, best.v);
                 prev = best;
             }
         }
         if (lane == 0) {
-            keys[i] = (uint64_t)ws_rank_key(acc) << 32 | (uint32_t)i;
+            keys[i] = (uint64_t)rank_key(acc) << 32 | (uint32_t)i;
             if (a.win_scores) a.win_scores[r * Wcap + i] = acc;
             if (to_bounds) {
                 bnd[2 * i] = lo;
@@ -191,7 +151,7 @@ __global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs 
         }
     }
     for (int i = W + tid; i < Wcap; i += WS_TPB) {
-        if (a.win_scores) a.win_scores[r * Wcap + i] = __int_as_float(0x7fc00000);
+        if (a.win_scores) a.win_scores[r * Wcap + i] = qnan();
         if (to_bounds) bnd[2 * i] = bnd[2 * i + 1] = -1;
         if (a.order) a.order[r * Wcap + i] = -1;
     }
@@ -201,19 +161,7 @@ __global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs 
         taken[i] = 0;
     }
     __syncthreads();
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += WS_TPB) {
-                const int i = 2 * t - (t & (j - 1)), l = i + j;      // the pair (i, i + j), bit j of i clear
-                const uint64_t x = keys[i], y = keys[l];
-                if ((x > y) == ((i & kk) == 0)) {
-                    keys[i] = y;
-                    keys[l] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort_u64<WS_TPB>(keys, P);
 
     const int n_sel = keep < W ? keep : W;
     const int limit = (a.order || a.hit_rank) ? W : n_sel;
@@ -263,7 +211,7 @@ __global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs 
         for (int p = tid; p < W; p += WS_TPB) a.order[r * Wcap + p] = seq[p];
     if (a.hit_rank) {
         const float gs = a.gt[r * 2], ge = a.gt[r * 2 + 1];
-        if (fabsf(gs) < INFINITY && fabsf(ge) < INFINITY && ge > gs) {
+        if (span_solid(gs, ge)) {
             int mine = 0x7fffffff;
             for (int p = tid; p < W; p += WS_TPB) {                    // ascending p: the first one found is this thread's smallest
                 int lo, hi;
@@ -311,7 +259,7 @@ extern "C" int rv_window_select(const float* sims, const float* mask, int32_t R,
     RV_CHECK_ARG(L >= 1 && L <= WS_MAX_L, "rv_window_select: L=%d must be in [1, %d]", L, WS_MAX_L);
     RV_CHECK_ARG(stride >= 1 && win >= stride && win <= L, "rv_window_select: win=%d frames with stride=%d (stride >= 1, stride <= win <= L=%d)", win, stride,
                  L);
-    RV_CHECK_ARG(k >= 1 && k <= 64, "rv_window_select: k=%d must be in [1, 64]", k);
+    RV_CHECK_ARG(k >= 1 && k <= TOPK_FRAMES_MAX, "rv_window_select: k=%d must be in [1, 64]", k);
     const int64_t hop = win / stride;
     const int64_t cap = cdiv(L, hop) - 1 > 1 ? cdiv(L, hop) - 1 : 1;
     RV_CHECK_ARG(cap <= WS_MAX_W, "rv_window_select: L=%d, win=%d, stride=%d give up to %lld windows (at most %d)", L, win, stride, (long long)cap, WS_MAX_W);
@@ -319,25 +267,7 @@ extern "C" int rv_window_select(const float* sims, const float* mask, int32_t R,
     RV_CHECK_ARG(keep >= 1 && keep <= Wcap, "rv_window_select: keep=%d must be in [1, Wcap=%d]", keep, Wcap);
     RV_CHECK_ARG(min_sep >= 1 && min_sep <= Wcap, "rv_window_select: min_sep=%d must be in [1, Wcap=%d]", min_sep, Wcap);
     RV_CHECK_ARG(gt || !hit_rank, "rv_window_select: hit_rank needs gt");
-    WindowArgs a{};
-    a.sims = sims;
-    a.mask = mask;
-    a.gt = gt;
-    a.select = select;
-    a.n_select = n_select;
-    a.n_windows = n_windows;
-    a.win_scores = win_scores;
-    a.bounds = bounds;
-    a.order = order;
-    a.hit_rank = hit_rank;
-    a.L = L;
-    a.rpm = rpm;
-    a.win = win;
-    a.stride = stride;
-    a.k = k;
-    a.keep = keep;
-    a.min_sep = min_sep;
-    a.Wcap = Wcap;
+    const WindowArgs a{sims, mask, gt, select, n_select, n_windows, win_scores, bounds, order, hit_rank, L, rpm, win, stride, k, keep, min_sep, Wcap};
     hipLaunchKernelGGL(window_select_kernel, dim3((unsigned)R), dim3(WS_TPB), 0, as_stream(stream), a);
     RV_CHECK_LAUNCH("rv_window_select");
     return RV_OK;

@@ -4,7 +4,7 @@
 //                     across levels dropped, (centre, width) spans in the form rv_span_scores / rv_span_rank read - one launch
 // The definition stands in include/revision_hip.h.  Every f32 operation is rounded on its own (__fadd_rn, __fsub_rn, __fmul_rn, __fdiv_rn), so a row's
 // result does not depend on R, on the row's place or on the tiling.
-#include "kernels.h"
+#include "grounding.h"
 
 namespace {
 
@@ -26,9 +26,6 @@ struct ProposeArgs {
     float levels[SP_LEVELS];
 };
 
-__device__ __forceinline__ uint64_t sp_low(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
-__device__ __forceinline__ int sp_top_bit(uint64_t w) { return 63 - __clzll((long long)w); }   // w != 0
-
 // s'[t0 + tid] of the row whose first D frames are s (NaN for a frame at or past D).  The tile and a halo of h frames on each side are staged in LDS;
 // no frame outside [0, D) is read.  The adds run in ascending order and one division follows.  The caller puts a barrier between two calls.
 __device__ __forceinline__ float sp_smooth(const float* __restrict__ s, float* stage, int t0, int D, int h) {
@@ -39,7 +36,7 @@ __device__ __forceinline__ float sp_smooth(const float* __restrict__ s, float* s
     }
     __syncthreads();
     const int t = t0 + tid;
-    float v = __int_as_float(0x7fc00000);
+    float v = qnan();
     if (t < D) {
         const int a = max(0, t - h), b = min(D - 1, t + h);
         const float* w = stage + (h - t0);                      // w[j] = s[j] for the frames staged
@@ -69,14 +66,8 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgs 
     const float* __restrict__ s = a.sims + r * L;
     const float* __restrict__ m = a.mask + (r / a.rpm) * L;
 
-    float part = 0.f;
-    for (int i = tid; i < L; i += SP_TPB) part = __fadd_rn(part, m[i]);
-    part = wave_sum(part);
-    if (lane == 0) red[0][wave] = part;
-    __syncthreads();
-    const float dur = __fadd_rn(__fadd_rn(__fadd_rn(red[0][0], red[0][1]), red[0][2]), red[0][3]);
-    int D = 0;
-    if (fabsf(dur) < INFINITY && dur >= 1.f) D = dur >= (float)L ? L : (int)floorf(dur);
+    const float dur = block_mask_sum<SP_TPB>(m, L, red[0]);
+    const int D = duration_frames(dur, L);
     const int ntiles = (D + SP_TPB - 1) / SP_TPB;
 
     // (1) s', its largest and smallest number (a NaN is skipped)
@@ -154,11 +145,11 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgs 
                     const uint64_t back = lane > 0 ? (cur << (64 - lane)) | (prv >> lane) : prv;              // bit i: frame t - 64 + i
                     const uint64_t fwd = lane < 63 ? (cur >> (lane + 1)) | (nxt << (63 - lane)) : nxt;        // bit i: frame t + 1 + i
                     const bool st = above && (back >> (64 - g1)) == 0ull;
-                    const bool en = above && (fwd & sp_low(g1)) == 0ull;
+                    const bool en = above && (fwd & low_bits(g1)) == 0ull;
                     const uint64_t sw = __ballot(st);
                     if (lane == 0) starts[l][wave] = sw;
-                    const uint64_t mine = sw & sp_low(lane + 1);
-                    if (mine) lo[l] = t0 + wave * 64 + sp_top_bit(mine);
+                    const uint64_t mine = sw & low_bits(lane + 1);
+                    if (mine) lo[l] = t0 + wave * 64 + top_bit(mine);
                     if (en) ends |= 1u << l;
                 }
             }
@@ -171,7 +162,7 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgs 
                     if ((ends >> l) & 1u) {
                         for (int w = wave - 1; w >= 0 && lo[l] < 0; --w) {
                             const uint64_t sw = starts[l][w];
-                            if (sw) lo[l] = t0 + w * 64 + sp_top_bit(sw);
+                            if (sw) lo[l] = t0 + w * 64 + top_bit(sw);
                         }
                         if (lo[l] < 0) lo[l] = open_lo[l];
                         const int len = t + 1 - lo[l];
@@ -181,7 +172,7 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgs 
                     }
                     const uint64_t ew = __ballot(e);
                     if (lane == 0) emits[l][wave] = ew;
-                    place[l] = __popcll(ew & sp_low(lane));
+                    place[l] = __popcll(ew & low_bits(lane));
                     if (e) emit |= 1u << l;
                 }
             }
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgs 
                         if (w < wave) before += c;
                         all += c;
                         const uint64_t sw = starts[l][w];
-                        if (sw) last = t0 + w * 64 + sp_top_bit(sw);
+                        if (sw) last = t0 + w * 64 + top_bit(sw);
                     }
                     if (pass == 1 && ((emit >> l) & 1u)) {
                         const int pos = base[l] + cnt[l] + before + place[l];
@@ -230,7 +221,7 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgs 
     const int kept = found < N ? found : N;
     for (int i = kept + tid; i < N; i += SP_TPB) {
         const int64_t o = (r * N + i) * 2;
-        a.spans[o] = a.spans[o + 1] = __int_as_float(0x7fc00000);
+        a.spans[o] = a.spans[o + 1] = qnan();
         if (a.windows) a.windows[o] = a.windows[o + 1] = -1;
     }
     if (tid == 0) {
@@ -259,23 +250,7 @@ extern "C" int rv_span_propose(const float* sims, const float* mask, int32_t R, 
     RV_CHECK_ARG(min_len >= 1, "rv_span_propose: min_len=%d must be >= 1", min_len);
     RV_CHECK_ARG(max_len >= 0 && (max_len == 0 || max_len >= min_len), "rv_span_propose: max_len=%d must be 0 (no limit) or >= min_len=%d", max_len, min_len);
     RV_CHECK_ARG(N >= 1 && N <= SP_MAX_N, "rv_span_propose: N=%d spans per row (1 to %d)", N, SP_MAX_N);
-    ProposeArgs a{};
-    a.sims = sims;
-    a.mask = mask;
-    a.spans = spans;
-    a.n_spans = n_spans;
-    a.n_found = n_found;
-    a.windows = windows;
-    a.smoothed = smoothed;
-    a.L = L;
-    a.rpm = rpm;
-    a.T = T;
-    a.relative = relative;
-    a.h = smooth / 2;
-    a.gap = gap;
-    a.min_len = min_len;
-    a.max_len = max_len;
-    a.N = N;
+    ProposeArgs a{sims, mask, spans, n_spans, n_found, windows, smoothed, L, rpm, T, relative, smooth / 2, gap, min_len, max_len, N, {}};
     for (int l = 0; l < T; ++l) a.levels[l] = levels[l];
     hipLaunchKernelGGL(span_propose_kernel, dim3((unsigned)R), dim3(SP_TPB), 0, as_stream(stream), a);
     RV_CHECK_LAUNCH("rv_span_propose");

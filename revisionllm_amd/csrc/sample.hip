@@ -3,23 +3,19 @@
 //                     entropy of the processed and of the raw next-token distribution
 //   rv_entropy_stats  get_entropy_statistics (funs_get_feature_X.py:120-146) over stacked per-step scores
 //   rv_topk_cosine    column-normalised top-k pooled cosine score (eval_nlq_retrieval_e2e2.py:380-386)
-//   rv_frame_cosine   per-frame cosine row of a whole video against its text CLS   } forward_clip_matching / _get_predicted_proposal_feat
-//   rv_span_scores    (centre, width) proposals -> windows -> top-k / softmax score  } (eval/similarity.py:24-69) without a host round trip
-//   rv_span_scores_multi  the same kernel over [B,Q] rows of similarities and proposals that share their video's mask row (after rv_frame_cosine_multi of similarity.hip)
-//   rv_attn_pool      _attention_pooling (eval/similarity.py:96-113)
-#include "kernels.h"
+//   rv_topk_pool      _topk_pooling (eval/similarity.py:71-94)
+// The two stage-2 scores rank frames in the grounding chain's order (grounding.h); the chain's own stages live in similarity.hip, rank.hip,
+// propose.hip and prefilter.hip.
+#include "grounding.h"
 
 namespace {
 
 constexpr int TPB = 1024;   // threads per row
 constexpr int ITEMS = 32;   // V <= 32768
-constexpr int KCAP = 64;
+constexpr int KCAP = 64;    // the sampler's candidate list (hip.TOPK_CAP)
 
-struct ArgMax {
-    float v;
-    int i;
-};
-__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {  // larger value, then smaller index
+// sample_kernel's order: larger value, then smaller index.  Its candidates are keys, never NaN, so it does not need rank_before()'s NaN rule.
+__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {
     return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
 __device__ __forceinline__ ArgMax wave_argmax(ArgMax a) {
@@ -27,29 +23,6 @@ __device__ __forceinline__ ArgMax wave_argmax(ArgMax a) {
     for (int o = 32; o > 0; o >>= 1) {
         ArgMax b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
         a = better(a, b);
-    }
-    return a;
-}
-
-// The order of the score kernels (torch.topk's): NaN before every number, then the larger value, then the smaller frame index.  A strict total
-// order over (value, index) pairs with distinct indices, so "the first entry strictly after the previous pick" walks the frames in rank order
-// without marking the picked ones: no round can return a frame twice or, while rounds <= frames, none at all.  (sample_kernel keeps better():
-// its candidates are keys, never NaN.)
-__device__ __forceinline__ bool rank_before(ArgMax a, ArgMax b) {  // a ranks strictly before b
-    const bool an = a.v != a.v, bn = b.v != b.v;
-    if (an != bn) return an;
-    return (an || a.v == b.v) ? a.i < b.i : a.v > b.v;
-}
-__device__ __forceinline__ ArgMax rank_none() { return ArgMax{-INFINITY, 0x7fffffff}; }                  // after every frame's entry
-__device__ __forceinline__ ArgMax rank_start() { return ArgMax{__int_as_float(0x7fc00000), -1}; }       // before every frame's entry
-__device__ __forceinline__ ArgMax rank_next(ArgMax best, ArgMax prev, ArgMax c) {  // the earlier of best and c among the entries after prev
-    return (rank_before(prev, c) && rank_before(c, best)) ? c : best;
-}
-__device__ __forceinline__ ArgMax wave_rank_first(ArgMax a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ArgMax b{__shfl_xor(a.v, o, 64), __shfl_xor(a.i, o, 64)};
-        a = rank_before(b, a) ? b : a;
     }
     return a;
 }
@@ -666,16 +639,9 @@ __global__ __launch_bounds__(TPB) void entropy_stats_kernel(const float* __restr
         out[b * 4 + 0] = mx;
         out[b * 4 + 1] = mn;
         out[b * 4 + 2] = mean;
-        out[b * 4 + 3] = G > 1 ? sqrtf(q / (float)(G - 1)) : __int_as_float(0x7fc00000);
+        out[b * 4 + 3] = G > 1 ? sqrtf(q / (float)(G - 1)) : qnan();
     }
 }
-
-template <typename T>
-__device__ __forceinline__ float ld(const T* p);
-template <>
-__device__ __forceinline__ float ld<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ld<op16_t>(const op16_t* p) { return op16_to_f32(*p); }
 
 // one block (1024 threads) per segment: column norms over frames, sims[t] = <f_t / norm, q>, sum of the k largest
 // (k <= 0: mean).  Phase 1 splits the frames over 4 thread groups per column block to keep ~T/4 loads per thread.
@@ -744,17 +710,6 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__
     float* sims = psum + groups * d;  // [Tn]
     const T* f = feat + (int64_t)blockIdx.x * Tn * d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto load = [&](const T* p, float (&v)[VEC]) {
-        if constexpr (sizeof(T) == 2) {
-            const op16x8 r = *(const op16x8*)p;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = op16_to_f32((op16_t)r[e]);
-        } else {
-            const f32x4 r = *(const f32x4*)p;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = r[e];
-        }
-    };
     if (tid < chunks * groups) {
         const int cc = tid % chunks, fg = tid / chunks;
         float ss[VEC];
@@ -762,7 +717,7 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__
         for (int e = 0; e < VEC; ++e) ss[e] = 0.f;
         for (int t = fg; t < Tn; t += groups) {
             float v[VEC];
-            load(f + (int64_t)t * d + cc * VEC, v);
+            load_features<T, VEC>(f + (int64_t)t * d + cc * VEC, v);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) ss[e] += v[e] * v[e];
         }
@@ -780,7 +735,7 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__
         float s1 = 0.f;
         for (int cc = lane; cc < chunks; cc += 64) {
             float v[VEC];
-            load(f + (int64_t)t * d + cc * VEC, v);
+            load_features<T, VEC>(f + (int64_t)t * d + cc * VEC, v);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) s1 += v[e] * qn[cc * VEC + e];
         }
@@ -815,7 +770,7 @@ __global__ __launch_bounds__(256) void topk_pool_kernel(const T* __restrict__ vi
     extern __shared__ float smem[];
     float* qs = smem;          // [d]
     float* sims = smem + d;    // [Tn]
-    __shared__ int sel[64];
+    __shared__ int sel[TOPK_FRAMES_MAX];
     const int v = blockIdx.x, tx = blockIdx.y;
     const T* f = video + (int64_t)v * Tn * d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -846,246 +801,6 @@ __global__ __launch_bounds__(256) void topk_pool_kernel(const T* __restrict__ vi
         o[c] = a;
     }
     if (out_idx && tid < k) out_idx[((int64_t)v * Nt + tx) * k + tid] = sel[tid];
-}
-
-// ---- proposal-query matching (eval/similarity.py:24-69) --------------------------------------------------------------------------------------
-// The reference scores a proposal by slicing its window out of the video, normalising every frame of the slice, pooling the top-k frames by
-// <frame / |frame|, text / |text|> and taking the pooled row's dot product with the text: the SUM of the top-k cosines of the window.  So the features
-// are read once into a cosine row (frame_cosine_kernel) and every span works on that row (span_scores_kernel).
-
-constexpr int FC_TPB = 256;        // 4 waves
-constexpr int FC_FRAMES = 32;      // frames of one block (8 per wave): the text row is normalised once per 32 frames
-constexpr int FC_FLIGHT = 4;       // frames a wave of the 16-byte-load path reads at a time
-constexpr int FC_DMAX = 8192;      // the staged text row: 32 KB of LDS
-
-// out[b, l] = <f_l, t_b> / (|f_l| |t_b|): the text row goes to LDS as t / |t| (a zero text: 0 / 0 = NaN in every column), a wave takes a frame, the dot
-// product and the sum of squares come from the same loads, and the division by |f_l| is the reference's (a zero frame: 0 / 0 = NaN).
-// VECTOR: 16-byte loads (d a multiple of 16 B / sizeof(T), 16-byte aligned rows), FC_FLIGHT frames of a wave in flight; else one element per lane and step.
-template <typename T, bool VECTOR>
-__global__ __launch_bounds__(FC_TPB) void frame_cosine_kernel(const T* __restrict__ video, const float* __restrict__ text, int L, int d,
-                                                              float* __restrict__ out) {
-    constexpr int VEC = 16 / (int)sizeof(T);
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // [d] t / |t|
-    __shared__ float red[FC_TPB / 64];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* t = text + (int64_t)b * d;
-    float ss = 0.f;
-    for (int c = tid; c < d; c += FC_TPB) {
-        const float v = t[c];
-        smem[c] = v;
-        ss += v * v;
-    }
-    ss = wave_sum(ss);
-    if (lane == 0) red[wave] = ss;
-    __syncthreads();
-    const float tnorm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-    for (int c = tid; c < d; c += FC_TPB) smem[c] = smem[c] / tnorm;    // (each thread rewrites the elements it wrote)
-    __syncthreads();
-    const int l0 = blockIdx.x * FC_FRAMES + wave * (FC_FRAMES / 4);
-    const int l1 = l0 + FC_FRAMES / 4 < L ? l0 + FC_FRAMES / 4 : L;
-    const T* f = video + (int64_t)b * L * d;
-    float* o = out + (int64_t)b * L;
-    if constexpr (VECTOR) {
-        const int chunks = d / VEC;
-        auto load = [&](const T* p, float (&v)[VEC]) {
-            if constexpr (sizeof(T) == 2) {
-                const op16x8 r = *(const op16x8*)p;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) v[e] = op16_to_f32((op16_t)r[e]);
-            } else {
-                const f32x4 r = *(const f32x4*)p;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) v[e] = r[e];
-            }
-        };
-        for (int l = l0; l < l1; l += FC_FLIGHT) {
-            const T* fr[FC_FLIGHT];
-            float dot[FC_FLIGHT], sq[FC_FLIGHT];
-#pragma unroll
-            for (int j = 0; j < FC_FLIGHT; ++j) {
-                fr[j] = f + (int64_t)(l + j < l1 ? l + j : l1 - 1) * d;     // (past the wave's last frame: that frame again, never a row outside the video)
-                dot[j] = sq[j] = 0.f;
-            }
-            for (int cc = lane; cc < chunks; cc += 64) {
-                float v[FC_FLIGHT][VEC];
-#pragma unroll
-                for (int j = 0; j < FC_FLIGHT; ++j) load(fr[j] + cc * VEC, v[j]);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const float tn = smem[cc * VEC + e];
-#pragma unroll
-                    for (int j = 0; j < FC_FLIGHT; ++j) {
-                        dot[j] += v[j][e] * tn;
-                        sq[j] += v[j][e] * v[j][e];
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < FC_FLIGHT; ++j) {
-                const float dj = wave_sum(dot[j]), qj = wave_sum(sq[j]);
-                if (lane == 0 && l + j < l1) o[l + j] = dj / sqrtf(qj);
-            }
-        }
-    } else {
-        for (int l = l0; l < l1; ++l) {
-            const T* fa = f + (int64_t)l * d;
-            float da = 0.f, qa = 0.f;
-            for (int c = lane; c < d; c += 64) {
-                const float v = ld<T>(fa + c);
-                da += v * smem[c];
-                qa += v * v;
-            }
-            da = wave_sum(da);
-            qa = wave_sum(qa);
-            if (lane == 0) o[l] = da / sqrtf(qa);
-        }
-    }
-}
-
-// f32 -> int32 as torch's .to(torch.int32) gives it for the values the reference meets; outside int32's range (undefined there) the value saturates
-__device__ __forceinline__ int sat_i32(float v) {
-    return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
-}
-
-// One wave per span (4 spans per block, all of row blockIdx.y).  A row is a video (rpm = 1, rv_span_scores) or one of a video's rpm queries
-// (rv_span_scores_multi): similarities, spans and outputs are indexed by the row, the mask - and hence the duration - by row / rpm ("rows per mask").
-// The block adds the row's mask row up first (duration; 0 / 1 masks: exact in any
-// order up to 2^24 frames; every block of a video repeats that sum - N / 4 reads of an L2-resident row of 4 L bytes - which is the price of keeping the
-// matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row:
-//   x1 = c - 0.5 w, x2 = c + 0.5 w, p = x * duration (every operation rounded to f32 on its own: no contraction), start = max(0, int(floor(p1))),
-//   end = int(ceil(p2)), and Python's range(L)[start:end] over the ARRAY length L: lo = min(start, L), hi = end < 0 ? max(end + L, 0) : min(end, L).
-// Every read of sims lies in [b L + lo, b L + hi).  MODE 0: the sum of the min(k, hi - lo) first entries in rank order (NaN, larger value, smaller
-// index: k wave-wide rank rounds over a lane-strided window, no LDS); MODE 1: sum_t softmax_t(s / tau) s_t in two lane-strided passes - the maximum, then both sums - (a NaN in
-// the window is carried next to the running maximum, which fmaxf would drop).  An empty window scores 0; a non-finite p1 / p2 gives NaN and the
-// window (-1, -1).
-template <int MODE>
-__global__ __launch_bounds__(256) void span_scores_kernel(const float* __restrict__ sims, const float* __restrict__ spans, const float* __restrict__ mask,
-                                                          int rpm, int L, int N, int k, float tau, float* __restrict__ scores,
-                                                          int32_t* __restrict__ windows) {
-    __shared__ float red[4];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {
-        const float* m = mask + (int64_t)(b / rpm) * L;
-        float s = 0.f;
-        for (int l = tid; l < L; l += 256) s += m[l];
-        s = wave_sum(s);
-        if (lane == 0) red[wave] = s;
-    }
-    __syncthreads();
-    const float duration = (red[0] + red[1]) + (red[2] + red[3]);
-    const int n = blockIdx.x * 4 + wave;
-    if (n >= N) return;
-    const int64_t sp = (int64_t)b * N + n;
-    const float c = spans[sp * 2], w = spans[sp * 2 + 1];
-    const float hw = __fmul_rn(0.5f, w);
-    const float p1 = __fmul_rn(__fsub_rn(c, hw), duration), p2 = __fmul_rn(__fadd_rn(c, hw), duration);
-    if (!(fabsf(p1) < INFINITY) || !(fabsf(p2) < INFINITY)) {      // NaN or +-inf
-        if (lane == 0) {
-            scores[sp] = __int_as_float(0x7fc00000);
-            if (windows) windows[sp * 2] = windows[sp * 2 + 1] = -1;
-        }
-        return;
-    }
-    int start = sat_i32(floorf(p1));
-    start = start < 0 ? 0 : start;
-    const int end = sat_i32(ceilf(p2));
-    const int lo = start < L ? start : L;
-    int hi;
-    if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
-    else hi = end < L ? end : L;
-    if (lane == 0 && windows) {
-        windows[sp * 2] = lo;
-        windows[sp * 2 + 1] = hi;
-    }
-    const float* s = sims + (int64_t)b * L;
-    float acc = 0.f;
-    if (hi > lo) {
-        if constexpr (MODE == 0) {
-            ArgMax prev = rank_start();
-            const int rounds = k < hi - lo ? k : hi - lo;
-            for (int r = 0; r < rounds; ++r) {
-                ArgMax best = rank_none();
-                for (int t = lo + lane; t < hi; t += 64) best = rank_next(best, prev, ArgMax{s[t], t});
-                best = wave_rank_first(best);
-                acc += best.v;
-                prev = best;
-            }
-        } else {
-            float mx = -INFINITY;
-            bool nan = false;
-            for (int t = lo + lane; t < hi; t += 64) {
-                const float x = s[t] / tau;
-                nan |= x != x;
-                mx = fmaxf(mx, x);
-            }
-            mx = wave_max(mx);
-            if (__ballot(nan) != 0ull) mx = __int_as_float(0x7fc00000);
-            float z = 0.f, zs = 0.f;
-            for (int t = lo + lane; t < hi; t += 64) {
-                const float v = s[t];
-                const float e = expf(v / tau - mx);
-                z += e;
-                zs += e * v;
-            }
-            acc = wave_sum(zs) / wave_sum(z);
-        }
-    }
-    if (lane == 0) scores[sp] = acc;
-}
-
-// _attention_pooling (similarity.py:96-113) for one (video, text) pair per block, laid out as topk_pool_kernel: x[t] = <f_t, q> / tau to LDS (one wave per
-// frame), the softmax over the frames with the maximum subtracted (a NaN x is carried into the maximum: the whole row is NaN then, as torch.softmax's
-// is), then out[c] = sum_t p[t] f[t][c] with the threads over the columns, frames in ascending order.
-template <typename T>
-__global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ video, const float* __restrict__ text, int Tn, int d, int Nt, float tau,
-                                                        float* __restrict__ out) {
-    extern __shared__ float smem[];
-    float* qs = smem;          // [d]
-    float* xs = smem + d;      // [Tn] x, then p
-    __shared__ float red[64];
-    const int v = blockIdx.x, tx = blockIdx.y;
-    const T* f = video + (int64_t)v * Tn * d;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int c = tid; c < d; c += 256) qs[c] = text[(int64_t)tx * d + c];
-    __syncthreads();
-    for (int t = wave; t < Tn; t += 4) {
-        float s = 0.f;
-        for (int c = lane; c < d; c += 64) s += ld<T>(f + (int64_t)t * d + c) * qs[c];
-        s = wave_sum(s);
-        if (lane == 0) xs[t] = s / tau;
-    }
-    __syncthreads();
-    float mx = -INFINITY;
-    bool nan = false;
-    for (int t = tid; t < Tn; t += 256) {
-        const float x = xs[t];
-        nan |= x != x;
-        mx = fmaxf(mx, x);
-    }
-    mx = wave_max(mx);
-    if (__ballot(nan) != 0ull) mx = __int_as_float(0x7fc00000);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    if (red[0] != red[0] || red[1] != red[1] || red[2] != red[2] || red[3] != red[3]) mx = __int_as_float(0x7fc00000);
-    float z = 0.f;
-    for (int t = tid; t < Tn; t += 256) {
-        const float e = expf(xs[t] - mx);
-        xs[t] = e;                                  // (each thread rewrites the elements it read)
-        z += e;
-    }
-    z = wave_sum(z);
-    if (lane == 0) red[4 + wave] = z;
-    __syncthreads();
-    z = (red[4] + red[5]) + (red[6] + red[7]);
-    for (int t = tid; t < Tn; t += 256) xs[t] = xs[t] / z;
-    __syncthreads();
-    float* o = out + ((int64_t)v * Nt + tx) * d;
-    for (int c = tid; c < d; c += 256) {
-        float a = 0.f;
-        for (int t = 0; t < Tn; ++t) a += xs[t] * ld<T>(f + (int64_t)t * d + c);
-        o[c] = a;
-    }
 }
 
 }  // namespace
@@ -1144,7 +859,7 @@ extern "C" int rv_topk_pool(const void* video, int dtype, const float* text, int
                             float* out, int32_t* out_idx, void* stream) {
     RV_CHECK_ARG(video && text && out && Nv > 0 && T > 0 && d > 0 && Nt > 0, "rv_topk_pool: bad arguments");
     RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_topk_pool: dtype must be f32 or bf16");
-    RV_CHECK_ARG(k >= 1 && k <= 64 && k <= T, "rv_topk_pool: k=%d must be in [1, min(64, T=%d)]", k, T);
+    RV_CHECK_ARG(k >= 1 && k <= TOPK_FRAMES_MAX && k <= T, "rv_topk_pool: k=%d must be in [1, min(64, T=%d)]", k, T);
     RV_CHECK_ARG(Nt <= 65535, "rv_topk_pool: at most 65535 texts per launch");
     const size_t sm = (size_t)(d + T) * sizeof(float);
     RV_CHECK_ARG(sm + 64 * sizeof(int) <= 64 * 1024, "rv_topk_pool: d + T too large for LDS (dynamic %zu B + 256 B static)", sm);
@@ -1153,76 +868,5 @@ extern "C" int rv_topk_pool(const void* video, int dtype, const float* text, int
     else
         hipLaunchKernelGGL(topk_pool_kernel<float>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const float*)video, text, T, d, Nt, k, out, out_idx);
     RV_CHECK_LAUNCH("rv_topk_pool");
-    return RV_OK;
-}
-
-extern "C" int rv_frame_cosine(const void* video, int dtype, const float* text, int32_t B, int32_t L, int32_t d, float* out, void* stream) {
-    RV_CHECK_ARG(video && text && out && B > 0 && L > 0 && d > 0, "rv_frame_cosine: bad arguments");
-    RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_frame_cosine: dtype must be f32 or %s", RV_OP16_NAME);
-    RV_CHECK_ARG(d <= FC_DMAX, "rv_frame_cosine: d=%d exceeds the %d columns of the staged text row", d, FC_DMAX);
-    RV_CHECK_ARG(B <= 65535, "rv_frame_cosine: at most 65535 videos per launch");
-    const int vec = dtype == RV_OP16 ? 8 : 4;
-    const bool vector = d % vec == 0 && ((uintptr_t)video & 15u) == 0;
-    const dim3 grid((unsigned)cdiv(L, FC_FRAMES), B);
-    const size_t sm = (size_t)d * sizeof(float);
-    hipStream_t st = as_stream(stream);
-    if (dtype == RV_OP16) {
-        if (vector) hipLaunchKernelGGL((frame_cosine_kernel<op16_t, true>), grid, dim3(FC_TPB), sm, st, (const op16_t*)video, text, L, d, out);
-        else hipLaunchKernelGGL((frame_cosine_kernel<op16_t, false>), grid, dim3(FC_TPB), sm, st, (const op16_t*)video, text, L, d, out);
-    } else {
-        if (vector) hipLaunchKernelGGL((frame_cosine_kernel<float, true>), grid, dim3(FC_TPB), sm, st, (const float*)video, text, L, d, out);
-        else hipLaunchKernelGGL((frame_cosine_kernel<float, false>), grid, dim3(FC_TPB), sm, st, (const float*)video, text, L, d, out);
-    }
-    RV_CHECK_LAUNCH("rv_frame_cosine");
-    return RV_OK;
-}
-
-extern "C" int rv_span_scores(const float* sims, const float* spans, const float* mask, int32_t B, int32_t L, int32_t N, int32_t mode, int32_t k,
-                              float temperature, float* scores, int32_t* windows, void* stream) {
-    RV_CHECK_ARG(sims && spans && mask && scores && B > 0 && L > 0 && N > 0, "rv_span_scores: bad arguments");
-    RV_CHECK_ARG(mode == 0 || mode == 1, "rv_span_scores: mode=%d must be 0 (top-k) or 1 (attention)", mode);
-    RV_CHECK_ARG(B <= 65535, "rv_span_scores: at most 65535 videos per launch");
-    const dim3 grid((unsigned)cdiv(N, 4), B);
-    if (mode == 0) {
-        RV_CHECK_ARG(k >= 1 && k <= KCAP, "rv_span_scores: k=%d must be in [1, %d]", k, KCAP);
-        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, 1, L, N, k, 1.0f, scores, windows);
-    } else {
-        RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_span_scores: temperature must be finite and not 0");
-        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, 1, L, N, k, temperature, scores, windows);
-    }
-    RV_CHECK_LAUNCH("rv_span_scores");
-    return RV_OK;
-}
-
-extern "C" int rv_span_scores_multi(const float* sims, const float* spans, const float* mask, int32_t B, int32_t Q, int32_t L, int32_t N, int32_t mode,
-                                    int32_t k, float temperature, float* scores, int32_t* windows, void* stream) {
-    RV_CHECK_ARG(sims && spans && mask && scores && B > 0 && Q > 0 && L > 0 && N > 0, "rv_span_scores_multi: bad arguments");
-    RV_CHECK_ARG(mode == 0 || mode == 1, "rv_span_scores_multi: mode=%d must be 0 (top-k) or 1 (attention)", mode);
-    RV_CHECK_ARG((int64_t)B * Q <= 65535, "rv_span_scores_multi: at most 65535 (video, query) rows per launch (B=%d, Q=%d)", B, Q);
-    const dim3 grid((unsigned)cdiv(N, 4), (unsigned)(B * Q));
-    if (mode == 0) {
-        RV_CHECK_ARG(k >= 1 && k <= KCAP, "rv_span_scores_multi: k=%d must be in [1, %d]", k, KCAP);
-        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, Q, L, N, k, 1.0f, scores, windows);
-    } else {
-        RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_span_scores_multi: temperature must be finite and not 0");
-        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, Q, L, N, k, temperature, scores, windows);
-    }
-    RV_CHECK_LAUNCH("rv_span_scores_multi");
-    return RV_OK;
-}
-
-extern "C" int rv_attn_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, float temperature,
-                            float* out, void* stream) {
-    RV_CHECK_ARG(video && text && out && Nv > 0 && T > 0 && d > 0 && Nt > 0, "rv_attn_pool: bad arguments");
-    RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_attn_pool: dtype must be f32 or %s", RV_OP16_NAME);
-    RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_attn_pool: temperature must be finite and not 0");
-    RV_CHECK_ARG(Nt <= 65535, "rv_attn_pool: at most 65535 texts per launch");
-    const size_t sm = (size_t)(d + T) * sizeof(float);
-    RV_CHECK_ARG(sm + 64 * sizeof(float) <= 64 * 1024, "rv_attn_pool: d + T too large for LDS (dynamic %zu B + 256 B static)", sm);
-    if (dtype == RV_OP16)
-        hipLaunchKernelGGL(attn_pool_kernel<op16_t>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const op16_t*)video, text, T, d, Nt, temperature, out);
-    else
-        hipLaunchKernelGGL(attn_pool_kernel<float>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const float*)video, text, T, d, Nt, temperature, out);
-    RV_CHECK_LAUNCH("rv_attn_pool");
     return RV_OK;
 }

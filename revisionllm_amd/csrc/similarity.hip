@@ -1,16 +1,250 @@
-// Proposal-query matching with several texts per video (forward_clip_matching, eval/similarity.py:24-69, for Q queries on the same features):
+// Proposal-query matching (forward_clip_matching / _get_predicted_proposal_feat, eval/similarity.py:24-69) without a host round trip, for one text
+// per video and for Q texts on the same features, and the two poolings beside it:
+//   rv_frame_cosine         per-frame cosine row of a whole video against its text CLS
 //   rv_frame_cosine_multi   the cosine rows of Q texts against every frame of their video, the features read once for all of them
-// (rv_span_scores_multi, the span kernel of rv_span_scores with one mask row per Q rows, lives next to that kernel in sample.hip.)
-// and the stage behind the scores (no counterpart in the reference, whose eval/metrics.py ranks on the host from JSON logs):
-//   rv_span_rank            per row of scored proposals: rank order, greedy temporal NMS, top-M, IoU against a ground-truth span and first hits
-//
-// With Q texts the rows are a small matrix product [Q x d] . [d x L] per video, which goes to the f32-input MFMA (v_mfma_f32_16x16x4_f32): per output
-// element that instruction is a k-ordered fmaf chain with no wider accumulation, so "all arithmetic f32" (the single-text kernel's contract) holds, a
-// 16-bit feature converted to f32 in a register is exact, and both builds and f32 features share this one code path and one error bound.
-#include "kernels.h"
+//   rv_span_scores          (centre, width) proposals -> windows -> top-k / softmax score
+//   rv_span_scores_multi    the same kernel over [B,Q] rows of similarities and proposals that share their video's mask row
+//   rv_attn_pool            _attention_pooling (eval/similarity.py:96-113)
+// (rv_topk_pool, the other pooling, stands with rv_topk_cosine in sample.hip.)  The stages behind the scores are rank.hip, propose.hip, prefilter.hip.
+#include "grounding.h"
 
 namespace {
 
+// ---- one text per video ----
+// The reference scores a proposal by slicing its window out of the video, normalising every frame of the slice, pooling the top-k frames by
+// <frame / |frame|, text / |text|> and taking the pooled row's dot product with the text: the SUM of the top-k cosines of the window.  So the features
+// are read once into a cosine row (frame_cosine_kernel) and every span works on that row (span_scores_kernel).
+
+constexpr int FC_TPB = 256;        // 4 waves
+constexpr int FC_FRAMES = 32;      // frames of one block (8 per wave): the text row is normalised once per 32 frames
+constexpr int FC_FLIGHT = 4;       // frames a wave of the 16-byte-load path reads at a time
+constexpr int FC_DMAX = 8192;      // the staged text row: 32 KB of LDS
+
+// out[b, l] = <f_l, t_b> / (|f_l| |t_b|): the text row goes to LDS as t / |t| (a zero text: 0 / 0 = NaN in every column), a wave takes a frame, the dot
+// product and the sum of squares come from the same loads, and the division by |f_l| is the reference's (a zero frame: 0 / 0 = NaN).
+// VECTOR: 16-byte loads (d a multiple of 16 B / sizeof(T), 16-byte aligned rows), FC_FLIGHT frames of a wave in flight; else one element per lane and step.
+template <typename T, bool VECTOR>
+__global__ __launch_bounds__(FC_TPB) void frame_cosine_kernel(const T* __restrict__ video, const float* __restrict__ text, int L, int d,
+                                                              float* __restrict__ out) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    // [d] t / |t|.  One symbol with the other kernels' smem: an aligned(16) here took effect or not with its neighbours in the file, so none is claimed
+    // (with it: two 16-byte LDS reads per chunk and 91 VGPRs instead of 110 in the 16-bit instance - not timed yet)
+    extern __shared__ float smem[];
+    __shared__ float red[FC_TPB / 64];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* t = text + (int64_t)b * d;
+    float ss = 0.f;
+    for (int c = tid; c < d; c += FC_TPB) {
+        const float v = t[c];
+        smem[c] = v;
+        ss += v * v;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) red[wave] = ss;
+    __syncthreads();
+    const float tnorm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    for (int c = tid; c < d; c += FC_TPB) smem[c] = smem[c] / tnorm;    // (each thread rewrites the elements it wrote)
+    __syncthreads();
+    const int l0 = blockIdx.x * FC_FRAMES + wave * (FC_FRAMES / 4);
+    const int l1 = l0 + FC_FRAMES / 4 < L ? l0 + FC_FRAMES / 4 : L;
+    const T* f = video + (int64_t)b * L * d;
+    float* o = out + (int64_t)b * L;
+    if constexpr (VECTOR) {
+        const int chunks = d / VEC;
+        for (int l = l0; l < l1; l += FC_FLIGHT) {
+            const T* fr[FC_FLIGHT];
+            float dot[FC_FLIGHT], sq[FC_FLIGHT];
+#pragma unroll
+            for (int j = 0; j < FC_FLIGHT; ++j) {
+                fr[j] = f + (int64_t)(l + j < l1 ? l + j : l1 - 1) * d;     // (past the wave's last frame: that frame again, never a row outside the video)
+                dot[j] = sq[j] = 0.f;
+            }
+            for (int cc = lane; cc < chunks; cc += 64) {
+                float v[FC_FLIGHT][VEC];
+#pragma unroll
+                for (int j = 0; j < FC_FLIGHT; ++j) load_features<T, VEC>(fr[j] + cc * VEC, v[j]);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const float tn = smem[cc * VEC + e];
+#pragma unroll
+                    for (int j = 0; j < FC_FLIGHT; ++j) {
+                        dot[j] += v[j][e] * tn;
+                        sq[j] += v[j][e] * v[j][e];
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < FC_FLIGHT; ++j) {
+                const float dj = wave_sum(dot[j]), qj = wave_sum(sq[j]);
+                if (lane == 0 && l + j < l1) o[l + j] = dj / sqrtf(qj);
+            }
+        }
+    } else {
+        for (int l = l0; l < l1; ++l) {
+            const T* fa = f + (int64_t)l * d;
+            float da = 0.f, qa = 0.f;
+            for (int c = lane; c < d; c += 64) {
+                const float v = ld<T>(fa + c);
+                da += v * smem[c];
+                qa += v * v;
+            }
+            da = wave_sum(da);
+            qa = wave_sum(qa);
+            if (lane == 0) o[l] = da / sqrtf(qa);
+        }
+    }
+}
+
+// f32 -> int32 as torch's .to(torch.int32) gives it for the values the reference meets; outside int32's range (undefined there) the value saturates
+__device__ __forceinline__ int sat_i32(float v) {
+    return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
+}
+
+// One wave per span (4 spans per block, all of row blockIdx.y).  A row is a video (rpm = 1, rv_span_scores) or one of a video's rpm queries
+// (rv_span_scores_multi): similarities, spans and outputs are indexed by the row, the mask - and hence the duration - by row / rpm ("rows per mask").
+// The block adds the row's mask row up first (duration; 0 / 1 masks: exact in any
+// order up to 2^24 frames; every block of a video repeats that sum - N / 4 reads of an L2-resident row of 4 L bytes - which is the price of keeping the
+// matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row:
+//   x1 = c - 0.5 w, x2 = c + 0.5 w, p = x * duration (every operation rounded to f32 on its own: no contraction), start = max(0, int(floor(p1))),
+//   end = int(ceil(p2)), and Python's range(L)[start:end] over the ARRAY length L: lo = min(start, L), hi = end < 0 ? max(end + L, 0) : min(end, L).
+// Every read of sims lies in [b L + lo, b L + hi).  MODE 0: the sum of the min(k, hi - lo) first entries in rank order (NaN, larger value, smaller
+// index: k wave-wide rank rounds over a lane-strided window, no LDS); MODE 1: sum_t softmax_t(s / tau) s_t in two lane-strided passes - the maximum, then both sums - (a NaN in
+// the window is carried next to the running maximum, which fmaxf would drop).  An empty window scores 0; a non-finite p1 / p2 gives NaN and the
+// window (-1, -1).
+template <int MODE>
+__global__ __launch_bounds__(256) void span_scores_kernel(const float* __restrict__ sims, const float* __restrict__ spans, const float* __restrict__ mask,
+                                                          int rpm, int L, int N, int k, float tau, float* __restrict__ scores,
+                                                          int32_t* __restrict__ windows) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    {   // not block_mask_sum(): the contract here is the raw f32 sum with the wave partials added pairwise - other bits on a mask that is not 0 / 1
+        const float* m = mask + (int64_t)(b / rpm) * L;
+        float s = 0.f;
+        for (int l = tid; l < L; l += 256) s += m[l];
+        s = wave_sum(s);
+        if (lane == 0) red[wave] = s;
+    }
+    __syncthreads();
+    const float duration = (red[0] + red[1]) + (red[2] + red[3]);
+    const int n = blockIdx.x * 4 + wave;
+    if (n >= N) return;
+    const int64_t sp = (int64_t)b * N + n;
+    const float c = spans[sp * 2], w = spans[sp * 2 + 1];
+    const float hw = __fmul_rn(0.5f, w);
+    const float p1 = __fmul_rn(__fsub_rn(c, hw), duration), p2 = __fmul_rn(__fadd_rn(c, hw), duration);
+    if (!(fabsf(p1) < INFINITY) || !(fabsf(p2) < INFINITY)) {      // NaN or +-inf
+        if (lane == 0) {
+            scores[sp] = qnan();
+            if (windows) windows[sp * 2] = windows[sp * 2 + 1] = -1;
+        }
+        return;
+    }
+    int start = sat_i32(floorf(p1));
+    start = start < 0 ? 0 : start;
+    const int end = sat_i32(ceilf(p2));
+    const int lo = start < L ? start : L;
+    int hi;
+    if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
+    else hi = end < L ? end : L;
+    if (lane == 0 && windows) {
+        windows[sp * 2] = lo;
+        windows[sp * 2 + 1] = hi;
+    }
+    const float* s = sims + (int64_t)b * L;
+    float acc = 0.f;
+    if (hi > lo) {
+        if constexpr (MODE == 0) {
+            ArgMax prev = rank_start();
+            const int rounds = k < hi - lo ? k : hi - lo;
+            for (int r = 0; r < rounds; ++r) {
+                ArgMax best = rank_none();
+                for (int t = lo + lane; t < hi; t += 64) best = rank_next(best, prev, ArgMax{s[t], t});
+                best = wave_rank_first(best);
+                acc += best.v;
+                prev = best;
+            }
+        } else {
+            float mx = -INFINITY;
+            bool nan = false;
+            for (int t = lo + lane; t < hi; t += 64) {
+                const float x = s[t] / tau;
+                nan |= x != x;
+                mx = fmaxf(mx, x);
+            }
+            mx = wave_max(mx);
+            if (__ballot(nan) != 0ull) mx = qnan();
+            float z = 0.f, zs = 0.f;
+            for (int t = lo + lane; t < hi; t += 64) {
+                const float v = s[t];
+                const float e = expf(v / tau - mx);
+                z += e;
+                zs += e * v;
+            }
+            acc = wave_sum(zs) / wave_sum(z);
+        }
+    }
+    if (lane == 0) scores[sp] = acc;
+}
+
+// _attention_pooling (similarity.py:96-113) for one (video, text) pair per block, laid out as topk_pool_kernel: x[t] = <f_t, q> / tau to LDS (one wave per
+// frame), the softmax over the frames with the maximum subtracted (a NaN x is carried into the maximum: the whole row is NaN then, as torch.softmax's
+// is), then out[c] = sum_t p[t] f[t][c] with the threads over the columns, frames in ascending order.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_pool_kernel(const T* __restrict__ video, const float* __restrict__ text, int Tn, int d, int Nt, float tau,
+                                                        float* __restrict__ out) {
+    extern __shared__ float smem[];
+    float* qs = smem;          // [d]
+    float* xs = smem + d;      // [Tn] x, then p
+    __shared__ float red[64];
+    const int v = blockIdx.x, tx = blockIdx.y;
+    const T* f = video + (int64_t)v * Tn * d;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int c = tid; c < d; c += 256) qs[c] = text[(int64_t)tx * d + c];
+    __syncthreads();
+    for (int t = wave; t < Tn; t += 4) {
+        float s = 0.f;
+        for (int c = lane; c < d; c += 64) s += ld<T>(f + (int64_t)t * d + c) * qs[c];
+        s = wave_sum(s);
+        if (lane == 0) xs[t] = s / tau;
+    }
+    __syncthreads();
+    float mx = -INFINITY;
+    bool nan = false;
+    for (int t = tid; t < Tn; t += 256) {
+        const float x = xs[t];
+        nan |= x != x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if (__ballot(nan) != 0ull) mx = qnan();
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (red[0] != red[0] || red[1] != red[1] || red[2] != red[2] || red[3] != red[3]) mx = qnan();
+    float z = 0.f;
+    for (int t = tid; t < Tn; t += 256) {
+        const float e = expf(xs[t] - mx);
+        xs[t] = e;                                  // (each thread rewrites the elements it read)
+        z += e;
+    }
+    z = wave_sum(z);
+    if (lane == 0) red[4 + wave] = z;
+    __syncthreads();
+    z = (red[4] + red[5]) + (red[6] + red[7]);
+    for (int t = tid; t < Tn; t += 256) xs[t] = xs[t] / z;
+    __syncthreads();
+    float* o = out + ((int64_t)v * Nt + tx) * d;
+    for (int c = tid; c < d; c += 256) {
+        float a = 0.f;
+        for (int t = 0; t < Tn; ++t) a += xs[t] * ld<T>(f + (int64_t)t * d + c);
+        o[c] = a;
+    }
+}
+
+// ---- several texts per video ----
+// With Q texts the rows are a small matrix product [Q x d] . [d x L] per video, which goes to the f32-input MFMA (v_mfma_f32_16x16x4_f32): per output
+// element that instruction is a k-ordered fmaf chain with no wider accumulation, so "all arithmetic f32" (the single-text kernel's contract) holds, a
+// 16-bit feature converted to f32 in a register is exact, and both builds and f32 features share this one code path and one error bound.
 constexpr int CM_TPB = 256;      // 4 waves
 constexpr int CM_FT = 2;         // 16-frame MFMA tiles of a wave: a text fragment is loaded once for both
 constexpr int CM_FRAMES = 4 * 16 * CM_FT;   // frames of one block (128)
@@ -29,22 +263,6 @@ __global__ __launch_bounds__(256) void text_unit_kernel(const float* __restrict_
     const float norm = sqrtf(wave_sum(ss));
     float* u = unit + r * d;
     for (int c = lane; c < d; c += 64) u[c] = t[c] / norm;
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_features(const T* p, float (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        if constexpr (sizeof(T) == 2) v[0] = op16_to_f32(*p);
-        else v[0] = *p;
-    } else if constexpr (sizeof(T) == 2) {
-        const op16x8 r = *(const op16x8*)p;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = op16_to_f32((op16_t)r[e]);
-    } else {
-        const f32x4 r = *(const f32x4*)p;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = r[e];
-    }
 }
 
 template <int VEC>
@@ -177,226 +395,28 @@ __global__ __launch_bounds__(CM_TPB) void frame_cosine_multi_kernel(const T* __r
     }
 }
 
-
-// ---- rv_span_rank: sort, greedy temporal NMS, top-M and hits against a ground-truth span, one launch ----
-// Rank key of a score: an unsigned number that is SMALLER for what ranks earlier.  Numbers in descending order (-0 counts as +0, so the index decides
-// between them), every NaN behind -inf with the largest key.  Ties go to the smaller index: the pair (key, index) is compared, and a padding entry
-// carries the NaN key with an index >= N, so it lands behind every proposal.
-__device__ __forceinline__ uint32_t rank_key(float x) {
-    if (x != x) return 0xffffffffu;
-    uint32_t b = (uint32_t)__float_as_int(x);
-    if (b == 0x80000000u) b = 0u;
-    const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // ascending with the value
-    return ~asc;                                                         // (-inf: 0xff800000, below the NaN key)
-}
-// (start, end) of a proposal: form 1 is (centre, width) under span_cxw_to_xx's rule, each operation rounded on its own
-__device__ __forceinline__ void span_bounds(const float* __restrict__ p, int form, float& s, float& e) {
-    const float a = p[0], b = p[1];
-    if (form == 1) {
-        const float hw = __fmul_rn(0.5f, b);
-        s = __fsub_rn(a, hw);
-        e = __fadd_rn(a, hw);
-    } else {
-        s = a;
-        e = b;
-    }
-}
-__device__ __forceinline__ bool span_solid(float s, float e) { return fabsf(s) < INFINITY && fabsf(e) < INFINITY && e > s; }   // not void
-// inter and union of two SOLID spans (a void one never gets here)
-__device__ __forceinline__ void span_overlap(float sa, float ea, float sb, float eb, float& inter, float& uni) {
-    const float d = __fsub_rn(fminf(ea, eb), fmaxf(sa, sb));
-    inter = d > 0.f ? d : 0.f;
-    uni = __fsub_rn(__fadd_rn(__fsub_rn(ea, sa), __fsub_rn(eb, sb)), inter);
-}
-__device__ __forceinline__ float span_iou(float sa, float ea, float sb, float eb) {
-    float inter, uni;
-    span_overlap(sa, ea, sb, eb, inter, uni);
-    return uni > 0.f ? __fdiv_rn(inter, uni) : 0.f;
-}
-__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : (1ull << n) - 1ull; }
-
-// N <= 64: a wave per row, four rows per block, no LDS and no barrier.  Lane i loads proposal i; its rank is the number of lanes whose (key, index) is
-// smaller (64 broadcasts), a forward cross-lane permute sends index and bounds to lane `rank`, and from there lane p is the p-th proposal in rank order.
-// NMS: the undecided proposals are a 64-bit mask; its lowest set bit is the next kept pivot, whose bounds are broadcast, every lane tests itself against
-// them and the ballot of the suppressed leaves the mask.  A void pivot is kept and suppresses nothing.
-__global__ __launch_bounds__(256) void span_rank_wave_kernel(const float* __restrict__ scores, const float* __restrict__ spans, int form, int64_t R, int N,
-                                                             int top, float nms, const float* __restrict__ gt, const float* __restrict__ hit, int T,
-                                                             int32_t* __restrict__ order, int32_t* __restrict__ keep, int32_t* __restrict__ n_keep,
-                                                             float* __restrict__ keep_iou, int32_t* __restrict__ first_hit) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    uint32_t key = 0xffffffffu;
-    float s = 0.f, e = 0.f;
-    if (lane < N) {
-        key = rank_key(scores[r * N + lane]);
-        span_bounds(spans + (r * N + lane) * 2, form, s, e);
-    }
-    int rank = 0;
-#pragma unroll
-    for (int j = 0; j < 64; ++j) {
-        const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)key, j);
-        rank += (kj < key || (kj == key && j < lane)) ? 1 : 0;
-    }
-    const int si = __builtin_amdgcn_ds_permute(rank << 2, lane);                                   // lane p: the index of the p-th in rank order
-    const float ss = __int_as_float(__builtin_amdgcn_ds_permute(rank << 2, __float_as_int(s)));
-    const float se = __int_as_float(__builtin_amdgcn_ds_permute(rank << 2, __float_as_int(e)));
-    const bool solid = lane < N && span_solid(ss, se);
-    if (order && lane < N) order[r * N + lane] = si;
-
-    uint64_t kept;
-    int nk;
-    if (nms >= 1.f) {                                   // inter <= union: nothing is ever suppressed
-        kept = low_bits(top);
-        nk = top;
-    } else {
-        uint64_t live = low_bits(N);
-        kept = 0ull;
-        nk = 0;
-        while (live != 0ull && nk < top) {
-            const int p = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)live) - 1);
-            kept |= 1ull << p;
-            live &= live - 1ull;
-            ++nk;
-            const float ps = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ss), p));
-            const float pe = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(se), p));
-            if (nk < top && span_solid(ps, pe)) {      // (the pivot that fills the list suppresses nobody who could still be kept)
-                bool dies = false;
-                if (solid) {
-                    float inter, uni;
-                    span_overlap(ps, pe, ss, se, inter, uni);
-                    dies = inter > __fmul_rn(nms, uni);
-                }
-                live &= ~__ballot(dies);               // (lanes at or before p are out of the mask already)
-            }
-        }
-    }
-    const bool mine = (kept >> lane) & 1ull;
-    const int pos = __popcll(kept & low_bits(lane));   // place of this lane's proposal among the kept
-    const int64_t kb = r * top;
-    if (mine) keep[kb + pos] = si;
-    if (lane >= nk && lane < top) keep[kb + lane] = -1;
-    if (lane == 0) n_keep[r] = nk;
-    if (!gt) return;
-    const float gs = gt[r * 2], ge = gt[r * 2 + 1];
-    const float iou = mine && solid && span_solid(gs, ge) ? span_iou(ss, se, gs, ge) : 0.f;
-    if (keep_iou) {
-        if (mine) keep_iou[kb + pos] = iou;
-        if (lane >= nk && lane < top) keep_iou[kb + lane] = 0.f;
-    }
-    if (first_hit) {
-        int fh = -1;
-        for (int t = 0; t < T; ++t) {
-            const uint64_t m = __ballot(mine && iou > hit[t]);
-            const int v = m ? __popcll(kept & low_bits(__ffsll((unsigned long long)m) - 1)) : -1;
-            if (lane == t) fh = v;
-        }
-        if (lane < T) first_hit[r * T + lane] = fh;
-    }
-}
-
-// 65 <= N <= 2048: a block per row.  (key, index) pairs (8 B) and bounds (8 B) of up to 2048 entries in static LDS, the live flags (1 B) and the kept
-// list (2 B) beside them: 38 KB.  Bitonic sort of P = N rounded up to a power of two; a padding entry has the NaN key and an index >= N.
-// NMS walks the sorted order: every thread reads the pivot's flag (one broadcast read); a dead pivot costs nothing more, a live one is kept and, unless
-// void, the threads clear the flags of the later proposals it suppresses, then one barrier - at most `top` barriers.  The flag reads of one round and the
-// flag writes of the next cannot meet: a thread writes only behind the barrier that ends the round in which the others read.
-constexpr int SR_MAX = 2048;
-__global__ __launch_bounds__(256) void span_rank_block_kernel(const float* __restrict__ scores, const float* __restrict__ spans, int form, int N, int P,
-                                                              int top, float nms, const float* __restrict__ gt, const float* __restrict__ hit, int T,
-                                                              int32_t* __restrict__ order, int32_t* __restrict__ keep, int32_t* __restrict__ n_keep,
-                                                              float* __restrict__ keep_iou, int32_t* __restrict__ first_hit) {
-    __shared__ uint64_t keys[SR_MAX];        // key << 32 | index, ascending = rank order
-    __shared__ float bs[SR_MAX], be[SR_MAX]; // bounds by ORIGINAL index
-    __shared__ uint16_t kept[SR_MAX];        // original indices of the kept, in rank order
-    __shared__ uint8_t live[SR_MAX];         // by sorted position
-    __shared__ int fh[16];
-    const int tid = threadIdx.x;
-    const int64_t r = blockIdx.x;
-    const float* sc = scores + r * N;
-    const float* sp = spans + r * N * 2;
-    for (int i = tid; i < P; i += 256) {
-        uint32_t key = 0xffffffffu;
-        if (i < N) {
-            key = rank_key(sc[i]);
-            float s, e;
-            span_bounds(sp + 2 * i, form, s, e);
-            bs[i] = s;
-            be[i] = e;
-        }
-        keys[i] = (uint64_t)key << 32 | (uint32_t)i;
-        live[i] = 1;
-    }
-    if (tid < 16) fh[tid] = 0x7fffffff;
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (P >> 1); t += 256) {
-                const int i = 2 * t - (t & (j - 1)), l = i + j;      // the pair (i, i + j), bit j of i clear
-                const uint64_t a = keys[i], b = keys[l];
-                if ((a > b) == ((i & k) == 0)) {
-                    keys[i] = b;
-                    keys[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (order)
-        for (int p = tid; p < N; p += 256) order[r * N + p] = (int32_t)(uint32_t)keys[p];
-
-    int nk = 0;
-    if (nms >= 1.f) {                                   // inter <= union: nothing is ever suppressed
-        for (int p = tid; p < top; p += 256) kept[p] = (uint16_t)(uint32_t)keys[p];
-        nk = top;
-    } else {
-        for (int p = 0; p < N && nk < top; ++p) {
-            if (!live[p]) continue;                     // (the same value in every thread: the last write to it lies behind a barrier)
-            const int ip = (int)(uint32_t)keys[p];
-            if (tid == 0) kept[nk] = (uint16_t)ip;
-            ++nk;
-            const float ps = bs[ip], pe = be[ip];
-            if (!span_solid(ps, pe) || nk == top) continue;
-            for (int q = p + 1 + tid; q < N; q += 256) {
-                if (!live[q]) continue;
-                const int iq = (int)(uint32_t)keys[q];
-                const float qs = bs[iq], qe = be[iq];
-                if (!span_solid(qs, qe)) continue;
-                float inter, uni;
-                span_overlap(ps, pe, qs, qe, inter, uni);
-                if (inter > __fmul_rn(nms, uni)) live[q] = 0;
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    const int64_t kb = r * top;
-    float gs = 0.f, ge = 0.f;
-    bool gsolid = false;
-    if (gt) {
-        gs = gt[r * 2];
-        ge = gt[r * 2 + 1];
-        gsolid = span_solid(gs, ge);
-    }
-    for (int q = tid; q < top; q += 256) {
-        const bool in = q < nk;
-        const int i = in ? (int)kept[q] : -1;
-        keep[kb + q] = i;
-        if (!gt) continue;
-        float iou = 0.f;
-        if (in && gsolid && span_solid(bs[i], be[i])) iou = span_iou(bs[i], be[i], gs, ge);
-        if (keep_iou) keep_iou[kb + q] = iou;
-        if (first_hit)
-            for (int t = 0; t < T; ++t)
-                if (iou > hit[t]) atomicMin(&fh[t], q);   // (LDS; the minimum does not depend on the order of arrival)
-    }
-    if (tid == 0) n_keep[r] = nk;
-    if (gt && first_hit) {
-        __syncthreads();
-        if (tid < T) first_hit[r * T + tid] = fh[tid] == 0x7fffffff ? -1 : fh[tid];
-    }
-}
-
 }  // namespace
+
+extern "C" int rv_frame_cosine(const void* video, int dtype, const float* text, int32_t B, int32_t L, int32_t d, float* out, void* stream) {
+    RV_CHECK_ARG(video && text && out && B > 0 && L > 0 && d > 0, "rv_frame_cosine: bad arguments");
+    RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_frame_cosine: dtype must be f32 or %s", RV_OP16_NAME);
+    RV_CHECK_ARG(d <= FC_DMAX, "rv_frame_cosine: d=%d exceeds the %d columns of the staged text row", d, FC_DMAX);
+    RV_CHECK_ARG(B <= 65535, "rv_frame_cosine: at most 65535 videos per launch");
+    const int vec = dtype == RV_OP16 ? 8 : 4;
+    const bool vector = d % vec == 0 && ((uintptr_t)video & 15u) == 0;
+    const dim3 grid((unsigned)cdiv(L, FC_FRAMES), B);
+    const size_t sm = (size_t)d * sizeof(float);
+    hipStream_t st = as_stream(stream);
+    if (dtype == RV_OP16) {
+        if (vector) hipLaunchKernelGGL((frame_cosine_kernel<op16_t, true>), grid, dim3(FC_TPB), sm, st, (const op16_t*)video, text, L, d, out);
+        else hipLaunchKernelGGL((frame_cosine_kernel<op16_t, false>), grid, dim3(FC_TPB), sm, st, (const op16_t*)video, text, L, d, out);
+    } else {
+        if (vector) hipLaunchKernelGGL((frame_cosine_kernel<float, true>), grid, dim3(FC_TPB), sm, st, (const float*)video, text, L, d, out);
+        else hipLaunchKernelGGL((frame_cosine_kernel<float, false>), grid, dim3(FC_TPB), sm, st, (const float*)video, text, L, d, out);
+    }
+    RV_CHECK_LAUNCH("rv_frame_cosine");
+    return RV_OK;
+}
 
 extern "C" int rv_frame_cosine_multi(const void* video, int dtype, const float* text, int32_t B, int32_t Q, int32_t L, int32_t d, float* text_unit,
                                      float* out, void* stream) {
@@ -419,28 +439,49 @@ extern "C" int rv_frame_cosine_multi(const void* video, int dtype, const float* 
     return RV_OK;
 }
 
-extern "C" int rv_span_rank(const float* scores, const float* spans, int32_t form, int32_t R, int32_t N, int32_t top, float nms_iou, const float* gt,
-                            const float* hit_iou, int32_t T, int32_t* order, int32_t* keep, int32_t* n_keep, float* keep_iou, int32_t* first_hit,
-                            void* stream) {
-    RV_CHECK_ARG(scores && spans && keep && n_keep && R > 0 && N > 0, "rv_span_rank: bad arguments");
-    RV_CHECK_ARG(N <= SR_MAX, "rv_span_rank: N=%d proposals per row (at most %d)", N, SR_MAX);
-    RV_CHECK_ARG(top >= 1 && top <= N, "rv_span_rank: top=%d must be in [1, N=%d]", top, N);
-    RV_CHECK_ARG(form == 0 || form == 1, "rv_span_rank: form=%d must be 0 (start, end) or 1 (centre, width)", form);
-    RV_CHECK_ARG(nms_iou >= 0.f && nms_iou < INFINITY, "rv_span_rank: nms_iou must be finite and >= 0");
-    RV_CHECK_ARG(T >= 0 && T <= 16, "rv_span_rank: T=%d thresholds (at most 16)", T);
-    RV_CHECK_ARG(gt || (!hit_iou && T == 0 && !keep_iou && !first_hit), "rv_span_rank: hit_iou, T > 0, keep_iou and first_hit need gt");
-    RV_CHECK_ARG(T == 0 || hit_iou, "rv_span_rank: T=%d thresholds without hit_iou", T);
-    RV_CHECK_ARG(!gt || T > 0 || keep_iou, "rv_span_rank: gt with neither thresholds nor keep_iou");
-    hipStream_t st = as_stream(stream);
-    if (N <= 64) {
-        hipLaunchKernelGGL(span_rank_wave_kernel, dim3((unsigned)cdiv(R, 4)), dim3(256), 0, st, scores, spans, form, (int64_t)R, N, top, nms_iou, gt, hit_iou,
-                           T, order, keep, n_keep, keep_iou, first_hit);
+// the part rv_span_scores and rv_span_scores_multi share, behind each entry's own refusals: rows = rows of sims, rpm of them per mask row
+static int launch_span_scores(const char* who, const float* sims, const float* spans, const float* mask, int rows, int rpm, int L, int N, int mode, int k,
+                              float temperature, float* scores, int32_t* windows, void* stream) {
+    const dim3 grid((unsigned)cdiv(N, 4), (unsigned)rows);
+    if (mode == 0) {
+        RV_CHECK_ARG(k >= 1 && k <= TOPK_FRAMES_MAX, "%s: k=%d must be in [1, %d]", who, k, TOPK_FRAMES_MAX);
+        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, rpm, L, N, k, 1.0f, scores, windows);
     } else {
-        int P = 128;
-        while (P < N) P <<= 1;
-        hipLaunchKernelGGL(span_rank_block_kernel, dim3((unsigned)R), dim3(256), 0, st, scores, spans, form, N, P, top, nms_iou, gt, hit_iou, T, order, keep,
-                           n_keep, keep_iou, first_hit);
+        RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "%s: temperature must be finite and not 0", who);
+        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, rpm, L, N, k, temperature, scores, windows);
     }
-    RV_CHECK_LAUNCH("rv_span_rank");
+    RV_CHECK_LAUNCH(who);
+    return RV_OK;
+}
+
+extern "C" int rv_span_scores(const float* sims, const float* spans, const float* mask, int32_t B, int32_t L, int32_t N, int32_t mode, int32_t k,
+                              float temperature, float* scores, int32_t* windows, void* stream) {
+    RV_CHECK_ARG(sims && spans && mask && scores && B > 0 && L > 0 && N > 0, "rv_span_scores: bad arguments");
+    RV_CHECK_ARG(mode == 0 || mode == 1, "rv_span_scores: mode=%d must be 0 (top-k) or 1 (attention)", mode);
+    RV_CHECK_ARG(B <= 65535, "rv_span_scores: at most 65535 videos per launch");
+    return launch_span_scores("rv_span_scores", sims, spans, mask, B, 1, L, N, mode, k, temperature, scores, windows, stream);
+}
+
+extern "C" int rv_span_scores_multi(const float* sims, const float* spans, const float* mask, int32_t B, int32_t Q, int32_t L, int32_t N, int32_t mode,
+                                    int32_t k, float temperature, float* scores, int32_t* windows, void* stream) {
+    RV_CHECK_ARG(sims && spans && mask && scores && B > 0 && Q > 0 && L > 0 && N > 0, "rv_span_scores_multi: bad arguments");
+    RV_CHECK_ARG(mode == 0 || mode == 1, "rv_span_scores_multi: mode=%d must be 0 (top-k) or 1 (attention)", mode);
+    RV_CHECK_ARG((int64_t)B * Q <= 65535, "rv_span_scores_multi: at most 65535 (video, query) rows per launch (B=%d, Q=%d)", B, Q);
+    return launch_span_scores("rv_span_scores_multi", sims, spans, mask, B * Q, Q, L, N, mode, k, temperature, scores, windows, stream);
+}
+
+extern "C" int rv_attn_pool(const void* video, int dtype, const float* text, int32_t Nv, int32_t T, int32_t d, int32_t Nt, float temperature,
+                            float* out, void* stream) {
+    RV_CHECK_ARG(video && text && out && Nv > 0 && T > 0 && d > 0 && Nt > 0, "rv_attn_pool: bad arguments");
+    RV_CHECK_ARG(dtype == RV_OP16 || dtype == RV_F32, "rv_attn_pool: dtype must be f32 or %s", RV_OP16_NAME);
+    RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "rv_attn_pool: temperature must be finite and not 0");
+    RV_CHECK_ARG(Nt <= 65535, "rv_attn_pool: at most 65535 texts per launch");
+    const size_t sm = (size_t)(d + T) * sizeof(float);
+    RV_CHECK_ARG(sm + 64 * sizeof(float) <= 64 * 1024, "rv_attn_pool: d + T too large for LDS (dynamic %zu B + 256 B static)", sm);
+    if (dtype == RV_OP16)
+        hipLaunchKernelGGL(attn_pool_kernel<op16_t>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const op16_t*)video, text, T, d, Nt, temperature, out);
+    else
+        hipLaunchKernelGGL(attn_pool_kernel<float>, dim3(Nv, Nt), dim3(256), sm, as_stream(stream), (const float*)video, text, T, d, Nt, temperature, out);
+    RV_CHECK_LAUNCH("rv_attn_pool");
     return RV_OK;
 }

@@ -1,0 +1,357 @@
+"""The CLIP grounding chain's wrappers (cosine rows, span scores, ranking, span proposals, window selection, the two poolings) with their checkers, constants
+and namedtuples; ``ops`` re-exports every public name.  Every function takes / returns torch DEVICE tensors and enqueues on torch's current stream."""
+import collections
+import math
+import numbers
+import struct
+
+import torch
+
+from . import hip
+
+
+def _score_lib(t):
+    return hip.lib(None if t.dtype == torch.float32 else t)
+
+
+def topk_pool(text_embeds, video_embeds, k, return_index=False):
+    """``_topk_pooling`` (similarity.py:71-94) on the device: text [Nt,d], video [Nv,T,d] (bf16 or f32) -> f32 [Nv,Nt,d], the SUM
+    of each video's k frames most similar to each text."""
+    Nv, T, d = video_embeds.shape
+    Nt = text_embeds.shape[0]
+    out = torch.empty(Nv, Nt, d, dtype=torch.float32, device=video_embeds.device)
+    idx = torch.empty(Nv, Nt, k, dtype=torch.int32, device=video_embeds.device) if return_index else None
+    hip.check(_score_lib(video_embeds).rv_topk_pool(hip.ptr(video_embeds.contiguous()), hip.dtype_code(video_embeds), hip.ptr(text_embeds.float().contiguous()), Nv, T, d,
+                                                    Nt, int(k), hip.ptr(out), hip.ptr(idx), hip.stream()), "rv_topk_pool")
+    return (out, idx) if return_index else out
+
+
+def frame_cosine(text, video):
+    """The per-frame cosine row of ``forward_clip_matching`` (similarity.py:36, :61-64): text f32 [B,d], video [B,L,d] (16-bit operands or f32) -> f32 [B,L],
+    ``<f_l, t_b> / (|f_l| |t_b|)``; a zero frame or a zero text gives NaN as the reference's divisions do."""
+    if video.dim() != 3 or text.dim() != 2 or text.shape != (video.shape[0], video.shape[2]):
+        raise ValueError(f"frame_cosine: text {tuple(text.shape)} / video {tuple(video.shape)}")
+    B, L, d = video.shape
+    out = torch.empty(B, L, dtype=torch.float32, device=video.device)
+    hip.check(_score_lib(video).rv_frame_cosine(hip.ptr(video.contiguous()), hip.dtype_code(video), hip.ptr(text.float().contiguous()), B, L, d, hip.ptr(out), hip.stream()),
+              "rv_frame_cosine")
+    return out
+
+
+SPAN_POOLINGS = {"topk": 0, "attention": 1}
+
+
+def _span_scores(who, sims, spans, mask, k, pooling, temperature, return_windows):
+    """``span_scores`` (rows [B]) and ``span_scores_multi`` (rows [B,Q], one mask row per video): one body, the entry point named by ``who``."""
+    nd = 3 if who == "span_scores_multi" else 2
+    if pooling not in SPAN_POOLINGS:
+        raise ValueError(f"{who}: pooling={pooling!r} (expected one of {sorted(SPAN_POOLINGS)})")
+    if (sims.dim() != nd or spans.dim() != nd + 1 or spans.shape[:-2] != sims.shape[:-1] or spans.shape[-1] != 2
+            or mask.shape != (sims.shape[0], sims.shape[-1])):
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / spans {tuple(spans.shape)} / mask {tuple(mask.shape)}")
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    lead, L, N = tuple(sims.shape[:-1]), sims.shape[-1], spans.shape[-2]
+    scores = torch.empty(lead + (N,), dtype=torch.float32, device=sims.device)
+    win = torch.empty(lead + (N, 2), dtype=torch.int32, device=sims.device) if return_windows else None
+    if N > 0:
+        hip.check(getattr(hip.lib(), "rv_" + who)(hip.ptr(sims.contiguous()), hip.ptr(spans.float().contiguous()), hip.ptr(mask.float().contiguous()), *lead, L, N,
+                                                  SPAN_POOLINGS[pooling], int(k), float(temperature), hip.ptr(scores), hip.ptr(win), hip.stream()),
+                  "rv_" + who)
+    return (scores, win) if return_windows else scores
+
+
+def span_scores(sims, spans, mask, k=3, pooling="topk", temperature=0.01, return_windows=False):
+    """sims f32 [B,L], spans [B,N,2] as (centre, width), mask [B,L] -> scores f32 [B,N] (and the windows i32 [B,N,2] as (lo, hi) of ``range(L)[start:end]``):
+    the reference's window rule (similarity.py:52-60) and, per window, the sum of its min(k, len) largest sims (``pooling="topk"``) or
+    ``sum softmax(s / temperature) s`` (``"attention"``).  Nothing comes back to the host."""
+    return _span_scores("span_scores", sims, spans, mask, k, pooling, temperature, return_windows)
+
+
+def frame_cosine_multi(text, video):
+    """``frame_cosine`` for Q texts per video: text f32 [B,Q,d], video [B,L,d] (16-bit operands or f32, passed as it is when contiguous) -> f32 [B,Q,L],
+    ``<f_bl, t_bq> / (|f_bl| |t_bq|)`` with the features read once for all Q texts (``rv_frame_cosine_multi``: f32-input MFMA).  A query's row does not
+    depend on Q, on its slot or on the other texts.  A zero text gives a NaN row, a zero frame a NaN column.  No synchronisation."""
+    if video.dim() != 3 or text.dim() != 3 or text.shape[0] != video.shape[0] or text.shape[2] != video.shape[2]:
+        raise ValueError(f"frame_cosine_multi: text {tuple(text.shape)} / video {tuple(video.shape)} (expected [B, Q, d] and [B, L, d])")
+    B, L, d = video.shape
+    Q = text.shape[1]
+    text = text.float().contiguous()
+    unit = torch.empty_like(text)                       # the kernel's workspace: text / |text|
+    out = torch.empty(B, Q, L, dtype=torch.float32, device=video.device)
+    hip.check(_score_lib(video).rv_frame_cosine_multi(hip.ptr(video.contiguous()), hip.dtype_code(video), hip.ptr(text), B, Q, L, d, hip.ptr(unit), hip.ptr(out),
+                                                      hip.stream()), "rv_frame_cosine_multi")
+    return out
+
+
+def span_scores_multi(sims, spans, mask, k=3, pooling="topk", temperature=0.01, return_windows=False):
+    """``span_scores`` for Q queries per video: sims f32 [B,Q,L], spans [B,Q,N,2] (each query's own (centre, width) proposals), mask [B,L] (one duration
+    per video) -> scores f32 [B,Q,N] (and the windows i32 [B,Q,N,2]).  The kernel of ``span_scores``: each (b, q) row equals ``span_scores`` on that
+    row bit for bit.  No synchronisation."""
+    return _span_scores("span_scores_multi", sims, spans, mask, k, pooling, temperature, return_windows)
+
+
+SPAN_FORMS = {"xx": 0, "cxw": 1}
+SPAN_RANK_MAX = 2048
+HIT_IOU = (0.1, 0.3, 0.5, 0.7, 0.9)
+SpanRank = collections.namedtuple("SpanRank", "keep n_keep keep_iou first_hit order")
+_hit_tables = collections.OrderedDict()
+_HIT_TABLES_MAX = 16
+
+
+def _hit_table(hit_iou, device):
+    """The thresholds as an f32 device vector, uploaded once per (values, device, stream) and kept for the last 16 such keys: a ranking call then queues no
+    copy.  The stream is part of the key because the upload is ordered on the stream that was current when it was queued: a call on another stream gets a
+    table of its own, uploaded on that stream, instead of reading this one without ordering."""
+    key = (hit_iou, str(device), torch.cuda.current_stream(device).cuda_stream)
+    table = _hit_tables.get(key)
+    if table is None:
+        from .ops import h2d                   # (ops imports this module: at call time both are complete)
+        table = _hit_tables[key] = h2d(torch.tensor(hit_iou, dtype=torch.float32), device)
+        while len(_hit_tables) > _HIT_TABLES_MAX:
+            _hit_tables.popitem(last=False)        # (the allocator keeps a freed block ordered behind the work queued on its stream)
+    else:
+        _hit_tables.move_to_end(key)
+    return table
+
+
+def span_rank_keywords(who, top, nms_iou, hit_iou):
+    """The keyword refusals of ``span_rank`` (raised before any device is looked for) -> (nms_iou as float, hit_iou as a tuple of floats)."""
+    if top is not None and not (isinstance(top, numbers.Integral) and not isinstance(top, bool) and top >= 1):
+        raise ValueError(f"{who}: top={top!r} must be a positive integer or None")
+    try:
+        nms_iou, hit_iou = float(nms_iou), tuple(float(h) for h in hit_iou)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: nms_iou={nms_iou!r} must be a number and hit_iou={hit_iou!r} a sequence of numbers") from None
+    if not (math.isfinite(nms_iou) and nms_iou >= 0.0):
+        raise ValueError(f"{who}: nms_iou={nms_iou} must be finite and >= 0")
+    if len(hit_iou) > 16:
+        raise ValueError(f"{who}: {len(hit_iou)} thresholds in hit_iou (at most 16)")
+    return nms_iou, hit_iou
+
+
+def span_rank(scores, spans, top=None, nms_iou=1.0, form="cxw", gt=None, hit_iou=HIT_IOU, return_order=False):
+    """Rank scored proposals on the device (``rv_span_rank``): scores [R,N] or [B,Q,N], spans [...,N,2] as (centre, width) (``form="cxw"``) or (start, end)
+    (``"xx"``), gt [...,2] as (start, end) or None -> SpanRank(keep i32 [...,top], n_keep i32 [...], keep_iou f32 [...,top], first_hit i32 [...,T], order
+    i32 [...,N]); parts not asked for are None (keep_iou and first_hit need ``gt``, order ``return_order``).  Descending score, ties to the smaller index,
+    NaN last; greedy NMS at ``inter > nms_iou * union`` (1.0: none); ``keep`` is padded with -1, ``keep_iou`` with 0; ``first_hit[..., t]`` is the first
+    kept place whose IoU with gt exceeds ``hit_iou[t]``, or -1.  ``top=None`` means N, a larger ``top`` is N.  One launch, no synchronisation, no host copy."""
+    if form not in SPAN_FORMS:
+        raise ValueError(f"span_rank: form={form!r} (expected one of {sorted(SPAN_FORMS)})")
+    if not torch.is_tensor(scores) or not torch.is_tensor(spans) or (gt is not None and not torch.is_tensor(gt)):
+        raise ValueError("span_rank: scores, spans and gt must be tensors")
+    if scores.dim() not in (2, 3) or spans.shape != scores.shape + (2,):
+        raise ValueError(f"span_rank: scores {tuple(scores.shape)} / spans {tuple(spans.shape)} (expected [R, N] or [B, Q, N] and [..., N, 2])")
+    if gt is not None and gt.shape != scores.shape[:-1] + (2,):
+        raise ValueError(f"span_rank: gt {tuple(gt.shape)} for scores {tuple(scores.shape)} (expected [..., 2] rows of (start, end))")
+    if scores.dtype != torch.float32:
+        raise ValueError(f"span_rank: scores must be float32 (got {scores.dtype})")
+    for name, t in (("spans", spans), ("gt", gt)):
+        if t is not None and not t.dtype.is_floating_point:
+            raise ValueError(f"span_rank: {name} must be a floating-point tensor (got {t.dtype})")
+    lead, N = tuple(scores.shape[:-1]), scores.shape[-1]
+    if N > SPAN_RANK_MAX:
+        raise ValueError(f"span_rank: N={N} proposals per row (at most {SPAN_RANK_MAX})")
+    nms_iou, hit_iou = span_rank_keywords("span_rank", top, nms_iou, hit_iou if gt is not None else ())
+    top = N if top is None else min(int(top), N)
+    T, dev = len(hit_iou), scores.device
+    R = math.prod(lead)
+    keep = torch.empty(lead + (top,), dtype=torch.int32, device=dev)
+    n_keep = torch.empty(lead, dtype=torch.int32, device=dev)
+    keep_iou = torch.empty(lead + (top,), dtype=torch.float32, device=dev) if gt is not None else None
+    first_hit = torch.empty(lead + (T,), dtype=torch.int32, device=dev) if gt is not None else None
+    order = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_order else None
+    if N > 0 and R > 0:
+        hip.check(hip.lib().rv_span_rank(hip.ptr(scores.contiguous()), hip.ptr(spans.float().contiguous()), SPAN_FORMS[form], R, N, top, nms_iou,
+                                         hip.ptr(gt.float().contiguous()) if gt is not None else None, hip.ptr(_hit_table(hit_iou, dev)) if T else None, T,
+                                         hip.ptr(order), hip.ptr(keep), hip.ptr(n_keep), hip.ptr(keep_iou), hip.ptr(first_hit if T else None), hip.stream()),
+                  "rv_span_rank")
+    elif R > 0:                                          # no proposals: nothing kept, no hit (no launch)
+        n_keep.zero_()
+        if first_hit is not None:
+            first_hit.fill_(-1)
+    return SpanRank(keep, n_keep, keep_iou, first_hit, order)
+
+
+SPAN_PROPOSE_MAX_LEVELS = 8
+SPAN_PROPOSE_MAX_FRAMES = 1 << 20
+SPAN_PROPOSE_LEVELS = (0.5, 0.6, 0.7, 0.8, 0.9)
+SpanProposals = collections.namedtuple("SpanProposals", "spans n_spans n_found windows smoothed")
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _f32(v):
+    """A Python float rounded to float32 (inf when it is out of range)."""
+    try:
+        return struct.unpack("f", struct.pack("f", v))[0]
+    except OverflowError:
+        return math.copysign(math.inf, v)
+
+
+def span_propose_keywords(who, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None, max_spans=256):
+    """The keyword refusals of ``span_propose`` (raised before any device is looked for) -> (levels as a tuple of floats, relative as 0 / 1, smooth, gap,
+    min_len, max_len with None as 0, max_spans) as ``rv_span_propose`` takes them."""
+    try:
+        levels = tuple(float(v) for v in levels)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: levels={levels!r} must be a sequence of numbers") from None
+    if not 1 <= len(levels) <= SPAN_PROPOSE_MAX_LEVELS:
+        raise ValueError(f"{who}: {len(levels)} levels (1 to {SPAN_PROPOSE_MAX_LEVELS})")
+    if not (isinstance(relative, (bool, numbers.Integral)) and relative in (0, 1)):
+        raise ValueError(f"{who}: relative={relative!r} must be True or False")
+    as_f32 = [_f32(v) for v in levels]                   # what the kernel compares
+    for i, v in enumerate(as_f32):
+        if not math.isfinite(v):
+            raise ValueError(f"{who}: level {levels[i]} is not a finite float32")
+        if i and not v > as_f32[i - 1]:
+            raise ValueError(f"{who}: levels={levels} must be strictly ascending (as float32)")
+        if relative and not 0.0 <= v < 1.0:
+            raise ValueError(f"{who}: relative level {levels[i]} outside [0, 1)")
+    if not (_is_int(smooth) and 1 <= smooth <= 65 and smooth % 2 == 1):
+        raise ValueError(f"{who}: smooth={smooth!r} must be an odd integer in [1, 65]")
+    if not (_is_int(gap) and 0 <= gap <= 63):
+        raise ValueError(f"{who}: gap={gap!r} must be an integer in [0, 63]")
+    if not (_is_int(min_len) and 1 <= min_len < 2 ** 31):
+        raise ValueError(f"{who}: min_len={min_len!r} must be a positive integer")
+    if max_len is not None and not (_is_int(max_len) and min_len <= max_len < 2 ** 31):
+        raise ValueError(f"{who}: max_len={max_len!r} must be None or an integer >= min_len={min_len}")
+    if not (_is_int(max_spans) and 1 <= max_spans <= SPAN_RANK_MAX):
+        raise ValueError(f"{who}: max_spans={max_spans!r} must be an integer in [1, {SPAN_RANK_MAX}]")
+    return tuple(as_f32), int(bool(relative)), int(smooth), int(gap), int(min_len), 0 if max_len is None else int(max_len), int(max_spans)
+
+
+def span_propose_shapes(who, sims, mask):
+    """The tensor refusals of ``span_propose`` -> (leading shape, R, rows per mask row, L)."""
+    if not torch.is_tensor(sims) or not torch.is_tensor(mask):
+        raise ValueError(f"{who}: sims and mask must be tensors")
+    if sims.dim() not in (2, 3) or mask.dim() != 2 or mask.shape[-1] != sims.shape[-1]:
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / mask {tuple(mask.shape)} (expected [R, L] or [B, Q, L] and [R, L] / [B, L])")
+    lead, L = tuple(sims.shape[:-1]), sims.shape[-1]
+    R, M = math.prod(lead), mask.shape[0]
+    if min(R, L, M) < 1 or (sims.dim() == 3 and M != lead[0]) or R % M != 0:
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / mask {tuple(mask.shape)} (one mask row per video: a whole number of rows of sims for each)")
+    if L > SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={L} frames (at most {SPAN_PROPOSE_MAX_FRAMES})")
+    if not sims.dtype.is_floating_point:
+        raise ValueError(f"{who}: sims must be a floating-point tensor (got {sims.dtype})")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    return lead, R, R // M, L
+
+
+def span_propose(sims, mask, *, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None, max_spans=256, return_windows=False,
+                 return_smoothed=False):
+    """Candidate spans from similarity rows on the device (``rv_span_propose``): sims f32 [R,L] or [B,Q,L] (``frame_cosine`` / ``frame_cosine_multi``'s
+    rows), mask [R,L] / [B,L] of any bool, integer or float dtype (its row sum is the duration; with fewer rows than sims each serves a whole number of
+    consecutive rows) -> SpanProposals(spans f32 [...,max_spans,2] as (centre, width) with NaN padding, n_spans i32 [...], n_found i32 [...], windows i32
+    [...,max_spans,2] with (-1, -1) padding, smoothed f32 [...,L]); ``windows`` and ``smoothed`` are None unless asked for, and ``smoothed`` is written
+    inside each row's duration only (NaN elsewhere).  The row is box-smoothed over ``smooth`` frames and thresholded at every level (``relative``: a
+    fraction of the way from the row's smallest to its largest value); a maximal stretch above a threshold, gaps of at most ``gap`` frames closed, is a
+    span if its length lies in [min_len, max_len] and the next level has no identical one.  Highest level first, then ascending start;
+    ``n_found > n_spans`` shows that ``max_spans`` cut the list.  One launch (a mask that is not f32 adds a cast kernel, ``return_smoothed`` a fill), no
+    synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
+    who = "span_propose"
+    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    lv, relative, smooth, gap, min_len, max_len, N = kw
+    dev = sims.device
+    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
+    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
+    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
+    table = (hip.C.c_float * len(lv))(*lv)
+    hip.check(hip.lib().rv_span_propose(hip.ptr(sims.contiguous()), hip.ptr(mask.float().contiguous()), R, rpm, L, table, len(lv), relative, smooth, gap, min_len, max_len, N,
+                                        hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows), hip.ptr(smoothed), hip.stream()),
+              "rv_span_propose")
+    return SpanProposals(spans, n_spans, n_found, windows, smoothed)
+
+
+WINDOW_SELECT_MAX = 2048
+WindowSelection = collections.namedtuple("WindowSelection", "select n_select n_windows scores bounds order hit_rank")
+
+
+def window_select_keywords(who, win, stride, keep, k=3, min_sep=1):
+    """The keyword refusals of ``window_select`` that need no tensor (raised before any device is looked for) -> the five as ints."""
+    for name, v in (("win", win), ("stride", stride), ("keep", keep), ("k", k), ("min_sep", min_sep)):
+        if not (_is_int(v) and 1 <= v < 2 ** 31):
+            raise ValueError(f"{who}: {name}={v!r} must be a positive integer")
+    if win < stride:
+        raise ValueError(f"{who}: win={win} frames with stride={stride} (stride <= win)")
+    if k > 64:
+        raise ValueError(f"{who}: k={k} must be in [1, 64]")
+    return int(win), int(stride), int(keep), int(k), int(min_sep)
+
+
+def window_select_capacity(who, L, win, stride, min_sep=1):
+    """Wcap = max(1, ceil(L / (win // stride)) - 1), the most windows a row of L frames can have; refuses win > L, more than 2048 windows and
+    min_sep > Wcap."""
+    if win > L:
+        raise ValueError(f"{who}: win={win} frames for rows of L={L}")
+    hop = win // stride
+    cap = max(1, -(-L // hop) - 1)
+    if cap > WINDOW_SELECT_MAX:
+        raise ValueError(f"{who}: L={L}, win={win}, stride={stride} give up to {cap} windows (at most {WINDOW_SELECT_MAX})")
+    if min_sep > cap:
+        raise ValueError(f"{who}: min_sep={min_sep} must be in [1, {cap}] (the most windows a row of L={L} can have)")
+    return cap
+
+
+def window_select_gt(who, gt, lead):
+    if gt is None:
+        return
+    if not torch.is_tensor(gt) or gt.shape != lead + (2,):
+        raise ValueError(f"{who}: gt {tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__} (expected {lead + (2,)}: rows of (start, end) in frames)")
+    if not gt.dtype.is_floating_point:
+        raise ValueError(f"{who}: gt must be a floating-point tensor (got {gt.dtype})")
+
+
+def window_select(sims, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):
+    """Choose the recursion's windows from similarity rows on the device (``rv_window_select``): sims f32 [R,L] or [B,Q,L] (``frame_cosine`` /
+    ``frame_cosine_multi``'s rows), mask [R,L] / [B,L] of any bool, integer or float dtype (its row sum is the duration; with fewer rows than sims each
+    serves a whole number of consecutive rows), gt [...,2] rows of (start, end) in frames or None -> WindowSelection(select i32 [...,keep] ascending
+    with -1 padding, n_select i32 [...], n_windows i32 [...], scores f32 [...,Wcap] with NaN padding, bounds i32 [mask rows,Wcap,2] as (lo, hi) with
+    (-1, -1) padding, order i32 [...,Wcap] with -1 padding, hit_rank i32 [...]); ``scores``, ``bounds`` and ``order`` are None unless asked for,
+    ``hit_rank`` unless ``gt`` is given.  The windows are ``stage2.cut_windows``' for ``clip_length = win``; a window's score is the sum of its ``k``
+    largest sims; the windows are taken in rank order, a taken one removing the others within ``min_sep`` indices of it, then topped up in rank order;
+    ``select`` is the first ``min(keep, n_windows)`` of that sequence sorted, ``hit_rank`` the first place of the sequence whose window overlaps gt.
+    ``Wcap = max(1, ceil(L / (win // stride)) - 1)``; a ``keep`` above it is Wcap.  One launch (a mask that is not f32 adds a cast kernel), no
+    synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
+    who = "window_select"
+    win, stride, keep, k, min_sep = window_select_keywords(who, win, stride, keep, k, min_sep)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    Wcap = window_select_capacity(who, L, win, stride, min_sep)
+    window_select_gt(who, gt, lead)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    keep = min(keep, Wcap)
+    dev = sims.device
+    select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
+    n_select = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
+    scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
+    bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
+    order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
+    hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
+    hip.check(hip.lib().rv_window_select(hip.ptr(sims.contiguous()), hip.ptr(mask.float().contiguous()), R, rpm, L, win, stride, k, keep, min_sep, Wcap,
+                                         hip.ptr(gt.float().contiguous()) if gt is not None else None, hip.ptr(select), hip.ptr(n_select), hip.ptr(n_windows),
+                                         hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()), "rv_window_select")
+    return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
+
+
+def attn_pool(text_embeds, video_embeds, temperature):
+    """``_attention_pooling`` (similarity.py:96-113) on the device: text [Nt,d], video [Nv,T,d] (16-bit operands or f32) -> f32 [Nv,Nt,d] =
+    ``sum_t softmax_t(<f_t, text_j> / temperature) f_t``."""
+    if text_embeds.dim() != 2 or video_embeds.dim() != 3 or text_embeds.shape[1] != video_embeds.shape[2]:
+        raise ValueError(f"attn_pool: text {tuple(text_embeds.shape)} / video {tuple(video_embeds.shape)}")
+    Nv, T, d = video_embeds.shape
+    Nt = text_embeds.shape[0]
+    out = torch.empty(Nv, Nt, d, dtype=torch.float32, device=video_embeds.device)
+    hip.check(_score_lib(video_embeds).rv_attn_pool(hip.ptr(video_embeds.contiguous()), hip.dtype_code(video_embeds), hip.ptr(text_embeds.float().contiguous()), Nv, T, d, Nt,
+                                                    float(temperature), hip.ptr(out), hip.stream()), "rv_attn_pool")
+    return out

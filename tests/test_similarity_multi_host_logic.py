@@ -163,6 +163,26 @@ def test_host_side_refusals_come_before_the_device_is_looked_for():
             forward_clip_matching_multi(text, video, mask, spans)
 
 
+GROUNDING_NAMES = ["topk_pool", "frame_cosine", "SPAN_POOLINGS", "span_scores", "frame_cosine_multi", "span_scores_multi", "SPAN_FORMS", "SPAN_RANK_MAX",
+                   "HIT_IOU", "SpanRank", "span_rank_keywords", "span_rank", "SPAN_PROPOSE_MAX_LEVELS", "SPAN_PROPOSE_MAX_FRAMES", "SPAN_PROPOSE_LEVELS",
+                   "SpanProposals", "span_propose_keywords", "span_propose_shapes", "span_propose", "WINDOW_SELECT_MAX", "WindowSelection",
+                   "window_select_keywords", "window_select_capacity", "window_select_gt", "window_select", "attn_pool"]
+
+
+def test_ops_hands_out_the_grounding_modules_own_objects():
+    """The grounding wrappers live in revisionllm_amd.grounding; every public name of theirs is the same object under ``ops``."""
+    from revisionllm_amd import grounding, ops
+    for name in GROUNDING_NAMES:
+        assert getattr(ops, name) is getattr(grounding, name), name
+        if callable(getattr(grounding, name)):
+            assert getattr(grounding, name).__module__ == "revisionllm_amd.grounding", name
+    assert ops.h2d.__module__ == "revisionllm_amd.ops"
+    # ops imports grounding, and grounding takes h2d from ops at call time: importing grounding FIRST, in a fresh interpreter, must work too
+    code = f"import sys; sys.path.insert(0, {ROOT!r}); import revisionllm_amd.grounding as g; from revisionllm_amd import ops; assert ops.span_rank is g.span_rank"
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd="/tmp")
+    assert r.returncode == 0, r.stderr
+
+
 def test_multi_oracle_against_g17(g17):
     """[b, q = b] is the pair the reference recorded: scores within the suite's oracle bound, windows, zeros and the NaN pattern of the zeroed frame exactly."""
     text, video, mask, spans = g17_multi(g17)
