@@ -782,6 +782,38 @@ int rv_window_select(const float* sims, const float* mask, int32_t R, int32_t rp
                      int32_t min_sep, int32_t Wcap, const float* gt, int32_t* select, int32_t* n_select, int32_t* n_windows, float* win_scores,
                      int32_t* bounds, int32_t* order, int32_t* hit_rank, void* stream);
 
+/* ---- the recursion's window tensor from features that stay on the device (what the driver builds on the host per query: stage2.cut_windows'
+ * np.linspace frame indices, a fancy-index of the movie's feature array, a cast and an upload - data/feature_store.py WindowStager.stage_windows;
+ * e2e2.py:262-277, :303-306) ----
+ * video [M,L,d] with M = R / rpm, f32 or this library's 16-bit operand type (video_dtype, as rv_frame_cosine takes it; the other 16-bit type is
+ * refused), frame stride ldv >= d elements, video stride L * ldv; mask f32 [M,L] or NULL (NULL: D = L); select i32 [R,keep]: rv_window_select's
+ * `select` as it lies, -1 padding included - or any other list of window indices, unsorted or with repeats ->
+ *   out        [R,keep,F,d] contiguous, out_dtype = f32 or the library's 16-bit operand type
+ *   frame_idx  i32 [R,keep,F]  (optional) the source frame of every output row, -1 for an invalid entry
+ * Duration (rv_window_select's rule, the same code): dur = the f32 sum of the video's mask row, D = min(L, max(0, int(floor(dur)))), D = 0 for a
+ * non-finite dur; defined for 0 / 1 masks.  No frame at or past D is read.
+ * Windows (rv_window_select's integer rule, the same code): hop = win / stride, W_r = max(0, ceil(D / hop) - 1); for entry i in [0, W_r):
+ * s = (i * win) / stride, e = min(s + win, D - 1), if e - s < win then s = e - win, s = max(s, 0); the window is frames [s, e + 1).  Index i means
+ * what it means in `select` and in cut_windows' `times`.
+ * Sampled frames: np.linspace(s, e, F, dtype=int32), operation by operation in float64, each operation rounded on its own (round to nearest even):
+ * step = (e - s) / (F - 1); y_j = j * step, or (j * (e - s)) / (F - 1) when step == 0; y_j = y_j + s; y_{F-1} = e; idx_j = floor(y_j); F = 1 gives
+ * s.  The multiply and the add are NOT fused.  (The integer shortcut s + j * (e - s) / (F - 1) is another function: it differs at
+ * (s, e, F) = (0, 130, 31), j = 27: 117 against linspace's 116.)  s <= idx_j <= e for every j.
+ * Output: out[r, n, j, :] = video[r / rpm, idx_j, :] converted to out_dtype.  The same type on both sides is a copy of the bits.  f32 -> 16 bits
+ * is the library's store conversion: round to nearest even, a NaN stays a NaN; the fp16 build saturates at +-65504 (an infinity included) and counts
+ * it in the numeric status (rv_numeric_status_bind), the bf16 build stores infinities and large values as they round.  For a finite input that rounds
+ * inside the 16-bit range that is torch.Tensor.to(dtype) bit for bit.  16 bits -> f32 is exact (a signalling NaN comes back quiet).
+ * Invalid entries: a select entry outside [0, W_r) - the -1 padding, an index past a short row's windows, any other int32 - gives an all-zero
+ * out[r, n] and frame_idx[r, n, :] = -1; nothing is read for it.  No value of select makes the kernel read or write outside its buffers.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null video / select / out; R < 1; rpm < 1; R not a multiple of rpm; L < 1 or
+ * L > 1048576; d < 1; ldv < d; stride < 1; win < stride; win > L; keep < 1; F < 1 or F > 65536; a video_dtype / out_dtype that is not f32 or this
+ * library's 16-bit type; R * keep > 16777215.
+ * 256-thread workgroups of 16 output rows, (R * keep) x ceil(F / 16) of them with 64-bit offsets; 16-byte loads and stores when d is a multiple of
+ * 8 (4 for f32 -> f32), ldv * sizeof(element) a multiple of 16 and both base addresses 16-byte aligned, one element per lane otherwise - the same
+ * bits either way.  With a mask every workgroup sums its video's mask row again (L floats per 16 output rows); callers whose rows are full pass NULL. */
+int rv_window_gather(const void* video, int32_t video_dtype, int64_t ldv, const float* mask, const int32_t* select, int32_t R, int32_t rpm, int32_t L,
+                     int32_t d, int32_t win, int32_t stride, int32_t keep, int32_t F, void* out, int32_t out_dtype, int32_t* frame_idx, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, FLAVOURS["f16"][0])
 
 def lib_path(flavour):
     return os.path.join(HERE, FLAVOURS[flavour][0])
-SOURCES = ["error.hip", "init.hip", "gemm.hip", "gemm_pp.hip", "gemm_arows.hip", "gemm_rows.hip", "gemm_rows_p1.hip", "gemm_rows_p2.hip", "gemm_rows_p3.hip", "rowops.hip", "attention.hip", "sample.hip", "similarity.hip", "rank.hip", "propose.hip", "prefilter.hip", "frames.hip", "frames_yuv.hip", "engine.hip"]
+SOURCES = ["error.hip", "init.hip", "gemm.hip", "gemm_pp.hip", "gemm_arows.hip", "gemm_rows.hip", "gemm_rows_p1.hip", "gemm_rows_p2.hip", "gemm_rows_p3.hip", "rowops.hip", "attention.hip", "sample.hip", "similarity.hip", "rank.hip", "propose.hip", "prefilter.hip", "gather.hip", "frames.hip", "frames_yuv.hip", "engine.hip"]
 HEADERS = ["exports.map", "common.h", "kernels.h", "gemv_finish.h", "frames_common.h", "grounding.h", "gemm_rows.hip", os.path.join("..", "..", "include", "revision_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]

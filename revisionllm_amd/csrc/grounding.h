@@ -1,6 +1,6 @@
 // What the stages of the CLIP grounding chain share, one definition each: the frame order of the score kernels, the rank key of a score, the bitonic
-// sort of (key, index) pairs, the duration rule and the small helpers around them.  Included by the chain's translation units only (sample.hip for
-// rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip): two stages that have to agree bit for bit call the same code.
+// sort of (key, index) pairs, the duration rule, the window rule and the small helpers around them.  Included by the chain's translation units only (sample.hip for
+// rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip, gather.hip): two stages that have to agree bit for bit call the same code.
 #pragma once
 #include "kernels.h"
 
@@ -114,6 +114,23 @@ __device__ __forceinline__ float block_mask_sum(const float* __restrict__ m, int
 __device__ __forceinline__ int duration_frames(float dur, int L) {
     if (!(fabsf(dur) < INFINITY && dur >= 1.f)) return 0;
     return dur >= (float)L ? L : (int)floorf(dur);
+}
+
+// ---- windows ----
+// frames [lo, hi) of window i of a row of D frames: stage2.cut_windows' rule in integers, the start clamped at 0 (rv_window_select scores these
+// windows, rv_window_gather samples them: an index means the same window in both)
+__device__ __forceinline__ void ws_bounds(int i, int win, int stride, int D, int& lo, int& hi) {
+    int64_t s = (int64_t)i * win / stride;
+    int64_t e = s + win < (int64_t)D - 1 ? s + win : (int64_t)D - 1;
+    if (e - s < win) s = e - win;
+    lo = s > 0 ? (int)s : 0;
+    hi = (int)e + 1;
+}
+// W_r = max(0, ceil(D / hop) - 1) windows, hop = win / stride
+__device__ __forceinline__ int ws_count(int win, int stride, int D) {
+    const int hop = win / stride;
+    const int W = (D + hop - 1) / hop - 1;
+    return W < 0 ? 0 : W;
 }
 
 }  // namespace

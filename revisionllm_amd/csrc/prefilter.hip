@@ -47,15 +47,6 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t a) {
     return a;
 }
 
-// frames [lo, hi) of window i of a row of D frames: stage2.cut_windows' rule in integers, the start clamped at 0
-__device__ __forceinline__ void ws_bounds(int i, int win, int stride, int D, int& lo, int& hi) {
-    int64_t s = (int64_t)i * win / stride;
-    int64_t e = s + win < (int64_t)D - 1 ? s + win : (int64_t)D - 1;
-    if (e - s < win) s = e - win;
-    lo = s > 0 ? (int)s : 0;
-    hi = (int)e + 1;
-}
-
 // how many of the counts c of the threads before this one (all threads call; wsum: WS_WAVES ints)
 __device__ __forceinline__ int ws_before(int c, int* wsum) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -98,9 +89,7 @@ __global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs 
 
     if (tid == 0) first = 0x7fffffff;           // (in front of the sum: its barrier covers this store)
     const int D = duration_frames(block_mask_sum<WS_TPB>(m, L, red), L);
-    const int hop = win / stride;
-    int W = (D + hop - 1) / hop - 1;
-    W = W < 0 ? 0 : W;                       // (W <= Wcap: D <= L)
+    const int W = ws_count(win, stride, D);   // (W <= Wcap: D <= L)
     int P = 1;
     while (P < W) P <<= 1;
     const bool to_bounds = a.bounds && r % a.rpm == 0;

@@ -9,7 +9,11 @@ without it ``data/mdb_reader.py`` reads the environment's ``data.mdb`` itself; a
 ``stage_windows`` is the step right before the hot path: gather the window frames on the host into a PINNED staging
 buffer and copy them to the GPU asynchronously on a side stream, so the H2D transfer of query i+1 overlaps the
 recursion of query i (PCIe Gen5 x16 ~ 63 GB/s: a 290-window MAD movie is 290*250*768*2 B = 111 MB ~ 2 ms).
+
+``ResidentFeatures`` + ``WindowStager.stage_resident`` are the route without the host gather: a movie's features are uploaded once and stay on the
+device across its queries, and the window tensor is cut there by one kernel (``rv_window_gather``), with the same bits.
 """
+import collections
 import io
 import os
 
@@ -76,6 +80,8 @@ class StagedWindows:
         self.tensor, self.event = tensor, event
 
     def wait(self, stream=None):
+        if self.event is None:       # produced on the consumer's own stream (the driver's --device_features --clip_prefilter branch): already in order
+            return self.tensor
         stream = stream or torch.cuda.current_stream(self.tensor.device)
         stream.wait_event(self.event)
         self.tensor.record_stream(stream)
@@ -120,3 +126,99 @@ class WindowStager:
             ev.record(self.stream)
         slot["event"] = ev
         return StagedWindows(dev, ev)
+
+    def stage_resident(self, features_dev, windows, **geometry):
+        """``stage_windows`` for features that are already on the device (``ResidentFeatures.get``): features_dev [ctx_l, d], windows a Python list of
+        window indices (or a device i32 row), geometry = ``debug_window``, ``feature_fps``, ``stride``, ``num_frames`` as ``stage2.cut_windows`` takes
+        them -> ``StagedWindows`` with the same tensor ``stage_windows(features, cut_windows(...)[1][windows])`` hands over, bit for bit, made by one
+        kernel on the staging stream (``stage2.gather_windows``): no host gather, no upload of the frames, no synchronisation."""
+        from ..eval import stage2
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))      # whatever made features_dev on the caller's stream comes first
+        with torch.cuda.stream(self.stream):
+            dev = stage2.gather_windows(features_dev, windows, dtype=self.op_dtype, **geometry)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        features_dev.record_stream(self.stream)
+        return StagedWindows(dev, ev)
+
+
+class ResidentFeatures:
+    """Movies' feature arrays kept on the device across the queries of a movie: an LRU cache by bytes, keyed by movie.  ``get(movie, array)`` -> the
+    device tensor [ctx_l, d], uploaded on the first use (through a pinned buffer, asynchronously, on ``stream`` - the stager's) and handed back from the
+    cache afterwards; each entry keeps the event of its upload and ``get`` orders the caller's current stream behind it.  f32 arrays stay f32; a
+    16-bit array stays as stored when that is the engine's operand type (``op_dtype``) and becomes f32 otherwise (exact), so what the kernels read
+    has the values of the array; anything else becomes f32.  An array larger than the whole budget is uploaded and handed back without being kept.
+    ``device="cpu"`` keeps host tensors (no stream, no event): the policy runs without a GPU."""
+
+    def __init__(self, device, budget_bytes, op_dtype=None, stream=None):
+        from .. import hip
+        self.device = torch.device(device)
+        self.budget = int(budget_bytes)
+        self.op_dtype = hip.op_dtype(op_dtype)
+        self.stream = stream
+        if self.device.type == "cuda" and stream is None:
+            self.stream = torch.cuda.Stream(self.device)
+        self._entries = collections.OrderedDict()       # movie -> (tensor, event, bytes), least recently used first
+        self._pinned, self._pinned_event = None, None
+        self.bytes = self.hits = self.misses = self.evictions = 0
+
+    def __len__(self):
+        return len(self._entries)
+
+    def __contains__(self, movie):
+        return movie in self._entries
+
+    def movies(self):
+        """The cached movies, least recently used first."""
+        return list(self._entries)
+
+    def kept_dtype(self, dtype):
+        """The dtype an array of torch ``dtype`` is kept in."""
+        return dtype if dtype in (torch.float32, self.op_dtype) else torch.float32
+
+    def _upload(self, array):
+        src = array if torch.is_tensor(array) else torch.from_numpy(np.ascontiguousarray(array))
+        if src.dim() != 2 or not src.dtype.is_floating_point:
+            raise ValueError(f"ResidentFeatures: features {tuple(src.shape)} {src.dtype} (expected a floating-point array [ctx_l, d])")
+        dtype = self.kept_dtype(src.dtype)
+        if self.device.type != "cuda":
+            return src.to(self.device, dtype).contiguous(), None
+        if src.is_cuda:
+            return src.to(self.device, dtype).contiguous(), None
+        if self._pinned_event is not None:
+            self._pinned_event.synchronize()             # the previous upload has finished reading the buffer
+        nbytes = src.numel() * torch.empty((), dtype=dtype).element_size()
+        if self._pinned is None or self._pinned.numel() < nbytes:
+            self._pinned = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        host = self._pinned[:nbytes].view(dtype).view(src.shape)
+        host.copy_(src)
+        with torch.cuda.stream(self.stream):
+            dev = host.to(self.device, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._pinned_event = ev
+        return dev, ev
+
+    def get(self, movie, array):
+        entry = self._entries.get(movie)
+        if entry is not None:
+            self.hits += 1
+            self._entries.move_to_end(movie)
+        else:
+            self.misses += 1
+            tensor, event = self._upload(array)
+            nbytes = tensor.numel() * tensor.element_size()
+            entry = (tensor, event, nbytes)
+            if nbytes <= self.budget:
+                while self._entries and self.bytes + nbytes > self.budget:
+                    _, (_, _, freed) = self._entries.popitem(last=False)     # (a block freed while kernels still read it stays ordered behind them: record_stream below)
+                    self.bytes -= freed
+                    self.evictions += 1
+                self._entries[movie] = entry
+                self.bytes += nbytes
+        tensor, event, _ = entry
+        if event is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(event)
+            tensor.record_stream(cur)
+        return tensor

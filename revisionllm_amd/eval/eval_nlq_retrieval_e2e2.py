@@ -12,7 +12,8 @@ cutting (:262-277), the optional stage-1 pre-filter (``--grounding_path``, :278-
 per-query ``try / except`` that records the id in ``errors`` and goes on (:418-421).  What differs: the recursion runs as
 ``stage2.run_query`` (``--mode batched`` by default: CLS once per window, the calls of a recursion in one generate; ``--mode
 reference`` = the per-call loop), features are read through ``data.feature_store`` (npy / npz directory / LMDB) and staged to the GPU
-through a pinned double buffer while the previous query is still running.
+through a pinned double buffer while the previous query is still running; ``--device_features`` keeps a movie's
+features on the device across its queries and cuts the windows there (``rv_window_gather``), with the same records.
 """
 import argparse
 import json
@@ -96,6 +97,12 @@ def parse_args(argv=None):
     p.add_argument("--clip_prefilter", action="store_true",
                    help="a query without a stage-1 record in --grounding_path gets its --batch windows from its CLS feature's per-frame cosines "
                         "(stage2.clip_grounding_windows) instead of running every window; off: every code path is what it was")
+    p.add_argument("--device_features", action="store_true",
+                   help="keep each movie's features on the device across its queries (data.feature_store.ResidentFeatures) and cut the recursion's windows "
+                        "there (WindowStager.stage_resident; with --clip_prefilter stage2.clip_stage_windows: the movie is uploaded once, not twice) instead of "
+                        "gathering them on the host and uploading them per query; a video no longer than one window keeps the host route; off: every code path "
+                        "is what it was")
+    p.add_argument("--device_features_mb", type=int, default=2048, help="budget of the resident feature cache in MiB (--device_features)")
     p.add_argument("--pool_rows", type=int, default=56, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per call at most (--in_flight > 1; answers are a dozen tokens)")
     return p.parse_args(argv)
@@ -174,6 +181,39 @@ def prefilter_windows(stage1_answers, n_windows, batch, stride):
     return gw
 
 
+def _resident_cache(args, stager, device):
+    """The movie cache of ``--device_features`` (None without the flag)."""
+    if not getattr(args, "device_features", False):
+        return None
+    from ..data.feature_store import ResidentFeatures
+    return ResidentFeatures(device, getattr(args, "device_features_mb", 2048) << 20, op_dtype=getattr(stager, "op_dtype", None),
+                            stream=getattr(stager, "stream", None))
+
+
+def _on_device(args, resident, ctx_l):
+    """Whether a video's windows are cut on the device: ``--device_features``, and longer than one window (``cut_windows`` lets a shorter video's negative
+    start wrap where the device chain clamps it at 0: those keep the host route, so no record changes) with a whole number of frames per window."""
+    clip_length = args.debug_window * args.feature_fps
+    return resident is not None and clip_length == int(clip_length) and ctx_l > clip_length
+
+
+def _stage_on_device(args, stager, resident, movie, features, query_cls, stage1, batch):
+    """The three window branches of the loops with the movie resident on the device -> (grounding_windows, StagedWindows): the same lists and the same
+    tensor as ``cut_windows`` + ``stage_windows`` give."""
+    from ..data.feature_store import StagedWindows
+    geometry = dict(debug_window=args.debug_window, feature_fps=args.feature_fps, stride=args.stride)
+    features_dev = resident.get(movie, features)
+    if stage1 is not None:
+        grounding_windows = prefilter_windows(stage1["answer"], stage2.window_count(len(features), **geometry), batch, args.stride)
+    elif getattr(args, "clip_prefilter", False) and query_cls is not None:
+        grounding_windows, windows = stage2.clip_stage_windows(features_dev, query_cls, batch=batch, num_frames=args.num_frames,
+                                                               dtype=getattr(stager, "op_dtype", None), **geometry)
+        return grounding_windows, StagedWindows(windows, None)
+    else:
+        grounding_windows = list(range(stage2.window_count(len(features), **geometry)))
+    return grounding_windows, stager.stage_resident(features_dev, grounding_windows, num_frames=args.num_frames, **geometry)
+
+
 def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     """-> (number of records written, ids that raised).  ``tokenizer`` / ``model``: pass ready objects (tests, notebooks); by default
     they come from ``load_pretrained_model(args, args.stage2, args.stage3, load_ckp=args.load_ckp)`` (e2e2.py:180)."""
@@ -189,6 +229,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
         model = model.bfloat16().cuda()
     store = FeatureStore(args.feat_folder, q_feat_dir=args.q_feat_dir, vis_feat_storage="npy" if args.vis_feat_storage == "pth" else args.vis_feat_storage)
     stager = WindowStager(model.device, op_dtype=getattr(model, "dtype", None))
+    resident = _resident_cache(args, stager, model.device)
     done = set(done_query_ids(prediction_path))
     items = split_items(load_items(args.data_path), args.split, args.total_split)
     batch = args.batch
@@ -199,7 +240,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
             grounding_dict[gl["query_id"]] = gl
     errors, written = [], 0
     if getattr(args, "in_flight", 1) > 1 and args.mode == "batched" and args.task in ("grounding", "all"):
-        return _eval_in_flight(args, tokenizer, model, store, stager, items, done, grounding_dict, prediction_path)
+        return _eval_in_flight(args, tokenizer, model, store, stager, items, done, grounding_dict, prediction_path, resident)
     for id_, data in items:
         if id_ in done:
             continue
@@ -211,17 +252,20 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
                 continue
             ctx_l = len(features)
             assert ctx_l > 0, ctx_l
-            _, frame_idx = stage2.cut_windows(ctx_l, args.debug_window, args.feature_fps, args.stride, args.num_frames)
-            if id_ in grounding_dict:
-                grounding_windows = prefilter_windows(grounding_dict[id_]["answer"], frame_idx.shape[0], batch, args.stride)
-                frame_idx = frame_idx[grounding_windows]
-            elif getattr(args, "clip_prefilter", False) and query_cls is not None:
-                grounding_windows = stage2.clip_grounding_windows(features, query_cls, debug_window=args.debug_window, feature_fps=args.feature_fps,
-                                                                  stride=args.stride, batch=batch)
-                frame_idx = frame_idx[grounding_windows]
+            if _on_device(args, resident, ctx_l):
+                grounding_windows, staged = _stage_on_device(args, stager, resident, movie, features, query_cls, grounding_dict.get(id_), batch)
             else:
-                grounding_windows = list(range(frame_idx.shape[0]))
-            staged = stager.stage_windows(features, frame_idx)
+                _, frame_idx = stage2.cut_windows(ctx_l, args.debug_window, args.feature_fps, args.stride, args.num_frames)
+                if id_ in grounding_dict:
+                    grounding_windows = prefilter_windows(grounding_dict[id_]["answer"], frame_idx.shape[0], batch, args.stride)
+                    frame_idx = frame_idx[grounding_windows]
+                elif getattr(args, "clip_prefilter", False) and query_cls is not None:
+                    grounding_windows = stage2.clip_grounding_windows(features, query_cls, debug_window=args.debug_window, feature_fps=args.feature_fps,
+                                                                      stride=args.stride, batch=batch)
+                    frame_idx = frame_idx[grounding_windows]
+                else:
+                    grounding_windows = list(range(frame_idx.shape[0]))
+                staged = stager.stage_windows(features, frame_idx)
             dev = model.device
             qf = torch.from_numpy(np.asarray(query_feats)).to(dev).to(getattr(model, "dtype", torch.float32)) if query_feats is not None else None
             qc = torch.from_numpy(np.asarray(query_cls)).to(dev).float() if query_cls is not None else None
@@ -243,7 +287,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     return written, errors
 
 
-def _eval_in_flight(args, tokenizer, model, store, stager, items, done, grounding_dict, prediction_path):
+def _eval_in_flight(args, tokenizer, model, store, stager, items, done, grounding_dict, prediction_path, resident=None):
     """``--in_flight N``: the same per-query work as the loop in ``eval`` (features -> windows -> recursion -> one JSONL record, per-query
     ``try / except``, records appended in annotation order), with up to N queries in flight as ``sched`` tasks: a query's feature staging
     and adapter overlap the others' LLM passes, their prefills are batched and their decode steps merged by a ``serve.DecodeServer``."""
@@ -285,17 +329,21 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, groundin
             if "movie_duration" in data and data["movie_duration"] <= args.debug_window:
                 continue
             assert len(features) > 0, len(features)
-            _, frame_idx = stage2.cut_windows(len(features), args.debug_window, args.feature_fps, args.stride, args.num_frames)
-            if id_ in grounding_dict:
-                grounding_windows = prefilter_windows(grounding_dict[id_]["answer"], frame_idx.shape[0], args.batch, args.stride)
-                frame_idx = frame_idx[grounding_windows]
-            elif getattr(args, "clip_prefilter", False) and query_cls is not None:
-                grounding_windows = stage2.clip_grounding_windows(features, query_cls, debug_window=args.debug_window, feature_fps=args.feature_fps,
-                                                                  stride=args.stride, batch=args.batch)
-                frame_idx = frame_idx[grounding_windows]
+            if _on_device(args, resident, len(features)):
+                grounding_windows, staged = _stage_on_device(args, stager, resident, movie, features, query_cls, grounding_dict.get(id_), args.batch)
+                windows = staged.wait()
             else:
-                grounding_windows = list(range(frame_idx.shape[0]))
-            windows = stager.stage_windows(features, frame_idx).wait()
+                _, frame_idx = stage2.cut_windows(len(features), args.debug_window, args.feature_fps, args.stride, args.num_frames)
+                if id_ in grounding_dict:
+                    grounding_windows = prefilter_windows(grounding_dict[id_]["answer"], frame_idx.shape[0], args.batch, args.stride)
+                    frame_idx = frame_idx[grounding_windows]
+                elif getattr(args, "clip_prefilter", False) and query_cls is not None:
+                    grounding_windows = stage2.clip_grounding_windows(features, query_cls, debug_window=args.debug_window, feature_fps=args.feature_fps,
+                                                                      stride=args.stride, batch=args.batch)
+                    frame_idx = frame_idx[grounding_windows]
+                else:
+                    grounding_windows = list(range(frame_idx.shape[0]))
+                windows = stager.stage_windows(features, frame_idx).wait()
             qf = torch.from_numpy(np.asarray(query_feats)).to(dev).to(getattr(model, "dtype", torch.float32))
             qc = torch.from_numpy(np.asarray(query_cls)).to(dev).float()
             sentence = data["sentence"].strip().lower() if "sentence" in data else data["query"].strip(".?").lower()

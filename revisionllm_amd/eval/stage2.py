@@ -72,6 +72,79 @@ def clip_grounding_windows(features, query_cls, *, debug_window=125, feature_fps
     return [i for i in sel.select[0].tolist() if i >= 0]
 
 
+def _whole_clip_length(who, debug_window, feature_fps):
+    """``debug_window * feature_fps`` as an int; refused unless it is a positive whole number of frames."""
+    clip_length = debug_window * feature_fps
+    if not (isinstance(clip_length, numbers.Real) and not isinstance(clip_length, bool) and math.isfinite(clip_length) and clip_length == int(clip_length)
+            and clip_length >= 1):
+        raise ValueError(f"{who}: debug_window * feature_fps = {clip_length!r} must be a positive whole number of frames")
+    return int(clip_length)
+
+
+def window_count(ctx_l, debug_window=125, feature_fps=5, stride=5):
+    """How many windows ``cut_windows`` makes of ``ctx_l`` frames (its own expression, without the frame indices)."""
+    clip_length = debug_window * feature_fps
+    return max(0, math.ceil(ctx_l / (clip_length // stride)) - 1)
+
+
+def _resident_features(who, features_dev, clip_length):
+    if not torch.is_tensor(features_dev) or features_dev.dim() != 2 or min(features_dev.shape) == 0 or not features_dev.dtype.is_floating_point:
+        raise ValueError(f"{who}: features {tuple(features_dev.shape) if torch.is_tensor(features_dev) else type(features_dev).__name__} "
+                         f"(expected a floating-point tensor [ctx_l, d])")
+    if features_dev.shape[0] <= clip_length:
+        raise ValueError(f"{who}: ctx_l={features_dev.shape[0]} frames for windows of {clip_length}: cut_windows lets such a video's negative start wrap, "
+                         f"the device chain clamps it at 0 - take the host route (cut_windows + WindowStager.stage_windows)")
+
+
+def gather_windows(features_dev, windows, *, debug_window=125, feature_fps=5, stride=5, num_frames=250, dtype=None):
+    """The recursion's input from features that are already on the device: features_dev [ctx_l, d] (f32 or 16-bit operands), windows a Python list of
+    window indices or a device i32 row of them -> [n, num_frames, d] in ``dtype`` (None: ``ops.window_gather``'s default), equal to
+    ``features[cut_windows(ctx_l, debug_window, feature_fps, stride, num_frames)[1][windows]]`` cast to ``dtype`` (``rv_window_gather``: one launch, no
+    synchronisation; a list is uploaded through a pinned buffer).  A list is indexed as numpy indexes: a negative index counts from the end, one out of
+    range raises IndexError; in a device row an entry outside the windows (``window_select``'s -1 padding) gives a zero window.
+    ``debug_window * feature_fps`` must be a whole number of frames and the video longer than one window."""
+    who = "gather_windows"
+    clip_length = _whole_clip_length(who, debug_window, feature_fps)
+    _resident_features(who, features_dev, clip_length)
+    if not torch.is_tensor(windows):
+        W = window_count(features_dev.shape[0], debug_window, feature_fps, stride)
+        rows = []
+        for i in windows:
+            if not (isinstance(i, numbers.Integral) and not isinstance(i, bool) and -W <= i < W):
+                raise IndexError(f"{who}: window {i!r} is out of bounds for a video of {W} windows")
+            rows.append(int(i) % W)
+        if not rows:
+            return torch.empty((0, num_frames, features_dev.shape[1]), dtype=ops.window_gather_dtypes(who, features_dev.dtype, dtype)[0], device=features_dev.device)
+        windows = ops.h2d(torch.tensor(rows, dtype=torch.int32), features_dev.device)
+    elif windows.dim() != 1:
+        raise ValueError(f"{who}: windows {tuple(windows.shape)} (expected a list or a device int32 row)")
+    return ops.window_gather(features_dev, windows, win=clip_length, stride=stride, num_frames=num_frames, out_dtype=dtype)
+
+
+def clip_stage_windows(features_dev, query_cls, *, debug_window=125, feature_fps=5, stride=5, batch=100, num_frames=250, dtype=None, k=3, min_sep=1):
+    """``clip_grounding_windows`` and the staging of its windows in one pass over features that are on the device: features_dev [ctx_l, d], query_cls [d]
+    (host or device) -> (the sorted Python list ``clip_grounding_windows`` returns, the window tensor [len(list), num_frames, d] in ``dtype``).  Three
+    launches - the cosine row, ``rv_window_select``, ``rv_window_gather`` fed from the device ``select`` row - and the gather is enqueued BEFORE the
+    ``.tolist()`` of that row, the one device -> host copy: when the list arrives the tensor is already on its way, and the movie is uploaded once, not
+    once for the cosines and again in pieces."""
+    who = "clip_stage_windows"
+    from . import similarity
+    clip_length = _whole_clip_length(who, debug_window, feature_fps)
+    if not (isinstance(batch, numbers.Integral) and not isinstance(batch, bool) and batch >= 1):
+        raise ValueError(f"{who}: batch={batch!r} must be a positive integer")
+    _resident_features(who, features_dev, clip_length)
+    query_cls = query_cls if torch.is_tensor(query_cls) else torch.from_numpy(np.ascontiguousarray(query_cls))
+    if query_cls.dim() != 1 or query_cls.shape[0] != features_dev.shape[1] or not query_cls.dtype.is_floating_point:
+        raise ValueError(f"{who}: features {tuple(features_dev.shape)} / query_cls {tuple(query_cls.shape)} {query_cls.dtype} (expected [ctx_l, d] and a floating-point [d])")
+    dev, ctx_l = features_dev.device, features_dev.shape[0]
+    sel = similarity.select_windows(ops.h2d(query_cls, dev)[None], features_dev[None], torch.ones(1, ctx_l, device=dev), win=clip_length, stride=stride,
+                                    keep=batch, k=k, min_sep=min_sep)
+    row = sel.select[0]
+    frames = ops.window_gather(features_dev, row, win=clip_length, stride=stride, num_frames=num_frames, out_dtype=dtype)
+    grounding_windows = [i for i in row.tolist() if i >= 0]         # ascending, the -1 padding behind them: the first len(list) windows of frames
+    return grounding_windows, frames[:len(grounding_windows)]
+
+
 def plan_groups(W, batch, zooms=(4, 2, 1)):
     """[(zoom, start, end)] in the order the reference visits them (e2e2.py:337-346); the last group of a level is
     shifted back so that it also holds ``batch // zoom`` windows."""

@@ -1,4 +1,4 @@
-"""The CLIP grounding chain's wrappers (cosine rows, span scores, ranking, span proposals, window selection, the two poolings) with their checkers, constants
+"""The CLIP grounding chain's wrappers (cosine rows, span scores, ranking, span proposals, window selection, window gather, the two poolings) with their checkers, constants
 and namedtuples; ``ops`` re-exports every public name.  Every function takes / returns torch DEVICE tensors and enqueues on torch's current stream."""
 import collections
 import math
@@ -342,6 +342,83 @@ def window_select(sims, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, ret
                                          hip.ptr(gt.float().contiguous()) if gt is not None else None, hip.ptr(select), hip.ptr(n_select), hip.ptr(n_windows),
                                          hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()), "rv_window_select")
     return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
+
+
+WINDOW_GATHER_MAX_FRAMES = 1 << 16
+_GATHER_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def window_gather_keywords(who, win, stride, num_frames):
+    """The keyword refusals of ``window_gather`` that need no tensor (raised before any device is looked for) -> the three as ints."""
+    for name, v in (("win", win), ("stride", stride), ("num_frames", num_frames)):
+        if not (_is_int(v) and 1 <= v < 2 ** 31):
+            raise ValueError(f"{who}: {name}={v!r} must be a positive integer")
+    if win < stride:
+        raise ValueError(f"{who}: win={win} frames with stride={stride} (stride <= win)")
+    if num_frames > WINDOW_GATHER_MAX_FRAMES:
+        raise ValueError(f"{who}: num_frames={num_frames} (at most {WINDOW_GATHER_MAX_FRAMES})")
+    return int(win), int(stride), int(num_frames)
+
+
+def window_gather_dtypes(who, video_dtype, out_dtype):
+    """(the output dtype, the flavour of the library that runs the call): ``out_dtype=None`` is the video's dtype when that is 16-bit, else the default
+    library's operand type.  Each library reads and writes f32 and its OWN 16-bit type, so a call that names both 16-bit types is refused."""
+    if video_dtype not in _GATHER_DTYPES:
+        raise ValueError(f"{who}: video must be float32, float16 or bfloat16 (got {video_dtype})")
+    if out_dtype is None:
+        out_dtype = video_dtype if video_dtype != torch.float32 else hip.op_dtype()
+    if out_dtype not in _GATHER_DTYPES:
+        raise ValueError(f"{who}: out_dtype must be float32, float16 or bfloat16 (got {out_dtype!r})")
+    sixteen = {t for t in (video_dtype, out_dtype) if t != torch.float32}
+    if len(sixteen) == 2:
+        raise ValueError(f"{who}: {video_dtype} features cannot become {out_dtype}: the {hip.flavour_of(video_dtype)} library converts between float32 "
+                         f"and its own 16-bit type only (no cross-type 16-bit conversion); pass float32 features, or out_dtype={video_dtype}")
+    return out_dtype, hip.flavour_of(sixteen.pop() if sixteen else None)
+
+
+def window_gather(video, select, *, win, stride, num_frames, mask=None, out_dtype=None, return_index=False):
+    """The recursion's window tensor from features that live on the device (``rv_window_gather``): video [L,d] or [B,L,d] (f32 or 16-bit operands; a
+    view with a frame stride above d is read in place), select i32 [keep], [R,keep] or [B,Q,keep] - ``window_select``'s ``select`` as it lies, -1
+    padding included, or any other window indices - mask [L] / [B,L] or None (its row sum is the duration; None: every frame counts) -> frames
+    [...,keep,num_frames,d] in ``out_dtype`` (None: the video's dtype when it is 16-bit, else the default library's operand type), and with
+    ``return_index`` the sampled frame of every output row as well, i32 [...,keep,num_frames].  Window i is ``stage2.cut_windows``' for ``clip_length =
+    win`` and its frames are that function's ``np.linspace(start, end, num_frames, dtype=int32)``, so with a full mask ``frames[..., n, :, :]`` is
+    ``video[cut_windows(...)[1][select[..., n]]]`` cast to ``out_dtype``; an entry outside the row's windows (the -1 padding) gives zeros and index -1.
+    With [B,L,d] features the R rows of ``select`` belong to the videos in consecutive groups of R / B.  One launch (a mask that is not f32 adds a cast
+    kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
+    who = "window_gather"
+    win, stride, F = window_gather_keywords(who, win, stride, num_frames)
+    if not torch.is_tensor(video) or not torch.is_tensor(select) or (mask is not None and not torch.is_tensor(mask)):
+        raise ValueError(f"{who}: video, select and mask must be tensors")
+    if video.dim() not in (2, 3) or not 1 <= select.dim() <= 3 or min(video.shape) == 0 or min(select.shape) == 0:
+        raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (expected [L, d] or [B, L, d] and [keep], [R, keep] or [B, Q, keep])")
+    if select.dtype != torch.int32:
+        raise ValueError(f"{who}: select must be int32 (got {select.dtype})")
+    M = video.shape[0] if video.dim() == 3 else 1
+    L, d = video.shape[-2:]
+    lead, keep = tuple(select.shape[:-1]), select.shape[-1]
+    R = math.prod(lead)
+    if (select.dim() == 3 and (video.dim() != 3 or lead[0] != M)) or R % M != 0:
+        raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (a whole number of rows of select for each video)")
+    if mask is not None:
+        if mask.shape != tuple(video.shape[:-1]):
+            raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected {tuple(video.shape[:-1])})")
+        if mask.dtype.is_complex:
+            raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    if L > SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={L} frames (at most {SPAN_PROPOSE_MAX_FRAMES})")
+    if win > L:
+        raise ValueError(f"{who}: win={win} frames for rows of L={L}")
+    out_dtype, flavour = window_gather_dtypes(who, video.dtype, out_dtype)
+    if video.stride(-1) != 1 or video.stride(-2) < d or (video.dim() == 3 and M > 1 and video.stride(0) != L * video.stride(-2)):
+        video = video.contiguous()
+    dev = video.device
+    frames = torch.empty(lead + (keep, F, d), dtype=out_dtype, device=dev)
+    index = torch.empty(lead + (keep, F), dtype=torch.int32, device=dev) if return_index else None
+    hip.check(hip.lib(flavour).rv_window_gather(hip.ptr(video), hip.dtype_code(video), video.stride(-2), hip.ptr(mask.float().contiguous()) if mask is not None else None,
+                                                hip.ptr(select.contiguous()), R, R // M, L, d, win, stride, keep, F, hip.ptr(frames), hip.dtype_code(frames),
+                                                hip.ptr(index), hip.stream()), "rv_window_gather")
+    return (frames, index) if return_index else frames
 
 
 def attn_pool(text_embeds, video_embeds, temperature):

@@ -183,6 +183,7 @@ SIGNATURES = {
     "rv_span_rank": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _f, _p, _p, _i32, _p, _p, _p, _p, _p, _p]),
     "rv_span_propose": (C.c_int, [_p, _p, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "rv_window_select": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "rv_window_gather": (C.c_int, [_p, _i32, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
 }
 
 

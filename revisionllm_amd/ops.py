@@ -10,11 +10,12 @@ from . import hip
 # the CLIP front end (frames / surfaces -> patches) lives in ``frontend``; its public names stay reachable here
 from .frontend import (CLIP_MEAN, CLIP_STD, PACKED_PIX_FMTS, PIX_FMTS, RGB_PIX_FMTS, frames_to_patches, hdr_map, orientation, packed_frame_bytes,  # noqa: F401
                        packed_to_patches, split_yuv, split_yuv420, yuv_frame_bytes, yuv_surface_to_patches, yuv_to_patches)
-# so does the CLIP grounding chain (cosine rows -> span scores -> ranking / proposals / window selection, the poolings), in ``grounding``
+# so does the CLIP grounding chain (cosine rows -> span scores -> ranking / proposals / window selection / window gather, the poolings), in ``grounding``
 from .grounding import (HIT_IOU, SPAN_FORMS, SPAN_POOLINGS, SPAN_PROPOSE_LEVELS, SPAN_PROPOSE_MAX_FRAMES, SPAN_PROPOSE_MAX_LEVELS, SPAN_RANK_MAX,  # noqa: F401
                         WINDOW_SELECT_MAX, SpanProposals, SpanRank, WindowSelection, attn_pool, frame_cosine, frame_cosine_multi, span_propose,
                         span_propose_keywords, span_propose_shapes, span_rank, span_rank_keywords, span_scores, span_scores_multi, topk_pool,
-                        window_select, window_select_capacity, window_select_gt, window_select_keywords)
+                        WINDOW_GATHER_MAX_FRAMES, window_gather, window_gather_dtypes, window_gather_keywords, window_select, window_select_capacity,
+                        window_select_gt, window_select_keywords)
 from .utils import hashinit
 
 
