@@ -814,6 +814,49 @@ int rv_window_select(const float* sims, const float* mask, int32_t R, int32_t rp
 int rv_window_gather(const void* video, int32_t video_dtype, int64_t ldv, const float* mask, const int32_t* select, int32_t R, int32_t rpm, int32_t L,
                      int32_t d, int32_t win, int32_t stride, int32_t keep, int32_t F, void* out, int32_t out_dtype, int32_t* frame_idx, void* stream);
 
+/* ---- the stage-1 driver on the device: its window tensor and the cosine score of every proposal (what eval/eval_nlq_negative.py does on the host
+ * per query: stage1.cut_windows' linspace indices, a fancy-index of the movie, a cast and an upload; then one rv_topk_cosine launch and one host
+ * synchronisation per proposal - negative.py:224-235, :299-337) ----
+ * rv_window_gather_rule is rv_window_gather with the window rule as an argument and an optional select.  Everything not named here is
+ * rv_window_gather's definition word for word (the kernel is the same template): video, ldv, the duration from the mask or D = L, the sampled frames
+ * np.linspace(s, e, F, dtype=int32) in un-fused float64 with the last index set to e, the copy or the store conversion with its saturation count, an
+ * all-zero out[r, n] and frame_idx = -1 for an invalid entry, 64-bit offsets, the 16-byte and the one-element form, the clamp in front of the loads.
+ * rule = RV_WINDOWS_SHIFTED (0): rv_window_gather's windows (stage2.cut_windows), stride as there.
+ * rule = RV_WINDOWS_CLIPPED (1): stage1.cut_windows' windows for clip_length = win - half-overlapping, the last ones clipped and NOT shifted back.
+ *   stride must be 2 and is otherwise unused.  half = win / 2, W_r = max(0, ceil(D / half) - 1) (rv_window_gather's count at stride 2); for i in
+ *   [0, W_r): s = (i * win) / 2 in 64-bit integers - for an odd win NOT i * half: win = 625 starts at 0, 312, 625, 937 - and e = min(s + win, D - 1);
+ *   the window is frames [s, e + 1), up to win + 1 of them and fewer at the end of the row.  s == e is a window of one frame.  s > e is a VOID window:
+ *   it exists for an odd win only (first at D = 15 for win = 5 and at D = 195625 for win = 625; never for an even win), the host's linspace leaves the
+ *   array there, and here it is an invalid entry: zeros and -1, nothing read.
+ * select i32 [R,keep] as rv_window_gather reads it, -1 padding included, or NULL: entry n of a row is then window n (keep = the number of windows
+ *   gives them all with nothing uploaded; an n at or past W_r is an invalid entry like any other).
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: everything rv_window_gather refuses except a null select; a rule that is neither
+ * 0 nor 1; rule 1 with stride != 2. */
+#define RV_WINDOWS_SHIFTED 0
+#define RV_WINDOWS_CLIPPED 1
+int rv_window_gather_rule(const void* video, int32_t video_dtype, int64_t ldv, const float* mask, const int32_t* select, int32_t R, int32_t rpm,
+                          int32_t L, int32_t d, int32_t win, int32_t stride, int32_t keep, int32_t F, void* out, int32_t out_dtype, int32_t* frame_idx,
+                          int32_t rule, void* stream);
+/* The cosine score of P ragged proposals in one launch: feat [W,T,d] contiguous, f32 or this library's 16-bit operand type (16-byte aligned when d
+ * is a whole number of 16-byte chunks, as rv_topk_cosine's), q_cls f32 [d], props i32 [P,3] in DEVICE memory as (window, a, b) -> out f32 [P].
+ * The slice is Python's feat[window][a : b + 1]: lo = min(a, T), hi = min(b + 1, T), frames [lo, hi).  A proposal is VOID when window lies outside
+ * [0, W), when a < 0 or when hi <= lo (b < a, or a >= T): out[p] = NaN (0x7fc00000) and nothing of feat is read - no value of props makes the kernel
+ * read or write outside its buffers.  Otherwise out[p] is rv_topk_cosine's score of the slice: the column norms over the slice's hi - lo frames
+ * only, sims[t] = <f_t, q / norm>, the sum of the min(k, hi - lo) largest in torch.topk's order (a NaN first, then the larger value, then the smaller
+ * index); k <= 0: the mean.  A NaN feature or an all-zero column inside a slice gives NaN for that proposal and no other.
+ * One launch, one 1024-thread workgroup per proposal on the grid's x dimension.  The two kernel bodies are rv_topk_cosine's own device functions,
+ * taking a base pointer and a frame count, so out[p] equals rv_topk_cosine(feat + (window * T + lo) * d, n = 1, T = hi - lo, d, k) BIT FOR BIT whenever
+ * that call takes the kernel form this entry takes.  The form and the LDS size are chosen as rv_topk_cosine chooses them for the full window
+ * length T: the 16-byte form when d is a multiple of vec (8 for 16-bit features, 4 for f32), d / vec <= 1024 and ((1024 / (d / vec) + 1) * d + T)
+ * floats fit 64 KB, else the generic form with 5 * d + T floats.  A slice's own call chooses by hi - lo <= T, so the forms coincide for EVERY slice
+ * exactly when T itself takes the 16-byte form or d rules that form out at any length (d not a multiple of vec, or d / vec > 1024); at d = 768
+ * that is every T <= 7936 for both element types (16-bit: 11 * 768 + T <= 16384).  Past that, a long window runs the generic form while a short
+ * slice's own call would run the 16-byte one: the same definition, sums in another order.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null feat / q_cls / props / out; P < 1; W < 1; T < 1; d < 1; a dtype that is not
+ * f32 or this library's 16-bit type; 5 * d + T floats above 64 KB when the 16-byte form is not taken (rv_topk_cosine's bound at T). */
+int rv_proposal_cosine(const void* feat, int feat_dtype, const float* q_cls, const int32_t* props, int32_t P, int32_t W, int32_t T, int32_t d,
+                       int32_t k, float* out, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -1,5 +1,5 @@
 // What the stages of the CLIP grounding chain share, one definition each: the frame order of the score kernels, the rank key of a score, the bitonic
-// sort of (key, index) pairs, the duration rule, the window rule and the small helpers around them.  Included by the chain's translation units only (sample.hip for
+// sort of (key, index) pairs, the duration rule, the two window rules (stage 2's shifted windows, stage 1's clipped ones) and the small helpers around them.  Included by the chain's translation units only (sample.hip for
 // rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip, gather.hip): two stages that have to agree bit for bit call the same code.
 #pragma once
 #include "kernels.h"
@@ -131,6 +131,16 @@ __device__ __forceinline__ int ws_count(int win, int stride, int D) {
     const int hop = win / stride;
     const int W = (D + hop - 1) / hop - 1;
     return W < 0 ? 0 : W;
+}
+// frames [lo, hi) of window i of stage1.cut_windows' rule (half-overlapping windows, the last ones clipped at D - 1 and NOT shifted back): there are
+// ws_count(win, 2, D) of them, s = (i * win) / 2 (for an odd win not i * (win / 2)), e = min(s + win, D - 1).  -> false for a void window (s > e:
+// an odd win only, first at D = 15 for win = 5, where the host's linspace runs past the array); s == e is a window of one frame.
+__device__ __forceinline__ bool ws_bounds_clipped(int i, int win, int D, int& lo, int& hi) {
+    const int64_t s = (int64_t)i * win / 2;
+    const int64_t e = s + win < (int64_t)D - 1 ? s + win : (int64_t)D - 1;
+    lo = (int)s;
+    hi = (int)e + 1;
+    return s <= e;
 }
 
 }  // namespace

@@ -3,6 +3,8 @@
 //                     entropy of the processed and of the raw next-token distribution
 //   rv_entropy_stats  get_entropy_statistics (funs_get_feature_X.py:120-146) over stacked per-step scores
 //   rv_topk_cosine    column-normalised top-k pooled cosine score (eval_nlq_retrieval_e2e2.py:380-386)
+//   rv_proposal_cosine  rv_topk_cosine's score of P ragged slices feat[window][a : b + 1] in one launch (the stage-1 driver's proposals,
+//                     eval_nlq_negative.py:299-337): the same two kernel bodies, as device functions
 //   rv_topk_pool      _topk_pooling (eval/similarity.py:71-94)
 // The two stage-2 scores rank frames in the grounding chain's order (grounding.h); the chain's own stages live in similarity.hip, rank.hip,
 // propose.hip and prefilter.hip.
@@ -645,14 +647,13 @@ __global__ __launch_bounds__(TPB) void entropy_stats_kernel(const float* __restr
 
 // one block (1024 threads) per segment: column norms over frames, sims[t] = <f_t / norm, q>, sum of the k largest
 // (k <= 0: mean).  Phase 1 splits the frames over 4 thread groups per column block to keep ~T/4 loads per thread.
+// The body of a segment of Tn frames at f (all 1024 threads call; smem: 5 * d + Tn floats) -> the score, in thread 0: rv_topk_cosine's segments and
+// rv_proposal_cosine's slices run this one piece of code.
 template <typename T>
-__global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __restrict__ feat, const float* __restrict__ q, int Tn, int d,
-                                                           int k, float* __restrict__ out) {
-    extern __shared__ float smem[];
+__device__ __forceinline__ float topk_cosine_generic(const T* __restrict__ f, const float* __restrict__ q, int Tn, int d, int k, float* smem) {
     float* qn = smem;            // [d] q / column norm
     float* psum = smem + d;      // [4][d] partial sums of squares (summed in fixed order: deterministic)
     float* sims = smem + 5 * d;  // [Tn]
-    const T* f = feat + (int64_t)blockIdx.x * Tn * d;
     {
         const int part = threadIdx.x >> 8, c0 = threadIdx.x & 255;   // 4 frame partitions x 256 column lanes
         for (int c = c0; c < d; c += 256) {
@@ -675,8 +676,8 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __re
         if (lane == 0) sims[t] = s;
     }
     __syncthreads();
+    float acc = 0.f;
     if (threadIdx.x == 0) {
-        float acc = 0.f;
         if (k <= 0) {
             for (int t = 0; t < Tn; ++t) acc += sims[t];
             acc /= (float)Tn;
@@ -689,8 +690,16 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __re
                 prev = best;
             }
         }
-        out[blockIdx.x] = acc;
     }
+    return acc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __restrict__ feat, const float* __restrict__ q, int Tn, int d,
+                                                           int k, float* __restrict__ out) {
+    extern __shared__ float smem[];
+    const float acc = topk_cosine_generic<T>(feat + (int64_t)blockIdx.x * Tn * d, q, Tn, d, k, smem);
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
 
@@ -699,16 +708,14 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel_generic(const T* __re
 // and are added in group order (deterministic).  The scores take one wave per frame with the same 16-byte loads, and the
 // top-k is k wave-wide rank rounds (rank_before: NaN, then largest value, then smallest frame index: the serial scan's choice).  39 MB of bf16 features
 // for 100 segments: 157 -> ~25 us.
+// The body, as above (smem: (groups + 1) * d + Tn floats; f 16-byte aligned) -> the score, in thread 0.
 template <typename T>
-__global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__ feat, const float* __restrict__ q, int Tn, int d,
-                                                           int k, float* __restrict__ out) {
+__device__ __forceinline__ float topk_cosine_vector(const T* __restrict__ f, const float* __restrict__ q, int Tn, int d, int k, float* smem) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    extern __shared__ float smem[];
     const int chunks = d / VEC, groups = 1024 / chunks;
     float* qn = smem;                 // [d]
     float* psum = smem + d;           // [groups][d]
     float* sims = psum + groups * d;  // [Tn]
-    const T* f = feat + (int64_t)blockIdx.x * Tn * d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < chunks * groups) {
         const int cc = tid % chunks, fg = tid / chunks;
@@ -743,8 +750,8 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__
         if (lane == 0) sims[t] = s1;
     }
     __syncthreads();
-    if (wave != 0) return;
     float acc = 0.f;
+    if (wave != 0) return acc;
     if (k <= 0) {
         for (int t = lane; t < Tn; t += 64) acc += sims[t];
         acc = wave_sum(acc) / (float)Tn;
@@ -758,7 +765,35 @@ __global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__
             prev = best;
         }
     }
-    if (lane == 0) out[blockIdx.x] = acc;
+    return acc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void topk_cosine_kernel(const T* __restrict__ feat, const float* __restrict__ q, int Tn, int d,
+                                                           int k, float* __restrict__ out) {
+    extern __shared__ float smem[];
+    const float acc = topk_cosine_vector<T>(feat + (int64_t)blockIdx.x * Tn * d, q, Tn, d, k, smem);
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
+// rv_proposal_cosine: block p scores the ragged slice feat[window][a : b + 1] of proposal p = (window, a, b) with the body rv_topk_cosine runs on an
+// equal-length segment (VECTOR: topk_cosine_vector, else topk_cosine_generic; the entry chooses as rv_topk_cosine does for Tn frames, and the LDS is sized
+// for Tn, so every slice fits).  lo = min(a, Tn), hi = min(b + 1, Tn); a window outside [0, W), a < 0 or hi <= lo is void: NaN, nothing of feat is read.  The
+// three ints are the same in every thread, so the block leaves as one in front of the body's first barrier.
+template <typename T, bool VECTOR>
+__global__ __launch_bounds__(1024) void proposal_cosine_kernel(const T* __restrict__ feat, const float* __restrict__ q, const int32_t* __restrict__ props,
+                                                               int W, int Tn, int d, int k, float* __restrict__ out) {
+    extern __shared__ float smem[];
+    const int64_t p = blockIdx.x;
+    const int w = props[3 * p], a = props[3 * p + 1], b = props[3 * p + 2];
+    const int lo = a < Tn ? a : Tn, hi = b < Tn ? b + 1 : Tn;      // (b + 1 is formed below Tn only: no overflow)
+    if (w < 0 || w >= W || a < 0 || hi <= lo) {
+        if (threadIdx.x == 0) out[p] = qnan();
+        return;
+    }
+    const T* f = feat + ((int64_t)w * Tn + lo) * d;              // frames [lo, hi) of window w: inside feat
+    const float acc = VECTOR ? topk_cosine_vector<T>(f, q, hi - lo, d, k, smem) : topk_cosine_generic<T>(f, q, hi - lo, d, k, smem);
+    if (threadIdx.x == 0) out[p] = acc;
 }
 
 // _topk_pooling (similarity.py:71-94) for one (video, text) pair per block: sims[t] = <f_t, q>, the k frames with the largest
@@ -831,27 +866,61 @@ extern "C" int rv_entropy_stats(const float* logits, int32_t B, int32_t G, int32
     return RV_OK;
 }
 
-extern "C" int rv_topk_cosine(const void* feat, int feat_dtype, const float* q_cls, int32_t n, int32_t T, int32_t d, int32_t k,
-                              float* out, void* stream) {
-    RV_CHECK_ARG(feat && q_cls && out && n > 0 && T > 0 && d > 0, "rv_topk_cosine: bad arguments");
-    RV_CHECK_ARG(feat_dtype == RV_OP16 || feat_dtype == RV_F32, "rv_topk_cosine: dtype must be f32 or bf16");
+// rv_topk_cosine's choice of kernel for segments of T frames: the 16-byte form when d is a whole number of 16-byte chunks, at most 1024 of them, and its
+// (groups + 1) * d + T floats fit the 64 KB of LDS; else the generic form with 5 * d + T floats (*lds = 0 when that does not fit either)
+static bool topk_cosine_form(int feat_dtype, int T, int d, size_t* lds) {
     const int vec = feat_dtype == RV_OP16 ? 8 : 4;
     const int chunks = d / vec, groups = chunks > 0 && chunks <= 1024 ? 1024 / chunks : 0;
     const size_t sm_fast = ((size_t)(groups + 1) * d + T) * sizeof(float);
     if (d % vec == 0 && groups > 0 && sm_fast <= 64 * 1024) {
+        *lds = sm_fast;
+        return true;
+    }
+    const size_t sm = ((size_t)5 * d + T) * sizeof(float);
+    *lds = sm <= 64 * 1024 ? sm : 0;
+    return false;
+}
+
+extern "C" int rv_topk_cosine(const void* feat, int feat_dtype, const float* q_cls, int32_t n, int32_t T, int32_t d, int32_t k,
+                              float* out, void* stream) {
+    RV_CHECK_ARG(feat && q_cls && out && n > 0 && T > 0 && d > 0, "rv_topk_cosine: bad arguments");
+    RV_CHECK_ARG(feat_dtype == RV_OP16 || feat_dtype == RV_F32, "rv_topk_cosine: dtype must be f32 or bf16");
+    size_t sm = 0;
+    if (topk_cosine_form(feat_dtype, T, d, &sm)) {
         if (feat_dtype == RV_OP16)
-            hipLaunchKernelGGL(topk_cosine_kernel<op16_t>, dim3(n), dim3(1024), sm_fast, as_stream(stream), (const op16_t*)feat, q_cls, T, d, k, out);
+            hipLaunchKernelGGL(topk_cosine_kernel<op16_t>, dim3(n), dim3(1024), sm, as_stream(stream), (const op16_t*)feat, q_cls, T, d, k, out);
         else
-            hipLaunchKernelGGL(topk_cosine_kernel<float>, dim3(n), dim3(1024), sm_fast, as_stream(stream), (const float*)feat, q_cls, T, d, k, out);
+            hipLaunchKernelGGL(topk_cosine_kernel<float>, dim3(n), dim3(1024), sm, as_stream(stream), (const float*)feat, q_cls, T, d, k, out);
     } else {
-        RV_CHECK_ARG((size_t)(5 * d + T) * 4 <= 64 * 1024, "rv_topk_cosine: 5*d + T too large for LDS");
-        const size_t sm = (size_t)(5 * d + T) * sizeof(float);
+        RV_CHECK_ARG(sm != 0, "rv_topk_cosine: 5*d + T too large for LDS");
         if (feat_dtype == RV_OP16)
             hipLaunchKernelGGL(topk_cosine_kernel_generic<op16_t>, dim3(n), dim3(1024), sm, as_stream(stream), (const op16_t*)feat, q_cls, T, d, k, out);
         else
             hipLaunchKernelGGL(topk_cosine_kernel_generic<float>, dim3(n), dim3(1024), sm, as_stream(stream), (const float*)feat, q_cls, T, d, k, out);
     }
     RV_CHECK_LAUNCH("rv_topk_cosine");
+    return RV_OK;
+}
+
+template <typename T>
+static void proposal_cosine_launch(bool vector, size_t sm, hipStream_t st, const void* feat, const float* q_cls, const int32_t* props, int P, int W, int Tn,
+                                   int d, int k, float* out) {
+    if (vector) hipLaunchKernelGGL((proposal_cosine_kernel<T, true>), dim3(P), dim3(1024), sm, st, (const T*)feat, q_cls, props, W, Tn, d, k, out);
+    else hipLaunchKernelGGL((proposal_cosine_kernel<T, false>), dim3(P), dim3(1024), sm, st, (const T*)feat, q_cls, props, W, Tn, d, k, out);
+}
+
+extern "C" int rv_proposal_cosine(const void* feat, int feat_dtype, const float* q_cls, const int32_t* props, int32_t P, int32_t W, int32_t T, int32_t d,
+                                  int32_t k, float* out, void* stream) {
+    RV_CHECK_ARG(feat && q_cls && props && out, "rv_proposal_cosine: bad arguments (a null feat, q_cls, props or out)");
+    RV_CHECK_ARG(P >= 1 && W >= 1 && T >= 1 && d >= 1, "rv_proposal_cosine: P=%d proposals in W=%d windows of T=%d frames and d=%d columns (all at least 1)", P,
+                 W, T, d);
+    RV_CHECK_ARG(feat_dtype == RV_OP16 || feat_dtype == RV_F32, "rv_proposal_cosine: dtype must be f32 or %s", RV_OP16_NAME);
+    size_t sm = 0;
+    const bool vector = topk_cosine_form(feat_dtype, T, d, &sm);
+    RV_CHECK_ARG(sm != 0, "rv_proposal_cosine: 5*d + T too large for LDS (d=%d, T=%d)", d, T);
+    if (feat_dtype == RV_OP16) proposal_cosine_launch<op16_t>(vector, sm, as_stream(stream), feat, q_cls, props, P, W, T, d, k, out);
+    else proposal_cosine_launch<float>(vector, sm, as_stream(stream), feat, q_cls, props, P, W, T, d, k, out);
+    RV_CHECK_LAUNCH("rv_proposal_cosine");
     return RV_OK;
 }
 

@@ -12,6 +12,7 @@ recursion of query i (PCIe Gen5 x16 ~ 63 GB/s: a 290-window MAD movie is 290*250
 
 ``ResidentFeatures`` + ``WindowStager.stage_resident`` are the route without the host gather: a movie's features are uploaded once and stay on the
 device across its queries, and the window tensor is cut there by one kernel (``rv_window_gather``), with the same bits.
+``stage_resident_clipped`` is the same for the stage-1 driver's half-overlapping windows (``rv_window_gather_rule``).
 """
 import collections
 import io
@@ -136,6 +137,20 @@ class WindowStager:
         self.stream.wait_stream(torch.cuda.current_stream(self.device))      # whatever made features_dev on the caller's stream comes first
         with torch.cuda.stream(self.stream):
             dev = stage2.gather_windows(features_dev, windows, dtype=self.op_dtype, **geometry)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        features_dev.record_stream(self.stream)
+        return StagedWindows(dev, ev)
+
+    def stage_resident_clipped(self, features_dev, **geometry):
+        """``stage_resident`` for the stage-1 driver: every window of ``stage1.cut_windows`` (half-overlapping, the last ones clipped), geometry =
+        ``debug_window``, ``feature_fps``, ``num_frames`` as that function takes them -> ``StagedWindows`` with the tensor
+        ``stage_windows(features, stage1.cut_windows(ctx_l, ...))`` hands over, bit for bit, made by one kernel on the staging stream
+        (``stage1.gather_windows``): no host gather, no upload, no synchronisation."""
+        from ..eval import stage1
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))      # whatever made features_dev on the caller's stream comes first
+        with torch.cuda.stream(self.stream):
+            dev = stage1.gather_windows(features_dev, dtype=self.op_dtype, **geometry)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         features_dev.record_stream(self.stream)

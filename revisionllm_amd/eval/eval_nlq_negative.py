@@ -15,7 +15,9 @@ partition (:187-188), RESUME over ``predictions_streaming_<split>.txt`` (:165-17
 ``--batch`` windows as the LLM's batch rows (:281-298), entropy / cosine scores and their merge (:299-336), one record per query and the
 per-query ``try / except`` that records the id in ``errors`` and goes on (:338-341).  What differs: features come through
 ``data.feature_store`` (npy / npz directory / LMDB) and a pinned staging buffer; ``--in_flight N`` (build-defined) runs N queries as
-scheduler tasks whose window batches prefill in the ``serve.DecodeServer``'s batched passes and decode in its merged steps.
+scheduler tasks whose window batches prefill in the ``serve.DecodeServer``'s batched passes and decode in its merged steps; ``--device_features``
+(build-defined, off by default) keeps a movie's features on the device across its queries, cuts the windows there and scores a query's proposals in
+one launch, with the same records.
 """
 import argparse
 import json
@@ -83,6 +85,12 @@ def parse_args(argv=None):
     p.add_argument("--mixed_prefill", action="store_true",
                    help="(build-defined; --in_flight > 1) prefills of different geometry (query length, window count) share a pass, adapter calls of different query "
                         "lengths a call (serve.DecodeServer(mixed_prefill=True)); default off")
+    p.add_argument("--device_features", action="store_true",
+                   help="keep each movie's features on the device across its queries (data.feature_store.ResidentFeatures), cut the windows there "
+                        "(WindowStager.stage_resident_clipped) and score a query's proposals in one launch (stage1.score_query_device) instead of gathering "
+                        "the windows on the host, uploading them per query and scoring proposal by proposal; --baseline, --plus_baseline, the short-video "
+                        "subsample and a movie shorter than one window or with a void last window keep the host route; off: every code path is what it was")
+    p.add_argument("--device_features_mb", type=int, default=2048, help="budget of the resident feature cache in MiB (--device_features)")
     p.add_argument("--pool_rows", type=int, default=32, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per generate at most (--in_flight > 1; answers are a dozen tokens)")
     return p.parse_args(argv)
@@ -138,22 +146,40 @@ def _sentence(data):
     return sentence
 
 
-def _prepare(args, store, stager, dev, id_, data):
-    """Everything of one query in front of the LLM: -> None (skipped) or a dict of staged inputs."""
+def _on_device(args, resident, ctx_l, subsampled):
+    """Whether a query's windows are cut and its proposals scored on the device: ``--device_features`` with the plain window form (no ``--baseline``, no
+    ``--plus_baseline``, no short-video subsample), a whole number of frames per window, a movie of at least one window's length and no void window
+    (``ops.clipped_window_void``, where ``cut_windows`` indexes past the array).  Everything else keeps the host route, so no record changes."""
+    from .. import ops
+    clip_length = args.debug_window * args.feature_fps
+    if resident is None or args.baseline or args.plus_baseline or subsampled or clip_length != int(clip_length) or not 2 <= clip_length <= ctx_l:
+        return False
+    return not ops.clipped_window_void(ctx_l, int(clip_length))
+
+
+def _prepare(args, store, stager, dev, id_, data, resident=None):
+    """Everything of one query in front of the LLM: -> None (skipped) or a dict of staged inputs (``device``: the windows were cut on the device and the
+    proposals are scored there)."""
     movie = data["movie"] if "movie" in data else data["clip_id"]
     movie = data["query_id"] if "val_frame" in args.feat_folder else movie
     features = store.video(movie)
     query_feats, query_cls = store.query(id_) if args.q_feat_dir is not None else (None, None)
+    subsampled = False
     if "movie_duration" in data and data["movie_duration"] <= args.debug_window:
         if args.skip_small_videos:
             return None
         features = features[np.linspace(0, features.shape[0] - 1, args.num_frames, dtype=np.int32)]
-    frame_idx = window_features(features, args)
-    windows = stager.stage_windows(features, frame_idx).wait()
+        subsampled = True
+    device = _on_device(args, resident, features.shape[0], subsampled)
+    if device:
+        windows = stager.stage_resident_clipped(resident.get(movie, features), debug_window=args.debug_window, feature_fps=args.feature_fps,
+                                                num_frames=args.num_frames).wait()
+    else:
+        windows = stager.stage_windows(features, window_features(features, args)).wait()
     qf = torch.from_numpy(np.asarray(query_feats)).to(dev).to(getattr(stager, "op_dtype", torch.float32)) if query_feats is not None else None
     qc = torch.from_numpy(np.asarray(query_cls)).to(dev).float() if query_cls is not None else None
     duration = data["movie_duration"] if "movie_duration" in data else data["duration"]
-    return dict(movie=movie, windows=windows, qf=qf, qc=qc, sentence=_sentence(data), timestamps=data["timestamps"], duration=duration)
+    return dict(movie=movie, windows=windows, qf=qf, qc=qc, sentence=_sentence(data), timestamps=data["timestamps"], duration=duration, device=device)
 
 
 def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
@@ -161,6 +187,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     come from ``load_pretrained_model(args, args.stage2, args.stage3, load_ckp=args.load_ckp)`` (negative.py:143)."""
     from ..data.feature_store import FeatureStore, WindowStager
     from ..utils import disable_torch_init
+    from .eval_nlq_retrieval_e2e2 import _resident_cache
     os.makedirs(args.log_path, exist_ok=True)
     prediction_path = args.log_path + f"/predictions_streaming_{args.split}.txt"
     print("prediction_path: ", prediction_path)
@@ -173,23 +200,25 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
         model = model.bfloat16().cuda()
     store = FeatureStore(args.feat_folder, q_feat_dir=args.q_feat_dir, vis_feat_storage="npy" if args.vis_feat_storage == "pth" else args.vis_feat_storage)
     stager = WindowStager(model.device, op_dtype=getattr(model, "dtype", None))
+    resident = _resident_cache(args, stager, model.device)
     done = set(done_query_ids(prediction_path))
     items = split_items(load_items(args.data_path), args.split, args.total_split)
     print("batch: ", args.batch)
     kw = dict(num_frames=args.num_frames, debug_window=args.debug_window, score=args.score, score_merge=args.score_merge, normalize=args.normalize,
               topk_pool=args.topk_pool, plus_baseline=args.plus_baseline)
     if getattr(args, "in_flight", 1) > 1:
-        return _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw)
+        return _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw, resident)
     errors, written = [], 0
     for id_, data in items:
         if id_ in done:
             continue
         try:
-            q = _prepare(args, store, stager, model.device, id_, data)
+            q = _prepare(args, store, stager, model.device, id_, data, resident)
             if q is None:
                 continue
-            answers, info = stage1.run_query(model, tokenizer, q["windows"], q["qf"], q["qc"], q["sentence"], q["timestamps"], q["duration"],
-                                             batch=args.batch, prompt=args.mad_prompt, **kw)
+            run_query = stage1.run_query_device if q["device"] else stage1.run_query
+            answers, info = run_query(model, tokenizer, q["windows"], q["qf"], q["qc"], q["sentence"], q["timestamps"], q["duration"],
+                                      batch=args.batch, prompt=args.mad_prompt, **kw)
             write_log(prediction_path, q["movie"], "grounding", id_, answers, info=info)
             written += 1
         except Exception:  # noqa: BLE001 - the reference's per-query handler (negative.py:338-341)
@@ -200,7 +229,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     return written, errors
 
 
-def _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw):
+def _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw, resident=None):
     """``--in_flight N``: the same per-query work with up to N queries in flight as ``sched`` tasks (records appended in annotation order)."""
     from .. import sched, serve
     dev = model.device
@@ -216,7 +245,8 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, predicti
         task, id_, q = pending.pop(0)
         try:
             answers, ent = stage1.collect_query(model, tokenizer, inter.finish(task), args.score)
-            answers, info = stage1.score_query(q["windows"], answers, ent, q["qc"], q["timestamps"], q["duration"], **kw)
+            score_query = stage1.score_query_device if q["device"] else stage1.score_query
+            answers, info = score_query(q["windows"], answers, ent, q["qc"], q["timestamps"], q["duration"], **kw)
             write_log(prediction_path, q["movie"], "grounding", id_, answers, info=info)
             written += 1
         except Exception:  # noqa: BLE001 - the reference's per-query handler (negative.py:338-341)
@@ -231,7 +261,7 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, predicti
         if id_ in done:
             continue
         try:
-            q = _prepare(args, store, stager, dev, id_, data)
+            q = _prepare(args, store, stager, dev, id_, data, resident)
             if q is None:
                 continue
             gen = (lambda t, q=q: stage1.launch_query_steps(model, tokenizer, q["windows"], q["qf"], q["sentence"], batch=args.batch, score=args.score,

@@ -1,11 +1,13 @@
 """Stage-1 (dense / sparse) grounding driver for one query: half-overlapping windows, batches of windows straight into
-``inference()`` (LLM batch > 1), ``"From a to b."`` parsing, IoU and entropy / cosine scores.
+``inference()`` (LLM batch > 1), ``"From a to b."`` parsing, IoU and entropy / cosine scores; and the same on the device for features that stay
+there (``gather_windows``, ``proposal_cosines``, ``score_query_device``, ``run_query_device``: the driver's ``--device_features``).
 
 Counterpart of revisionllm/eval/eval_nlq_negative.py:224-337.  (The reference file imports ``vtimellm.*`` and cannot run
 as shipped - SURVEY section 2 #12 - so this follows the cited lines; its ``iou`` helper is pinned by
 tests/golden/g9_driver.json.)
 """
 import math
+import numbers
 import re
 
 import numpy as np
@@ -86,11 +88,99 @@ def score_query(features, answers, ent, query_cls, timestamps, duration, num_fra
     return answers, {"iou": ious, "scores": scores}
 
 
+def gather_windows(features_dev, *, debug_window=125, feature_fps=5, num_frames=250, dtype=None):
+    """``cut_windows`` + the host gather for features that are already on the device: features_dev [ctx_l, d] (f32 or 16-bit operands) ->
+    [W, num_frames, d] in ``dtype`` (None: ``ops.window_gather``'s default), equal to ``features[cut_windows(ctx_l, debug_window, feature_fps,
+    num_frames)]`` cast to ``dtype`` (``rv_window_gather_rule``: one launch, every window, nothing uploaded, no synchronisation).
+    ``debug_window * feature_fps`` must be a whole number of frames, at least 2 and at most ctx_l, and no window void (``ops.clipped_window_void``: the
+    host route indexes past the array there)."""
+    who = "stage1.gather_windows"
+    clip_length = debug_window * feature_fps
+    if not (isinstance(clip_length, numbers.Real) and not isinstance(clip_length, bool) and math.isfinite(clip_length) and clip_length == int(clip_length)
+            and clip_length >= 2):
+        raise ValueError(f"{who}: debug_window * feature_fps = {clip_length!r} must be a whole number of frames, at least 2")
+    clip_length = int(clip_length)
+    if not torch.is_tensor(features_dev) or features_dev.dim() != 2 or min(features_dev.shape) == 0 or not features_dev.dtype.is_floating_point:
+        raise ValueError(f"{who}: features {tuple(features_dev.shape) if torch.is_tensor(features_dev) else type(features_dev).__name__} "
+                         f"(expected a floating-point tensor [ctx_l, d])")
+    ctx_l = features_dev.shape[0]
+    if ctx_l < clip_length or ops.clipped_window_void(ctx_l, clip_length):
+        raise ValueError(f"{who}: ctx_l={ctx_l} frames for windows of {clip_length} (a video shorter than one window, or one whose last window starts "
+                         f"behind its end) - take the host route (cut_windows + WindowStager.stage_windows)")
+    return ops.window_gather_clipped(features_dev, win=clip_length, num_frames=num_frames, out_dtype=dtype)
+
+
+def proposal_cosines(features, frames, query_cls, topk_pool):
+    """The cosine score of every proposal of ``iou``'s ``frames`` dict {window: (a, b)}: features [W,T,d] (device) -> the list of Python floats that the
+    loop in ``score_query`` produces, from ONE launch (``ops.proposal_cosine``) and ONE ``.tolist()`` instead of a launch and a host synchronisation per
+    proposal.  A proposal the loop would not score - an empty slice, a window past W - sends the whole query through that loop, per proposal, so the
+    exception is the host route's."""
+    if not frames:
+        return []
+    W, T = features.shape[0], features.shape[1]
+    triples = [(k, a, b) for k, (a, b) in frames.items()]
+    for k, a, b in triples:
+        lo, hi = ops.proposal_slice(a, b, T)
+        if not (0 <= k < W and a >= 0 and hi > lo):
+            return _proposal_cosines_each(features, frames, query_cls, topk_pool)
+    return ops.proposal_cosine(features, query_cls, triples, k=3 if topk_pool else 0).tolist()
+
+
+def _proposal_cosines_each(features, frames, query_cls, topk_pool):
+    """``score_query``'s loop: one ``ops.topk_cosine`` and one ``float()`` per proposal."""
+    cos = []
+    for k, (a, b) in frames.items():
+        prop = features[k][a:b + 1]
+        cos.append(float(ops.topk_cosine(prop[None], query_cls, min(prop.shape[0], 3) if topk_pool else 0)[0]))
+    return cos
+
+
+def score_query_device(features, answers, ent, query_cls, timestamps, duration, num_frames=250, debug_window=125, score="mean_entropy",
+                       score_merge="multiply", normalize=True, topk_pool=False, plus_baseline=False):
+    """``score_query`` with the proposals' cosine scores from ``proposal_cosines``: the same parameters, the same result.  The max-normalisation and the
+    entropy merge stay here in Python floats (float64 arithmetic on a few dozen numbers: on the device it would change the records)."""
+    gt = (timestamps[0] / duration, timestamps[1] / duration)
+    num_frames_video = int(duration * num_frames / debug_window)
+    frames, ious, ent = iou(answers, gt, num_frames, num_frames_video, ent, plus_baseline)
+    cos = proposal_cosines(features, frames, query_cls, topk_pool)
+    if normalize:
+        if cos:
+            cos = [c / max(cos) for c in cos]
+        if ent:
+            ent = [e / max(ent) for e in ent]
+    if "entropy" in score:
+        if score_merge == "add":
+            scores = [c - e for c, e in zip(cos, ent)]
+        elif score_merge == "multiply":
+            scores = [c / e for c, e in zip(cos, ent)]
+        else:
+            scores = [-e for e in ent]
+    else:
+        scores = cos
+    return answers, {"iou": ious, "scores": scores}
+
+
 def run_query(model, tokenizer, features, query_feats, query_cls, sentence, timestamps, duration, batch=8, num_frames=250,
               debug_window=125, score="mean_entropy", score_merge="multiply", normalize=True, topk_pool=False,
               prompt="mad_grounding", plus_baseline=False):
     """features [W,T,768] (device).  Returns (answers, info) with info = {'iou': [...], 'scores': [...]} (negative.py:337).
     The reference's own loop: one ``inference()`` per batch of windows, entropy statistics from the returned scores."""
+    answers, ent = answer_windows(model, tokenizer, features, query_feats, sentence, batch, score, prompt)
+    return score_query(features, answers, ent, query_cls, timestamps, duration, num_frames, debug_window, score, score_merge, normalize, topk_pool,
+                       plus_baseline)
+
+
+def run_query_device(model, tokenizer, features, query_feats, query_cls, sentence, timestamps, duration, batch=8, num_frames=250,
+                     debug_window=125, score="mean_entropy", score_merge="multiply", normalize=True, topk_pool=False,
+                     prompt="mad_grounding", plus_baseline=False):
+    """``run_query`` with ``score_query_device`` as its epilogue (the driver's ``--device_features``): the same parameters, the same result."""
+    answers, ent = answer_windows(model, tokenizer, features, query_feats, sentence, batch, score, prompt)
+    return score_query_device(features, answers, ent, query_cls, timestamps, duration, num_frames, debug_window, score, score_merge, normalize, topk_pool,
+                              plus_baseline)
+
+
+def answer_windows(model, tokenizer, features, query_feats, sentence, batch=8, score="mean_entropy", prompt="mad_grounding"):
+    """The LLM part of ``run_query``: -> (the answer of every window, one raw entropy statistic per window or [])."""
     query = "<video>\n" + QUESTIONS[prompt].format(sentence)
     answers, ent = [], []
     for g in range(math.ceil(features.shape[0] / batch)):
@@ -104,8 +194,7 @@ def run_query(model, tokenizer, features, query_feats, query_cls, sentence, time
             st = ops.entropy_stats(torch.stack(out["scores"], 1))
             col = 0 if score == "max_entropy" else 2
             ent.extend(float(e[col]) for e in st)
-    return score_query(features, answers, ent, query_cls, timestamps, duration, num_frames, debug_window, score, score_merge, normalize, topk_pool,
-                       plus_baseline)
+    return answers, ent
 
 
 def launch_query_steps(model, tokenizer, features, query_feats, sentence, batch=8, score="mean_entropy", prompt="mad_grounding",

@@ -1,5 +1,5 @@
-"""The CLIP grounding chain's wrappers (cosine rows, span scores, ranking, span proposals, window selection, window gather, the two poolings) with their checkers, constants
-and namedtuples; ``ops`` re-exports every public name.  Every function takes / returns torch DEVICE tensors and enqueues on torch's current stream."""
+"""The CLIP grounding chain's wrappers (cosine rows, span scores, ranking, span proposals, window selection, window gather under both window rules, the proposals' cosine scores, the two
+poolings) with their checkers, constants and namedtuples; ``ops`` re-exports every public name.  Every function takes / returns torch DEVICE tensors and enqueues on torch's current stream."""
 import collections
 import math
 import numbers
@@ -419,6 +419,115 @@ def window_gather(video, select, *, win, stride, num_frames, mask=None, out_dtyp
                                                 hip.ptr(select.contiguous()), R, R // M, L, d, win, stride, keep, F, hip.ptr(frames), hip.dtype_code(frames),
                                                 hip.ptr(index), hip.stream()), "rv_window_gather")
     return (frames, index) if return_index else frames
+
+
+def clipped_window_count(L, win):
+    """How many windows ``stage1.cut_windows`` makes of ``L`` frames for ``clip_length = win``: max(0, ceil(L / (win // 2)) - 1)."""
+    return max(0, -(-L // (win // 2)) - 1)
+
+
+def clipped_window_void(L, win):
+    """Whether the last of those windows starts behind its end (``(i * win) // 2 > L - 1``: an odd ``win`` only, first at L = 15 for win = 5 and at
+    L = 195625 for win = 625).  The host's ``np.linspace`` indexes past the array there; the device stores zeros."""
+    W = clipped_window_count(L, win)
+    return W > 0 and (W - 1) * win // 2 > L - 1
+
+
+def window_gather_clipped(video, *, win, num_frames, select=None, mask=None, out_dtype=None, return_index=False):
+    """The stage-1 driver's window tensor from features that live on the device (``rv_window_gather_rule`` with the clipped rule): video [L,d] or
+    [B,L,d] (f32 or 16-bit operands; a view with a frame stride above d is read in place), select None - every window in order, nothing uploaded - or
+    i32 [keep], [R,keep] or [B,Q,keep] as ``window_gather`` takes it, mask [L] / [B,L] or None -> frames [W,num_frames,d] / [B,W,num_frames,d] with
+    ``W = clipped_window_count(L, win)`` (with ``select``: [...,keep,num_frames,d]) in ``out_dtype`` (None: as ``window_gather``), and with
+    ``return_index`` the sampled frame of every output row as well.  Window i is ``stage1.cut_windows``' for ``clip_length = win``: frames
+    ``np.linspace((i * win) // 2, min((i * win) // 2 + win, D - 1), num_frames, dtype=int32)``, half-overlapping, the last ones clipped and not shifted
+    back, so with a full mask ``frames`` is ``video[cut_windows(L, ...)]`` cast to ``out_dtype``.  A window past a masked row's duration, an entry of
+    ``select`` outside the row's windows and a void window (``clipped_window_void``) give zeros and index -1.  One launch (a mask that is not f32 adds a
+    cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
+    who = "window_gather_clipped"
+    win, _, F = window_gather_keywords(who, win, 2, num_frames)
+    if not torch.is_tensor(video) or (select is not None and not torch.is_tensor(select)) or (mask is not None and not torch.is_tensor(mask)):
+        raise ValueError(f"{who}: video, select and mask must be tensors")
+    if video.dim() not in (2, 3) or min(video.shape) == 0:
+        raise ValueError(f"{who}: video {tuple(video.shape)} (expected [L, d] or [B, L, d])")
+    M = video.shape[0] if video.dim() == 3 else 1
+    L, d = video.shape[-2:]
+    if select is not None:
+        if not 1 <= select.dim() <= 3 or min(select.shape) == 0:
+            raise ValueError(f"{who}: select {tuple(select.shape)} (expected [keep], [R, keep] or [B, Q, keep])")
+        if select.dtype != torch.int32:
+            raise ValueError(f"{who}: select must be int32 (got {select.dtype})")
+        lead, keep = tuple(select.shape[:-1]), select.shape[-1]
+        R = math.prod(lead)
+        if (select.dim() == 3 and (video.dim() != 3 or lead[0] != M)) or R % M != 0:
+            raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (a whole number of rows of select for each video)")
+    if mask is not None:
+        if mask.shape != tuple(video.shape[:-1]):
+            raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected {tuple(video.shape[:-1])})")
+        if mask.dtype.is_complex:
+            raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    if L > SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={L} frames (at most {SPAN_PROPOSE_MAX_FRAMES})")
+    if win > L:
+        raise ValueError(f"{who}: win={win} frames for rows of L={L}")
+    out_dtype, flavour = window_gather_dtypes(who, video.dtype, out_dtype)
+    if select is None:
+        lead, keep, R = tuple(video.shape[:-2]), clipped_window_count(L, win), M
+    if video.stride(-1) != 1 or video.stride(-2) < d or (video.dim() == 3 and M > 1 and video.stride(0) != L * video.stride(-2)):
+        video = video.contiguous()
+    dev = video.device
+    frames = torch.empty(lead + (keep, F, d), dtype=out_dtype, device=dev)
+    index = torch.empty(lead + (keep, F), dtype=torch.int32, device=dev) if return_index else None
+    hip.check(hip.lib(flavour).rv_window_gather_rule(hip.ptr(video), hip.dtype_code(video), video.stride(-2),
+                                                     hip.ptr(mask.float().contiguous()) if mask is not None else None,
+                                                     hip.ptr(select.contiguous()) if select is not None else None, R, R // M, L, d, win, 2, keep, F,
+                                                     hip.ptr(frames), hip.dtype_code(frames), hip.ptr(index), hip.RV_WINDOWS_CLIPPED, hip.stream()),
+              "rv_window_gather_rule")      # (win <= L: at least one window, keep >= 1)
+    return (frames, index) if return_index else frames
+
+
+def proposal_slice(a, b, T):
+    """(lo, hi) of ``range(T)[a : b + 1]`` for a >= 0 as ``rv_proposal_cosine`` cuts it: lo = min(a, T), hi = min(b + 1, T); hi <= lo is an empty slice."""
+    return min(a, T), min(b + 1, T)
+
+
+def proposal_cosine(windows, text, proposals, *, k):
+    """``topk_cosine`` of ragged proposals in one launch (``rv_proposal_cosine``): windows [W,T,d] (f32 or 16-bit operands), text [d], proposals an
+    int32 device tensor [P,3] of (window, a, b) - or a Python list of such triples, uploaded through a pinned buffer - -> f32 [P], entry p the score
+    ``topk_cosine(windows[window][a : b + 1][None], text, k)[0]`` of the slice: column norms over the slice's frames, the sum of its min(k, length)
+    largest ``<f_t, text / norm>`` (``k <= 0``: their mean).  A proposal whose window lies outside [0, W), whose ``a`` is negative or whose slice is empty
+    gives NaN and reads nothing.  One launch (none for P = 0), no synchronisation, no host copy of the scores.  The full rule and the (d, T) for which a
+    score is bit for bit ``topk_cosine``'s stand in include/revision_hip.h."""
+    who = "proposal_cosine"
+    if not _is_int(k) or not -2 ** 31 <= k < 2 ** 31:
+        raise ValueError(f"{who}: k={k!r} must be an integer (<= 0: the mean)")
+    if not torch.is_tensor(windows) or not torch.is_tensor(text):
+        raise ValueError(f"{who}: windows and text must be tensors")
+    if windows.dim() != 3 or min(windows.shape) == 0 or text.shape != (windows.shape[2],):
+        raise ValueError(f"{who}: windows {tuple(windows.shape)} / text {tuple(text.shape)} (expected [W, T, d] and [d])")
+    if windows.dtype not in _GATHER_DTYPES or not text.dtype.is_floating_point:
+        raise ValueError(f"{who}: windows must be float32, float16 or bfloat16 and text floating point (got {windows.dtype}, {text.dtype})")
+    if torch.is_tensor(proposals):
+        if proposals.dim() != 2 or proposals.shape[1] != 3 or proposals.dtype != torch.int32:
+            raise ValueError(f"{who}: proposals {tuple(proposals.shape)} {proposals.dtype} (expected an int32 tensor [P, 3] of (window, a, b))")
+    else:
+        try:
+            rows = [tuple(t) for t in proposals]
+        except TypeError:
+            raise ValueError(f"{who}: proposals must be an int32 tensor [P, 3] or a list of (window, a, b) triples") from None
+        if any(len(t) != 3 or not all(_is_int(v) and -2 ** 31 <= v < 2 ** 31 for v in t) for t in rows):
+            raise ValueError(f"{who}: proposals must be (window, a, b) triples of int32 integers")
+        from .ops import h2d                   # (ops imports this module: at call time both are complete)
+        proposals = h2d(torch.tensor(rows, dtype=torch.int32).view(-1, 3), windows.device)
+    W, T, d = windows.shape
+    P = proposals.shape[0]
+    out = torch.empty(P, dtype=torch.float32, device=windows.device)
+    if P > 0:
+        windows = windows.contiguous()
+        if windows.data_ptr() % 16:
+            windows = windows.clone()            # (the 16-byte loads; torch's own allocations are aligned)
+        hip.check(_score_lib(windows).rv_proposal_cosine(hip.ptr(windows), hip.dtype_code(windows), hip.ptr(text.float().contiguous()), hip.ptr(proposals.contiguous()),
+                                                         P, W, T, d, int(k), hip.ptr(out), hip.stream()), "rv_proposal_cosine")
+    return out
 
 
 def attn_pool(text_embeds, video_embeds, temperature):

@@ -23,6 +23,7 @@ RV_F32, RV_BF16, RV_I32, RV_I64, RV_U8, RV_F16 = 0, 1, 2, 3, 4, 5
 RV_ACT_NONE, RV_ACT_RELU, RV_ACT_SILU_MUL, RV_ACT_QUICK_GELU = 0, 1, 2, 3
 RV_FEAT_CLS, RV_FEAT_ALL = 0, 2
 TOPK_CAP = 64
+RV_WINDOWS_SHIFTED, RV_WINDOWS_CLIPPED = 0, 1
 
 _DT = {torch.float32: RV_F32, torch.bfloat16: RV_BF16, torch.float16: RV_F16, torch.int32: RV_I32, torch.int64: RV_I64, torch.uint8: RV_U8}
 
@@ -184,6 +185,8 @@ SIGNATURES = {
     "rv_span_propose": (C.c_int, [_p, _p, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "rv_window_select": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "rv_window_gather": (C.c_int, [_p, _i32, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
+    "rv_window_gather_rule": (C.c_int, [_p, _i32, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _i32, _p]),
+    "rv_proposal_cosine": (C.c_int, [_p, C.c_int, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
 }
 
 

@@ -15,7 +15,8 @@ from .grounding import (HIT_IOU, SPAN_FORMS, SPAN_POOLINGS, SPAN_PROPOSE_LEVELS,
                         WINDOW_SELECT_MAX, SpanProposals, SpanRank, WindowSelection, attn_pool, frame_cosine, frame_cosine_multi, span_propose,
                         span_propose_keywords, span_propose_shapes, span_rank, span_rank_keywords, span_scores, span_scores_multi, topk_pool,
                         WINDOW_GATHER_MAX_FRAMES, window_gather, window_gather_dtypes, window_gather_keywords, window_select, window_select_capacity,
-                        window_select_gt, window_select_keywords)
+                        window_select_gt, window_select_keywords, clipped_window_count, clipped_window_void, proposal_cosine, proposal_slice,
+                        window_gather_clipped)
 from .utils import hashinit
 
 
