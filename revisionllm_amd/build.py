@@ -1,6 +1,8 @@
 """Build the HIP library (gfx950) in-tree with hipcc, in its two operand flavours: ``librevision_hip.so`` (fp16 operands, the default) and
 ``librevision_hip_bf16.so`` (bf16 operands) - the same sources compiled with ``-DRV_OP_F16=1`` / ``0`` (csrc/common.h).  No JIT cache: the
-``.so`` files ship with the tree.  Only the entry points ``include/revision_hip.h`` declares are exported (``-fvisibility=hidden``)."""
+``.so`` files ship with the tree.  Only the entry points ``include/revision_hip.h`` declares are exported (``-fvisibility=hidden``).  After the two
+flavours comes the companion library ``librevision_hip_ext.so`` (``include/revision_hip_ext.h``, the ``rvx_*`` entries): f32-only kernels, one build
+for both flavours, linked with its own copy of ``error.o`` and its own version script."""
 import os
 import subprocess
 import sys
@@ -16,7 +18,11 @@ LIB = os.path.join(HERE, FLAVOURS["f16"][0])
 def lib_path(flavour):
     return os.path.join(HERE, FLAVOURS[flavour][0])
 SOURCES = ["error.hip", "init.hip", "gemm.hip", "gemm_pp.hip", "gemm_arows.hip", "gemm_rows.hip", "gemm_rows_p1.hip", "gemm_rows_p2.hip", "gemm_rows_p3.hip", "rowops.hip", "attention.hip", "sample.hip", "similarity.hip", "rank.hip", "propose.hip", "prefilter.hip", "gather.hip", "frames.hip", "frames_yuv.hip", "engine.hip"]
-HEADERS = ["exports.map", "common.h", "kernels.h", "gemv_finish.h", "frames_common.h", "grounding.h", "gemm_rows.hip", os.path.join("..", "..", "include", "revision_hip.h")]
+HEADERS = ["exports.map", "common.h", "kernels.h", "gemv_finish.h", "frames_common.h", "grounding.h", "window_select.h", "gemm_rows.hip", os.path.join("..", "..", "include", "revision_hip.h")]
+EXT_LIB = os.path.join(HERE, "librevision_hip_ext.so")
+EXT_SOURCES = ["prefilter_ext.hip"]          # compiled once (in the f16 object directory: nothing in them depends on the flavour)
+EXT_SHARED = ["error.hip"]                   # objects of the f16 build linked in as well, their rv_* names local
+EXT_HEADERS = ["exports_ext.map", os.path.join("..", "..", "include", "revision_hip_ext.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]
 
@@ -36,10 +42,19 @@ def _stale(target, deps):
 
 
 def build_library(force=False, verbose=False, flavours=("f16", "bf16")):
-    """Compile every HIP translation unit for gfx950 in each flavour and link the shared libraries. Returns the default library's path."""
+    """Compile every HIP translation unit for gfx950 in each flavour and link the shared libraries, then the companion library. Returns the default
+    library's path."""
     hipcc = _hipcc()
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     jobs = []
+    ext_dir = os.path.join(OBJ, "f16")
+    os.makedirs(ext_dir, exist_ok=True)
+    ext_hdrs = hdrs + [os.path.join(CSRC, h) for h in EXT_HEADERS]
+    for s in EXT_SOURCES + ([] if "f16" in flavours else EXT_SHARED):
+        src = os.path.join(CSRC, s)
+        obj = os.path.join(ext_dir, s.replace(".hip", ".o"))
+        if force or _stale(obj, [src] + ext_hdrs):
+            jobs.append([hipcc] + FLAGS + [FLAVOURS["f16"][1], "-DRV_TU=" + s.replace(".hip", ""), "-c", src, "-o", obj])
     for fl in flavours:
         os.makedirs(os.path.join(OBJ, fl), exist_ok=True)
         for s in SOURCES:
@@ -62,6 +77,9 @@ def build_library(force=False, verbose=False, flavours=("f16", "bf16")):
         lib = lib_path(fl)
         if force or _stale(lib, objs):
             run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", lib] + objs)
+    ext_objs = [os.path.join(ext_dir, s.replace(".hip", ".o")) for s in EXT_SOURCES + EXT_SHARED]
+    if force or _stale(EXT_LIB, ext_objs + [os.path.join(CSRC, "exports_ext.map")]):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports_ext.map"), "-o", EXT_LIB] + ext_objs)
     return LIB
 
 

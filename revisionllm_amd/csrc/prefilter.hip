@@ -2,241 +2,8 @@
 // stage-1 LLM log, e2e2.py:278-294; here the choice comes from the per-frame cosine row):
 //   rv_window_select   per row: duration from the mask, every window of stage2.cut_windows' geometry scored by the sum of its top-k sims, rank order,
 //                      greedy selection with a minimum separation, top up in rank order, the first `keep` handed back ascending - one launch
-// The definition stands in include/revision_hip.h.  A window's score is accumulated add by add in rank order, as span_scores_kernel (similarity.hip) does
-// it, and everything after the scores is integer work, so a row's result does not depend on R, on the row's place or on any tiling.
-#include "grounding.h"
-
-namespace {
-
-constexpr int WS_TPB = 1024;         // 16 waves: the windows of a row are scored 16 at a time
-constexpr int WS_WAVES = WS_TPB / 64;
-constexpr int WS_REG = 16;           // a window of up to 64 * 16 frames is loaded once and ranked from registers
-constexpr int WS_MAX_W = 2048;       // = SR_MAX of rv_span_rank
-constexpr int WS_MAX_L = 1 << 20;    // = rv_span_propose's limit
-constexpr int WS_PER = WS_MAX_W / WS_TPB;   // consecutive entries of a thread in the two prefix sums
-
-struct WindowArgs {
-    const float* sims;
-    const float* mask;
-    const float* gt;
-    int32_t* select;
-    int32_t* n_select;
-    int32_t* n_windows;
-    float* win_scores;
-    int32_t* bounds;
-    int32_t* order;
-    int32_t* hit_rank;
-    int L, rpm, win, stride, k, keep, min_sep, Wcap;
-};
-
-// The frame order (grounding.h) as one unsigned number per frame, for a window held in registers: (frame key << 32 | frame index), SMALLER for what ranks earlier.
-// A NaN has the key 0, a number its rank_key (from 0x007fffff for +inf to 0xff800000 for -inf; -0 as +0, so the index decides between them as
-// rank_before()'s a.v == b.v does); 0xffffffff marks a slot behind the window's end.
-__device__ __forceinline__ uint32_t ws_frame_key(float x) { return x != x ? 0u : rank_key(x); }
-// the number behind a frame key != 0 (-0 comes back as +0: added to a sum that started at +0 it gives the same bits)
-__device__ __forceinline__ float ws_key_value(uint32_t key) {
-    const uint32_t asc = ~key;
-    return __uint_as_float((asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc);
-}
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t b = (uint64_t)__shfl_xor((unsigned long long)a, o, 64);
-        a = b < a ? b : a;
-    }
-    return a;
-}
-
-// how many of the counts c of the threads before this one (all threads call; wsum: WS_WAVES ints)
-__device__ __forceinline__ int ws_before(int c, int* wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    __syncthreads();
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    return base + inc - c;
-}
-
-// One workgroup per row.  (1) duration: block sum of the mask row; (2) the waves take windows in turn and score each with k wave-wide rank rounds over
-// the lane-strided window - loaded once and kept as frame keys in registers when it has at most 64 * WS_REG frames, so that its loads are in flight
-// together and a round is two 64-bit compares per frame and a wave-wide minimum; read again from the row in every round when it is longer (the same
-// order, the same picks) - and the (key, index) pair goes to LDS; (3) bitonic sort of the pairs: ascending = rank order; (4) pass 1 walks the rank order with one live flag per WINDOW INDEX: every thread
-// reads the pivot's flag (one broadcast read); a dead pivot costs nothing more, a live one is taken,
-// the threads clear the flags of its neighbours (at most 2 min_sep - 2 of them; never its own, so that a slower thread still reads it as live) and one
-// barrier follows.  The walk stops once `limit` windows are taken: n_select of them, or all W when order / hit_rank want the whole sequence (a greedy
-// prefix does not depend on what follows it); (5) pass 2 puts the windows not taken behind them in rank order, places by a block prefix sum; (6) the
-// first n_select entries are flagged by index and a second prefix sum hands them back ascending.
-__global__ __launch_bounds__(WS_TPB) void window_select_kernel(const WindowArgs a) {
-    __shared__ uint64_t keys[WS_MAX_W];      // key << 32 | index, ascending = rank order
-    __shared__ uint16_t seq[WS_MAX_W];       // the selection sequence
-    __shared__ uint8_t live[WS_MAX_W];       // by window index: pass 1's flags, then "among the first n_select"
-    __shared__ uint8_t taken[WS_MAX_W];      // by window index
-    __shared__ float red[WS_WAVES];
-    __shared__ int wsum[WS_WAVES];
-    __shared__ int first;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r = blockIdx.x;
-    const int L = a.L, win = a.win, stride = a.stride, Wcap = a.Wcap, keep = a.keep, min_sep = a.min_sep;
-    const float* __restrict__ s = a.sims + r * L;
-    const float* __restrict__ m = a.mask + (r / a.rpm) * L;
-
-    if (tid == 0) first = 0x7fffffff;           // (in front of the sum: its barrier covers this store)
-    const int D = duration_frames(block_mask_sum<WS_TPB>(m, L, red), L);
-    const int W = ws_count(win, stride, D);   // (W <= Wcap: D <= L)
-    int P = 1;
-    while (P < W) P <<= 1;
-    const bool to_bounds = a.bounds && r % a.rpm == 0;
-    int32_t* __restrict__ bnd = to_bounds ? a.bounds + (r / a.rpm) * Wcap * 2 : nullptr;
-
-    for (int i = wave; i < W; i += WS_WAVES) {
-        int lo, hi;
-        ws_bounds(i, win, stride, D, lo, hi);
-        const int rounds = a.k < hi - lo ? a.k : hi - lo;
-        float acc = 0.f;
-        if (hi - lo <= 64 * WS_REG) {
-            uint32_t kk[WS_REG];
-#pragma unroll
-            for (int j = 0; j < WS_REG; ++j) {
-                const int t = lo + lane + 64 * j;
-                kk[j] = t < hi ? ws_frame_key(s[t]) : 0xffffffffu;
-            }
-            uint64_t from = 0ull;                                       // the smallest (key, index) a round may still pick
-            for (int q = 0; q < rounds; ++q) {
-                uint64_t best = ~0ull;
-#pragma unroll
-                for (int j = 0; j < WS_REG; ++j) {
-                    const uint64_t c = (uint64_t)kk[j] << 32 | (uint32_t)(lo + lane + 64 * j);
-                    if (c >= from && c < best) best = c;
-                }
-                best = wave_min_u64(best);                              // (rounds <= hi - lo: a frame of the window, never an empty slot)
-                const uint32_t key = (uint32_t)(best >> 32);
-                acc = __fadd_rn(acc, key ? ws_key_value(key) : s[(uint32_t)best]);      // a NaN frame: its own bits from the row
-                from = best + 1ull;
-            }
-        } else {
-            ArgMax prev = rank_start();
-            for (int q = 0; q < rounds; ++q) {
-                ArgMax best = rank_none();
-                for (int t = lo + lane; t < hi; t += 64) best = rank_next(best, prev, ArgMax{s[t], t});
-                best = wave_rank_first(best);
-                acc = __fadd_rn(acc, best.v);
-                prev = best;
-            }
-        }
-        if (lane == 0) {
-            keys[i] = (uint64_t)rank_key(acc) << 32 | (uint32_t)i;
-            if (a.win_scores) a.win_scores[r * Wcap + i] = acc;
-            if (to_bounds) {
-                bnd[2 * i] = lo;
-                bnd[2 * i + 1] = hi;
-            }
-        }
-    }
-    for (int i = W + tid; i < Wcap; i += WS_TPB) {
-        if (a.win_scores) a.win_scores[r * Wcap + i] = qnan();
-        if (to_bounds) bnd[2 * i] = bnd[2 * i + 1] = -1;
-        if (a.order) a.order[r * Wcap + i] = -1;
-    }
-    for (int i = tid; i < P; i += WS_TPB) {
-        if (i >= W) keys[i] = (uint64_t)0xffffffffu << 32 | (uint32_t)i;
-        live[i] = 1;
-        taken[i] = 0;
-    }
-    __syncthreads();
-    bitonic_sort_u64<WS_TPB>(keys, P);
-
-    const int n_sel = keep < W ? keep : W;
-    const int limit = (a.order || a.hit_rank) ? W : n_sel;
-    if (min_sep == 1) {                      // nothing dies: the sequence is the rank order
-        for (int p = tid; p < limit; p += WS_TPB) seq[p] = (uint16_t)(uint32_t)keys[p];
-    } else {
-        int nt = 0;
-        for (int p = 0; p < W && nt < limit; ++p) {
-            const int i = (int)(uint32_t)keys[p];
-            if (!live[i]) continue;          // (the same value in every thread: the last write to it lies behind a barrier)
-            if (tid == 0) {
-                seq[nt] = (uint16_t)i;
-                taken[i] = 1;
-            }
-            ++nt;
-            if (nt < limit) {
-                const int j1 = i + min_sep - 1 < W - 1 ? i + min_sep - 1 : W - 1;
-                for (int j = (i - min_sep + 1 > 0 ? i - min_sep + 1 : 0) + tid; j <= j1; j += WS_TPB)
-                    if (j != i) live[j] = 0;
-            }
-            __syncthreads();
-        }
-        __syncthreads();
-        if (nt < limit) {                    // pass 1 ran dry: the rest in rank order
-            int c = 0;
-            for (int e = 0; e < WS_PER; ++e) {
-                const int p = tid * WS_PER + e;
-                c += (p < W && !taken[(uint32_t)keys[p]]) ? 1 : 0;
-            }
-            int pos = nt + ws_before(c, wsum);
-            for (int e = 0; e < WS_PER; ++e) {
-                const int p = tid * WS_PER + e;
-                if (p < W) {
-                    const int i = (int)(uint32_t)keys[p];
-                    if (!taken[i]) {
-                        if (pos < limit) seq[pos] = (uint16_t)i;
-                        ++pos;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    for (int i = tid; i < W; i += WS_TPB) live[i] = 0;
-    if (a.order)
-        for (int p = tid; p < W; p += WS_TPB) a.order[r * Wcap + p] = seq[p];
-    if (a.hit_rank) {
-        const float gs = a.gt[r * 2], ge = a.gt[r * 2 + 1];
-        if (span_solid(gs, ge)) {
-            int mine = 0x7fffffff;
-            for (int p = tid; p < W; p += WS_TPB) {                    // ascending p: the first one found is this thread's smallest
-                int lo, hi;
-                ws_bounds(seq[p], win, stride, D, lo, hi);
-                if ((float)lo < ge && (float)hi > gs) {
-                    mine = p;
-                    break;
-                }
-            }
-            if (mine != 0x7fffffff) atomicMin(&first, mine);           // (LDS; the minimum does not depend on the order of arrival)
-        }
-    }
-    __syncthreads();
-    for (int p = tid; p < n_sel; p += WS_TPB) live[seq[p]] = 1;
-    __syncthreads();
-    {
-        int c = 0;
-        for (int e = 0; e < WS_PER; ++e) {
-            const int i = tid * WS_PER + e;
-            c += (i < W && live[i]) ? 1 : 0;
-        }
-        int pos = ws_before(c, wsum);
-        for (int e = 0; e < WS_PER; ++e) {
-            const int i = tid * WS_PER + e;
-            if (i < W && live[i]) a.select[r * keep + pos++] = i;
-        }
-    }
-    for (int p = n_sel + tid; p < keep; p += WS_TPB) a.select[r * keep + p] = -1;
-    if (tid == 0) {
-        a.n_select[r] = n_sel;
-        a.n_windows[r] = W;
-        if (a.hit_rank) a.hit_rank[r] = first == 0x7fffffff ? -1 : first;
-    }
-}
-
-}  // namespace
+// The definition stands in include/revision_hip.h; the kernel is window_select.h's, instantiated here for the shifted windows.
+#include "window_select.h"
 
 extern "C" int rv_window_select(const float* sims, const float* mask, int32_t R, int32_t rpm, int32_t L, int32_t win, int32_t stride, int32_t k,
                                 int32_t keep, int32_t min_sep, int32_t Wcap, const float* gt, int32_t* select, int32_t* n_select, int32_t* n_windows,
@@ -257,7 +24,7 @@ extern "C" int rv_window_select(const float* sims, const float* mask, int32_t R,
     RV_CHECK_ARG(min_sep >= 1 && min_sep <= Wcap, "rv_window_select: min_sep=%d must be in [1, Wcap=%d]", min_sep, Wcap);
     RV_CHECK_ARG(gt || !hit_rank, "rv_window_select: hit_rank needs gt");
     const WindowArgs a{sims, mask, gt, select, n_select, n_windows, win_scores, bounds, order, hit_rank, L, rpm, win, stride, k, keep, min_sep, Wcap};
-    hipLaunchKernelGGL(window_select_kernel, dim3((unsigned)R), dim3(WS_TPB), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(window_select_kernel<RV_WINDOWS_SHIFTED>, dim3((unsigned)R), dim3(WS_TPB), 0, as_stream(stream), a);
     RV_CHECK_LAUNCH("rv_window_select");
     return RV_OK;
 }

@@ -156,6 +156,26 @@ class WindowStager:
         features_dev.record_stream(self.stream)
         return StagedWindows(dev, ev)
 
+    def stage_resident_selected(self, features_dev, *, windows=None, query_cls=None, keep=None, **geometry):
+        """``stage_resident_clipped`` for a selection of the stage-1 windows, on the staging stream: either ``windows``, a list of window indices the
+        host has (``stage1.windows_from_retrieval`` -> ``stage1.gather_selected``), or ``query_cls`` and ``keep`` (the CLIP pre-filter:
+        ``stage1.clip_stage_windows``, which waits for its one ``select`` row) -> (the sorted list of windows, ``StagedWindows`` with row j =
+        ``stage_resident_clipped(...)``'s row ``list[j]``)."""
+        from ..eval import stage1
+        if (windows is None) == (query_cls is None):
+            raise ValueError("stage_resident_selected: pass either windows= or query_cls= with keep=")
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))      # whatever made features_dev on the caller's stream comes first
+        with torch.cuda.stream(self.stream):
+            if windows is not None:
+                windows = sorted(windows)
+                dev = stage1.gather_selected(features_dev, windows, dtype=self.op_dtype, **geometry)
+            else:
+                windows, dev = stage1.clip_stage_windows(features_dev, query_cls, keep=keep, dtype=self.op_dtype, **geometry)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        features_dev.record_stream(self.stream)
+        return windows, StagedWindows(dev, ev)
+
 
 class ResidentFeatures:
     """Movies' feature arrays kept on the device across the queries of a movie: an LRU cache by bytes, keyed by movie.  ``get(movie, array)`` -> the

@@ -17,7 +17,9 @@ per-query ``try / except`` that records the id in ``errors`` and goes on (:338-3
 ``data.feature_store`` (npy / npz directory / LMDB) and a pinned staging buffer; ``--in_flight N`` (build-defined) runs N queries as
 scheduler tasks whose window batches prefill in the ``serve.DecodeServer``'s batched passes and decode in its merged steps; ``--device_features``
 (build-defined, off by default) keeps a movie's features on the device across its queries, cuts the windows there and scores a query's proposals in
-one launch, with the same records.
+one launch, with the same records; ``--clip_prefilter_keep N`` / ``--retrieval_path DIR`` (build-defined, off by default, with ``--device_features``) send only a
+selection of a query's windows through the LLM - the N that the CLIP pre-filter picks on the device, or the ones a stage-2 log retrieved - and write a
+record of the same schema, the windows that did not run answering ``"Not Present"``.
 """
 import argparse
 import json
@@ -91,6 +93,15 @@ def parse_args(argv=None):
                         "the windows on the host, uploading them per query and scoring proposal by proposal; --baseline, --plus_baseline, the short-video "
                         "subsample and a movie shorter than one window or with a void last window keep the host route; off: every code path is what it was")
     p.add_argument("--device_features_mb", type=int, default=2048, help="budget of the resident feature cache in MiB (--device_features)")
+    p.add_argument("--clip_prefilter_keep", type=int, default=0,
+                   help="(--device_features) run the LLM on the N windows of a query that the CLIP pre-filter picks on the device (stage1.clip_stage_windows: "
+                        "cosine row, top-k window scores, the best N) instead of on every window; the other windows answer \"Not Present\" in the record and "
+                        "info.windows lists the ones that ran; queries that keep the host route run every window; 0 = off")
+    p.add_argument("--retrieval_path", type=str, default=None,
+                   help="(--device_features) a stage-2 log directory (metrics.load_predictions): run the LLM only on the stage-1 windows that the query's "
+                        "stage-2 record retrieved (stage1.windows_from_retrieval, the rule of metrics.merge_stage1_stage2); a query without a record, or "
+                        "with an empty retrieval, runs every window; not together with --clip_prefilter_keep")
+    p.add_argument("--retrieval_buffer", type=int, default=0, help="windows added on either side of a retrieved range (--retrieval_path; merge_stage1_stage2's buffer)")
     p.add_argument("--pool_rows", type=int, default=32, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per generate at most (--in_flight > 1; answers are a dozen tokens)")
     return p.parse_args(argv)
@@ -157,9 +168,40 @@ def _on_device(args, resident, ctx_l, subsampled):
     return not ops.clipped_window_void(ctx_l, int(clip_length))
 
 
-def _prepare(args, store, stager, dev, id_, data, resident=None):
+def selection_flags(args):
+    """The refusals of ``--clip_prefilter_keep`` / ``--retrieval_path`` -> the stage-2 records by query id ({} without ``--retrieval_path``), or None when
+    neither flag is given."""
+    keep, path = getattr(args, "clip_prefilter_keep", 0), getattr(args, "retrieval_path", None)
+    if keep < 0:
+        raise ValueError(f"--clip_prefilter_keep {keep}: a window count (0 = off)")
+    if not keep and path is None:
+        return None
+    if keep and path is not None:
+        raise ValueError("--clip_prefilter_keep and --retrieval_path both choose a query's windows: pass one of them")
+    if not getattr(args, "device_features", False):
+        raise ValueError("--clip_prefilter_keep / --retrieval_path select windows of features that live on the device: pass --device_features")
+    if keep and args.q_feat_dir is None:
+        raise ValueError("--clip_prefilter_keep scores windows against the query's CLIP feature: pass --q_feat_dir")
+    if path is None:
+        return {}
+    from .metrics import load_predictions
+    return {r["query_id"]: r for r in load_predictions(path)}
+
+
+def _selection(args, retrieval, id_, n_windows):
+    """What ``stage_resident_selected`` is to select for a device-route query: None (every window), dict(keep=N) or dict(windows=[...])."""
+    if retrieval is None:
+        return None
+    if args.clip_prefilter_keep:
+        return dict(keep=args.clip_prefilter_keep)
+    frames = retrieval.get(id_, {}).get("info", {}).get("frames")
+    windows = stage1.windows_from_retrieval(frames, n_windows, getattr(args, "retrieval_buffer", 0)) if frames else []
+    return dict(windows=windows) if windows else None
+
+
+def _prepare(args, store, stager, dev, id_, data, resident=None, retrieval=None):
     """Everything of one query in front of the LLM: -> None (skipped) or a dict of staged inputs (``device``: the windows were cut on the device and the
-    proposals are scored there)."""
+    proposals are scored there; ``selected``: the windows that were staged when a selection ran, else None)."""
     movie = data["movie"] if "movie" in data else data["clip_id"]
     movie = data["query_id"] if "val_frame" in args.feat_folder else movie
     features = store.video(movie)
@@ -171,7 +213,18 @@ def _prepare(args, store, stager, dev, id_, data, resident=None):
         features = features[np.linspace(0, features.shape[0] - 1, args.num_frames, dtype=np.int32)]
         subsampled = True
     device = _on_device(args, resident, features.shape[0], subsampled)
-    if device:
+    selected, n_windows, sel = None, None, None
+    if device and retrieval is not None:
+        from .. import ops
+        n_windows = ops.clipped_window_count(features.shape[0], int(args.debug_window * args.feature_fps))
+        sel = _selection(args, retrieval, id_, n_windows)
+    if sel is not None:
+        if "keep" in sel:
+            sel["query_cls"] = query_cls
+        selected, staged = stager.stage_resident_selected(resident.get(movie, features), debug_window=args.debug_window, feature_fps=args.feature_fps,
+                                                          num_frames=args.num_frames, **sel)
+        windows = staged.wait()
+    elif device:
         windows = stager.stage_resident_clipped(resident.get(movie, features), debug_window=args.debug_window, feature_fps=args.feature_fps,
                                                 num_frames=args.num_frames).wait()
     else:
@@ -179,7 +232,8 @@ def _prepare(args, store, stager, dev, id_, data, resident=None):
     qf = torch.from_numpy(np.asarray(query_feats)).to(dev).to(getattr(stager, "op_dtype", torch.float32)) if query_feats is not None else None
     qc = torch.from_numpy(np.asarray(query_cls)).to(dev).float() if query_cls is not None else None
     duration = data["movie_duration"] if "movie_duration" in data else data["duration"]
-    return dict(movie=movie, windows=windows, qf=qf, qc=qc, sentence=_sentence(data), timestamps=data["timestamps"], duration=duration, device=device)
+    return dict(movie=movie, windows=windows, qf=qf, qc=qc, sentence=_sentence(data), timestamps=data["timestamps"], duration=duration, device=device,
+                selected=selected, n_windows=n_windows)
 
 
 def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
@@ -201,24 +255,29 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     store = FeatureStore(args.feat_folder, q_feat_dir=args.q_feat_dir, vis_feat_storage="npy" if args.vis_feat_storage == "pth" else args.vis_feat_storage)
     stager = WindowStager(model.device, op_dtype=getattr(model, "dtype", None))
     resident = _resident_cache(args, stager, model.device)
+    retrieval = selection_flags(args)
     done = set(done_query_ids(prediction_path))
     items = split_items(load_items(args.data_path), args.split, args.total_split)
     print("batch: ", args.batch)
     kw = dict(num_frames=args.num_frames, debug_window=args.debug_window, score=args.score, score_merge=args.score_merge, normalize=args.normalize,
               topk_pool=args.topk_pool, plus_baseline=args.plus_baseline)
     if getattr(args, "in_flight", 1) > 1:
-        return _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw, resident)
+        return _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw, resident, retrieval)
     errors, written = [], 0
     for id_, data in items:
         if id_ in done:
             continue
         try:
-            q = _prepare(args, store, stager, model.device, id_, data, resident)
+            q = _prepare(args, store, stager, model.device, id_, data, resident, retrieval)
             if q is None:
                 continue
-            run_query = stage1.run_query_device if q["device"] else stage1.run_query
-            answers, info = run_query(model, tokenizer, q["windows"], q["qf"], q["qc"], q["sentence"], q["timestamps"], q["duration"],
-                                      batch=args.batch, prompt=args.mad_prompt, **kw)
+            if q["selected"] is not None:
+                answers, info = stage1.run_query_selected(model, tokenizer, q["windows"], q["selected"], q["n_windows"], q["qf"], q["qc"], q["sentence"],
+                                                          q["timestamps"], q["duration"], batch=args.batch, prompt=args.mad_prompt, **kw)
+            else:
+                run_query = stage1.run_query_device if q["device"] else stage1.run_query
+                answers, info = run_query(model, tokenizer, q["windows"], q["qf"], q["qc"], q["sentence"], q["timestamps"], q["duration"],
+                                          batch=args.batch, prompt=args.mad_prompt, **kw)
             write_log(prediction_path, q["movie"], "grounding", id_, answers, info=info)
             written += 1
         except Exception:  # noqa: BLE001 - the reference's per-query handler (negative.py:338-341)
@@ -229,7 +288,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     return written, errors
 
 
-def _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw, resident=None):
+def _eval_in_flight(args, tokenizer, model, store, stager, items, done, prediction_path, kw, resident=None, retrieval=None):
     """``--in_flight N``: the same per-query work with up to N queries in flight as ``sched`` tasks (records appended in annotation order)."""
     from .. import sched, serve
     dev = model.device
@@ -245,8 +304,12 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, predicti
         task, id_, q = pending.pop(0)
         try:
             answers, ent = stage1.collect_query(model, tokenizer, inter.finish(task), args.score)
-            score_query = stage1.score_query_device if q["device"] else stage1.score_query
-            answers, info = score_query(q["windows"], answers, ent, q["qc"], q["timestamps"], q["duration"], **kw)
+            if q["selected"] is not None:
+                answers, info = stage1.score_query_selected(q["windows"], q["selected"], q["n_windows"], answers, ent, q["qc"], q["timestamps"], q["duration"],
+                                                            **kw)
+            else:
+                score_query = stage1.score_query_device if q["device"] else stage1.score_query
+                answers, info = score_query(q["windows"], answers, ent, q["qc"], q["timestamps"], q["duration"], **kw)
             write_log(prediction_path, q["movie"], "grounding", id_, answers, info=info)
             written += 1
         except Exception:  # noqa: BLE001 - the reference's per-query handler (negative.py:338-341)
@@ -261,7 +324,7 @@ def _eval_in_flight(args, tokenizer, model, store, stager, items, done, predicti
         if id_ in done:
             continue
         try:
-            q = _prepare(args, store, stager, dev, id_, data, resident)
+            q = _prepare(args, store, stager, dev, id_, data, resident, retrieval)
             if q is None:
                 continue
             gen = (lambda t, q=q: stage1.launch_query_steps(model, tokenizer, q["windows"], q["qf"], q["sentence"], batch=args.batch, score=args.score,

@@ -277,7 +277,21 @@ def select_windows(text, video, mask, *, win, stride, keep, k=3, min_sep=1, gt=N
     topped up in rank order, the first ``keep`` handed back ascending - the form of ``run_query(grounding_windows=)``).  ``hit_rank`` feeds
     ``eval.metrics.window_recall``.  No synchronisation and no device -> host copy when the inputs live on the device; host tensors are staged and
     every result comes back on the device ``video`` lives on."""
-    who = "select_windows"
+    return _select_windows("select_windows", lambda sims, m, **kw: ops.window_select(sims, m, stride=stride, **kw), text, video, mask, win, stride, keep, k,
+                           min_sep, gt, return_scores, return_bounds, return_order)
+
+
+def select_windows_clipped(text, video, mask, *, win, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):
+    """``select_windows`` for the stage-1 driver's windows: the same inputs, checks and ``ops.WindowSelection``, with ``ops.window_select_clipped``
+    (``rvx_window_select_clipped``) behind the cosine rows - the half-overlapping windows of ``stage1.cut_windows`` for ``clip_length = win``, the void
+    ones left out; ``select`` is what ``ops.window_gather_clipped(select=)`` takes.  No synchronisation and no device -> host copy when the inputs
+    live on the device."""
+    return _select_windows("select_windows_clipped", ops.window_select_clipped, text, video, mask, win, 2, keep, k, min_sep, gt, return_scores, return_bounds,
+                           return_order)
+
+
+def _select_windows(who, call, text, video, mask, win, stride, keep, k, min_sep, gt, return_scores, return_bounds, return_order):
+    """``select_windows`` (``call``: ``ops.window_select`` at its stride) and ``select_windows_clipped`` (``ops.window_select_clipped``, stride 2): one body."""
     for name, t in (("text", text), ("video", video), ("mask", mask)):
         if not torch.is_tensor(t):
             raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
@@ -301,9 +315,8 @@ def select_windows(text, video, mask, *, win, stride, keep, k=3, min_sep=1, gt=N
     home = video.device
     dev = _device_of(video, who)
     sims = (ops.frame_cosine_multi if multi else ops.frame_cosine)(ops.h2d(text, dev).float(), _features_up(video, dev))
-    out = ops.window_select(sims, ops.h2d(mask, dev), win=win, stride=stride, keep=keep, k=k, min_sep=min_sep,
-                            gt=None if gt is None else ops.h2d(gt, dev).float(), return_scores=return_scores, return_bounds=return_bounds,
-                            return_order=return_order)
+    out = call(sims, ops.h2d(mask, dev), win=win, keep=keep, k=k, min_sep=min_sep, gt=None if gt is None else ops.h2d(gt, dev).float(),
+               return_scores=return_scores, return_bounds=return_bounds, return_order=return_order)
     return ops.WindowSelection(*(None if t is None else t.to(home) for t in out))
 
 

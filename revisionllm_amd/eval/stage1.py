@@ -1,6 +1,8 @@
 """Stage-1 (dense / sparse) grounding driver for one query: half-overlapping windows, batches of windows straight into
 ``inference()`` (LLM batch > 1), ``"From a to b."`` parsing, IoU and entropy / cosine scores; and the same on the device for features that stay
-there (``gather_windows``, ``proposal_cosines``, ``score_query_device``, ``run_query_device``: the driver's ``--device_features``).
+there (``gather_windows``, ``proposal_cosines``, ``score_query_device``, ``run_query_device``: the driver's ``--device_features``); and the LLM on a
+selection of the windows only (``clip_stage_windows``, ``windows_from_retrieval``, ``gather_selected``, ``expand_selected``, ``score_query_selected``,
+``run_query_selected``: the driver's ``--clip_prefilter_keep`` / ``--retrieval_path``), with records of the same schema.
 
 Counterpart of revisionllm/eval/eval_nlq_negative.py:224-337.  (The reference file imports ``vtimellm.*`` and cannot run
 as shipped - SURVEY section 2 #12 - so this follows the cited lines; its ``iou`` helper is pinned by
@@ -88,13 +90,8 @@ def score_query(features, answers, ent, query_cls, timestamps, duration, num_fra
     return answers, {"iou": ious, "scores": scores}
 
 
-def gather_windows(features_dev, *, debug_window=125, feature_fps=5, num_frames=250, dtype=None):
-    """``cut_windows`` + the host gather for features that are already on the device: features_dev [ctx_l, d] (f32 or 16-bit operands) ->
-    [W, num_frames, d] in ``dtype`` (None: ``ops.window_gather``'s default), equal to ``features[cut_windows(ctx_l, debug_window, feature_fps,
-    num_frames)]`` cast to ``dtype`` (``rv_window_gather_rule``: one launch, every window, nothing uploaded, no synchronisation).
-    ``debug_window * feature_fps`` must be a whole number of frames, at least 2 and at most ctx_l, and no window void (``ops.clipped_window_void``: the
-    host route indexes past the array there)."""
-    who = "stage1.gather_windows"
+def _clipped_geometry(who, features_dev, debug_window, feature_fps):
+    """The refusals of the device routes over ``cut_windows``' geometry -> clip_length as an int."""
     clip_length = debug_window * feature_fps
     if not (isinstance(clip_length, numbers.Real) and not isinstance(clip_length, bool) and math.isfinite(clip_length) and clip_length == int(clip_length)
             and clip_length >= 2):
@@ -107,6 +104,16 @@ def gather_windows(features_dev, *, debug_window=125, feature_fps=5, num_frames=
     if ctx_l < clip_length or ops.clipped_window_void(ctx_l, clip_length):
         raise ValueError(f"{who}: ctx_l={ctx_l} frames for windows of {clip_length} (a video shorter than one window, or one whose last window starts "
                          f"behind its end) - take the host route (cut_windows + WindowStager.stage_windows)")
+    return clip_length
+
+
+def gather_windows(features_dev, *, debug_window=125, feature_fps=5, num_frames=250, dtype=None):
+    """``cut_windows`` + the host gather for features that are already on the device: features_dev [ctx_l, d] (f32 or 16-bit operands) ->
+    [W, num_frames, d] in ``dtype`` (None: ``ops.window_gather``'s default), equal to ``features[cut_windows(ctx_l, debug_window, feature_fps,
+    num_frames)]`` cast to ``dtype`` (``rv_window_gather_rule``: one launch, every window, nothing uploaded, no synchronisation).
+    ``debug_window * feature_fps`` must be a whole number of frames, at least 2 and at most ctx_l, and no window void (``ops.clipped_window_void``: the
+    host route indexes past the array there)."""
+    clip_length = _clipped_geometry("stage1.gather_windows", features_dev, debug_window, feature_fps)
     return ops.window_gather_clipped(features_dev, win=clip_length, num_frames=num_frames, out_dtype=dtype)
 
 
@@ -135,6 +142,22 @@ def _proposal_cosines_each(features, frames, query_cls, topk_pool):
     return cos
 
 
+def _merge_scores(cos, ent, score, score_merge, normalize):
+    """``score_query``'s max-normalisation and entropy merge (negative.py:318-336) in Python floats -> the record's ``scores``."""
+    if normalize:
+        if cos:
+            cos = [c / max(cos) for c in cos]
+        if ent:
+            ent = [e / max(ent) for e in ent]
+    if "entropy" in score:
+        if score_merge == "add":
+            return [c - e for c, e in zip(cos, ent)]
+        if score_merge == "multiply":
+            return [c / e for c, e in zip(cos, ent)]
+        return [-e for e in ent]
+    return cos
+
+
 def score_query_device(features, answers, ent, query_cls, timestamps, duration, num_frames=250, debug_window=125, score="mean_entropy",
                        score_merge="multiply", normalize=True, topk_pool=False, plus_baseline=False):
     """``score_query`` with the proposals' cosine scores from ``proposal_cosines``: the same parameters, the same result.  The max-normalisation and the
@@ -143,21 +166,7 @@ def score_query_device(features, answers, ent, query_cls, timestamps, duration, 
     num_frames_video = int(duration * num_frames / debug_window)
     frames, ious, ent = iou(answers, gt, num_frames, num_frames_video, ent, plus_baseline)
     cos = proposal_cosines(features, frames, query_cls, topk_pool)
-    if normalize:
-        if cos:
-            cos = [c / max(cos) for c in cos]
-        if ent:
-            ent = [e / max(ent) for e in ent]
-    if "entropy" in score:
-        if score_merge == "add":
-            scores = [c - e for c, e in zip(cos, ent)]
-        elif score_merge == "multiply":
-            scores = [c / e for c, e in zip(cos, ent)]
-        else:
-            scores = [-e for e in ent]
-    else:
-        scores = cos
-    return answers, {"iou": ious, "scores": scores}
+    return answers, {"iou": ious, "scores": _merge_scores(cos, ent, score, score_merge, normalize)}
 
 
 def run_query(model, tokenizer, features, query_feats, query_cls, sentence, timestamps, duration, batch=8, num_frames=250,
@@ -177,6 +186,98 @@ def run_query_device(model, tokenizer, features, query_feats, query_cls, sentenc
     answers, ent = answer_windows(model, tokenizer, features, query_feats, sentence, batch, score, prompt)
     return score_query_device(features, answers, ent, query_cls, timestamps, duration, num_frames, debug_window, score, score_merge, normalize, topk_pool,
                               plus_baseline)
+
+
+def clip_stage_windows(features_dev, query_cls, *, debug_window=125, feature_fps=5, keep, num_frames=250, dtype=None, k=3, min_sep=1):
+    """The stage-1 pre-filter and the staging of its windows in one pass over features that are on the device: features_dev [ctx_l, d], query_cls [d]
+    (host or device) -> (the sorted Python list of the ``keep`` windows of ``cut_windows``' geometry that ``similarity.select_windows_clipped`` chooses,
+    the window tensor [len(list), num_frames, d] in ``dtype``, row j equal to ``gather_windows(...)[list[j]]``).  Three launches - the cosine row,
+    ``rvx_window_select_clipped``, ``rv_window_gather_rule`` fed from the device ``select`` row - and the gather is enqueued BEFORE the ``.tolist()`` of
+    that row, the one device -> host copy, as ``stage2.clip_stage_windows`` does.  The refusals are ``gather_windows``'."""
+    who = "stage1.clip_stage_windows"
+    from . import similarity
+    clip_length = _clipped_geometry(who, features_dev, debug_window, feature_fps)
+    if not (isinstance(keep, numbers.Integral) and not isinstance(keep, bool) and keep >= 1):
+        raise ValueError(f"{who}: keep={keep!r} must be a positive integer")
+    query_cls = query_cls if torch.is_tensor(query_cls) else torch.from_numpy(np.ascontiguousarray(query_cls))
+    if query_cls.dim() != 1 or query_cls.shape[0] != features_dev.shape[1] or not query_cls.dtype.is_floating_point:
+        raise ValueError(f"{who}: features {tuple(features_dev.shape)} / query_cls {tuple(query_cls.shape)} {query_cls.dtype} (expected [ctx_l, d] and a floating-point [d])")
+    dev, ctx_l = features_dev.device, features_dev.shape[0]
+    sel = similarity.select_windows_clipped(ops.h2d(query_cls, dev)[None], features_dev[None], torch.ones(1, ctx_l, device=dev), win=clip_length, keep=keep,
+                                            k=k, min_sep=min_sep)
+    row = sel.select[0]
+    frames = ops.window_gather_clipped(features_dev, win=clip_length, num_frames=num_frames, select=row, out_dtype=dtype)
+    windows = [i for i in row.tolist() if i >= 0]                   # ascending, the -1 padding behind them: the first len(list) windows of frames
+    return windows, frames[:len(windows)]
+
+
+def gather_selected(features_dev, windows, *, debug_window=125, feature_fps=5, num_frames=250, dtype=None):
+    """``gather_windows`` for a list of window indices that the host already has (``windows_from_retrieval``): -> [len(windows), num_frames, d], row j
+    equal to ``gather_windows(...)[windows[j]]``.  The list is uploaded as the ``select`` row of the same launch; no synchronisation."""
+    who = "stage1.gather_selected"
+    clip_length = _clipped_geometry(who, features_dev, debug_window, feature_fps)
+    W = ops.clipped_window_count(features_dev.shape[0], clip_length)
+    windows = list(windows)
+    if not windows or any(not (isinstance(i, numbers.Integral) and not isinstance(i, bool) and 0 <= i < W) for i in windows):
+        raise ValueError(f"{who}: windows={windows!r} must be a non-empty list of indices in [0, {W})")
+    row = ops.h2d(torch.tensor(windows, dtype=torch.int32), features_dev.device)
+    return ops.window_gather_clipped(features_dev, win=clip_length, num_frames=num_frames, select=row, out_dtype=dtype)
+
+
+def windows_from_retrieval(frames, n_windows, buffer=0):
+    """The stage-1 window indices that a stage-2 record retrieves, by the rule of ``metrics.merge_stage1_stage2``'s ``ranges``: frames = the record's
+    ``info["frames"]`` ({key: (f, t)} in stage-2 window units, or a list of such pairs), n_windows = the movie's stage-1 window count -> the distinct
+    indices of ``range(max(0, int(.4 * f) - buffer), min(int(.4 * t) + buffer, n_windows - 1))`` over all pairs, ascending.  Host code."""
+    pairs = list(frames.values()) if isinstance(frames, dict) else list(frames)
+    out = set()
+    for f, t in pairs:
+        out.update(range(max(0, int(.4 * f) - buffer), min(int(.4 * t) + buffer, n_windows - 1)))
+    return sorted(out)
+
+
+def expand_selected(answers, ent, windows, n_windows):
+    """The answers of a run over the windows ``windows`` (ascending, distinct, in [0, n_windows)) as a run over all ``n_windows`` would record them:
+    -> (answers of length n_windows, ent of length n_windows or []).  A window that did not run answers ``"Not Present"`` (``metrics.NOT_PRESENT[0]``:
+    no proposal), and its entropy slot holds NaN, which ``iou()`` never reads (it keeps the slots of parsed answers only)."""
+    from .metrics import NOT_PRESENT
+    windows = list(windows)
+    if len(answers) != len(windows) or (len(ent) not in (0, len(windows))):
+        raise ValueError(f"expand_selected: {len(answers)} answers and {len(ent)} entropy statistics for {len(windows)} windows")
+    if windows != sorted(set(windows)) or (windows and not 0 <= windows[0] <= windows[-1] < n_windows):
+        raise ValueError(f"expand_selected: windows={windows!r} must be ascending, distinct and in [0, {n_windows})")
+    full = [NOT_PRESENT[0]] * n_windows
+    full_ent = [float("nan")] * n_windows if len(ent) else []
+    for j, w in enumerate(windows):
+        full[w] = answers[j]
+        if full_ent:
+            full_ent[w] = ent[j]
+    return full, full_ent
+
+
+def score_query_selected(features_sel, windows, n_windows, answers_sel, ent_sel, query_cls, timestamps, duration, num_frames=250, debug_window=125,
+                         score="mean_entropy", score_merge="multiply", normalize=True, topk_pool=False, plus_baseline=False):
+    """``score_query_device`` for a query whose LLM ran on a selection: features_sel [len(windows), T, d] (row j = window ``windows[j]``), answers_sel /
+    ent_sel one entry per selected window, n_windows the movie's window count.  The answers are expanded (``expand_selected``) and ``iou()`` runs on them
+    unchanged, so the window indices in proposals and IoUs are the TRUE ones; proposal (window, a, b) is scored on row ``windows.index(window)`` of the
+    selected tensor through ``proposal_cosines``; normalisation and merge as ``score_query``.  -> (the expanded answers, {"iou", "scores", "windows"}):
+    the record ``score_query_device`` writes for the full tensor with the other windows' answers replaced by ``"Not Present"``."""
+    windows = [int(w) for w in windows]
+    answers, ent = expand_selected(answers_sel, ent_sel, windows, n_windows)
+    gt = (timestamps[0] / duration, timestamps[1] / duration)
+    num_frames_video = int(duration * num_frames / debug_window)
+    frames, ious, ent = iou(answers, gt, num_frames, num_frames_video, ent, plus_baseline)
+    row = {w: j for j, w in enumerate(windows)}
+    cos = proposal_cosines(features_sel, {row[w]: ab for w, ab in frames.items()}, query_cls, topk_pool)
+    return answers, {"iou": ious, "scores": _merge_scores(cos, ent, score, score_merge, normalize), "windows": windows}
+
+
+def run_query_selected(model, tokenizer, features_sel, windows, n_windows, query_feats, query_cls, sentence, timestamps, duration, batch=8, num_frames=250,
+                       debug_window=125, score="mean_entropy", score_merge="multiply", normalize=True, topk_pool=False, prompt="mad_grounding",
+                       plus_baseline=False):
+    """``run_query_device`` on a selection: ``answer_windows`` on the selected tensor, then ``score_query_selected``."""
+    answers, ent = answer_windows(model, tokenizer, features_sel, query_feats, sentence, batch, score, prompt)
+    return score_query_selected(features_sel, windows, n_windows, answers, ent, query_cls, timestamps, duration, num_frames, debug_window, score, score_merge,
+                                normalize, topk_pool, plus_baseline)
 
 
 def answer_windows(model, tokenizer, features, query_feats, sentence, batch=8, score="mean_entropy", prompt="mad_grounding"):

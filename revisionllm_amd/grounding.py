@@ -485,6 +485,42 @@ def window_gather_clipped(video, *, win, num_frames, select=None, mask=None, out
     return (frames, index) if return_index else frames
 
 
+def clipped_window_solid(L, win):
+    """How many of ``clipped_window_count(L, win)`` windows are not void (``(i * win) // 2 <= L - 1``): the void ones are a suffix, so these are the
+    indices below the result - what ``window_select_clipped`` reports as ``n_windows``."""
+    return min(clipped_window_count(L, win), (2 * L - 1) // win + 1) if L >= 1 else 0
+
+
+def window_select_clipped(sims, mask, *, win, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):
+    """Choose the stage-1 driver's windows from similarity rows on the device (``rvx_window_select_clipped`` of the companion library): the arguments
+    and the WindowSelection of ``window_select``, under ``stage1.cut_windows``' rule for ``clip_length = win`` - half-overlapping windows
+    ``[(i * win) // 2, min((i * win) // 2 + win, D - 1)]``, the last ones clipped and not shifted back, so an index means the same window as in
+    ``window_gather_clipped``.  A void window (``clipped_window_void``) is no candidate: ``n_windows`` counts the others (``clipped_window_solid``),
+    and a void index appears in neither ``select`` nor ``order``.  ``Wcap = max(1, ceil(L / (win // 2)) - 1)``; a ``keep`` above it is Wcap.  One
+    launch (a mask that is not f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip_ext.h."""
+    who = "window_select_clipped"
+    win, _, keep, k, min_sep = window_select_keywords(who, win, 2, keep, k, min_sep)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    Wcap = window_select_capacity(who, L, win, 2, min_sep)
+    window_select_gt(who, gt, lead)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    keep = min(keep, Wcap)
+    dev = sims.device
+    select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
+    n_select = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
+    scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
+    bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
+    order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
+    hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
+    hip.ext_check(hip.ext_lib().rvx_window_select_clipped(hip.ptr(sims.contiguous()), hip.ptr(mask.float().contiguous()), R, rpm, L, win, k, keep, min_sep, Wcap,
+                                                          hip.ptr(gt.float().contiguous()) if gt is not None else None, hip.ptr(select), hip.ptr(n_select),
+                                                          hip.ptr(n_windows), hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()),
+                  "rvx_window_select_clipped")
+    return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
+
+
 def proposal_slice(a, b, T):
     """(lo, hi) of ``range(T)[a : b + 1]`` for a >= 0 as ``rv_proposal_cosine`` cuts it: lo = min(a, T), hi = min(b + 1, T); hi <= lo is an empty slice."""
     return min(a, T), min(b + 1, T)

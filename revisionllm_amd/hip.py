@@ -190,6 +190,53 @@ SIGNATURES = {
 }
 
 
+#: the companion library (include/revision_hip_ext.h): f32-only entries, ONE build for both operand flavours; every exported name starts with rvx_.
+#: REVISION_HIP_LIB_EXT: load another build of it.
+EXT_LIB_PATH = os.environ.get("REVISION_HIP_LIB_EXT") or os.path.join(_HERE, "librevision_hip_ext.so")
+RVX_ABI_VERSION = 1
+#: every symbol include/revision_hip_ext.h declares: name -> (restype, argtypes)
+EXT_SIGNATURES = {
+    "rvx_abi_version": (C.c_int, []),
+    "rvx_last_error": (C.c_int, [C.c_char_p, _sz]),
+    "rvx_window_select_clipped": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+}
+_ext = None
+
+
+def ext_lib():
+    """Load (once) and return the ctypes handle of the companion library; raises HipLibraryError when it is missing (there is no fallback)."""
+    global _ext
+    if _ext is None:
+        if not os.path.exists(EXT_LIB_PATH):
+            raise HipLibraryError(f"{EXT_LIB_PATH} not found: build it with `python -m revisionllm_amd.build` (hipcc, gfx950). "
+                                  "revisionllm_amd has no CPU fallback.")
+        try:
+            h = C.CDLL(EXT_LIB_PATH)
+        except OSError as e:
+            raise HipLibraryError(f"cannot load {EXT_LIB_PATH}: {e}") from e
+        for name, (res, args) in EXT_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = res, args
+        if h.rvx_abi_version() != RVX_ABI_VERSION:
+            raise HipLibraryError(f"{EXT_LIB_PATH} has rvx_abi_version() = {h.rvx_abi_version()} (expected {RVX_ABI_VERSION})")
+        _ext = h
+    return _ext
+
+
+def ext_last_error():
+    """The calling thread's last error message of the companion library ("" when it is not loaded)."""
+    if _ext is None:
+        return ""
+    buf = C.create_string_buffer(512)
+    _ext.rvx_last_error(buf, 512)
+    return buf.value.decode()
+
+
+def ext_check(rc, what):
+    if rc != 0:
+        raise HipLibraryError(f"{what} failed (status {rc}): {ext_last_error()}")
+
+
 def lib(f=None):
     """Load (once) and return the ctypes handle of a flavour's library (f: flavour name, torch dtype, tensor or None = the default
     flavour); raises HipLibraryError when the extension is missing."""
