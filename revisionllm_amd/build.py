@@ -2,7 +2,8 @@
 ``librevision_hip_bf16.so`` (bf16 operands) - the same sources compiled with ``-DRV_OP_F16=1`` / ``0`` (csrc/common.h).  No JIT cache: the
 ``.so`` files ship with the tree.  Only the entry points ``include/revision_hip.h`` declares are exported (``-fvisibility=hidden``).  After the two
 flavours comes the companion library ``librevision_hip_ext.so`` (``include/revision_hip_ext.h``, the ``rvx_*`` entries): f32-only kernels, one build
-for both flavours, linked with its own copy of ``error.o`` and its own version script."""
+for both flavours, linked with its own copy of ``error.o`` and its own version script; and, built the same way, the chain library
+``librevision_hip_chain.so`` (``include/revision_hip_chain.h``, the ``rvc_*`` entries)."""
 import os
 import subprocess
 import sys
@@ -23,6 +24,11 @@ EXT_LIB = os.path.join(HERE, "librevision_hip_ext.so")
 EXT_SOURCES = ["prefilter_ext.hip"]          # compiled once (in the f16 object directory: nothing in them depends on the flavour)
 EXT_SHARED = ["error.hip"]                   # objects of the f16 build linked in as well, their rv_* names local
 EXT_HEADERS = ["exports_ext.map", os.path.join("..", "..", "include", "revision_hip_ext.h")]
+CHAIN_LIB = os.path.join(HERE, "librevision_hip_chain.so")
+CHAIN_SOURCES = ["prefilter_chain.hip"]      # compiled once, as the companion's
+CHAIN_HEADERS = ["exports_chain.map", os.path.join("..", "..", "include", "revision_hip_chain.h")]
+#: the f32-only libraries: (path, own sources, headers beyond HEADERS, version script); each links EXT_SHARED's objects with their rv_* names local
+COMPANIONS = [(EXT_LIB, EXT_SOURCES, EXT_HEADERS, "exports_ext.map"), (CHAIN_LIB, CHAIN_SOURCES, CHAIN_HEADERS, "exports_chain.map")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]
 
@@ -42,19 +48,20 @@ def _stale(target, deps):
 
 
 def build_library(force=False, verbose=False, flavours=("f16", "bf16")):
-    """Compile every HIP translation unit for gfx950 in each flavour and link the shared libraries, then the companion library. Returns the default
-    library's path."""
+    """Compile every HIP translation unit for gfx950 in each flavour and link the shared libraries, then the companion and the chain library. Returns
+    the default library's path."""
     hipcc = _hipcc()
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     jobs = []
     ext_dir = os.path.join(OBJ, "f16")
     os.makedirs(ext_dir, exist_ok=True)
-    ext_hdrs = hdrs + [os.path.join(CSRC, h) for h in EXT_HEADERS]
-    for s in EXT_SOURCES + ([] if "f16" in flavours else EXT_SHARED):
-        src = os.path.join(CSRC, s)
-        obj = os.path.join(ext_dir, s.replace(".hip", ".o"))
-        if force or _stale(obj, [src] + ext_hdrs):
-            jobs.append([hipcc] + FLAGS + [FLAVOURS["f16"][1], "-DRV_TU=" + s.replace(".hip", ""), "-c", src, "-o", obj])
+    for n, (_, sources, headers, _) in enumerate(COMPANIONS):
+        ext_hdrs = hdrs + [os.path.join(CSRC, h) for h in headers]
+        for s in sources + ([] if "f16" in flavours or n else EXT_SHARED):
+            src = os.path.join(CSRC, s)
+            obj = os.path.join(ext_dir, s.replace(".hip", ".o"))
+            if force or _stale(obj, [src] + ext_hdrs):
+                jobs.append([hipcc] + FLAGS + [FLAVOURS["f16"][1], "-DRV_TU=" + s.replace(".hip", ""), "-c", src, "-o", obj])
     for fl in flavours:
         os.makedirs(os.path.join(OBJ, fl), exist_ok=True)
         for s in SOURCES:
@@ -77,9 +84,10 @@ def build_library(force=False, verbose=False, flavours=("f16", "bf16")):
         lib = lib_path(fl)
         if force or _stale(lib, objs):
             run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", lib] + objs)
-    ext_objs = [os.path.join(ext_dir, s.replace(".hip", ".o")) for s in EXT_SOURCES + EXT_SHARED]
-    if force or _stale(EXT_LIB, ext_objs + [os.path.join(CSRC, "exports_ext.map")]):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports_ext.map"), "-o", EXT_LIB] + ext_objs)
+    for lib, sources, _, script in COMPANIONS:
+        ext_objs = [os.path.join(ext_dir, s.replace(".hip", ".o")) for s in sources + EXT_SHARED]
+        if force or _stale(lib, ext_objs + [os.path.join(CSRC, script)]):
+            run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, script), "-o", lib] + ext_objs)
     return LIB
 
 

@@ -4,11 +4,10 @@
 //   rv_window_gather_rule   the same with the window rule as an argument: stage 2's shifted windows or stage 1's clipped ones (stage1.cut_windows), and a
 //                           NULL select for "every window in order"
 // The definition stands in include/revision_hip.h.  The duration and the window rule are grounding.h's (rv_window_select's own code), the sampled frames
-// are np.linspace's float64 operations one by one, and the rows are copied or converted element by element: a row of the result does not depend on R, on
+// are np.linspace's float64 operations one by one (grounding.h gw_linspace: __ddiv_rn, __dmul_rn, __dadd_rn, each rounded on its own; one definition
+// with the window selection that scores the sampled frames), and the rows are copied or converted element by element: a row of the result does not depend on R, on
 // the row's place or on any tiling.
 #include "grounding.h"
-
-#pragma clang fp contract(off)   // the index rule below is a float64 multiply, then an add: each rounded on its own
 
 namespace {
 
@@ -28,20 +27,6 @@ struct GatherArgs {
     int64_t ldv;
     int L, rpm, d, win, stride, keep, F;
 };
-
-// np.linspace(s, e, F, dtype=int32)[j]: step = (e - s) / (F - 1), y = j * step (or (j * (e - s)) / (F - 1) when the step is 0), y += s, the last one is e,
-// floor - numpy's float64 operations in numpy's order.  The result lies in [s, e] (j * step <= (F - 2) / (F - 1) * (e - s) * (1 + 2^-52)^2 < e - s); the clamp
-// states that for the loads that follow and changes no value.
-__device__ __forceinline__ int gw_linspace(int s, int e, int F, int j) {
-    if (F == 1) return s;
-    if (j == F - 1) return e;
-    const double delta = (double)(e - s), div = (double)(F - 1);
-    const double step = __ddiv_rn(delta, div);
-    double y = step == 0.0 ? __ddiv_rn(__dmul_rn((double)j, delta), div) : __dmul_rn((double)j, step);
-    y = __dadd_rn(y, (double)s);
-    const int idx = (int)floor(y);
-    return idx < s ? s : idx > e ? e : idx;
-}
 
 // One lane's piece of a row between the load and the store.  VECTOR: 16-byte loads and 16-byte stores - 16 bytes of a copy, 8 elements of a conversion (two loads
 // per store from f32 to 16 bits, two stores per load the other way); else one element.  The same type on both sides moves the bits; f32 -> 16 bits is the

@@ -1,6 +1,6 @@
 // What the stages of the CLIP grounding chain share, one definition each: the frame order of the score kernels, the rank key of a score, the bitonic
-// sort of (key, index) pairs, the duration rule, the two window rules (stage 2's shifted windows, stage 1's clipped ones) and the small helpers around them.  Included by the chain's translation units only (sample.hip for
-// rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip, gather.hip): two stages that have to agree bit for bit call the same code.
+// sort of (key, index) pairs, the duration rule, the two window rules (stage 2's shifted windows, stage 1's clipped ones), the sampled frames of a window and the small helpers around them.  Included by the chain's translation units only (sample.hip for
+// rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip, prefilter_ext.hip, prefilter_chain.hip, gather.hip): two stages that have to agree bit for bit call the same code.
 #pragma once
 #include "kernels.h"
 
@@ -141,6 +141,23 @@ __device__ __forceinline__ bool ws_bounds_clipped(int i, int win, int D, int& lo
     lo = (int)s;
     hi = (int)e + 1;
     return s <= e;
+}
+
+// ---- sampled frames ----
+// np.linspace(s, e, F, dtype=int32)[j]: step = (e - s) / (F - 1), y = j * step (or (j * (e - s)) / (F - 1) when the step is 0), y += s, the last one is e,
+// floor - numpy's float64 operations in numpy's order, the multiply and the add rounded each on its own (no contraction inside this body).  The result
+// lies in [s, e] (j * step <= (F - 2) / (F - 1) * (e - s) * (1 + 2^-52)^2 < e - s); the clamp states that for the loads that follow and changes no
+// value.  rv_window_gather* samples a window's frames with it and rvc_window_select_frames scores those samples: entry j means the same frame in both.
+__device__ __forceinline__ int gw_linspace(int s, int e, int F, int j) {
+#pragma clang fp contract(off)
+    if (F == 1) return s;
+    if (j == F - 1) return e;
+    const double delta = (double)(e - s), div = (double)(F - 1);
+    const double step = __ddiv_rn(delta, div);
+    double y = step == 0.0 ? __ddiv_rn(__dmul_rn((double)j, delta), div) : __dmul_rn((double)j, step);
+    y = __dadd_rn(y, (double)s);
+    const int idx = (int)floor(y);
+    return idx < s ? s : idx > e ? e : idx;
 }
 
 }  // namespace

@@ -177,6 +177,21 @@ class WindowStager:
         return windows, StagedWindows(dev, ev)
 
 
+    def stage_resident_selected_frames(self, features_dev, *, query_cls, keep, score_frames="sampled", valid=None, **geometry):
+        """``stage_resident_selected(query_cls=, keep=)`` with the pre-filter's windows scored on a chosen frame set (``stage1.clip_stage_windows_frames``:
+        ``score_frames="sampled"`` ranks a window by the ``num_frames`` frames that are staged of it; ``valid`` [ctx_l] hides frames from the scores) ->
+        (the sorted list of windows, ``StagedWindows`` with row j = ``stage_resident_clipped(...)``'s row ``list[j]``)."""
+        from ..eval import stage1
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))      # whatever made features_dev on the caller's stream comes first
+        with torch.cuda.stream(self.stream):
+            windows, dev = stage1.clip_stage_windows_frames(features_dev, query_cls, keep=keep, dtype=self.op_dtype, score_frames=score_frames, valid=valid,
+                                                            **geometry)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        features_dev.record_stream(self.stream)
+        return windows, StagedWindows(dev, ev)
+
+
 class ResidentFeatures:
     """Movies' feature arrays kept on the device across the queries of a movie: an LRU cache by bytes, keyed by movie.  ``get(movie, array)`` -> the
     device tensor [ctx_l, d], uploaded on the first use (through a pinned buffer, asynchronously, on ``stream`` - the stager's) and handed back from the

@@ -97,6 +97,9 @@ def parse_args(argv=None):
                    help="(--device_features) run the LLM on the N windows of a query that the CLIP pre-filter picks on the device (stage1.clip_stage_windows: "
                         "cosine row, top-k window scores, the best N) instead of on every window; the other windows answer \"Not Present\" in the record and "
                         "info.windows lists the ones that ran; queries that keep the host route run every window; 0 = off")
+    p.add_argument("--clip_prefilter_frames", choices=("all", "sampled"), default="all",
+                   help="(--device_features --clip_prefilter_keep N) which frames of a window the CLIP pre-filter scores: all of them, or the --num_frames "
+                        "sampled ones the LLM is handed (stage1.clip_stage_windows_frames); all: every code path is what it was")
     p.add_argument("--retrieval_path", type=str, default=None,
                    help="(--device_features) a stage-2 log directory (metrics.load_predictions): run the LLM only on the stage-1 windows that the query's "
                         "stage-2 record retrieved (stage1.windows_from_retrieval, the rule of metrics.merge_stage1_stage2); a query without a record, or "
@@ -174,6 +177,13 @@ def selection_flags(args):
     keep, path = getattr(args, "clip_prefilter_keep", 0), getattr(args, "retrieval_path", None)
     if keep < 0:
         raise ValueError(f"--clip_prefilter_keep {keep}: a window count (0 = off)")
+    frames = getattr(args, "clip_prefilter_frames", "all")
+    if frames not in ("all", "sampled"):
+        raise ValueError(f"--clip_prefilter_frames {frames}: all or sampled")
+    if frames == "sampled" and not (keep and getattr(args, "device_features", False)):
+        raise ValueError("--clip_prefilter_frames sampled scores the frames that the device gather samples: pass --device_features and --clip_prefilter_keep N")
+    if frames == "sampled" and not 1 <= args.num_frames <= 1024:
+        raise ValueError(f"--clip_prefilter_frames sampled ranks a window's sampled frames from registers: --num_frames {args.num_frames} must be in [1, 1024]")
     if not keep and path is None:
         return None
     if keep and path is not None:
@@ -193,6 +203,8 @@ def _selection(args, retrieval, id_, n_windows):
     if retrieval is None:
         return None
     if args.clip_prefilter_keep:
+        if getattr(args, "clip_prefilter_frames", "all") == "sampled":
+            return dict(keep=args.clip_prefilter_keep, score_frames="sampled")
         return dict(keep=args.clip_prefilter_keep)
     frames = retrieval.get(id_, {}).get("info", {}).get("frames")
     windows = stage1.windows_from_retrieval(frames, n_windows, getattr(args, "retrieval_buffer", 0)) if frames else []
@@ -221,8 +233,9 @@ def _prepare(args, store, stager, dev, id_, data, resident=None, retrieval=None)
     if sel is not None:
         if "keep" in sel:
             sel["query_cls"] = query_cls
-        selected, staged = stager.stage_resident_selected(resident.get(movie, features), debug_window=args.debug_window, feature_fps=args.feature_fps,
-                                                          num_frames=args.num_frames, **sel)
+        stage = stager.stage_resident_selected_frames if "score_frames" in sel else stager.stage_resident_selected
+        selected, staged = stage(resident.get(movie, features), debug_window=args.debug_window, feature_fps=args.feature_fps, num_frames=args.num_frames,
+                                 **sel)
         windows = staged.wait()
     elif device:
         windows = stager.stage_resident_clipped(resident.get(movie, features), debug_window=args.debug_window, feature_fps=args.feature_fps,

@@ -102,6 +102,9 @@ def parse_args(argv=None):
                         "there (WindowStager.stage_resident; with --clip_prefilter stage2.clip_stage_windows: the movie is uploaded once, not twice) instead of "
                         "gathering them on the host and uploading them per query; a video no longer than one window keeps the host route; off: every code path "
                         "is what it was")
+    p.add_argument("--clip_prefilter_frames", choices=("all", "sampled"), default="all",
+                   help="(--device_features --clip_prefilter) which frames of a window the CLIP pre-filter scores: all of them, or the --num_frames sampled "
+                        "ones the LLM is handed (stage2.clip_stage_windows_frames); all: every code path is what it was")
     p.add_argument("--device_features_mb", type=int, default=2048, help="budget of the resident feature cache in MiB (--device_features)")
     p.add_argument("--pool_rows", type=int, default=56, help="rows of a KV pool of the DecodeServer (--in_flight > 1)")
     p.add_argument("--max_new_tokens", type=int, default=64, help="decode steps per call at most (--in_flight > 1; answers are a dozen tokens)")
@@ -197,6 +200,18 @@ def _on_device(args, resident, ctx_l):
     return resident is not None and clip_length == int(clip_length) and ctx_l > clip_length
 
 
+def prefilter_frames_flag(args):
+    """The refusals of ``--clip_prefilter_frames`` -> "all" or "sampled"."""
+    frames = getattr(args, "clip_prefilter_frames", "all")
+    if frames not in ("all", "sampled"):
+        raise ValueError(f"--clip_prefilter_frames {frames}: all or sampled")
+    if frames == "sampled" and not (getattr(args, "device_features", False) and getattr(args, "clip_prefilter", False)):
+        raise ValueError("--clip_prefilter_frames sampled scores the frames that the device gather samples: pass --device_features and --clip_prefilter")
+    if frames == "sampled" and not 1 <= args.num_frames <= 1024:
+        raise ValueError(f"--clip_prefilter_frames sampled ranks a window's sampled frames from registers: --num_frames {args.num_frames} must be in [1, 1024]")
+    return frames
+
+
 def _stage_on_device(args, stager, resident, movie, features, query_cls, stage1, batch):
     """The three window branches of the loops with the movie resident on the device -> (grounding_windows, StagedWindows): the same lists and the same
     tensor as ``cut_windows`` + ``stage_windows`` give."""
@@ -206,8 +221,12 @@ def _stage_on_device(args, stager, resident, movie, features, query_cls, stage1,
     if stage1 is not None:
         grounding_windows = prefilter_windows(stage1["answer"], stage2.window_count(len(features), **geometry), batch, args.stride)
     elif getattr(args, "clip_prefilter", False) and query_cls is not None:
-        grounding_windows, windows = stage2.clip_stage_windows(features_dev, query_cls, batch=batch, num_frames=args.num_frames,
-                                                               dtype=getattr(stager, "op_dtype", None), **geometry)
+        if getattr(args, "clip_prefilter_frames", "all") == "sampled":
+            grounding_windows, windows = stage2.clip_stage_windows_frames(features_dev, query_cls, batch=batch, num_frames=args.num_frames,
+                                                                          dtype=getattr(stager, "op_dtype", None), score_frames="sampled", **geometry)
+        else:
+            grounding_windows, windows = stage2.clip_stage_windows(features_dev, query_cls, batch=batch, num_frames=args.num_frames,
+                                                                   dtype=getattr(stager, "op_dtype", None), **geometry)
         return grounding_windows, StagedWindows(windows, None)
     else:
         grounding_windows = list(range(stage2.window_count(len(features), **geometry)))
@@ -222,6 +241,7 @@ def eval(args, tokenizer=None, model=None):  # noqa: A001 - the reference's name
     os.makedirs(args.log_path, exist_ok=True)
     prediction_path = args.log_path + f"/predictions_streaming_{args.split}.txt"
     print("prediction_path: ", prediction_path)
+    prefilter_frames_flag(args)
     disable_torch_init()
     if model is None:
         from ..model.builder import load_pretrained_model

@@ -290,8 +290,27 @@ def select_windows_clipped(text, video, mask, *, win, keep, k=3, min_sep=1, gt=N
                            return_order)
 
 
-def _select_windows(who, call, text, video, mask, win, stride, keep, k, min_sep, gt, return_scores, return_bounds, return_order):
-    """``select_windows`` (``call``: ``ops.window_select`` at its stride) and ``select_windows_clipped`` (``ops.window_select_clipped``, stride 2): one body."""
+def select_windows_frames(text, video, mask, *, rule, win, stride=None, keep, frames="all", num_frames=None, valid=None, k=3, min_sep=1, gt=None,
+                          return_scores=False, return_bounds=False, return_order=False):
+    """``select_windows`` (``rule="shifted"``) / ``select_windows_clipped`` (``rule="clipped"``) with ``ops.window_select_frames`` behind the cosine
+    rows: the same inputs and checks, the keywords of that function - a window is scored on ``frames="all"`` of its frames or on the ``num_frames``
+    ``"sampled"`` ones the gather hands to the LLM, and on the frames ``valid`` [B, L] does not hide - and its ``ops.FrameWindowSelection`` (the
+    fields of ``ops.WindowSelection`` and ``n_candidates``).  No synchronisation and no device -> host copy when the inputs live on the device."""
+    who = "select_windows_frames"
+    ops.window_select_frames_keywords(who, rule, win, stride, keep, frames, num_frames, k, min_sep)
+    ops.window_select_valid(who, valid, mask)
+    stride = 2 if rule == "clipped" else stride
+
+    def call(sims, m, **kw):
+        v = None if valid is None else ops.h2d(valid, sims.device)
+        return ops.window_select_frames(sims, m, rule=rule, stride=stride, frames=frames, num_frames=num_frames, valid=v, **kw)
+    return _select_windows(who, call, text, video, mask, win, stride, keep, k, min_sep, gt, return_scores, return_bounds, return_order,
+                           result=ops.FrameWindowSelection)
+
+
+def _select_windows(who, call, text, video, mask, win, stride, keep, k, min_sep, gt, return_scores, return_bounds, return_order, result=None):
+    """``select_windows`` (``call``: ``ops.window_select`` at its stride), ``select_windows_clipped`` (``ops.window_select_clipped``, stride 2) and
+    ``select_windows_frames`` (``ops.window_select_frames``, ``result`` its namedtuple): one body."""
     for name, t in (("text", text), ("video", video), ("mask", mask)):
         if not torch.is_tensor(t):
             raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
@@ -317,7 +336,7 @@ def _select_windows(who, call, text, video, mask, win, stride, keep, k, min_sep,
     sims = (ops.frame_cosine_multi if multi else ops.frame_cosine)(ops.h2d(text, dev).float(), _features_up(video, dev))
     out = call(sims, ops.h2d(mask, dev), win=win, keep=keep, k=k, min_sep=min_sep, gt=None if gt is None else ops.h2d(gt, dev).float(),
                return_scores=return_scores, return_bounds=return_bounds, return_order=return_order)
-    return ops.WindowSelection(*(None if t is None else t.to(home) for t in out))
+    return (result or ops.WindowSelection)(*(None if t is None else t.to(home) for t in out))
 
 
 def _get_predicted_proposal_feat(src_vid_appear, src_vid_appear_mask, pred_proposal, text_cls_features):

@@ -211,6 +211,33 @@ def clip_stage_windows(features_dev, query_cls, *, debug_window=125, feature_fps
     return windows, frames[:len(windows)]
 
 
+def clip_stage_windows_frames(features_dev, query_cls, *, debug_window=125, feature_fps=5, keep, num_frames=250, dtype=None, k=3, min_sep=1,
+                              score_frames="sampled", valid=None):
+    """``clip_stage_windows`` with the windows scored on the frames the LLM is handed: ``score_frames="sampled"`` ranks a window by the ``num_frames``
+    frames the gather samples of it (the selection's F is the gather's ``num_frames``), ``"all"`` by its every frame as ``clip_stage_windows`` does;
+    ``valid`` [ctx_l] (bool, uint8 or float, host or device; None: every frame) hides frames from the scores, and a window without a usable frame is
+    not chosen.  The same three launches (``similarity.select_windows_frames`` under the clipped rule in the middle), the same result, and the gather
+    is still enqueued BEFORE the ``.tolist()`` of the ``select`` row, the one device -> host copy."""
+    who = "stage1.clip_stage_windows_frames"
+    from . import similarity
+    from .stage2 import _frames_keywords
+    clip_length = _clipped_geometry(who, features_dev, debug_window, feature_fps)
+    if not (isinstance(keep, numbers.Integral) and not isinstance(keep, bool) and keep >= 1):
+        raise ValueError(f"{who}: keep={keep!r} must be a positive integer")
+    query_cls = query_cls if torch.is_tensor(query_cls) else torch.from_numpy(np.ascontiguousarray(query_cls))
+    if query_cls.dim() != 1 or query_cls.shape[0] != features_dev.shape[1] or not query_cls.dtype.is_floating_point:
+        raise ValueError(f"{who}: features {tuple(features_dev.shape)} / query_cls {tuple(query_cls.shape)} {query_cls.dtype} (expected [ctx_l, d] and a floating-point [d])")
+    valid = _frames_keywords(who, score_frames, valid, features_dev)
+    dev, ctx_l = features_dev.device, features_dev.shape[0]
+    sel = similarity.select_windows_frames(ops.h2d(query_cls, dev)[None], features_dev[None], torch.ones(1, ctx_l, device=dev), rule="clipped", win=clip_length,
+                                           keep=keep, frames=score_frames, num_frames=num_frames if score_frames == "sampled" else None,
+                                           valid=None if valid is None else ops.h2d(valid, dev), k=k, min_sep=min_sep)
+    row = sel.select[0]
+    frames = ops.window_gather_clipped(features_dev, win=clip_length, num_frames=num_frames, select=row, out_dtype=dtype)
+    windows = [i for i in row.tolist() if i >= 0]                   # ascending, the -1 padding behind them: the first len(list) windows of frames
+    return windows, frames[:len(windows)]
+
+
 def gather_selected(features_dev, windows, *, debug_window=125, feature_fps=5, num_frames=250, dtype=None):
     """``gather_windows`` for a list of window indices that the host already has (``windows_from_retrieval``): -> [len(windows), num_frames, d], row j
     equal to ``gather_windows(...)[windows[j]]``.  The list is uploaded as the ``select`` row of the same launch; no synchronisation."""

@@ -145,6 +145,46 @@ def clip_stage_windows(features_dev, query_cls, *, debug_window=125, feature_fps
     return grounding_windows, frames[:len(grounding_windows)]
 
 
+def _frames_keywords(who, score_frames, valid, features_dev):
+    """The refusals of ``score_frames`` / ``valid`` of the ``clip_stage_windows_frames`` pair -> valid as a [1, ctx_l] tensor or None."""
+    if score_frames not in ("all", "sampled"):
+        raise ValueError(f"{who}: score_frames={score_frames!r} (expected 'all' or 'sampled')")
+    if valid is None:
+        return None
+    valid = valid if torch.is_tensor(valid) else torch.from_numpy(np.ascontiguousarray(valid))
+    if valid.shape != (features_dev.shape[0],) or not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
+        raise ValueError(f"{who}: valid {tuple(valid.shape)} {valid.dtype} (expected a bool, uint8 or floating-point [ctx_l] = [{features_dev.shape[0]}])")
+    return valid[None]
+
+
+def clip_stage_windows_frames(features_dev, query_cls, *, debug_window=125, feature_fps=5, stride=5, batch=100, num_frames=250, dtype=None, k=3, min_sep=1,
+                              score_frames="sampled", valid=None):
+    """``clip_stage_windows`` with the windows scored on the frames the LLM is handed: ``score_frames="sampled"`` ranks a window by the ``num_frames``
+    frames the gather samples of it - the selection's F IS the gather's ``num_frames``, so the score is the top-k over exactly the rows of the window
+    tensor, what ``window_cosine`` computes of them - ``"all"`` by its every frame as ``clip_stage_windows`` does; ``valid`` [ctx_l] (bool, uint8 or
+    float, host or device; None: every frame) hides frames from the scores, and a window without a usable frame is not chosen.  The same three
+    launches (``similarity.select_windows_frames`` in the middle), the same result, and the gather is still enqueued BEFORE the ``.tolist()`` of the
+    ``select`` row, the one device -> host copy."""
+    who = "clip_stage_windows_frames"
+    from . import similarity
+    clip_length = _whole_clip_length(who, debug_window, feature_fps)
+    if not (isinstance(batch, numbers.Integral) and not isinstance(batch, bool) and batch >= 1):
+        raise ValueError(f"{who}: batch={batch!r} must be a positive integer")
+    _resident_features(who, features_dev, clip_length)
+    query_cls = query_cls if torch.is_tensor(query_cls) else torch.from_numpy(np.ascontiguousarray(query_cls))
+    if query_cls.dim() != 1 or query_cls.shape[0] != features_dev.shape[1] or not query_cls.dtype.is_floating_point:
+        raise ValueError(f"{who}: features {tuple(features_dev.shape)} / query_cls {tuple(query_cls.shape)} {query_cls.dtype} (expected [ctx_l, d] and a floating-point [d])")
+    valid = _frames_keywords(who, score_frames, valid, features_dev)
+    dev, ctx_l = features_dev.device, features_dev.shape[0]
+    sel = similarity.select_windows_frames(ops.h2d(query_cls, dev)[None], features_dev[None], torch.ones(1, ctx_l, device=dev), rule="shifted", win=clip_length,
+                                           stride=stride, keep=batch, frames=score_frames, num_frames=num_frames if score_frames == "sampled" else None,
+                                           valid=None if valid is None else ops.h2d(valid, dev), k=k, min_sep=min_sep)
+    row = sel.select[0]
+    frames = ops.window_gather(features_dev, row, win=clip_length, stride=stride, num_frames=num_frames, out_dtype=dtype)
+    grounding_windows = [i for i in row.tolist() if i >= 0]         # ascending, the -1 padding behind them: the first len(list) windows of frames
+    return grounding_windows, frames[:len(grounding_windows)]
+
+
 def plan_groups(W, batch, zooms=(4, 2, 1)):
     """[(zoom, start, end)] in the order the reference visits them (e2e2.py:337-346); the last group of a level is
     shifted back so that it also holds ``batch // zoom`` windows."""

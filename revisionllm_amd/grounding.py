@@ -521,6 +521,86 @@ def window_select_clipped(sims, mask, *, win, keep, k=3, min_sep=1, gt=None, ret
     return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
 
 
+WINDOW_RULES = {"shifted": hip.RV_WINDOWS_SHIFTED, "clipped": hip.RV_WINDOWS_CLIPPED}
+WINDOW_FRAME_SETS = {"all": hip.RV_FRAMES_ALL, "sampled": hip.RV_FRAMES_SAMPLED}
+WINDOW_SELECT_MAX_SAMPLED = hip.RVC_MAX_SAMPLED
+FrameWindowSelection = collections.namedtuple("FrameWindowSelection", WindowSelection._fields + ("n_candidates",))
+
+
+def window_select_frames_keywords(who, rule, win, stride, keep, frames="all", num_frames=None, k=3, min_sep=1):
+    """The keyword refusals of ``window_select_frames`` that need no tensor (raised before any device is looked for) -> (rule code, win, stride, keep,
+    frame set code, F, k, min_sep) as ``rvc_window_select_frames`` takes them: the clipped rule has stride 2 (None is 2), the shifted rule needs one;
+    ``frames="sampled"`` needs ``num_frames`` in [1, 1024], ``frames="all"`` takes none."""
+    if not isinstance(rule, str) or rule not in WINDOW_RULES:
+        raise ValueError(f"{who}: rule={rule!r} (expected one of {sorted(WINDOW_RULES)})")
+    if not isinstance(frames, str) or frames not in WINDOW_FRAME_SETS:
+        raise ValueError(f"{who}: frames={frames!r} (expected one of {sorted(WINDOW_FRAME_SETS)})")
+    if rule == "clipped":
+        if stride is not None and not (_is_int(stride) and stride == 2):
+            raise ValueError(f"{who}: stride={stride!r} with rule='clipped' (its windows overlap by half: stride 2, or None)")
+        stride = 2
+    elif stride is None:
+        raise ValueError(f"{who}: rule='shifted' needs a stride")
+    win, stride, keep, k, min_sep = window_select_keywords(who, win, stride, keep, k, min_sep)
+    if frames == "sampled":
+        if not (_is_int(num_frames) and 1 <= num_frames <= WINDOW_SELECT_MAX_SAMPLED):
+            raise ValueError(f"{who}: num_frames={num_frames!r} sampled frames per window must be an integer in [1, {WINDOW_SELECT_MAX_SAMPLED}]")
+    elif num_frames is not None:
+        raise ValueError(f"{who}: num_frames={num_frames!r} with frames='all' (every frame of a window counts: no num_frames)")
+    return WINDOW_RULES[rule], win, stride, keep, WINDOW_FRAME_SETS[frames], int(num_frames or 0), k, min_sep
+
+
+def window_select_valid(who, valid, mask):
+    """The refusals of ``valid``: None, or a bool, uint8 or floating-point tensor of ``mask``'s shape."""
+    if valid is None:
+        return
+    if not torch.is_tensor(valid) or not torch.is_tensor(mask) or valid.shape != mask.shape:
+        raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of mask's shape "
+                         f"{tuple(mask.shape) if torch.is_tensor(mask) else '?'})")
+    if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
+        raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+
+
+def window_select_frames(sims, mask, *, rule, win, stride=None, keep, frames="all", num_frames=None, valid=None, k=3, min_sep=1, gt=None, return_scores=False,
+                         return_bounds=False, return_order=False):
+    """``window_select`` (``rule="shifted"``, with its ``stride``) and ``window_select_clipped`` (``rule="clipped"``) with a say in which frames of a
+    window count (``rvc_window_select_frames`` of the chain library): the same sims, mask and gt -> FrameWindowSelection(select, n_select, n_windows,
+    scores, bounds, order, hit_rank, n_candidates i32 [...]).  ``frames="all"`` scores a window on its every frame; ``frames="sampled"`` on the
+    ``num_frames`` frames ``window_gather`` / ``window_gather_clipped`` hand on for the same ``num_frames`` (at most 1024; a frame sampled twice counts
+    twice).  ``valid`` [mask's shape] (bool, uint8 or float; None: every frame) hides the frames where it is 0: their sims are never looked at, and the
+    duration stays the mask's.  A window's score is the sum of its ``min(k, usable)`` best usable entries; a window without a usable entry is no
+    candidate - NaN in ``scores``, its geometry in ``bounds``, absent from ``select`` and ``order`` - while ``n_windows`` still counts it;
+    ``n_select = min(keep, n_candidates)``.  With ``frames="all"`` and ``valid=None`` every field equals the other two functions' bit for bit.  One
+    launch (a mask or a valid that is not f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in
+    include/revision_hip_chain.h."""
+    who = "window_select_frames"
+    rule, win, stride, keep, frames, F, k, min_sep = window_select_frames_keywords(who, rule, win, stride, keep, frames, num_frames, k, min_sep)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    Wcap = window_select_capacity(who, L, win, stride, min_sep)
+    window_select_gt(who, gt, lead)
+    window_select_valid(who, valid, mask)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    keep = min(keep, Wcap)
+    dev = sims.device
+    select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
+    n_select = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_candidates = torch.empty(lead, dtype=torch.int32, device=dev)
+    scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
+    bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
+    order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
+    hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
+    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+    sims, mask = sims.contiguous(), mask.float().contiguous()
+    valid = valid.float().contiguous() if valid is not None else None
+    gt = gt.float().contiguous() if gt is not None else None
+    hip.chain_check(hip.chain_lib().rvc_window_select_frames(
+        hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), R, rpm, L, rule, win, stride, frames, F, k, keep, min_sep, Wcap, hip.ptr(gt), hip.ptr(select), hip.ptr(n_select),
+        hip.ptr(n_windows), hip.ptr(n_candidates), hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()), "rvc_window_select_frames")
+    return FrameWindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank, n_candidates)
+
+
 def proposal_slice(a, b, T):
     """(lo, hi) of ``range(T)[a : b + 1]`` for a >= 0 as ``rv_proposal_cosine`` cuts it: lo = min(a, T), hi = min(b + 1, T); hi <= lo is an empty slice."""
     return min(a, T), min(b + 1, T)

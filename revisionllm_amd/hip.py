@@ -237,6 +237,57 @@ def ext_check(rc, what):
         raise HipLibraryError(f"{what} failed (status {rc}): {ext_last_error()}")
 
 
+#: the chain library (include/revision_hip_chain.h): the grounding chain's entries added after the companion library was closed too; f32-only, ONE
+#: build for both operand flavours; every exported name starts with rvc_.  This table is open: a new chain entry gets a line here.
+#: REVISION_HIP_LIB_CHAIN: load another build of it.
+CHAIN_LIB_PATH = os.environ.get("REVISION_HIP_LIB_CHAIN") or os.path.join(_HERE, "librevision_hip_chain.so")
+RVC_ABI_VERSION = 1
+RV_FRAMES_ALL, RV_FRAMES_SAMPLED = 0, 1
+RVC_MAX_SAMPLED = 1024
+#: every symbol include/revision_hip_chain.h declares: name -> (restype, argtypes)
+CHAIN_SIGNATURES = {
+    "rvc_abi_version": (C.c_int, []),
+    "rvc_last_error": (C.c_int, [C.c_char_p, _sz]),
+    "rvc_window_select_frames": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p,
+                                           _p, _p]),
+}
+_chain = None
+
+
+def chain_lib():
+    """Load (once) and return the ctypes handle of the chain library; raises HipLibraryError when it is missing (there is no fallback)."""
+    global _chain
+    if _chain is None:
+        if not os.path.exists(CHAIN_LIB_PATH):
+            raise HipLibraryError(f"{CHAIN_LIB_PATH} not found: build it with `python -m revisionllm_amd.build` (hipcc, gfx950). "
+                                  "revisionllm_amd has no CPU fallback.")
+        try:
+            h = C.CDLL(CHAIN_LIB_PATH)
+        except OSError as e:
+            raise HipLibraryError(f"cannot load {CHAIN_LIB_PATH}: {e}") from e
+        for name, (res, args) in CHAIN_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = res, args
+        if h.rvc_abi_version() != RVC_ABI_VERSION:
+            raise HipLibraryError(f"{CHAIN_LIB_PATH} has rvc_abi_version() = {h.rvc_abi_version()} (expected {RVC_ABI_VERSION})")
+        _chain = h
+    return _chain
+
+
+def chain_last_error():
+    """The calling thread's last error message of the chain library ("" when it is not loaded)."""
+    if _chain is None:
+        return ""
+    buf = C.create_string_buffer(512)
+    _chain.rvc_last_error(buf, 512)
+    return buf.value.decode()
+
+
+def chain_check(rc, what):
+    if rc != 0:
+        raise HipLibraryError(f"{what} failed (status {rc}): {chain_last_error()}")
+
+
 def lib(f=None):
     """Load (once) and return the ctypes handle of a flavour's library (f: flavour name, torch dtype, tensor or None = the default
     flavour); raises HipLibraryError when the extension is missing."""

@@ -16,7 +16,8 @@ from .grounding import (HIT_IOU, SPAN_FORMS, SPAN_POOLINGS, SPAN_PROPOSE_LEVELS,
                         span_propose_keywords, span_propose_shapes, span_rank, span_rank_keywords, span_scores, span_scores_multi, topk_pool,
                         WINDOW_GATHER_MAX_FRAMES, window_gather, window_gather_dtypes, window_gather_keywords, window_select, window_select_capacity,
                         window_select_gt, window_select_keywords, clipped_window_count, clipped_window_void, proposal_cosine, proposal_slice,
-                        window_gather_clipped, clipped_window_solid, window_select_clipped)
+                        window_gather_clipped, clipped_window_solid, window_select_clipped, FrameWindowSelection, WINDOW_FRAME_SETS, WINDOW_RULES,
+                        WINDOW_SELECT_MAX_SAMPLED, window_select_frames, window_select_frames_keywords, window_select_valid)
 from .utils import hashinit
 
 
