@@ -599,7 +599,9 @@ int rv_llm_decode_rows_shared(rv_ctx* ctx, float* h, int32_t R, const int32_t* r
  * do_sample == 0), plus the entropy of the processed and of the raw distribution
  * (vtimellm_llama.py:312-338; funs_get_feature_X.py:131-132).  logits f32 [B,V].
  * out_topk_idx i32 / out_topk_val f32 [B,top_k_cap]: kept candidates in descending order (processed
- * scores), n_keep i32 [B].  top_k in [1, 64], or 0 = NO top-k filter (HF: `top_k` None / 0 - TopKLogitsWarper is not instantiated; what a
+ * scores), n_keep i32 [B].  top_k in [1, 64]: the list holds the min(top_k, V) largest scores (HF's min(top_k, V): a vocabulary shorter than top_k
+ * is kept whole), -1 / -inf beyond them; -0.0 and +0.0 are equal scores (ties: the smaller index first); the draw never lands on a candidate without
+ * mass (a -inf score inside the list).  Or 0 = NO top-k filter (HF: `top_k` None / 0 - TopKLogitsWarper is not instantiated; what a
  * checkpoint's generation_config.json may ask for: inference.py:45-59 passes no top_k, so the config's value rules): every token is a candidate,
  * only top-p trims; no candidate list is produced then (out_topk_* = -1 / -inf, n_keep = the number kept) and the kept set is
  * {processed score >= out_threshold[b]}.  top_k > 64 (wider than the list; >= V removes nothing) runs the same way: TopKLogitsWarper's rule - every score

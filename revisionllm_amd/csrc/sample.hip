@@ -190,8 +190,10 @@ __global__ __launch_bounds__(TPB) void sample_kernel(const float* __restrict__ l
 #endif
 
     const float inv_t = do_sample ? 1.0f / temperature : 1.0f;
+    // the product as ONE fma with +0.0 added: the same rounding as the multiplication, and a -0.0 product becomes +0.0 (-0 + +0 = +0) - the integer keys below
+    // then order exactly as f32 comparison does (as raw bits -0.0 would rank strictly under +0.0, while the reference compares them equal and lets the index decide)
 #pragma unroll
-    for (int j = 0; j < ITEMS; ++j) v[j] = tid + j * TPB < V ? v[j] * inv_t : -INFINITY;
+    for (int j = 0; j < ITEMS; ++j) v[j] = tid + j * TPB < V ? __fmaf_rn(v[j], inv_t, 0.0f) : -INFINITY;
     if (do_sample && (top_k == 0 || top_k > KCAP)) {
         // ---- top_k = 0: HF's "filter disabled" (TopKLogitsWarper is not instantiated) - every token is a candidate, only top-p trims.  No list of
         // candidates can hold V entries, so nothing is sorted: the two places where the reference's order matters (the ascending cumulative
@@ -280,8 +282,9 @@ __global__ __launch_bounds__(TPB) void sample_kernel(const float* __restrict__ l
             at_or_above = block_sum(at_or_above, sh);
             if (at_or_above > u) pick = c2;
         }
-        // `pick` is an existing kept key (the sum above is a step function of the key) unless rounding left no key with a sum above u: then the
-        // LAST kept token (the smallest kept key) is taken, as the oracle's clamp does.  Ties share a key: the reference orders them by index -
+        // `pick` is an existing kept key (the sum above is a step function of the key) unless no key has a sum above u (for u < 1 the sum at the smallest key
+        // with mass IS z2 > u * z2, so only a uniform of 1 gets here): then the LAST kept token WITH MASS (the smallest kept key whose ex > 0, never a
+        // masked -inf score) is taken, as the oracle's clamp does.  Ties share a key: the reference orders them by index -
         // the n-th of them with n = how many whole tied probabilities fit between the sum above the tie and u
         float above = 0.f, tie_e = 0.f, ties = 0.f;
 #pragma unroll
@@ -291,7 +294,7 @@ __global__ __launch_bounds__(TPB) void sample_kernel(const float* __restrict__ l
             unsigned lowest = 0xffffffffu;
 #pragma unroll
             for (int j = 0; j < ITEMS; ++j)
-                if (tid + j * TPB < V && key[j] >= cut) lowest = key[j] < lowest ? key[j] : lowest;
+                if (tid + j * TPB < V && key[j] >= cut && ex[j] > 0.f) lowest = key[j] < lowest ? key[j] : lowest;   // (the largest key has ex = 1)
             pick = ~block_max_u32(~lowest, shu);
             ties = 0.f;
 #pragma unroll
@@ -335,7 +338,9 @@ __global__ __launch_bounds__(TPB) void sample_kernel(const float* __restrict__ l
         }
         return;
     }
-    const int K = do_sample ? top_k : 1;
+    // HF's min(top_k, V): a vocabulary shorter than top_k has V candidates (the padding keys below must never be selected: the K-th largest key has
+    // to be a real one); the outputs beyond K are -1 / -inf
+    const int K = do_sample ? (top_k < V ? top_k : V) : 1;
     // ---- top-K selection: radix select on order-preserving integer keys (2 bits per round, pure register counting +
     // one block reduction per round), then the <= K survivors are rank-sorted by (score desc, index asc).
     __shared__ int cnt_sh[16][4];
@@ -583,11 +588,15 @@ __global__ __launch_bounds__(TPB) void sample_kernel(const float* __restrict__ l
     }
     __syncthreads();
     const int keep = keep_sh;
+    float p_own = 0.f;
     if (tid < keep) {
-        const float p = e[tid] / z2_sh;
-        pr[tid] = p;
-        lg[tid] = logf(p + 1e-10f);
+        p_own = e[tid] / z2_sh;
+        pr[tid] = p_own;
+        lg[tid] = logf(p_own + 1e-10f);
     }
+    // the last candidate with mass (keep <= 64: all of them sit in wave 0, which thread 0 belongs to; candidate 0 has e = 1, so the ballot is never empty)
+    int last = 0;
+    if (wave == 0) last = 63 - __clzll((long long)__ballot(p_own > 0.f));
     __syncthreads();
     if (tid == 0) {
         float hp = 0.f, cum = 0.f;
@@ -599,7 +608,9 @@ __global__ __launch_bounds__(TPB) void sample_kernel(const float* __restrict__ l
             cum += p;
             if (cum <= u) pos = i + 1;
         }
-        pos = pos < keep - 1 ? pos : keep - 1;
+        // rounding may leave no candidate whose sum exceeds u: the last one WITH MASS is taken, as the oracle's clamp does - never a masked (-inf) or
+        // underflowed candidate behind it
+        pos = pos < last ? pos : last;
         out_tok[b] = topi[pos];
         out_hp[b] = -hp;
         out_nkeep[b] = keep;
