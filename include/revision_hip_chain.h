@@ -84,6 +84,55 @@ int rvc_window_select_frames(const float* sims, const float* mask, const float* 
                              int32_t* select, int32_t* n_select, int32_t* n_windows, int32_t* n_candidates, float* win_scores, int32_t* bounds,
                              int32_t* order, int32_t* hit_rank, void* stream);
 
+/* ---- span scores over the usable frames: rv_span_scores / rv_span_scores_multi (revision_hip.h) with a say in WHICH frames of a window count.  One
+ * kernel source with those two (csrc/span_scores.h), further instances ----
+ * sims f32 [rows,L], spans f32 [rows,N,2] as (centre, width), mask f32 [rows / rpm, L] (rpm = "rows per mask": 1 is rv_span_scores' layout, Q is
+ * rv_span_scores_multi's with rows = B Q), valid f32 [rows / rpm, L] or NULL ->
+ *   scores    f32 [rows,N]
+ *   windows   i32 [rows,N,2]   (optional) (lo, hi) of every span; (-1, -1) for a non-finite one
+ *   n_usable  i32 [rows,N]     (optional) n, the usable frames of the window; 0 for an empty or a non-finite span
+ * Duration, window rule and `windows`: rv_span_scores', operation for operation - the raw f32 sum of the mask row, x = c -+ 0.5 w and p = x * duration
+ * with each operation rounded on its own, start = max(0, int(floor(p1))), end = int(ceil(p2)), Python's range(L)[start:end] over the ARRAY length L
+ * with a negative end included; a non-finite p gives the score NaN and the window (-1, -1).  `valid` never changes the duration.
+ * USABLE: frame t of row r is usable when valid == NULL || valid[(r / rpm) * L + t] != 0 (the f32 comparison: -0 hides a frame, a NaN in valid does
+ * not - it compares unequal to 0) and, with skip_nan = 1, sims[r * L + t] == sims[r * L + t] as well (its similarity is a number).  A hidden frame's
+ * similarity never enters any arithmetic: NaN and infinities under it leave no trace.  valid is read only where sims is read: inside [lo, hi).
+ * mode 0 (top-k): with n usable frames in [lo, hi), the sum of the first min(k, n) of them in the frame order - NaN first, then the larger value, then
+ * the smaller index - accumulated from +0 in that order, each add rounded.  mode 1 (attention): sum_t softmax_t(s / temperature) s_t over the usable
+ * frames only; a hidden frame contributes neither to the maximum nor to either sum (it is skipped, not multiplied by 0).  An empty window (hi <= lo)
+ * scores 0; a window with hi > lo and n = 0 scores NaN (0x7fc00000).
+ * Identity: with valid = NULL and skip_nan = 0 every output equals rv_span_scores' (rpm = 1) / rv_span_scores_multi's (rpm = Q) bit for bit, in
+ * both modes.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null sims / spans / mask / scores; rows, L or N below 1; rpm < 1; rows not a
+ * multiple of rpm; rows > 65535; mode outside {0, 1}; skip_nan outside {0, 1}; mode 0 with k outside [1, 64]; mode 1 with a temperature that is 0 or
+ * not finite.
+ * One wave per span, four spans per 256-thread workgroup, the row on the grid's y dimension; 16 B of LDS; vector stores only, no global atomics, no
+ * scratch. */
+int rvc_span_scores_masked(const float* sims, const float* spans, const float* mask, const float* valid, int32_t rows, int32_t rpm, int32_t L, int32_t N,
+                           int32_t mode, int32_t k, float temperature, int32_t skip_nan, float* scores, int32_t* windows, int32_t* n_usable,
+                           void* stream);
+
+/* ---- span proposals from the usable frames: rv_span_propose (revision_hip.h) under the same validity.  One kernel source with it
+ * (csrc/span_propose.h), a further instance ----
+ * The arguments and outputs of rv_span_propose, with valid f32 [R / rpm, L] or NULL behind mask and skip_nan behind N.  USABLE is defined as above,
+ * for the frames [0, D) of the duration, which the mask alone gives.  The rule is rv_span_propose's with three changes, and nothing else moves:
+ *   (a) smoothing: for a usable t, s'[t] is the sum of the usable frames of [t - h, t + h] n [0, D), h = smooth / 2, taken in ascending order starting
+ *       from the first usable one, each add rounded, divided by their count as f32; for a hidden t, s'[t] is NaN (0x7fc00000).
+ *   (b) range: the row's largest and smallest s' are taken over the non-NaN s' as before, so the hidden frames drop out by (a).
+ *   (c) detection: a hidden frame is never above; it breaks a run unless `gap` closes it; a run's length hi - lo counts the hidden frames inside it.
+ * A row with no usable frame gives 0 spans and n_found 0.  `smoothed` holds NaN at the hidden frames.  Unchanged: the span encoding, the order
+ * (highest level first, ascending lo), the duplicate rule, the padding, the counts.
+ * Identities: valid = NULL with skip_nan = 0 is rv_span_propose bit for bit.  valid of ones is valid = NULL.  At smooth = 1 the call equals
+ * rv_span_propose on sims with NaN (0x7fc00000) written over the hidden frames, in every output.  At smooth = 1 skip_nan alone changes nothing (a NaN
+ * similarity is its own s' there; its bits in `smoothed` become 0x7fc00000 whatever NaN it was).
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: everything rv_span_propose refuses (a null sims / mask / levels / spans / n_spans
+ * among it) and skip_nan outside {0, 1}.
+ * One 256-thread workgroup per row, three walks over the row's 256-frame tiles; 2928 B of LDS whatever L (the parent's 2608 and one byte per staged
+ * frame); vector stores only, no global atomics, no scratch. */
+int rvc_span_propose_masked(const float* sims, const float* mask, const float* valid, int32_t R, int32_t rpm, int32_t L, const float* levels, int32_t T,
+                            int32_t relative, int32_t smooth, int32_t gap, int32_t min_len, int32_t max_len, int32_t N, int32_t skip_nan, float* spans,
+                            int32_t* n_spans, int32_t* n_found, int32_t* windows, float* smoothed, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -19,13 +19,13 @@ LIB = os.path.join(HERE, FLAVOURS["f16"][0])
 def lib_path(flavour):
     return os.path.join(HERE, FLAVOURS[flavour][0])
 SOURCES = ["error.hip", "init.hip", "gemm.hip", "gemm_pp.hip", "gemm_arows.hip", "gemm_rows.hip", "gemm_rows_p1.hip", "gemm_rows_p2.hip", "gemm_rows_p3.hip", "rowops.hip", "attention.hip", "sample.hip", "similarity.hip", "rank.hip", "propose.hip", "prefilter.hip", "gather.hip", "frames.hip", "frames_yuv.hip", "engine.hip"]
-HEADERS = ["exports.map", "common.h", "kernels.h", "gemv_finish.h", "frames_common.h", "grounding.h", "window_select.h", "gemm_rows.hip", os.path.join("..", "..", "include", "revision_hip.h")]
+HEADERS = ["exports.map", "common.h", "kernels.h", "gemv_finish.h", "frames_common.h", "grounding.h", "window_select.h", "span_scores.h", "span_propose.h", "gemm_rows.hip", os.path.join("..", "..", "include", "revision_hip.h")]
 EXT_LIB = os.path.join(HERE, "librevision_hip_ext.so")
 EXT_SOURCES = ["prefilter_ext.hip"]          # compiled once (in the f16 object directory: nothing in them depends on the flavour)
 EXT_SHARED = ["error.hip"]                   # objects of the f16 build linked in as well, their rv_* names local
 EXT_HEADERS = ["exports_ext.map", os.path.join("..", "..", "include", "revision_hip_ext.h")]
 CHAIN_LIB = os.path.join(HERE, "librevision_hip_chain.so")
-CHAIN_SOURCES = ["prefilter_chain.hip"]      # compiled once, as the companion's
+CHAIN_SOURCES = ["prefilter_chain.hip", "spans_chain.hip"]      # compiled once, as the companion's
 CHAIN_HEADERS = ["exports_chain.map", os.path.join("..", "..", "include", "revision_hip_chain.h")]
 #: the f32-only libraries: (path, own sources, headers beyond HEADERS, version script); each links EXT_SHARED's objects with their rv_* names local
 COMPANIONS = [(EXT_LIB, EXT_SOURCES, EXT_HEADERS, "exports_ext.map"), (CHAIN_LIB, CHAIN_SOURCES, CHAIN_HEADERS, "exports_chain.map")]

@@ -6,7 +6,7 @@
 //   rv_span_scores_multi    the same kernel over [B,Q] rows of similarities and proposals that share their video's mask row
 //   rv_attn_pool            _attention_pooling (eval/similarity.py:96-113)
 // (rv_topk_pool, the other pooling, stands with rv_topk_cosine in sample.hip.)  The stages behind the scores are rank.hip, propose.hip, prefilter.hip.
-#include "grounding.h"
+#include "span_scores.h"
 
 namespace {
 
@@ -95,96 +95,7 @@ __global__ __launch_bounds__(FC_TPB) void frame_cosine_kernel(const T* __restric
     }
 }
 
-// f32 -> int32 as torch's .to(torch.int32) gives it for the values the reference meets; outside int32's range (undefined there) the value saturates
-__device__ __forceinline__ int sat_i32(float v) {
-    return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
-}
-
-// One wave per span (4 spans per block, all of row blockIdx.y).  A row is a video (rpm = 1, rv_span_scores) or one of a video's rpm queries
-// (rv_span_scores_multi): similarities, spans and outputs are indexed by the row, the mask - and hence the duration - by row / rpm ("rows per mask").
-// The block adds the row's mask row up first (duration; 0 / 1 masks: exact in any
-// order up to 2^24 frames; every block of a video repeats that sum - N / 4 reads of an L2-resident row of 4 L bytes - which is the price of keeping the
-// matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row:
-//   x1 = c - 0.5 w, x2 = c + 0.5 w, p = x * duration (every operation rounded to f32 on its own: no contraction), start = max(0, int(floor(p1))),
-//   end = int(ceil(p2)), and Python's range(L)[start:end] over the ARRAY length L: lo = min(start, L), hi = end < 0 ? max(end + L, 0) : min(end, L).
-// Every read of sims lies in [b L + lo, b L + hi).  MODE 0: the sum of the min(k, hi - lo) first entries in rank order (NaN, larger value, smaller
-// index: k wave-wide rank rounds over a lane-strided window, no LDS); MODE 1: sum_t softmax_t(s / tau) s_t in two lane-strided passes - the maximum, then both sums - (a NaN in
-// the window is carried next to the running maximum, which fmaxf would drop).  An empty window scores 0; a non-finite p1 / p2 gives NaN and the
-// window (-1, -1).
-template <int MODE>
-__global__ __launch_bounds__(256) void span_scores_kernel(const float* __restrict__ sims, const float* __restrict__ spans, const float* __restrict__ mask,
-                                                          int rpm, int L, int N, int k, float tau, float* __restrict__ scores,
-                                                          int32_t* __restrict__ windows) {
-    __shared__ float red[4];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {   // not block_mask_sum(): the contract here is the raw f32 sum with the wave partials added pairwise - other bits on a mask that is not 0 / 1
-        const float* m = mask + (int64_t)(b / rpm) * L;
-        float s = 0.f;
-        for (int l = tid; l < L; l += 256) s += m[l];
-        s = wave_sum(s);
-        if (lane == 0) red[wave] = s;
-    }
-    __syncthreads();
-    const float duration = (red[0] + red[1]) + (red[2] + red[3]);
-    const int n = blockIdx.x * 4 + wave;
-    if (n >= N) return;
-    const int64_t sp = (int64_t)b * N + n;
-    const float c = spans[sp * 2], w = spans[sp * 2 + 1];
-    const float hw = __fmul_rn(0.5f, w);
-    const float p1 = __fmul_rn(__fsub_rn(c, hw), duration), p2 = __fmul_rn(__fadd_rn(c, hw), duration);
-    if (!(fabsf(p1) < INFINITY) || !(fabsf(p2) < INFINITY)) {      // NaN or +-inf
-        if (lane == 0) {
-            scores[sp] = qnan();
-            if (windows) windows[sp * 2] = windows[sp * 2 + 1] = -1;
-        }
-        return;
-    }
-    int start = sat_i32(floorf(p1));
-    start = start < 0 ? 0 : start;
-    const int end = sat_i32(ceilf(p2));
-    const int lo = start < L ? start : L;
-    int hi;
-    if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
-    else hi = end < L ? end : L;
-    if (lane == 0 && windows) {
-        windows[sp * 2] = lo;
-        windows[sp * 2 + 1] = hi;
-    }
-    const float* s = sims + (int64_t)b * L;
-    float acc = 0.f;
-    if (hi > lo) {
-        if constexpr (MODE == 0) {
-            ArgMax prev = rank_start();
-            const int rounds = k < hi - lo ? k : hi - lo;
-            for (int r = 0; r < rounds; ++r) {
-                ArgMax best = rank_none();
-                for (int t = lo + lane; t < hi; t += 64) best = rank_next(best, prev, ArgMax{s[t], t});
-                best = wave_rank_first(best);
-                acc += best.v;
-                prev = best;
-            }
-        } else {
-            float mx = -INFINITY;
-            bool nan = false;
-            for (int t = lo + lane; t < hi; t += 64) {
-                const float x = s[t] / tau;
-                nan |= x != x;
-                mx = fmaxf(mx, x);
-            }
-            mx = wave_max(mx);
-            if (__ballot(nan) != 0ull) mx = qnan();
-            float z = 0.f, zs = 0.f;
-            for (int t = lo + lane; t < hi; t += 64) {
-                const float v = s[t];
-                const float e = expf(v / tau - mx);
-                z += e;
-                zs += e * v;
-            }
-            acc = wave_sum(zs) / wave_sum(z);
-        }
-    }
-    if (lane == 0) scores[sp] = acc;
-}
+// (span_scores_kernel and the window rule: span_scores.h, one source with the chain library's masked instances)
 
 // _attention_pooling (similarity.py:96-113) for one (video, text) pair per block, laid out as topk_pool_kernel: x[t] = <f_t, q> / tau to LDS (one wave per
 // frame), the softmax over the frames with the maximum subtracted (a NaN x is carried into the maximum: the whole row is NaN then, as torch.softmax's
@@ -445,10 +356,10 @@ static int launch_span_scores(const char* who, const float* sims, const float* s
     const dim3 grid((unsigned)cdiv(N, 4), (unsigned)rows);
     if (mode == 0) {
         RV_CHECK_ARG(k >= 1 && k <= TOPK_FRAMES_MAX, "%s: k=%d must be in [1, %d]", who, k, TOPK_FRAMES_MAX);
-        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, rpm, L, N, k, 1.0f, scores, windows);
+        hipLaunchKernelGGL(span_scores_kernel<0>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, rpm, L, N, k, 1.0f, scores, windows, SpanMasking<false>{});
     } else {
         RV_CHECK_ARG(temperature != 0.f && fabsf(temperature) < INFINITY, "%s: temperature must be finite and not 0", who);
-        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, rpm, L, N, k, temperature, scores, windows);
+        hipLaunchKernelGGL(span_scores_kernel<1>, grid, dim3(256), 0, as_stream(stream), sims, spans, mask, rpm, L, N, k, temperature, scores, windows, SpanMasking<false>{});
     }
     RV_CHECK_LAUNCH(who);
     return RV_OK;

@@ -10,7 +10,10 @@ device -> host copies of the window bounds).  A proposal's score is the sum of t
 per-frame cosine row and one more launch scores every span on that row; durations and windows never leave the device.  Keywords after ``is_groundtruth``
 are this build's: ``k`` (the reference's 3), ``pooling`` ("topk", or "attention" = the alternative commented out at similarity.py:63 with ``temperature``),
 ``return_windows``.  Not taken: the reference's bf16 arithmetic (16-bit features are read as stored, all arithmetic is f32), per-frame
-masking (as in the reference the mask only gives each video's duration).
+masking (as in the reference the mask only gives each video's duration).  Per-frame masking is taken under new names only:
+``forward_clip_matching_masked``, ``propose_spans_masked`` and ``ground_queries_masked`` accept the ``valid`` rows of ``select_windows_frames`` and /
+or skip the NaN cosines of zeroed feature rows (``skip_nan``) - ``rvc_span_scores_masked`` and ``rvc_span_propose_masked`` of the chain library behind
+the unchanged cosine kernels, the same number of launches, no synchronisation.
 
 Several texts per video (this build's addition, no counterpart in the reference): ``forward_clip_matching_multi`` scores Q queries, each with its own
 proposals, against one pass over their video's features (``rv_frame_cosine_multi`` on the f32-input MFMA + ``rv_span_scores_multi``).
@@ -93,7 +96,8 @@ def _attention_pooling(text_embeds, video_embeds, temperature):
     return ops.attn_pool(text, video, temperature).to(device=home, dtype=dt if dt.is_floating_point else torch.float32)
 
 
-def _match(who, text, video, mask, proposal, k, pooling, temperature, return_windows, multi=False):
+def _match_checks(who, text, video, mask, proposal, k, pooling, temperature, multi):
+    """The refusals of the matching calls, raised before any device is looked for."""
     if proposal is None:
         raise TypeError(f"{who}: proposal is None (the reference fails there too: it has no default proposals)")
     for name, t in (("text", text), ("video", video), ("mask", mask), ("proposal", proposal)):
@@ -126,6 +130,10 @@ def _match(who, text, video, mask, proposal, k, pooling, temperature, return_win
         raise ValueError(f"{who}: k={k!r} must be an integer in [1, 64]")
     if pooling == "attention" and (float(temperature) == 0.0 or not math.isfinite(float(temperature))):
         raise ValueError(f"{who}: temperature={temperature} must be finite and not 0")
+
+
+def _match(who, text, video, mask, proposal, k, pooling, temperature, return_windows, multi=False):
+    _match_checks(who, text, video, mask, proposal, k, pooling, temperature, multi)
     home, dt = video.device, video.dtype
     dev = _device_of(video, who)
     video = _features_up(video, dev)
@@ -220,7 +228,12 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     places that hold a proposal (``rank.n_keep`` also counts padding spans, which rank last); ``proposals`` and ``rank`` are the ``SpanProposals`` and
     ``SpanRank`` they came from.  ``top`` above ``max_spans`` is ``max_spans``.  No synchronisation and no device -> host copy when the inputs live on
     the device; host tensors are staged and every result comes back on the device ``video`` lives on."""
-    who = "ground_queries"
+    return _ground("ground_queries", text, video, mask, None, False, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords)
+
+
+def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False):
+    """``ground_queries`` and ``ground_queries_masked`` (``masked``: the proposal and the score stage are the chain library's, under ``valid`` and
+    ``skip_nan``): one body."""
     for name, t in (("text", text), ("video", video), ("mask", mask)) + ((("gt", gt),) if gt is not None else ()):
         if not torch.is_tensor(t):
             raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
@@ -251,14 +264,22 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     if unknown:
         raise TypeError(f"{who}: unexpected keyword(s) {sorted(unknown)}")
     ops.span_propose_keywords(who, **{n: v for n, v in propose_keywords.items() if not n.startswith("return_")})
+    if masked:
+        ops.window_select_valid(who, valid, mask)
+        ops.skip_nan_flag(who, skip_nan)
     home = video.device
     dev = _device_of(video, who)
     video = _features_up(video, dev)
     mask = ops.h2d(mask, dev).float()
     cosine, score = (ops.frame_cosine_multi, ops.span_scores_multi) if multi else (ops.frame_cosine, ops.span_scores)
     sims = cosine(ops.h2d(text, dev).float(), video)
-    proposals = ops.span_propose(sims, mask, **propose_keywords)
-    scores = score(sims, proposals.spans, mask, k=k, pooling=pooling, temperature=temperature)
+    if masked:
+        valid = None if valid is None else ops.h2d(valid, dev)
+        proposals = ops.span_propose_masked(sims, mask, valid=valid, skip_nan=skip_nan, **propose_keywords)
+        scores = ops.span_scores_masked(sims, proposals.spans, mask, valid=valid, skip_nan=skip_nan, k=k, pooling=pooling, temperature=temperature).scores
+    else:
+        proposals = ops.span_propose(sims, mask, **propose_keywords)
+        scores = score(sims, proposals.spans, mask, k=k, pooling=pooling, temperature=temperature)
     rank = ops.span_rank(scores, proposals.spans, top=top, nms_iou=nms_iou, form="cxw", gt=None if gt is None else ops.h2d(gt, dev).float(), hit_iou=hit_iou)
     held = (rank.keep >= 0) & (rank.keep < proposals.n_spans.unsqueeze(-1))                 # kept places that hold a proposal: a prefix (NaN ranks last)
     at = rank.keep.clamp(min=0).long()
@@ -267,6 +288,63 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     kept_scores = torch.where(held, torch.gather(scores, -1, at), nan)
     back = lambda tup: type(tup)(*(None if t is None else t.to(home) for t in tup))                 # noqa: E731
     return Grounding(spans.to(home), kept_scores.to(home), held.sum(-1, dtype=torch.int32).to(home), back(proposals), back(rank))
+
+
+def forward_clip_matching_masked(src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, *, valid=None, skip_nan=False, k=3, pooling="topk",
+                                 temperature=0.01, return_windows=False, return_usable=False):
+    """``forward_clip_matching`` (src_cls_txt [B, d], proposal [B, N, 2]) / ``forward_clip_matching_multi`` (src_cls_txt [B, Q, d], proposal
+    [B, Q, N, 2]) over the frames that count -> ``ops.MaskedSpanScores(scores, windows, n_usable)``: the scores [B, N] / [B, Q, N] in the float dtype
+    of the video features, with ``return_windows`` the i32 windows and with ``return_usable`` the i32 count of usable frames of every window (None
+    unless asked for).  ``valid`` [B, L] (bool, uint8 or float; None: every frame) hides the frames where it is 0 and ``skip_nan`` the frames whose
+    cosine is NaN (a zeroed feature row); the duration and the windows stay the mask's.  A non-empty window without a usable frame scores NaN.  The
+    cosine rows come from the unchanged ``ops.frame_cosine[_multi]``, the scores from ``ops.span_scores_masked``: the launches, the device handling,
+    the refusals and the absence of any synchronisation are the unmasked calls'."""
+    who = "forward_clip_matching_masked"
+    multi = torch.is_tensor(src_cls_txt) and src_cls_txt.dim() == 3
+    if pooling == "topk" and isinstance(k, bool):
+        raise ValueError(f"{who}: k={k!r} must be an integer in [1, 64]")
+    if pooling == "attention" and (isinstance(temperature, bool) or not isinstance(temperature, (int, float))):
+        raise ValueError(f"{who}: temperature={temperature!r} must be a number")
+    _match_checks(who, src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, k, pooling, temperature, multi)
+    ops.window_select_valid(who, valid, src_vid_appear_mask)
+    ops.skip_nan_flag(who, skip_nan)
+    home, dt = src_vid_appear.device, src_vid_appear.dtype
+    dev = _device_of(src_vid_appear, who)
+    video = _features_up(src_vid_appear, dev)
+    sims = (ops.frame_cosine_multi if multi else ops.frame_cosine)(ops.h2d(src_cls_txt, dev).float(), video)
+    out = ops.span_scores_masked(sims, ops.h2d(proposal, dev).float(), ops.h2d(src_vid_appear_mask, dev).float(),
+                                 valid=None if valid is None else ops.h2d(valid, dev), skip_nan=skip_nan, k=k, pooling=pooling, temperature=temperature,
+                                 return_windows=return_windows, return_usable=return_usable)
+    return ops.MaskedSpanScores(out.scores.to(device=home, dtype=dt), *(None if t is None else t.to(home) for t in out[1:]))
+
+
+def propose_spans_masked(sims, mask, *, valid=None, skip_nan=False, levels=ops.SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1,
+                         max_len=None, max_spans=256, return_windows=False, return_smoothed=False):
+    """``propose_spans`` from the frames that count (``ops.span_propose_masked``): the same sims, mask, keywords, device handling and
+    ``ops.SpanProposals``, with ``valid`` [mask's shape] hiding the frames where it is 0 and ``skip_nan`` the frames whose cosine is NaN.  One launch,
+    no synchronisation and no device -> host copy when the inputs live on the device."""
+    who = "propose_spans_masked"
+    ops.span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    ops.span_propose_shapes(who, sims, mask)
+    ops.window_select_valid(who, valid, mask)
+    ops.skip_nan_flag(who, skip_nan)
+    home = sims.device
+    dev = _device_of(sims, who)
+    out = ops.span_propose_masked(ops.h2d(sims, dev).float(), ops.h2d(mask, dev), valid=None if valid is None else ops.h2d(valid, dev), skip_nan=skip_nan,
+                                  levels=levels, relative=relative, smooth=smooth, gap=gap, min_len=min_len, max_len=max_len, max_spans=max_spans,
+                                  return_windows=return_windows, return_smoothed=return_smoothed)
+    return ops.SpanProposals(*(None if t is None else t.to(home) for t in out))
+
+
+def ground_queries_masked(text, video, mask, *, valid=None, skip_nan=False, top=10, nms_iou=0.5, k=3, pooling="topk", temperature=0.01, gt=None,
+                          hit_iou=ops.HIT_IOU, **propose_keywords):
+    """``ground_queries`` over the frames that count: the same inputs, keywords and ``Grounding``, with ``valid`` [B, L] (bool, uint8 or float; None:
+    every frame) hiding the frames where it is 0 and ``skip_nan`` the frames whose cosine is NaN - black frames, padding inside a movie, decoder
+    drop-outs, whose zeroed feature rows would otherwise turn every proposal around them into a NaN score that ranks last.  The four stages are
+    ``ops.frame_cosine[_multi]`` (unchanged), ``ops.span_propose_masked``, ``ops.span_scores_masked`` and ``ops.span_rank`` (unchanged: a NaN score
+    already ranks last): as many launches as ``ground_queries``, no synchronisation and no device -> host copy when the inputs live on the device."""
+    return _ground("ground_queries_masked", text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords,
+                   masked=True)
 
 
 def select_windows(text, video, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):

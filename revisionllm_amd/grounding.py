@@ -601,6 +601,109 @@ def window_select_frames(sims, mask, *, rule, win, stride=None, keep, frames="al
     return FrameWindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank, n_candidates)
 
 
+MaskedSpanScores = collections.namedtuple("MaskedSpanScores", "scores windows n_usable")
+
+
+def skip_nan_flag(who, skip_nan):
+    """The refusal of ``skip_nan`` (raised before any device is looked for) -> 0 / 1."""
+    if not (isinstance(skip_nan, (bool, numbers.Integral)) and skip_nan in (0, 1)):
+        raise ValueError(f"{who}: skip_nan={skip_nan!r} must be True or False")
+    return int(bool(skip_nan))
+
+
+def span_scores_masked_checks(who, sims, spans, mask, valid=None, skip_nan=False, k=3, pooling="topk", temperature=0.01):
+    """The refusals of ``span_scores_masked`` (raised before any device is looked for) -> (leading shape, rows, rows per mask row, L, N, mode, k,
+    temperature, skip_nan) as ``rvc_span_scores_masked`` takes them."""
+    if pooling not in SPAN_POOLINGS:
+        raise ValueError(f"{who}: pooling={pooling!r} (expected one of {sorted(SPAN_POOLINGS)})")
+    skip_nan = skip_nan_flag(who, skip_nan)
+    if not torch.is_tensor(sims) or not torch.is_tensor(spans) or not torch.is_tensor(mask):
+        raise ValueError(f"{who}: sims, spans and mask must be tensors")
+    if (sims.dim() not in (2, 3) or spans.dim() != sims.dim() + 1 or spans.shape[:-2] != sims.shape[:-1] or spans.shape[-1] != 2
+            or mask.shape != (sims.shape[0], sims.shape[-1])):
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / spans {tuple(spans.shape)} / mask {tuple(mask.shape)} (expected [R, L], [R, N, 2] and [R, L], "
+                         f"or [B, Q, L], [B, Q, N, 2] and [B, L])")
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    if not spans.dtype.is_floating_point:
+        raise ValueError(f"{who}: spans must be a floating-point tensor (got {spans.dtype})")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    window_select_valid(who, valid, mask)
+    lead, L, N = tuple(sims.shape[:-1]), sims.shape[-1], spans.shape[-2]
+    rows = math.prod(lead)
+    if min(rows, L) < 1:
+        raise ValueError(f"{who}: empty sims {tuple(sims.shape)}")
+    if rows > 65535:
+        raise ValueError(f"{who}: {rows} rows (at most 65535 per call)")
+    if pooling == "topk" and not (_is_int(k) and 1 <= k <= 64):
+        raise ValueError(f"{who}: k={k!r} must be an integer in [1, 64]")
+    try:
+        temperature = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: temperature={temperature!r} must be a number") from None
+    if pooling == "attention" and (temperature == 0.0 or not math.isfinite(temperature)):
+        raise ValueError(f"{who}: temperature={temperature} must be finite and not 0")
+    return lead, rows, rows // mask.shape[0], L, N, SPAN_POOLINGS[pooling], int(k) if pooling == "topk" else 1, temperature, skip_nan
+
+
+def span_scores_masked(sims, spans, mask, *, valid=None, skip_nan=False, k=3, pooling="topk", temperature=0.01, return_windows=False, return_usable=False):
+    """``span_scores`` / ``span_scores_multi`` over the frames that count (``rvc_span_scores_masked`` of the chain library): sims f32 [R,L] with spans
+    [R,N,2] and mask [R,L], or sims f32 [B,Q,L] with spans [B,Q,N,2] and mask [B,L] -> MaskedSpanScores(scores f32 [...,N], windows i32 [...,N,2],
+    n_usable i32 [...,N]); ``windows`` and ``n_usable`` are None unless asked for.  ``valid`` [mask's shape] (bool, uint8 or float; None: every frame)
+    hides the frames where it is 0, ``skip_nan`` the frames whose similarity is NaN (a zeroed feature row); a hidden frame's similarity is never looked
+    at, and the duration and the windows stay the mask's.  A window's score is the sum of its ``min(k, usable)`` best usable frames (``"topk"``) or the
+    softmax pooling over its usable frames (``"attention"``); a non-empty window without a usable frame scores NaN, an empty one 0.  With
+    ``valid=None`` and ``skip_nan=False`` scores and windows equal the other two functions' bit for bit.  One launch (a mask or a valid that is not
+    f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip_chain.h."""
+    who = "span_scores_masked"
+    lead, rows, rpm, L, N, mode, k, temperature, skip_nan = span_scores_masked_checks(who, sims, spans, mask, valid, skip_nan, k, pooling, temperature)
+    dev = sims.device
+    scores = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+    win = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    usable = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_usable else None
+    if N > 0:
+        # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+        sims, spans, mask = sims.contiguous(), spans.float().contiguous(), mask.float().contiguous()
+        valid = valid.float().contiguous() if valid is not None else None
+        hip.chain_check(hip.chain_lib().rvc_span_scores_masked(hip.ptr(sims), hip.ptr(spans), hip.ptr(mask), hip.ptr(valid), rows, rpm, L, N, mode, k, temperature,
+                                                               skip_nan, hip.ptr(scores), hip.ptr(win), hip.ptr(usable), hip.stream()), "rvc_span_scores_masked")
+    return MaskedSpanScores(scores, win, usable)
+
+
+def span_propose_masked(sims, mask, *, valid=None, skip_nan=False, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None,
+                        max_spans=256, return_windows=False, return_smoothed=False):
+    """``span_propose`` from the frames that count (``rvc_span_propose_masked`` of the chain library): the same sims, mask, keywords and
+    SpanProposals.  ``valid`` [mask's shape] (bool, uint8 or float; None: every frame) hides the frames where it is 0, ``skip_nan`` the frames whose
+    similarity is NaN.  A usable frame is smoothed over the usable frames of its box alone (their sum divided by their count), a hidden frame's smoothed
+    value is NaN: it is left out of the row's range, is never above a threshold and breaks a run unless ``gap`` closes it (a run's length counts the
+    hidden frames inside it).  A row without a usable frame gives no span.  The duration stays the mask's.  With ``valid=None`` and ``skip_nan=False``
+    every field equals ``span_propose``'s bit for bit.  One launch (a mask or a valid that is not f32 adds a cast kernel, ``return_smoothed`` a fill),
+    no synchronisation, no host copy.  The full rule stands in include/revision_hip_chain.h."""
+    who = "span_propose_masked"
+    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    skip_nan = skip_nan_flag(who, skip_nan)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    window_select_valid(who, valid, mask)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    lv, relative, smooth, gap, min_len, max_len, N = kw
+    dev = sims.device
+    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
+    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
+    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
+    table = (hip.C.c_float * len(lv))(*lv)
+    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+    sims, mask = sims.contiguous(), mask.float().contiguous()
+    valid = valid.float().contiguous() if valid is not None else None
+    hip.chain_check(hip.chain_lib().rvc_span_propose_masked(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), R, rpm, L, table, len(lv), relative, smooth, gap, min_len,
+                                                            max_len, N, skip_nan, hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows),
+                                                            hip.ptr(smoothed), hip.stream()), "rvc_span_propose_masked")
+    return SpanProposals(spans, n_spans, n_found, windows, smoothed)
+
+
 def proposal_slice(a, b, T):
     """(lo, hi) of ``range(T)[a : b + 1]`` for a >= 0 as ``rv_proposal_cosine`` cuts it: lo = min(a, T), hi = min(b + 1, T); hi <= lo is an empty slice."""
     return min(a, T), min(b + 1, T)

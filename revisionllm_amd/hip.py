@@ -250,6 +250,8 @@ CHAIN_SIGNATURES = {
     "rvc_last_error": (C.c_int, [C.c_char_p, _sz]),
     "rvc_window_select_frames": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p,
                                            _p, _p]),
+    "rvc_span_scores_masked": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32, _p, _p, _p, _p]),
+    "rvc_span_propose_masked": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p]),
 }
 _chain = None
 

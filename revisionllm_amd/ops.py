@@ -17,7 +17,8 @@ from .grounding import (HIT_IOU, SPAN_FORMS, SPAN_POOLINGS, SPAN_PROPOSE_LEVELS,
                         WINDOW_GATHER_MAX_FRAMES, window_gather, window_gather_dtypes, window_gather_keywords, window_select, window_select_capacity,
                         window_select_gt, window_select_keywords, clipped_window_count, clipped_window_void, proposal_cosine, proposal_slice,
                         window_gather_clipped, clipped_window_solid, window_select_clipped, FrameWindowSelection, WINDOW_FRAME_SETS, WINDOW_RULES,
-                        WINDOW_SELECT_MAX_SAMPLED, window_select_frames, window_select_frames_keywords, window_select_valid)
+                        WINDOW_SELECT_MAX_SAMPLED, window_select_frames, window_select_frames_keywords, window_select_valid, MaskedSpanScores, span_propose_masked,
+                        span_scores_masked, span_scores_masked_checks, skip_nan_flag)
 from .utils import hashinit
 
 
