@@ -133,6 +133,51 @@ int rvc_span_propose_masked(const float* sims, const float* mask, const float* v
                             int32_t relative, int32_t smooth, int32_t gap, int32_t min_len, int32_t max_len, int32_t N, int32_t skip_nan, float* spans,
                             int32_t* n_spans, int32_t* n_found, int32_t* windows, float* smoothed, void* stream);
 
+/* ---- a window selection becomes a validity row: the joint between the coarse half (rvc_window_select_frames) and the fine half (the masked span
+ * entries).  "Search each query only inside the windows chosen for it" is this launch in front of the two _rows entries below ----
+ * select i32 [R,keep] (rvc_window_select_frames' `select` as it lies, -1 padding included, or window indices from anywhere: the LLM's answers, a
+ * retrieval log), mask f32 [R / rpm, L] (rpm = "rows per mask"; R a multiple of rpm), valid_in f32 [R / rpm, L] or NULL ->
+ *   valid     f32 [R,L]   1.0f at the frames the row's named windows cover, +0.0f elsewhere; EVERY element of [r, 0 .. L) is written, so the caller may
+ *                         pass uninitialised memory
+ *   n_valid   i32 [R]     (optional) the ones of the row
+ * Duration: D from the mask row (r / rpm) by the code of rvc_window_select_frames (the block sum of csrc/grounding.h at that kernel's width and
+ * duration_frames): bit for bit that entry's duration.
+ * Windows: the window count W_r and the frames [lo, hi) of window i are rvc_window_select_frames' for the same rule / win / stride (ws_count,
+ * ws_bounds, ws_bounds_clipped); the clipped rule's void windows are no windows, so W_r counts the others as n_windows does there.
+ * Frame set of a window: rvc_window_select_frames' - frames = RV_FRAMES_ALL (0), F = 0: every frame of [lo, hi); frames = RV_FRAMES_SAMPLED (1):
+ * np.linspace(lo, hi - 1, F, dtype=int32)[j] for j < F, the frames rv_window_gather[_rule] hands on.  An index means the same frames in the selection,
+ * in the gather and here.
+ * Ignored entries: an entry of select outside [0, W_r) names nothing and is ignored, as rv_window_gather ignores it: the -1 padding, anything negative,
+ * anything >= W_r, a void window.  Order and duplicates do not matter.
+ * valid[r, t] = 1.0f when all three hold: t < D; t is in the frame set of at least one named window of row r; valid_in is NULL or
+ * valid_in[(r / rpm) * L + t] != 0 (the f32 comparison of the entries above: -0 hides a frame, a NaN in valid_in does not).  Otherwise +0.0f; the
+ * frames at or behind D are 0.  valid_in is read only at frames a named window covers.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null select / mask / valid; rule outside {0, 1}; frames outside {0, 1}; R < 1;
+ * rpm < 1; R not a multiple of rpm; L < 1 or L > 1048576; rule 1 with stride != 2; stride < 1; win < stride; win > L; RV_FRAMES_SAMPLED with F < 1 or
+ * F > 1024; RV_FRAMES_ALL with F != 0; keep outside [1, 2048].
+ * One 1024-thread workgroup per row, rows on the grid's x dimension with 64-bit offsets: the duration, a zero fill of the row (16-byte stores between
+ * its 16-byte boundaries), behind a barrier the named windows' frames stored as 0 / 1 (overlapping windows store the same value to a frame, so the
+ * order does not show), behind another barrier the count.  128 B of LDS whatever L; vector stores only, no atomics, no scratch. */
+int rvc_windows_valid(const int32_t* select, const float* mask, const float* valid_in, int32_t R, int32_t rpm, int32_t L, int32_t rule, int32_t win,
+                      int32_t stride, int32_t frames, int32_t F, int32_t keep, float* valid, int32_t* n_valid, void* stream);
+
+/* ---- the two masked span entries with a validity row per ROW: rvc_span_scores_masked and rvc_span_propose_masked with one more argument, rpv ("rows
+ * per validity row"), directly behind valid ----
+ * valid is f32 [rows / rpv, L] (or NULL), and frame t of row r is usable by valid[(r / rpv) * L + t]; everything else is the definition of the entry
+ * without _rows word for word.  The mask row, hence the duration, stays row (r / rpm).  rpv = 1 with rpm = Q on a [B,Q,L] layout gives every query
+ * its own validity row - rvc_windows_valid's output for a per-query selection - under its video's one duration.
+ * Identities: with rpv = rpm every output equals the entry without _rows bit for bit.  With rpv = 1 on a [B,Q,L] layout every (b, q) equals that
+ * entry on the row alone (rpm = 1, its video's mask row, its own validity row) bit for bit.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: everything the entry without _rows refuses, under the same conditions, and rpv < 1
+ * or rows not a multiple of rpv.
+ * The kernels, the launch geometry and the resources are those entries': one more scalar argument. */
+int rvc_span_scores_masked_rows(const float* sims, const float* spans, const float* mask, const float* valid, int32_t rpv, int32_t rows, int32_t rpm,
+                                int32_t L, int32_t N, int32_t mode, int32_t k, float temperature, int32_t skip_nan, float* scores, int32_t* windows,
+                                int32_t* n_usable, void* stream);
+int rvc_span_propose_masked_rows(const float* sims, const float* mask, const float* valid, int32_t rpv, int32_t R, int32_t rpm, int32_t L,
+                                 const float* levels, int32_t T, int32_t relative, int32_t smooth, int32_t gap, int32_t min_len, int32_t max_len, int32_t N,
+                                 int32_t skip_nan, float* spans, int32_t* n_spans, int32_t* n_found, int32_t* windows, float* smoothed, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

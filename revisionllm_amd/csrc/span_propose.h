@@ -1,4 +1,4 @@
-// The span-proposal kernel of the CLIP grounding chain, one source for rv_span_propose (propose.hip: the default instance) and rvc_span_propose_masked
+// The span-proposal kernel of the CLIP grounding chain, one source for rv_span_propose (propose.hip: the default instance) and rvc_span_propose_masked[_rows]
 // (spans_chain.hip: MASKED = true, a per-frame validity row and / or the non-finite similarities skipped), with the smoothing and the refusals the two
 // entries share.  The definition stands in include/revision_hip.h, what MASKED changes in include/revision_hip_chain.h.  Every f32 operation is rounded
 // on its own (__fadd_rn, __fsub_rn, __fmul_rn, __fdiv_rn), so a row's result does not depend on R, on the row's place or on the tiling.
@@ -28,8 +28,9 @@ struct ProposeArgs {
 };
 // the masked instance's argument block: the default one's (unchanged, so the default instance's argument loads are the parent's) and the validity behind it
 struct ProposeMaskedArgs : ProposeArgs {
-    const float* valid;      // f32 [R / rpm, L] or null
+    const float* valid;      // f32 [R / rpv, L] or null
     int skip_nan;            // 1: a frame whose similarity is NaN is hidden as well
+    int rpv;                 // "rows per validity row": rpm for rvc_span_propose_masked (one per mask row), 1 for a validity row per row of sims
 };
 template <bool MASKED>
 using ProposeArgsOf = std::conditional_t<MASKED, ProposeMaskedArgs, ProposeArgs>;
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgsO
     }
     auto smooth_tile = [&](int t0, int D) {
         if constexpr (MASKED) {
-            return sp_smooth<true>(s, stage, t0, D, h, a.valid ? a.valid + (r / a.rpm) * L : nullptr, a.skip_nan != 0, ok);
+            return sp_smooth<true>(s, stage, t0, D, h, a.valid ? a.valid + (int64_t)((int)blockIdx.x / a.rpv) * L : nullptr, a.skip_nan != 0, ok);
         } else {
             return sp_smooth<false>(s, stage, t0, D, h);
         }

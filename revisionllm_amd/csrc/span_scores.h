@@ -1,5 +1,5 @@
 // The span-score kernel of the CLIP grounding chain, one source for rv_span_scores / rv_span_scores_multi (similarity.hip: the default instances) and
-// rvc_span_scores_masked (spans_chain.hip: MASKED = true, a per-frame validity row and / or the non-finite similarities skipped).  The window rule
+// rvc_span_scores_masked / rvc_span_scores_masked_rows (spans_chain.hip: MASKED = true, a per-frame validity row and / or the non-finite similarities skipped).  The window rule
 // lives here with it: the two entries agree on a window bit for bit because they run this code.
 #pragma once
 #include "grounding.h"
@@ -16,9 +16,10 @@ template <bool MASKED>
 struct SpanMasking {};
 template <>
 struct SpanMasking<true> {
-    const float* valid;      // f32 [rows / rpm, L] or null: every frame inside the window counts
+    const float* valid;      // f32 [rows / rpv, L] or null: every frame inside the window counts
     int32_t* n_usable;       // i32 [rows, N] or null
     int skip_nan;            // 1: a frame whose similarity is NaN is hidden as well
+    int rpv;                 // "rows per validity row": rpm for rvc_span_scores_masked (one per mask row), 1 for a validity row per row of sims
 };
 
 // One wave per span (4 spans per block, all of row blockIdx.y).  A row is a video (rpm = 1, rv_span_scores) or one of a video's rpm queries
@@ -32,7 +33,7 @@ struct SpanMasking<true> {
 // index: k wave-wide rank rounds over a lane-strided window, no LDS); MODE 1: sum_t softmax_t(s / tau) s_t in two lane-strided passes - the maximum, then both sums - (a NaN in
 // the window is carried next to the running maximum, which fmaxf would drop).  An empty window scores 0; a non-finite p1 / p2 gives NaN and the
 // window (-1, -1).
-// MASKED: frame t of the window is USABLE when its validity entry (row b / rpm, read only where sims is read) is not 0 and, under skip_nan, its
+// MASKED: frame t of the window is USABLE when its validity entry (row b / rpv, read only where sims is read) is not 0 and, under skip_nan, its
 // similarity is a number; a hidden frame's similarity enters no comparison and no sum (it is skipped, not multiplied by 0).  With n usable frames the
 // rank rounds are min(k, n) and walk the usable frames only, the softmax runs over them only, a window with hi > lo and n = 0 scores NaN, and
 // n_usable takes n (0 for an empty or void span).
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(256) void span_scores_kernel(const float* __restric
             }
         }
     } else {
-        const float* vr = mk.valid ? mk.valid + (int64_t)(b / rpm) * L : nullptr;
+        const float* vr = mk.valid ? mk.valid + (int64_t)(b / mk.rpv) * L : nullptr;
         const bool skip = mk.skip_nan != 0;
         // (t in [lo, hi): the validity entry first, the similarity only behind a usable one; v: the similarity of a usable frame)
         auto usable = [&](int t, float& v) {

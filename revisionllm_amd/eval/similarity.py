@@ -30,7 +30,12 @@ ranking - into a grounder that needs no proposals from outside and never synchro
 Window selection (the reference evaluates this stage in evaluate_pre_filtered_window.py and feeds it from a stage-1 LLM log, e2e2.py:278-294):
 ``select_windows`` turns the cosine rows into the sorted window list ``run_query(grounding_windows=)`` takes - every window of ``cut_windows``'
 geometry scored by its top-k cosines, the best ``keep`` spread at least ``min_sep`` apart (``rv_window_select``, one launch) - and, given a ground
-truth, the place of the first window that overlaps it (``eval.metrics.window_recall``)."""
+truth, the place of the first window that overlaps it (``eval.metrics.window_recall``).
+
+Coarse to fine (this build's addition): ``ground_queries_in_windows`` joins the two halves per query - the cosine rows once, the windows chosen on
+them (or given: the LLM's answers, a retrieval log), ``windows_valid`` turning each query's windows into its own validity row
+(``rvc_windows_valid``), and the proposal, score and rank stages run under those rows (``rvc_span_propose_masked_rows``,
+``rvc_span_scores_masked_rows``) - in a fixed number of launches whatever Q, with no synchronisation."""
 import collections
 import math
 
@@ -231,9 +236,11 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     return _ground("ground_queries", text, video, mask, None, False, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords)
 
 
-def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False):
-    """``ground_queries`` and ``ground_queries_masked`` (``masked``: the proposal and the score stage are the chain library's, under ``valid`` and
-    ``skip_nan``): one body."""
+def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False, windows=None):
+    """``ground_queries``, ``ground_queries_masked`` (``masked``: the proposal and the score stage are the chain library's, under ``valid`` and
+    ``skip_nan``) and ``ground_queries_in_windows`` (the rows form - ``windows``: a callable ``(sims, mask, valid, gt) -> (selection or None,
+    ops.WindowsValid)`` that runs behind the cosine rows; the proposal and the score stage then run under ITS validity rows, one per row of sims, and
+    the result is ``(Grounding, selection, WindowsValid)``): one body."""
     for name, t in (("text", text), ("video", video), ("mask", mask)) + ((("gt", gt),) if gt is not None else ()):
         if not torch.is_tensor(t):
             raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
@@ -273,21 +280,30 @@ def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, t
     mask = ops.h2d(mask, dev).float()
     cosine, score = (ops.frame_cosine_multi, ops.span_scores_multi) if multi else (ops.frame_cosine, ops.span_scores)
     sims = cosine(ops.h2d(text, dev).float(), video)
-    if masked:
+    gt = None if gt is None else ops.h2d(gt, dev).float()
+    if windows is not None:
+        selection, rows_valid = windows(sims, mask, None if valid is None else ops.h2d(valid, dev), gt)
+        proposals = ops.span_propose_masked_rows(sims, mask, valid=rows_valid.valid, skip_nan=skip_nan, **propose_keywords)
+        scores = ops.span_scores_masked_rows(sims, proposals.spans, mask, valid=rows_valid.valid, skip_nan=skip_nan, k=k, pooling=pooling,
+                                             temperature=temperature).scores
+    elif masked:
         valid = None if valid is None else ops.h2d(valid, dev)
         proposals = ops.span_propose_masked(sims, mask, valid=valid, skip_nan=skip_nan, **propose_keywords)
         scores = ops.span_scores_masked(sims, proposals.spans, mask, valid=valid, skip_nan=skip_nan, k=k, pooling=pooling, temperature=temperature).scores
     else:
         proposals = ops.span_propose(sims, mask, **propose_keywords)
         scores = score(sims, proposals.spans, mask, k=k, pooling=pooling, temperature=temperature)
-    rank = ops.span_rank(scores, proposals.spans, top=top, nms_iou=nms_iou, form="cxw", gt=None if gt is None else ops.h2d(gt, dev).float(), hit_iou=hit_iou)
+    rank = ops.span_rank(scores, proposals.spans, top=top, nms_iou=nms_iou, form="cxw", gt=gt, hit_iou=hit_iou)
     held = (rank.keep >= 0) & (rank.keep < proposals.n_spans.unsqueeze(-1))                 # kept places that hold a proposal: a prefix (NaN ranks last)
     at = rank.keep.clamp(min=0).long()
     nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
     spans = torch.where(held.unsqueeze(-1), torch.gather(proposals.spans, -2, at.unsqueeze(-1).expand(at.shape + (2,))), nan)
     kept_scores = torch.where(held, torch.gather(scores, -1, at), nan)
     back = lambda tup: type(tup)(*(None if t is None else t.to(home) for t in tup))                 # noqa: E731
-    return Grounding(spans.to(home), kept_scores.to(home), held.sum(-1, dtype=torch.int32).to(home), back(proposals), back(rank))
+    grounding = Grounding(spans.to(home), kept_scores.to(home), held.sum(-1, dtype=torch.int32).to(home), back(proposals), back(rank))
+    if windows is not None:
+        return grounding, None if selection is None else back(selection), back(rows_valid)
+    return grounding
 
 
 def forward_clip_matching_masked(src_cls_txt, src_vid_appear, src_vid_appear_mask, proposal, *, valid=None, skip_nan=False, k=3, pooling="topk",
@@ -345,6 +361,66 @@ def ground_queries_masked(text, video, mask, *, valid=None, skip_nan=False, top=
     already ranks last): as many launches as ``ground_queries``, no synchronisation and no device -> host copy when the inputs live on the device."""
     return _ground("ground_queries_masked", text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords,
                    masked=True)
+
+
+def windows_valid(select, mask, *, rule, win, stride=None, frames="all", num_frames=None, valid=None, return_count=False):
+    """``ops.windows_valid`` with the device handling of ``propose_spans_masked``: select i32 [R, keep] or [B, Q, keep] (``select_windows_frames``'
+    ``select``, or window indices from anywhere), mask [R, L] / [B, L], the keywords of that function -> ``ops.WindowsValid(valid, n_valid)``: f32
+    [..., L] rows that are 1 at the frames the named windows cover - the ``valid`` of ``ops.span_scores_masked_rows`` /
+    ``ops.span_propose_masked_rows``.  One launch, no synchronisation and no device -> host copy when the inputs live on the device; host tensors are
+    staged and the results come back on the device ``select`` lives on."""
+    who = "windows_valid"
+    ops.windows_valid_checks(who, select, mask, rule, win, stride, frames, num_frames, valid, return_count)
+    home = select.device
+    dev = _device_of(select, who)
+    out = ops.windows_valid(ops.h2d(select, dev), ops.h2d(mask, dev), rule=rule, win=win, stride=stride, frames=frames, num_frames=num_frames,
+                            valid=None if valid is None else ops.h2d(valid, dev), return_count=return_count)
+    return ops.WindowsValid(*(None if t is None else t.to(home) for t in out))
+
+
+WindowedGrounding = collections.namedtuple("WindowedGrounding", "grounding selection valid n_valid")
+
+
+def ground_queries_in_windows(text, video, mask, *, rule, win, stride=None, select=None, keep=None, frames="all", num_frames=None, select_k=3, min_sep=1,
+                              valid=None, skip_nan=False, top=10, nms_iou=0.5, k=3, pooling="topk", temperature=0.01, gt=None, hit_iou=ops.HIT_IOU,
+                              **propose_keywords):
+    """Coarse to fine: ground every query only inside the windows chosen for it.  text [B, d] or [B, Q, d], video [B, L, d], mask [B, L], the inputs
+    and keywords of ``ground_queries_masked`` -> ``WindowedGrounding(grounding, selection, valid, n_valid)``: the ``Grounding``, the
+    ``ops.FrameWindowSelection`` the windows came from (None when ``select`` was given), the f32 [..., L] validity rows the fine half ran under and
+    their i32 [...] counts of usable frames.  Exactly one of ``select`` and ``keep`` is given: ``select`` i32 [..., n] names each query's windows
+    (the LLM's answers, a retrieval log; -1 and indices outside the row's windows name nothing); ``keep`` chooses them here with
+    ``ops.window_select_frames`` (``rule``, ``win``, ``stride``, ``frames``, ``num_frames``, ``valid``, ``k=select_k``, ``min_sep``; ``gt`` - (start, end)
+    as fractions of the duration, as the ranking takes it - times the mask's row sum as its frames).  The cosine rows are computed once and feed both
+    halves: ``ops.frame_cosine[_multi]``, (``ops.window_select_frames``,) ``ops.windows_valid`` under the caller's ``valid``,
+    ``ops.span_propose_masked_rows``, ``ops.span_scores_masked_rows``, ``ops.span_rank`` and the gather of the kept spans - a fixed number of launches
+    whatever Q, no synchronisation and no device -> host copy when the inputs live on the device."""
+    who = "ground_queries_in_windows"
+    if (select is None) == (keep is None):
+        raise ValueError(f"{who}: exactly one of select (the windows to search) and keep (how many to choose here) must be given")
+    kw = ops.window_select_frames_keywords(who, rule, win, stride, 1 if keep is None else keep, frames, num_frames, select_k, min_sep)
+    stride = kw[2]
+    if select is not None:
+        if not torch.is_tensor(select) or not torch.is_tensor(text) or select.dtype != torch.int32 or select.dim() != text.dim() \
+                or select.shape[:-1] != text.shape[:-1] or not 1 <= select.shape[-1] <= ops.WINDOWS_VALID_MAX_KEEP:
+            raise ValueError(f"{who}: select must be an int32 tensor [..., n] over text's leading shape with 1 <= n <= {ops.WINDOWS_VALID_MAX_KEEP} "
+                             f"(got {tuple(select.shape) if torch.is_tensor(select) else type(select).__name__})")
+    if torch.is_tensor(video) and video.dim() == 3 and video.shape[1] >= 1:
+        if keep is not None:
+            ops.window_select_capacity(who, video.shape[1], kw[1], stride, kw[7])
+        elif kw[1] > video.shape[1]:
+            raise ValueError(f"{who}: win={kw[1]} frames for rows of L={video.shape[1]}")
+
+    def windows(sims, m, v, gt_dev):
+        selection = None
+        if keep is not None:
+            gt_frames = None if gt_dev is None else gt_dev * m.sum(-1).view((-1,) + (1,) * (gt_dev.dim() - 1))
+            selection = ops.window_select_frames(sims, m, rule=rule, win=win, stride=stride, keep=keep, frames=frames, num_frames=num_frames, valid=v,
+                                                 k=select_k, min_sep=min_sep, gt=gt_frames)
+        chosen = selection.select if selection is not None else ops.h2d(select, sims.device)
+        return selection, ops.windows_valid(chosen, m, rule=rule, win=win, stride=stride, frames=frames, num_frames=num_frames, valid=v, return_count=True)
+    grounding, selection, rows_valid = _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords,
+                                               masked=True, windows=windows)
+    return WindowedGrounding(grounding, selection, rows_valid.valid, rows_valid.n_valid)
 
 
 def select_windows(text, video, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, return_scores=False, return_bounds=False, return_order=False):

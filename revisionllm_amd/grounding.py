@@ -704,6 +704,121 @@ def span_propose_masked(sims, mask, *, valid=None, skip_nan=False, levels=SPAN_P
     return SpanProposals(spans, n_spans, n_found, windows, smoothed)
 
 
+WINDOWS_VALID_MAX_KEEP = 2048
+WindowsValid = collections.namedtuple("WindowsValid", "valid n_valid")
+
+
+def windows_valid_checks(who, select, mask, rule, win, stride=None, frames="all", num_frames=None, valid=None, return_count=False):
+    """The refusals of ``windows_valid`` (raised before any device is looked for) -> (rule code, win, stride, frame set code, F, leading shape, R, rows
+    per mask row, L, keep) as ``rvc_windows_valid`` takes them."""
+    rule, win, stride, _, frames, F, _, _ = window_select_frames_keywords(who, rule, win, stride, 1, frames, num_frames)
+    if not torch.is_tensor(select) or not torch.is_tensor(mask):
+        raise ValueError(f"{who}: select and mask must be tensors")
+    if select.dim() not in (2, 3) or mask.dim() != 2:
+        raise ValueError(f"{who}: select {tuple(select.shape)} / mask {tuple(mask.shape)} (expected [R, keep] or [B, Q, keep] and [R, L] / [B, L])")
+    if select.dtype != torch.int32:
+        raise ValueError(f"{who}: select must be int32 (got {select.dtype})")
+    lead, keep, (M, L) = tuple(select.shape[:-1]), select.shape[-1], mask.shape
+    R = math.prod(lead)
+    if min(R, keep, M, L) < 1 or (select.dim() == 3 and M != lead[0]) or R % M != 0:
+        raise ValueError(f"{who}: select {tuple(select.shape)} / mask {tuple(mask.shape)} (one mask row per video: a whole number of rows of select for each)")
+    if keep > WINDOWS_VALID_MAX_KEEP:
+        raise ValueError(f"{who}: keep={keep} entries per row (at most {WINDOWS_VALID_MAX_KEEP})")
+    if L > SPAN_PROPOSE_MAX_FRAMES:
+        raise ValueError(f"{who}: L={L} frames (at most {SPAN_PROPOSE_MAX_FRAMES})")
+    if win > L:
+        raise ValueError(f"{who}: win={win} frames for rows of L={L}")
+    if mask.dtype.is_complex:
+        raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
+    window_select_valid(who, valid, mask)
+    if not (isinstance(return_count, (bool, numbers.Integral)) and return_count in (0, 1)):
+        raise ValueError(f"{who}: return_count={return_count!r} must be True or False")
+    return rule, win, stride, frames, F, lead, R, R // M, L, keep
+
+
+def windows_valid(select, mask, *, rule, win, stride=None, frames="all", num_frames=None, valid=None, return_count=False):
+    """A window selection as the validity rows the ``_rows`` span functions take (``rvc_windows_valid`` of the chain library): select i32 [R,keep] with
+    mask [R,L], or select i32 [B,Q,keep] with mask [B,L] (with fewer mask rows than rows of select each serves a whole number of consecutive rows) ->
+    WindowsValid(valid f32 [...,L] over ``select``'s leading shape, n_valid i32 [...] or None unless ``return_count``).  ``select`` is
+    ``window_select_frames``' as it lies, -1 padding included, or window indices from anywhere (the LLM's answers, a retrieval log): an entry outside the
+    row's windows names nothing, order and duplicates do not matter.  ``rule``, ``win``, ``stride``, ``frames`` and ``num_frames`` are
+    ``window_select_frames``' and mean the same windows and the same frames of a window.  ``valid[r, t]`` is 1 where frame ``t`` lies inside the mask's
+    duration, in the frame set of a named window and - with ``valid`` [mask's shape] (bool, uint8 or float) given - where that is not 0; else 0.  One
+    launch (a mask or a valid that is not f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in
+    include/revision_hip_chain.h."""
+    rule, win, stride, frames, F, lead, R, rpm, L, keep = windows_valid_checks("windows_valid", select, mask, rule, win, stride, frames, num_frames, valid,
+                                                                               return_count)
+    dev = select.device
+    out = torch.empty(lead + (L,), dtype=torch.float32, device=dev)
+    n_valid = torch.empty(lead, dtype=torch.int32, device=dev) if return_count else None
+    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+    select, mask = select.contiguous(), mask.float().contiguous()
+    valid = valid.float().contiguous() if valid is not None else None
+    hip.chain_check(hip.chain_lib().rvc_windows_valid(hip.ptr(select), hip.ptr(mask), hip.ptr(valid), R, rpm, L, rule, win, stride, frames, F, keep, hip.ptr(out),
+                                                      hip.ptr(n_valid), hip.stream()), "rvc_windows_valid")
+    return WindowsValid(out, n_valid)
+
+
+def span_rows_valid(who, valid, sims):
+    """The refusals of a per-row ``valid``: a bool, uint8 or floating-point tensor of ``sims``' shape."""
+    if not torch.is_tensor(valid) or not torch.is_tensor(sims) or valid.shape != sims.shape:
+        raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of sims' shape "
+                         f"{tuple(sims.shape) if torch.is_tensor(sims) else '?'}: a validity row per row)")
+    if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
+        raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+
+
+def span_scores_masked_rows(sims, spans, mask, *, valid, skip_nan=False, k=3, pooling="topk", temperature=0.01, return_windows=False, return_usable=False):
+    """``span_scores_masked`` with a validity row per ROW (``rvc_span_scores_masked_rows`` of the chain library): the same sims, spans, mask, keywords
+    and MaskedSpanScores, with ``valid`` of ``sims``' shape ([R,L] or [B,Q,L]; bool, uint8 or float) - on the [B,Q,L] layout every query has its own
+    usable frames, what ``windows_valid`` makes of a per-query window selection, while the duration stays its video's.  Each (b, q) equals
+    ``span_scores_masked`` on that row alone bit for bit.  One launch (a mask or a valid that is not f32 adds a cast kernel), no synchronisation, no
+    host copy.  The full rule stands in include/revision_hip_chain.h."""
+    who = "span_scores_masked_rows"
+    lead, rows, rpm, L, N, mode, k, temperature, skip_nan = span_scores_masked_checks(who, sims, spans, mask, None, skip_nan, k, pooling, temperature)
+    span_rows_valid(who, valid, sims)
+    dev = sims.device
+    scores = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+    win = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    usable = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_usable else None
+    if N > 0:
+        # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+        sims, spans, mask, valid = sims.contiguous(), spans.float().contiguous(), mask.float().contiguous(), valid.float().contiguous()
+        hip.chain_check(hip.chain_lib().rvc_span_scores_masked_rows(hip.ptr(sims), hip.ptr(spans), hip.ptr(mask), hip.ptr(valid), 1, rows, rpm, L, N, mode, k,
+                                                                    temperature, skip_nan, hip.ptr(scores), hip.ptr(win), hip.ptr(usable), hip.stream()),
+                        "rvc_span_scores_masked_rows")
+    return MaskedSpanScores(scores, win, usable)
+
+
+def span_propose_masked_rows(sims, mask, *, valid, skip_nan=False, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None,
+                             max_spans=256, return_windows=False, return_smoothed=False):
+    """``span_propose_masked`` with a validity row per ROW (``rvc_span_propose_masked_rows`` of the chain library): the same sims, mask, keywords and
+    SpanProposals, with ``valid`` of ``sims``' shape ([R,L] or [B,Q,L]; bool, uint8 or float).  Each (b, q) equals ``span_propose_masked`` on that row
+    alone bit for bit.  One launch (a mask or a valid that is not f32 adds a cast kernel, ``return_smoothed`` a fill), no synchronisation, no host
+    copy.  The full rule stands in include/revision_hip_chain.h."""
+    who = "span_propose_masked_rows"
+    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    skip_nan = skip_nan_flag(who, skip_nan)
+    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    span_rows_valid(who, valid, sims)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    lv, relative, smooth, gap, min_len, max_len, N = kw
+    dev = sims.device
+    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
+    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
+    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
+    table = (hip.C.c_float * len(lv))(*lv)
+    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+    sims, mask, valid = sims.contiguous(), mask.float().contiguous(), valid.float().contiguous()
+    hip.chain_check(hip.chain_lib().rvc_span_propose_masked_rows(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), 1, R, rpm, L, table, len(lv), relative, smooth, gap,
+                                                                 min_len, max_len, N, skip_nan, hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found),
+                                                                 hip.ptr(windows), hip.ptr(smoothed), hip.stream()), "rvc_span_propose_masked_rows")
+    return SpanProposals(spans, n_spans, n_found, windows, smoothed)
+
+
 def proposal_slice(a, b, T):
     """(lo, hi) of ``range(T)[a : b + 1]`` for a >= 0 as ``rv_proposal_cosine`` cuts it: lo = min(a, T), hi = min(b + 1, T); hi <= lo is an empty slice."""
     return min(a, T), min(b + 1, T)
