@@ -178,6 +178,46 @@ int rvc_span_propose_masked_rows(const float* sims, const float* mask, const flo
                                  const float* levels, int32_t T, int32_t relative, int32_t smooth, int32_t gap, int32_t min_len, int32_t max_len, int32_t N,
                                  int32_t skip_nan, float* spans, int32_t* n_spans, int32_t* n_found, int32_t* windows, float* smoothed, void* stream);
 
+/* ---- boundary refinement: the stage behind the ranking.  A proposal's bounds are where a SMOOTHED row crosses a threshold, an LLM answer's or a
+ * retrieval log's are whatever they are; this entry moves every span to the neighbouring start / end pair with the largest contrast between the
+ * frames inside and the frames just outside, under the chain's validity rows, and hands the spans back in the encoding rv_span_scores and rv_span_rank
+ * read ----
+ * sims f32 [rows,L] (COSINE rows: values are clamped to [-1, 1]), spans f32 [rows,N,2], form (1: (centre, width), 0: (start, end); fractions of the
+ * duration, as rv_span_rank's forms), mask f32 [rows / rpm, L] (rpm = "rows per mask"), valid f32 [rows / rpv, L] or NULL (rpv = "rows per validity
+ * row": rpm for a row per mask row, 1 for a row per row of sims) ->
+ *   out_spans  f32 [rows,N,2]   ALWAYS (centre, width), rv_span_propose's encoding of the chosen window; two quiet NaNs (0x7fc00000) for a void span
+ *   windows    i32 [rows,N,2]   (optional) the chosen (a, b); (-1, -1) for a void span
+ *   contrast   f32 [rows,N]     (optional) (float)J of the choice; NaN when no candidate is admissible and for a void span
+ *   contrast0  f32 [rows,N]     (optional) (float)J of the original pair; NaN when it is not admissible and for a void span
+ * Duration and window: dur is the mask row's raw f32 sum as rv_span_scores takes it, D = min(L, floor(dur)) frames (none for a sum that is not finite
+ * or below 1: rvc_window_select_frames' duration_frames).  form 1: x1 = c - 0.5 w, x2 = c + 0.5 w; form 0: x1 = start, x2 = end.  From there the
+ * window [lo, hi) is rv_span_scores' rule, operation for operation: p = x * dur, each operation rounded on its own, start = max(0, int(floor(p1))),
+ * end = int(ceil(p2)), saturating, Python's range(L)[start:end] over the ARRAY length L with a negative end included.  Then lo0 = min(lo, D),
+ * hi0 = min(hi, D).  A VOID span names nothing: a non-finite p1 / p2, or hi0 <= lo0.
+ * USABLE: frame t < D is usable when valid == NULL || valid[(r / rpv) * L + t] != 0 (the f32 comparison of the entries above: -0 hides a frame, a
+ * NaN in valid does not) and its similarity is a number.  A usable frame's value is the integer q[t] = rint(clamp(s[t], -1, 1) * 16777216.f) (2^24
+ * steps to the unit; the product is exact in f32, the rounding is ties-to-even; +-inf clamps to +-1).  For an interval, S(x, y) is the int64 sum of q
+ * over the usable frames of [x, y) and C(x, y) their count: exact integers, so NO RESULT DEPENDS ON THE ORDER OF ANY SUM.  A hidden frame's similarity
+ * enters nothing; valid is read only where sims is read.
+ * Candidates: a in [max(0, lo0 - radius), min(lo0 + radius, D - 1)], b in [max(1, hi0 - radius), min(hi0 + radius, D)], b - a >= min_len - except
+ * that the original pair (lo0, hi0) is always a candidate.  A candidate is ADMISSIBLE when Cin = C(a, b) > 0 and
+ * Cout = C(max(0, a - margin), a) + C(b, min(D, b + margin)) > 0.  Its contrast, in float64 with each of the three operations rounded on its own, is
+ *   J(a, b) = (double)Sin / (double)Cin - (double)Sout / (double)Cout,   Sin = S(a, b), Sout = S(max(0, a - margin), a) + S(b, min(D, b + margin))
+ * (|S| <= 2^44: the conversions are exact and J is one well-defined double).
+ * Choice: the admissible candidate with the largest J; then the smallest |a - lo0| + |b - hi0|; then the smaller a; then the smaller b.  With no
+ * admissible candidate the original pair is kept and contrast is NaN.
+ * Output: windows = (a, b); out_spans: c = ((a + b) * 0.5) / dur, w = ((b - a) - 0.5) / dur in f32, each operation rounded - so rv_span_scores
+ * recovers exactly [a, b) from out_spans for L <= 2^20 under a 0 / 1 mask.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null sims / spans / mask / out_spans; form outside {0, 1}; rows or N below 1; L
+ * outside [1, 1048576]; rpm or rpv below 1, or rows not a multiple of either; rows > 65535; radius outside [1, 64]; margin outside [1, 128];
+ * min_len < 1.
+ * One wave per span, four spans per 256-thread workgroup, the row on the grid's y dimension.  Every read of sims and valid lies in front of D, inside
+ * the zones [lo0 - radius - margin, lo0 + radius) and [hi0 - radius, hi0 + radius + margin) or inside the span.  24688 B of LDS whatever L (514
+ * prefix pairs per wave); vector stores only, no atomics, no scratch. */
+int rvc_span_refine(const float* sims, const float* spans, int32_t form, const float* mask, const float* valid, int32_t rpv, int32_t rows, int32_t rpm,
+                    int32_t L, int32_t N, int32_t radius, int32_t margin, int32_t min_len, float* out_spans, int32_t* windows, float* contrast,
+                    float* contrast0, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -236,9 +236,10 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     return _ground("ground_queries", text, video, mask, None, False, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords)
 
 
-def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False, windows=None):
+def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False, windows=None, refine=None):
     """``ground_queries``, ``ground_queries_masked`` (``masked``: the proposal and the score stage are the chain library's, under ``valid`` and
-    ``skip_nan``) and ``ground_queries_in_windows`` (the rows form - ``windows``: a callable ``(sims, mask, valid, gt) -> (selection or None,
+    ``skip_nan``), ``ground_queries_refined`` (``refine``: a callable ``(sims, mask, valid, kept spans) -> (ops.RefinedSpans, scores)`` that runs behind
+    the gather of the kept spans, on the device; the result is ``(Grounding, RefinedSpans, scores)``) and ``ground_queries_in_windows`` (the rows form - ``windows``: a callable ``(sims, mask, valid, gt) -> (selection or None,
     ops.WindowsValid)`` that runs behind the cosine rows; the proposal and the score stage then run under ITS validity rows, one per row of sims, and
     the result is ``(Grounding, selection, WindowsValid)``): one body."""
     for name, t in (("text", text), ("video", video), ("mask", mask)) + ((("gt", gt),) if gt is not None else ()):
@@ -303,6 +304,9 @@ def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, t
     grounding = Grounding(spans.to(home), kept_scores.to(home), held.sum(-1, dtype=torch.int32).to(home), back(proposals), back(rank))
     if windows is not None:
         return grounding, None if selection is None else back(selection), back(rows_valid)
+    if refine is not None:
+        refined, refined_scores = refine(sims, mask, valid, spans)
+        return grounding, back(refined), refined_scores.to(home)
     return grounding
 
 
@@ -361,6 +365,52 @@ def ground_queries_masked(text, video, mask, *, valid=None, skip_nan=False, top=
     already ranks last): as many launches as ``ground_queries``, no synchronisation and no device -> host copy when the inputs live on the device."""
     return _ground("ground_queries_masked", text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords,
                    masked=True)
+
+
+def refine_spans(sims, spans, mask, *, form="cxw", radius, margin, min_len=1, valid=None, return_windows=False, return_contrast=False):
+    """``ops.span_refine`` with the device handling of ``propose_spans_masked``: sims [R, L] or [B, Q, L] (the cosine rows; 16-bit rows are read as
+    f32, which is exact), spans [..., N, 2] as (centre, width) (``form="cxw"``) or (start, end) (``"xx"``) - kept proposals, an LLM's answers, a
+    retrieval log - mask [R, L] / [B, L], ``valid`` of the mask's shape or of ``sims``' shape -> ``ops.RefinedSpans(spans, windows, contrast,
+    contrast0)``: every span moved to the neighbouring (start, end) pair with the largest contrast between the usable frames inside and those within
+    ``margin`` frames outside, ALWAYS as (centre, width).  One launch, no synchronisation and no device -> host copy when the inputs live on the
+    device; host tensors are staged and the results come back on the device ``sims`` lives on."""
+    who = "refine_spans"
+    ops.span_refine_keywords(who, radius, margin, min_len, form, return_windows, return_contrast)
+    ops.span_refine_checks(who, sims.float() if torch.is_tensor(sims) and sims.dtype in _FLOATS else sims, spans, mask, valid)
+    home = sims.device
+    dev = _device_of(sims, who)
+    out = ops.span_refine(ops.h2d(sims, dev).float(), ops.h2d(spans, dev), ops.h2d(mask, dev), form=form, radius=radius, margin=margin, min_len=min_len,
+                          valid=None if valid is None else ops.h2d(valid, dev), return_windows=return_windows, return_contrast=return_contrast)
+    return ops.RefinedSpans(*(None if t is None else t.to(home) for t in out))
+
+
+RefinedGrounding = collections.namedtuple("RefinedGrounding", "grounding refined scores")
+
+
+def ground_queries_refined(text, video, mask, *, radius, margin, min_len=1, form="cxw", valid=None, skip_nan=False, top=10, nms_iou=0.5, k=3,
+                           pooling="topk", temperature=0.01, gt=None, hit_iou=ops.HIT_IOU, **propose_keywords):
+    """``ground_queries_masked`` with the kept spans' bounds refined behind the ranking: the same inputs and keywords ->
+    ``RefinedGrounding(grounding, refined, scores)``.  ``grounding`` is what ``ground_queries_masked`` returns for the same keywords (``min_len``
+    among its proposal keywords), untouched.  ``refined`` is ``ops.span_refine`` on its kept ``[..., top, 2]`` spans under the same ``valid``, with
+    ``radius``, ``margin`` and ``min_len``, windows and contrasts included: ``ops.RefinedSpans(spans, windows, contrast, contrast0)`` in rank order, a
+    padding place NaN / (-1, -1).  ``skip_nan`` is implied in this stage - a NaN cosine is never usable there - and applies to the proposal and score
+    stages as given.  ``scores`` f32 [..., top] are ``ops.span_scores_masked``' scores of the refined spans (``valid``, ``skip_nan``, ``k``,
+    ``pooling``, ``temperature``); the order stays the ranking's.  ``form`` is the form ``refined.spans`` comes back in: "cxw" as the kernel writes it,
+    "xx" converted with ``span_cxw_to_xx`` (the scores are taken on the (centre, width) spans either way).  There is NO second NMS: two kept spans
+    may refine onto each other, or onto the same window.  The launches are ``ground_queries_masked``' and two more (three with ``form="xx"``), a fixed
+    number whatever Q; no synchronisation and no device -> host copy when the inputs live on the device."""
+    who = "ground_queries_refined"
+    ops.span_refine_keywords(who, radius, margin, min_len, form)
+    if "min_len" in propose_keywords:                                  # (cannot happen through the signature; stated for a caller's **dict)
+        raise TypeError(f"{who}: min_len given twice")
+
+    def refine(sims, m, v, kept):
+        out = ops.span_refine(sims, kept, m, form="cxw", radius=radius, margin=margin, min_len=min_len, valid=v, return_windows=True, return_contrast=True)
+        scores = ops.span_scores_masked(sims, out.spans, m, valid=v, skip_nan=skip_nan, k=k, pooling=pooling, temperature=temperature).scores
+        return (out._replace(spans=span_cxw_to_xx(out.spans)) if form == "xx" else out), scores
+    grounding, refined, scores = _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou,
+                                         dict(propose_keywords, min_len=min_len), masked=True, refine=refine)
+    return RefinedGrounding(grounding, refined, scores)
 
 
 def windows_valid(select, mask, *, rule, win, stride=None, frames="all", num_frames=None, valid=None, return_count=False):

@@ -819,6 +819,84 @@ def span_propose_masked_rows(sims, mask, *, valid, skip_nan=False, levels=SPAN_P
     return SpanProposals(spans, n_spans, n_found, windows, smoothed)
 
 
+SPAN_REFINE_MAX_RADIUS = 64
+SPAN_REFINE_MAX_MARGIN = 128
+RefinedSpans = collections.namedtuple("RefinedSpans", "spans windows contrast contrast0")
+
+
+def span_refine_keywords(who, radius, margin, min_len=1, form="cxw", return_windows=False, return_contrast=False):
+    """The keyword refusals of ``span_refine`` (raised before any device is looked for) -> (form code, radius, margin, min_len) as ``rvc_span_refine``
+    takes them."""
+    if not isinstance(form, str) or form not in SPAN_FORMS:
+        raise ValueError(f"{who}: form={form!r} (expected one of {sorted(SPAN_FORMS)})")
+    if not (_is_int(radius) and 1 <= radius <= SPAN_REFINE_MAX_RADIUS):
+        raise ValueError(f"{who}: radius={radius!r} must be an integer in [1, {SPAN_REFINE_MAX_RADIUS}]")
+    if not (_is_int(margin) and 1 <= margin <= SPAN_REFINE_MAX_MARGIN):
+        raise ValueError(f"{who}: margin={margin!r} must be an integer in [1, {SPAN_REFINE_MAX_MARGIN}]")
+    if not (_is_int(min_len) and 1 <= min_len < 2 ** 31):
+        raise ValueError(f"{who}: min_len={min_len!r} must be a positive integer")
+    for name, v in (("return_windows", return_windows), ("return_contrast", return_contrast)):
+        if not (isinstance(v, (bool, numbers.Integral)) and v in (0, 1)):
+            raise ValueError(f"{who}: {name}={v!r} must be True or False")
+    return SPAN_FORMS[form], int(radius), int(margin), int(min_len)
+
+
+def span_refine_checks(who, sims, spans, mask, valid=None):
+    """The tensor refusals of ``span_refine`` (raised before any device is looked for) -> (leading shape, rows, rows per mask row, rows per validity
+    row, L, N).  ``valid`` has the mask's shape (a row per mask row) or ``sims``' shape (a row per row)."""
+    if not torch.is_tensor(spans):
+        raise ValueError(f"{who}: sims, spans and mask must be tensors")
+    lead, rows, rpm, L = span_propose_shapes(who, sims, mask)
+    if spans.dim() != sims.dim() + 1 or spans.shape[:-2] != sims.shape[:-1] or spans.shape[-1] != 2:
+        raise ValueError(f"{who}: sims {tuple(sims.shape)} / spans {tuple(spans.shape)} (expected [R, L] and [R, N, 2], or [B, Q, L] and [B, Q, N, 2])")
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    if not spans.dtype.is_floating_point:
+        raise ValueError(f"{who}: spans must be a floating-point tensor (got {spans.dtype})")
+    if rows > 65535:
+        raise ValueError(f"{who}: {rows} rows (at most 65535 per call)")
+    rpv = rpm
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.shape not in (mask.shape, sims.shape):
+            raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of mask's shape "
+                             f"{tuple(mask.shape)}, a validity row per mask row, or of sims' shape {tuple(sims.shape)}, one per row)")
+        if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
+            raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+        rpv = rpm if valid.shape == mask.shape else 1
+    return lead, rows, rpm, rpv, L, spans.shape[-2]
+
+
+def span_refine(sims, spans, mask, *, form="cxw", radius, margin, min_len=1, valid=None, return_windows=False, return_contrast=False):
+    """Refine spans' bounds on the device (``rvc_span_refine`` of the chain library), the stage behind the ranking: sims f32 [R,L] or [B,Q,L] (cosine
+    rows), spans [...,N,2] as (centre, width) (``form="cxw"``) or (start, end) (``"xx"``) in fractions of the duration - kept proposals, an LLM's
+    answers, a retrieval log - mask [R,L] / [B,L] -> RefinedSpans(spans f32 [...,N,2], windows i32 [...,N,2], contrast f32 [...,N], contrast0 f32
+    [...,N]); ``windows`` is None unless ``return_windows``, the contrasts unless ``return_contrast``.  Every span's frame window [lo, hi) (the rule of
+    ``span_scores``, cut at the duration) is moved to the pair (a, b) with ``|a - lo| <= radius``, ``|b - hi| <= radius`` and ``b - a >= min_len`` that
+    has the largest contrast: the mean of the usable frames inside minus the mean of the usable frames within ``margin`` frames outside, on
+    similarities quantised to 2^-24 so that the sums are exact.  Ties go to the pair nearest the original one, which is always a candidate; a span
+    with no usable frame inside or outside any candidate stays where it is (``contrast`` NaN).  ``valid`` (bool, uint8 or float; None: every frame)
+    hides the frames where it is 0 - of the mask's shape it is a row per mask row, of ``sims``' shape a row per row; a NaN similarity is never
+    usable.  The result is ALWAYS (centre, width) in ``span_propose``'s encoding, so ``span_scores`` on it recovers ``windows``; a void span (NaN, empty,
+    outside the duration) gives NaN, (-1, -1) and NaN contrasts; ``contrast0`` is the original pair's contrast.  One launch (a mask or a valid that is
+    not f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip_chain.h."""
+    who = "span_refine"
+    code, radius, margin, min_len = span_refine_keywords(who, radius, margin, min_len, form, return_windows, return_contrast)
+    lead, rows, rpm, rpv, L, N = span_refine_checks(who, sims, spans, mask, valid)
+    dev = sims.device
+    out = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
+    win = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    contrast = torch.empty(lead + (N,), dtype=torch.float32, device=dev) if return_contrast else None
+    contrast0 = torch.empty(lead + (N,), dtype=torch.float32, device=dev) if return_contrast else None
+    if N > 0:
+        # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+        sims, spans, mask = sims.contiguous(), spans.float().contiguous(), mask.float().contiguous()
+        valid = valid.float().contiguous() if valid is not None else None
+        hip.chain_check(hip.chain_lib().rvc_span_refine(hip.ptr(sims), hip.ptr(spans), code, hip.ptr(mask), hip.ptr(valid), rpv, rows, rpm, L, N, radius, margin,
+                                                        min_len, hip.ptr(out), hip.ptr(win), hip.ptr(contrast), hip.ptr(contrast0), hip.stream()),
+                        "rvc_span_refine")
+    return RefinedSpans(out, win, contrast, contrast0)
+
+
 def proposal_slice(a, b, T):
     """(lo, hi) of ``range(T)[a : b + 1]`` for a >= 0 as ``rv_proposal_cosine`` cuts it: lo = min(a, T), hi = min(b + 1, T); hi <= lo is an empty slice."""
     return min(a, T), min(b + 1, T)

@@ -256,6 +256,7 @@ CHAIN_SIGNATURES = {
     "rvc_span_scores_masked_rows": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f, _i32, _p, _p, _p, _p]),
     "rvc_span_propose_masked_rows": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p,
                                                _p, _p, _p]),
+    "rvc_span_refine": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
 }
 _chain = None
 
