@@ -118,9 +118,11 @@ __global__ __launch_bounds__(512) void gemm_arows_kernel(const op16_t* __restric
     u32x4 pend[MF];
     op16_t* pend_ptr = nullptr;      // &C[r0 + fr][column of this lane's piece] of the pending slice; nullptr = nothing pending
     const int64_t mf_stride = 16 * ldc;
-    const bool row_ok_last = (MF - 1) * 16 + fr < nrows;       // rows of fragments 0 .. MF-2 are always inside the block
+    // row fragments of this lane that lie inside the block: row mf * 16 + fr < nrows.  (The LAST workgroup may hold fewer rows than
+    // (MF - 1) * 16 - down to one -, so no fragment is inside by construction: its rows past M belong to the caller.)
+    const int my_frags = nrows > fr ? (nrows - fr + 15) >> 4 : 0;
     auto store_pending = [&](int mf) {
-        if (OUT_BF16 && pend_ptr && (mf < MF - 1 || row_ok_last) && !(probe & 2)) *(u32x4*)(pend_ptr + mf * mf_stride) = pend[mf];
+        if (OUT_BF16 && pend_ptr && mf < my_frags && !(probe & 2)) *(u32x4*)(pend_ptr + mf * mf_stride) = pend[mf];
     };
 
     // one k-step: A fragments of the NEXT step -> NXT, W fragments of step +4 -> the other ring half, MFMAs of this step

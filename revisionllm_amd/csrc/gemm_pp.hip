@@ -1532,6 +1532,7 @@ int gemm_pp_launch(const void* A, int64_t lda, const void* Wp, const float* bias
         else if (ob && act == RV_ACT_RELU) rc = launch<1, RV_ACT_RELU, 3>(a, lda, w, bias, res, ldr, C, ldc, (int)M, (int)N, (int)K, st);
         else if (!ob && act == RV_ACT_NONE) rc = launch<0, RV_ACT_NONE, 3>(a, lda, w, bias, res, ldr, C, ldc, (int)M, (int)N, (int)K, st);
         else if (!ob && act == RV_ACT_RELU) rc = launch<0, RV_ACT_RELU, 3>(a, lda, w, bias, res, ldr, C, ldc, (int)M, (int)N, (int)K, st);
+        else if (ob) rc = launch<1, RV_ACT_QUICK_GELU, 3>(a, lda, w, bias, res, ldr, C, ldc, (int)M, (int)N, (int)K, st);   // (a 16-bit output must not get the f32 kernel)
         else rc = launch<0, RV_ACT_QUICK_GELU, 3>(a, lda, w, bias, res, ldr, C, ldc, (int)M, (int)N, (int)K, st);
         if (rc) return rc;
         RV_CHECK_LAUNCH("gemm_pp");
