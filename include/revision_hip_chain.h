@@ -218,6 +218,60 @@ int rvc_span_refine(const float* sims, const float* spans, int32_t form, const f
                     int32_t L, int32_t N, int32_t radius, int32_t margin, int32_t min_len, float* out_spans, int32_t* windows, float* contrast,
                     float* contrast0, void* stream);
 
+/* ---- multi-scale sliding-window proposals: the chain's SECOND generator of candidate moments, beside rv_span_propose.  That one thresholds the row at
+ * fractions of its range, so one outlier frame (a title card, a shot that matches the query text literally) compresses every level and a long, modest
+ * plateau is never proposed.  This one slides windows ("anchors") of up to eight lengths along the row, scores each from its own frames and their
+ * surroundings alone, and hands back each scale's local peaks in the encoding rv_span_scores, rv_span_rank and rvc_span_refine read ----
+ * sims f32 [rows,L] (COSINE rows: values are clamped to [-1, 1]), mask f32 [rows / rpm, L] (rpm = "rows per mask"), valid f32 [rows / rpv, L] or NULL
+ * (rpv = "rows per validity row": rpm for a row per mask row, 1 for a row per row of sims), scales: a HOST table of S int32 triples
+ * (len, stride, margin) in frames, 1 <= S <= 8 ->
+ *   out_spans  f32 [rows,max_spans,2]   (centre, width), rv_span_propose's encoding of the kept peaks' windows; two quiet NaNs (0x7fc00000) in the padding
+ *   scores     f32 [rows,max_spans]     (float)J of every kept peak; NaN (0x7fc00000) in the padding
+ *   n_spans    i32 [rows]               min(n_found, max_spans)
+ *   n_found    i32 [rows]               the peaks of the row, kept or not
+ *   windows    i32 [rows,max_spans,2]   (optional) (a, b) of every kept peak; (-1, -1) in the padding
+ *   scale      i32 [rows,max_spans]     (optional) the scale index of every kept peak; -1 in the padding
+ * Duration, usable frames, quantisation and sums are rvc_span_refine's: dur is the mask row's raw f32 sum as rv_span_scores takes it,
+ * D = min(L, floor(dur)) frames (none for a sum that is not finite or below 1).  USABLE: frame t < D is usable when valid == NULL ||
+ * valid[(r / rpv) * L + t] != 0 (the f32 comparison of the entries above: -0 hides a frame, a NaN in valid does not) and its similarity is a number.
+ * A usable frame's value is the integer q[t] = rint(clamp(s[t], -1, 1) * 16777216.f) (2^24 steps to the unit; the product is exact in f32, the
+ * rounding is ties-to-even; +-inf clamps to +-1).  S(x, y) is the int64 sum of q over the usable frames of [x, y) and C(x, y) their count: exact
+ * integers, so NO RESULT DEPENDS ON THE ORDER OF ANY SUM.  A hidden frame's similarity enters nothing; nothing at or behind D is read, of sims or
+ * of valid.
+ * Anchors: scale s has the anchors [a_i, a_i + len_s) with a_i = i * stride_s for every i >= 0 with a_i + len_s <= D and, if D >= len_s and
+ * (D - len_s) % stride_s != 0, ONE MORE, the last index, flush with the end: a = D - len_s.  A scale with len_s > D has no anchors.
+ * Score, by mode, with b = a + len_s, Sin = S(a, b), Cin = C(a, b):
+ *   RVC_ANCHORS_MEAN (0):      J = (double)Sin / (double)Cin.
+ *   RVC_ANCHORS_CONTRAST (1):  J = (double)Sin / (double)Cin - (double)Sout / (double)Cout, Sout = S(max(0, a - margin_s), a) + S(b, min(D, b + margin_s))
+ *                              and Cout likewise: rvc_span_refine's J, operation for operation, in float64 with each of the three operations rounded
+ *                              on its own.  An anchor touching 0 or D has one-sided context.
+ * An anchor is ADMISSIBLE when Cin >= min_usable and, in contrast mode, Cout > 0.
+ * Peaks (local suppression within a scale): order a scale's anchors by (J descending as float64 VALUES, index ascending).  An admissible anchor i is
+ * a PEAK when no admissible j != i of the same scale with |j - i| <= peak precedes it in that order.  peak = 0 makes every admissible anchor a peak.
+ * A FLAT STRETCH THEREFORE YIELDS ONLY ITS FIRST ANCHOR (and, where the stretch is longer than peak anchors, NOT one anchor every peak + 1: each later
+ * anchor is preceded by its left neighbour).  Scales do not suppress each other: rv_span_rank's NMS does that.
+ * Capacity: n_found is the number of peaks of the row.  If n_found > max_spans, the kept set is the first max_spans peaks in the order (J descending,
+ * scale index ascending, anchor index ascending): truncation is by score, not by position.
+ * Output order: the kept peaks in (scale index, anchor index) order.  out_spans: c = ((a + b) * 0.5) / dur, w = ((b - a) - 0.5) / dur in f32, each
+ * operation rounded - so rv_span_scores recovers exactly [a, b) from out_spans for L <= 2^20 under a 0 / 1 mask.
+ * Workspace: rvc_span_anchors_workspace(L, scales, S, rows) bytes of device memory, 16-byte aligned, contents arbitrary before and after: per row
+ * L + 1 prefix pairs (S, C) and two 64-bit keys for each anchor a row of D = L frames has.  That function refuses (returns RV_ERR_ARG) what the entry
+ * refuses of L, scales, S and rows, but for the margins.
+ * Refused with RV_ERR_ARG, outputs untouched, before any launch: a null sims / mask / out_spans / scores / n_spans / n_found / scales; mode outside
+ * {0, 1}; S outside [1, 8]; L outside [1, 1048576]; rows < 1; a scale with len < 1 or stride outside [1, len], or with margin < 1 in contrast mode;
+ * rpm or rpv below 1, or rows not a multiple of either; peak outside [0, 64]; min_usable < 1; max_spans outside [1, 2048] (rv_span_rank's N); a null
+ * or misaligned workspace, or workspace_bytes below rvc_span_anchors_workspace().
+ * One 1024-thread workgroup per row, rows on the grid's x dimension with 64-bit offsets (no 65535 limit): one walk over the row for the prefix pairs,
+ * one pass over the anchors for their scores, one for the peak test, then an ordered compaction; only a row with n_found > max_spans pays eight more
+ * passes over its anchors for the cut.  1664 B of LDS whatever L; vector stores only, no global atomics (integer LDS atomics count the cut's
+ * histogram), no scratch. */
+#define RVC_ANCHORS_MEAN 0
+#define RVC_ANCHORS_CONTRAST 1
+int64_t rvc_span_anchors_workspace(int32_t L, const int32_t* scales, int32_t S, int32_t rows);
+int rvc_span_anchors(const float* sims, const float* mask, const float* valid, int32_t rpv, int32_t rows, int32_t rpm, int32_t L, const int32_t* scales,
+                     int32_t S, int32_t mode, int32_t peak, int32_t min_usable, int32_t max_spans, float* out_spans, float* scores, int32_t* n_spans,
+                     int32_t* n_found, int32_t* windows, int32_t* scale, void* workspace, int64_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -25,7 +25,7 @@ EXT_SOURCES = ["prefilter_ext.hip"]          # compiled once (in the f16 object 
 EXT_SHARED = ["error.hip"]                   # objects of the f16 build linked in as well, their rv_* names local
 EXT_HEADERS = ["exports_ext.map", os.path.join("..", "..", "include", "revision_hip_ext.h")]
 CHAIN_LIB = os.path.join(HERE, "librevision_hip_chain.so")
-CHAIN_SOURCES = ["prefilter_chain.hip", "spans_chain.hip", "valid_chain.hip", "refine_chain.hip"]    # compiled once, as the companion's
+CHAIN_SOURCES = ["prefilter_chain.hip", "spans_chain.hip", "valid_chain.hip", "refine_chain.hip", "anchors_chain.hip"]    # compiled once, as the companion's
 CHAIN_HEADERS = ["exports_chain.map", os.path.join("..", "..", "include", "revision_hip_chain.h")]
 #: the f32-only libraries: (path, own sources, headers beyond HEADERS, version script); each links EXT_SHARED's objects with their rv_* names local
 COMPANIONS = [(EXT_LIB, EXT_SOURCES, EXT_HEADERS, "exports_ext.map"), (CHAIN_LIB, CHAIN_SOURCES, CHAIN_HEADERS, "exports_chain.map")]

@@ -236,12 +236,14 @@ def ground_queries(text, video, mask, *, top=10, nms_iou=0.5, k=3, pooling="topk
     return _ground("ground_queries", text, video, mask, None, False, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords)
 
 
-def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False, windows=None, refine=None):
+def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou, propose_keywords, masked=False, windows=None, refine=None,
+            anchors=None):
     """``ground_queries``, ``ground_queries_masked`` (``masked``: the proposal and the score stage are the chain library's, under ``valid`` and
     ``skip_nan``), ``ground_queries_refined`` (``refine``: a callable ``(sims, mask, valid, kept spans) -> (ops.RefinedSpans, scores)`` that runs behind
     the gather of the kept spans, on the device; the result is ``(Grounding, RefinedSpans, scores)``) and ``ground_queries_in_windows`` (the rows form - ``windows``: a callable ``(sims, mask, valid, gt) -> (selection or None,
     ops.WindowsValid)`` that runs behind the cosine rows; the proposal and the score stage then run under ITS validity rows, one per row of sims, and
-    the result is ``(Grounding, selection, WindowsValid)``): one body."""
+    the result is ``(Grounding, selection, WindowsValid)``) and ``ground_queries_anchored`` (``anchors``: a callable ``(sims, mask, valid) ->
+    ops.SpanAnchors`` that is the proposal AND the score stage; its caller has checked ``valid``): one body."""
     for name, t in (("text", text), ("video", video), ("mask", mask)) + ((("gt", gt),) if gt is not None else ()):
         if not torch.is_tensor(t):
             raise ValueError(f"{who}: {name} must be a tensor (got {type(t).__name__})")
@@ -275,6 +277,8 @@ def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, t
     if masked:
         ops.window_select_valid(who, valid, mask)
         ops.skip_nan_flag(who, skip_nan)
+    if anchors is not None:
+        ops.span_anchors_checks(who, torch.empty(text.shape[:-1] + (video.shape[1],), device="meta"), mask, valid)
     home = video.device
     dev = _device_of(video, who)
     video = _features_up(video, dev)
@@ -287,6 +291,10 @@ def _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, t
         proposals = ops.span_propose_masked_rows(sims, mask, valid=rows_valid.valid, skip_nan=skip_nan, **propose_keywords)
         scores = ops.span_scores_masked_rows(sims, proposals.spans, mask, valid=rows_valid.valid, skip_nan=skip_nan, k=k, pooling=pooling,
                                              temperature=temperature).scores
+    elif anchors is not None:
+        valid = None if valid is None else ops.h2d(valid, dev)
+        proposals = anchors(sims, mask, valid)
+        scores = proposals.scores
     elif masked:
         valid = None if valid is None else ops.h2d(valid, dev)
         proposals = ops.span_propose_masked(sims, mask, valid=valid, skip_nan=skip_nan, **propose_keywords)
@@ -387,6 +395,18 @@ def refine_spans(sims, spans, mask, *, form="cxw", radius, margin, min_len=1, va
 RefinedGrounding = collections.namedtuple("RefinedGrounding", "grounding refined scores")
 
 
+def _refine_kept(radius, margin, min_len, form, skip_nan, k, pooling, temperature):
+    """The stage behind the gather of the kept spans, for ``_ground(refine=)``: ``(sims, mask, valid, kept spans) -> (ops.RefinedSpans, scores)`` -
+    ``ops.span_refine`` with windows and contrasts, then ``ops.span_scores_masked``' scores of the refined spans (``ops.span_scores_masked_rows``
+    under a validity row per row of sims)."""
+    def refine(sims, m, v, kept):
+        out = ops.span_refine(sims, kept, m, form="cxw", radius=radius, margin=margin, min_len=min_len, valid=v, return_windows=True, return_contrast=True)
+        score = ops.span_scores_masked_rows if v is not None and v.shape == sims.shape and v.shape != m.shape else ops.span_scores_masked
+        scores = score(sims, out.spans, m, valid=v, skip_nan=skip_nan, k=k, pooling=pooling, temperature=temperature).scores
+        return (out._replace(spans=span_cxw_to_xx(out.spans)) if form == "xx" else out), scores
+    return refine
+
+
 def ground_queries_refined(text, video, mask, *, radius, margin, min_len=1, form="cxw", valid=None, skip_nan=False, top=10, nms_iou=0.5, k=3,
                            pooling="topk", temperature=0.01, gt=None, hit_iou=ops.HIT_IOU, **propose_keywords):
     """``ground_queries_masked`` with the kept spans' bounds refined behind the ranking: the same inputs and keywords ->
@@ -404,13 +424,59 @@ def ground_queries_refined(text, video, mask, *, radius, margin, min_len=1, form
     if "min_len" in propose_keywords:                                  # (cannot happen through the signature; stated for a caller's **dict)
         raise TypeError(f"{who}: min_len given twice")
 
-    def refine(sims, m, v, kept):
-        out = ops.span_refine(sims, kept, m, form="cxw", radius=radius, margin=margin, min_len=min_len, valid=v, return_windows=True, return_contrast=True)
-        scores = ops.span_scores_masked(sims, out.spans, m, valid=v, skip_nan=skip_nan, k=k, pooling=pooling, temperature=temperature).scores
-        return (out._replace(spans=span_cxw_to_xx(out.spans)) if form == "xx" else out), scores
     grounding, refined, scores = _ground(who, text, video, mask, valid, skip_nan, top, nms_iou, k, pooling, temperature, gt, hit_iou,
-                                         dict(propose_keywords, min_len=min_len), masked=True, refine=refine)
+                                         dict(propose_keywords, min_len=min_len), masked=True,
+                                         refine=_refine_kept(radius, margin, min_len, form, skip_nan, k, pooling, temperature))
     return RefinedGrounding(grounding, refined, scores)
+
+
+def propose_anchors(sims, mask, *, scales, score="contrast", peak=2, min_usable=1, valid=None, max_spans=256, return_windows=False, return_scale=False):
+    """``ops.span_anchors`` with the device handling of ``propose_spans``: sims [R, L] or [B, Q, L] (the cosine rows; 16-bit rows are read as f32,
+    which is exact), mask [R, L] / [B, L], ``valid`` of the mask's shape or of ``sims``' shape -> ``ops.SpanAnchors(spans, scores, n_spans, n_found,
+    windows, scale)``: per row the local peaks of sliding windows at every one of ``scales``, scored by their frames' mean cosine or its contrast
+    with the frames just outside - candidates that do not depend on the row's range of values, which ``propose_spans``' relative levels do.  One
+    launch, no synchronisation and no device -> host copy when the inputs live on the device; host tensors are staged and the results come back on
+    the device ``sims`` lives on."""
+    who = "propose_anchors"
+    ops.span_anchors_keywords(who, scales, score, peak, min_usable, max_spans, return_windows, return_scale)
+    ops.span_anchors_checks(who, sims, mask, valid)
+    home = sims.device
+    dev = _device_of(sims, who)
+    out = ops.span_anchors(ops.h2d(sims, dev).float(), ops.h2d(mask, dev), scales=scales, score=score, peak=peak, min_usable=min_usable,
+                           valid=None if valid is None else ops.h2d(valid, dev), max_spans=max_spans, return_windows=return_windows,
+                           return_scale=return_scale)
+    return ops.SpanAnchors(*(None if t is None else t.to(home) for t in out))
+
+
+def ground_queries_anchored(text, video, mask, *, scales, score="contrast", peak=2, min_usable=1, valid=None, max_spans=256, top=10, nms_iou=0.5,
+                            gt=None, hit_iou=ops.HIT_IOU, radius=None, margin=None, min_len=1):
+    """``ground_queries`` with the sliding-window generator in place of the threshold one - the zero-shot CLIP baseline of the MAD benchmark: text
+    [B, d] or [B, Q, d], video [B, L, d], mask [B, L], gt [..., 2] rows of (start, end) or None -> ``Grounding(spans, scores, n_keep, proposals,
+    rank)`` with ``proposals`` the ``ops.SpanAnchors`` (windows and scale indices included).  Three device stages: the cosine rows
+    (``ops.frame_cosine[_multi]``), ``ops.span_anchors`` on them (``scales``, ``score``, ``peak``, ``min_usable``, ``valid``, ``max_spans``) - the
+    proposal and the score stage in one: a window's score IS what ranks it - and ``ops.span_rank`` (``top``, ``nms_iou``, ``gt``, ``hit_iou``),
+    whose NMS is what suppresses across scales.  ``valid`` has the mask's shape (a row per video) or ``text``'s leading shape and L (a row per
+    query).  With ``radius`` and ``margin`` (both or neither) the kept spans' bounds are refined behind the ranking by the stage of
+    ``ground_queries_refined`` (``ops.span_refine`` with ``radius``, ``margin``, ``min_len``, then ``ops.span_scores_masked``' top-3 scores of the
+    refined spans with NaN cosines skipped) and the result is ``RefinedGrounding(grounding, refined, scores)``.  A fixed number of launches whatever
+    Q; no synchronisation and no device -> host copy when the inputs live on the device; host tensors are staged and every result comes back on the
+    device ``video`` lives on."""
+    who = "ground_queries_anchored"
+    ops.span_anchors_keywords(who, scales, score, peak, min_usable, max_spans)
+    if (radius is None) != (margin is None):
+        raise ValueError(f"{who}: radius={radius!r} and margin={margin!r} must be given together (refine the kept spans) or not at all")
+    refine = None
+    if radius is not None:
+        ops.span_refine_keywords(who, radius, margin, min_len)
+        refine = _refine_kept(radius, margin, min_len, "cxw", True, 3, "topk", 0.01)
+    elif not (isinstance(min_len, int) and not isinstance(min_len, bool) and min_len >= 1):
+        raise ValueError(f"{who}: min_len={min_len!r} must be a positive integer")
+
+    def anchors(sims, m, v):
+        return ops.span_anchors(sims, m, scales=scales, score=score, peak=peak, min_usable=min_usable, valid=v, max_spans=max_spans, return_windows=True,
+                                return_scale=True)
+    out = _ground(who, text, video, mask, valid, False, top, nms_iou, 3, "topk", 0.01, gt, hit_iou, {}, refine=refine, anchors=anchors)
+    return RefinedGrounding(*out) if refine is not None else out
 
 
 def windows_valid(select, mask, *, rule, win, stride=None, frames="all", num_frames=None, valid=None, return_count=False):

@@ -1,6 +1,7 @@
 """The CLIP grounding chain's wrappers (cosine rows, span scores, ranking, span proposals, window selection, window gather under both window rules, the proposals' cosine scores, the two
 poolings) with their checkers, constants and namedtuples; ``ops`` re-exports every public name.  Every function takes / returns torch DEVICE tensors and enqueues on torch's current stream."""
 import collections
+import collections.abc
 import math
 import numbers
 import struct
@@ -895,6 +896,106 @@ def span_refine(sims, spans, mask, *, form="cxw", radius, margin, min_len=1, val
                                                         min_len, hip.ptr(out), hip.ptr(win), hip.ptr(contrast), hip.ptr(contrast0), hip.stream()),
                         "rvc_span_refine")
     return RefinedSpans(out, win, contrast, contrast0)
+
+
+SPAN_ANCHORS_MAX_SCALES = 8
+SPAN_ANCHORS_MAX_PEAK = 64
+SPAN_ANCHOR_SCORES = {"mean": hip.RVC_ANCHORS_MEAN, "contrast": hip.RVC_ANCHORS_CONTRAST}
+SpanAnchors = collections.namedtuple("SpanAnchors", "spans scores n_spans n_found windows scale")
+
+
+def span_anchors_keywords(who, scales, score="contrast", peak=2, min_usable=1, max_spans=256, return_windows=False, return_scale=False):
+    """The keyword refusals of ``span_anchors`` (raised before any device is looked for) -> (scales as a tuple of (len, stride, margin) triples with
+    the defaults filled in, mode code, peak, min_usable, max_spans) as ``rvc_span_anchors`` takes them."""
+    if isinstance(scales, (str, bytes)) or not isinstance(scales, collections.abc.Sequence):
+        raise ValueError(f"{who}: scales={scales!r} must be a sequence of ints, (len, stride) or (len, stride, margin) tuples")
+    if not 1 <= len(scales) <= SPAN_ANCHORS_MAX_SCALES:
+        raise ValueError(f"{who}: {len(scales)} scales (1 to {SPAN_ANCHORS_MAX_SCALES})")
+    if not isinstance(score, str) or score not in SPAN_ANCHOR_SCORES:
+        raise ValueError(f"{who}: score={score!r} (expected one of {sorted(SPAN_ANCHOR_SCORES)})")
+    triples = []
+    for sc in scales:
+        sc = (sc,) if _is_int(sc) else sc
+        if not (isinstance(sc, (tuple, list)) and 1 <= len(sc) <= 3 and all(_is_int(v) for v in sc)):
+            raise ValueError(f"{who}: scale {sc!r} must be an int, (len, stride) or (len, stride, margin) of ints")
+        length = int(sc[0])
+        if not 1 <= length < 2 ** 31:
+            raise ValueError(f"{who}: scale {tuple(sc)!r} has len={length} (a positive integer)")
+        stride = int(sc[1]) if len(sc) > 1 else max(1, length // 4)
+        margin = int(sc[2]) if len(sc) > 2 else max(1, length // 2)
+        if not 1 <= stride <= length:
+            raise ValueError(f"{who}: scale {tuple(sc)!r} has stride={stride} (an integer in [1, len={length}])")
+        if not 1 <= margin < 2 ** 31:
+            raise ValueError(f"{who}: scale {tuple(sc)!r} has margin={margin} (a positive integer)")
+        triples.append((length, stride, margin))
+    if not (_is_int(peak) and 0 <= peak <= SPAN_ANCHORS_MAX_PEAK):
+        raise ValueError(f"{who}: peak={peak!r} must be an integer in [0, {SPAN_ANCHORS_MAX_PEAK}]")
+    if not (_is_int(min_usable) and 1 <= min_usable < 2 ** 31):
+        raise ValueError(f"{who}: min_usable={min_usable!r} must be a positive integer")
+    if not (_is_int(max_spans) and 1 <= max_spans <= SPAN_RANK_MAX):
+        raise ValueError(f"{who}: max_spans={max_spans!r} must be an integer in [1, {SPAN_RANK_MAX}]")
+    for name, v in (("return_windows", return_windows), ("return_scale", return_scale)):
+        if not (isinstance(v, (bool, numbers.Integral)) and v in (0, 1)):
+            raise ValueError(f"{who}: {name}={v!r} must be True or False")
+    return tuple(triples), SPAN_ANCHOR_SCORES[score], int(peak), int(min_usable), int(max_spans)
+
+
+def span_anchors_checks(who, sims, mask, valid=None):
+    """The tensor refusals of ``span_anchors`` (raised before any device is looked for) -> (leading shape, rows, rows per mask row, rows per validity
+    row, L).  ``valid`` has the mask's shape (a row per mask row) or ``sims``' shape (a row per row), as ``span_refine`` takes it."""
+    lead, rows, rpm, L = span_propose_shapes(who, sims, mask)
+    rpv = rpm
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.shape not in (mask.shape, sims.shape):
+            raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of mask's shape "
+                             f"{tuple(mask.shape)}, a validity row per mask row, or of sims' shape {tuple(sims.shape)}, one per row)")
+        if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
+            raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+        rpv = rpm if valid.shape == mask.shape else 1
+    return lead, rows, rpm, rpv, L
+
+
+def span_anchors(sims, mask, *, scales, score="contrast", peak=2, min_usable=1, valid=None, max_spans=256, return_windows=False, return_scale=False):
+    """Multi-scale sliding-window proposals on the device (``rvc_span_anchors`` of the chain library), the chain's second generator beside
+    ``span_propose``: sims f32 [R,L] or [B,Q,L] (cosine rows), mask [R,L] / [B,L] -> SpanAnchors(spans f32 [...,max_spans,2] as (centre, width) with
+    NaN padding, scores f32 [...,max_spans] with NaN padding, n_spans i32 [...], n_found i32 [...], windows i32 [...,max_spans,2] with (-1, -1)
+    padding, scale i32 [...,max_spans] with -1 padding); ``windows`` and ``scale`` are None unless asked for.  ``scales`` is a sequence of up to 8
+    window lengths in frames, or of (len, stride) or (len, stride, margin) tuples (``stride = max(1, len // 4)``, ``margin = max(1, len // 2)``
+    where left out).  Every scale's windows start at 0, stride, 2 stride, .. inside the duration, with one more flush with its end where that leaves
+    frames over.  ``score="mean"``: the mean of a window's usable frames; ``"contrast"``: that mean minus the mean of the usable frames within
+    ``margin`` frames outside - ``span_refine``'s contrast, on similarities quantised to 2^-24 so that the sums are exact.  A window needs
+    ``min_usable`` usable frames (and, for a contrast, one outside).  Within a scale a window is kept when none of the ``peak`` windows on either
+    side scores higher (ties: the earlier one stays, so a flat stretch gives one span); scales do not suppress each other - ``span_rank``'s NMS does.
+    Spans come in (scale, start) order; if a row has more peaks than ``max_spans`` (``n_found > n_spans``) the best-scoring ``max_spans`` are the ones
+    kept.  ``valid`` (bool, uint8 or float; None: every frame) hides the frames where it is 0 - of the mask's shape it is a row per mask row, of
+    ``sims``' shape a row per row; a NaN similarity is never usable.  Unlike ``span_propose``'s relative levels nothing depends on the row's range of
+    values.  One launch (a mask or a valid that is not f32 adds a cast kernel), no synchronisation, no host copy; the kernel's workspace comes from
+    torch's caching allocator.  The full rule stands in include/revision_hip_chain.h."""
+    who = "span_anchors"
+    table, mode, peak, min_usable, N = span_anchors_keywords(who, scales, score, peak, min_usable, max_spans, return_windows, return_scale)
+    lead, rows, rpm, rpv, L = span_anchors_checks(who, sims, mask, valid)
+    if sims.dtype != torch.float32:
+        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
+    dev = sims.device
+    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
+    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
+    scale = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_scale else None
+    flat = (hip.C.c_int32 * (3 * len(table)))(*(min(v, 2 ** 31 - 1) for t in table for v in t))
+    lib = hip.chain_lib()
+    nbytes = lib.rvc_span_anchors_workspace(L, flat, len(table), rows)
+    if nbytes < 0:
+        hip.chain_check(int(nbytes), "rvc_span_anchors_workspace")
+    work = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
+    sims, mask = sims.contiguous(), mask.float().contiguous()
+    valid = valid.float().contiguous() if valid is not None else None
+    hip.chain_check(lib.rvc_span_anchors(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), rpv, rows, rpm, L, flat, len(table), mode, peak, min_usable, N,
+                                         hip.ptr(spans), hip.ptr(scores), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows), hip.ptr(scale), hip.ptr(work),
+                                         work.numel(), hip.stream()), "rvc_span_anchors")
+    return SpanAnchors(spans, scores, n_spans, n_found, windows, scale)
 
 
 def proposal_slice(a, b, T):

@@ -244,6 +244,7 @@ CHAIN_LIB_PATH = os.environ.get("REVISION_HIP_LIB_CHAIN") or os.path.join(_HERE,
 RVC_ABI_VERSION = 1
 RV_FRAMES_ALL, RV_FRAMES_SAMPLED = 0, 1
 RVC_MAX_SAMPLED = 1024
+RVC_ANCHORS_MEAN, RVC_ANCHORS_CONTRAST = 0, 1
 #: every symbol include/revision_hip_chain.h declares: name -> (restype, argtypes)
 CHAIN_SIGNATURES = {
     "rvc_abi_version": (C.c_int, []),
@@ -257,6 +258,8 @@ CHAIN_SIGNATURES = {
     "rvc_span_propose_masked_rows": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, C.POINTER(_f), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p,
                                                _p, _p, _p]),
     "rvc_span_refine": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    "rvc_span_anchors_workspace": (_i64, [_i32, C.POINTER(_i32), _i32, _i32]),
+    "rvc_span_anchors": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 _chain = None
 

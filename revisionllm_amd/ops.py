@@ -20,7 +20,8 @@ from .grounding import (HIT_IOU, SPAN_FORMS, SPAN_POOLINGS, SPAN_PROPOSE_LEVELS,
                         WINDOW_SELECT_MAX_SAMPLED, window_select_frames, window_select_frames_keywords, window_select_valid, MaskedSpanScores, span_propose_masked,
                         span_scores_masked, span_scores_masked_checks, skip_nan_flag, WINDOWS_VALID_MAX_KEEP, WindowsValid, windows_valid, windows_valid_checks, span_rows_valid,
                         span_scores_masked_rows, span_propose_masked_rows, SPAN_REFINE_MAX_MARGIN, SPAN_REFINE_MAX_RADIUS, RefinedSpans, span_refine,
-                        span_refine_checks, span_refine_keywords)
+                        span_refine_checks, span_refine_keywords, SPAN_ANCHORS_MAX_PEAK, SPAN_ANCHORS_MAX_SCALES, SPAN_ANCHOR_SCORES, SpanAnchors, span_anchors,
+                        span_anchors_checks, span_anchors_keywords)
 from .utils import hashinit
 
 
