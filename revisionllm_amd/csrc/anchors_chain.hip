@@ -6,11 +6,9 @@
 // Nothing here depends on the row's range of values, which is what rv_span_propose's relative levels depend on: one outlier frame moves no anchor's
 // score but those it lies in or next to.
 // Similarities are quantised to integers (2^24 steps to the unit), so every sum is exact and no result depends on the order of any scan or reduction:
-// the kernel matches a numpy statement of the rule (tests/span_anchors_oracle.py) bit for bit.  The duration rule (the mask row's raw f32 sum in
-// span_scores_kernel's order, then duration_frames of grounding.h), the usable-frame rule and the quantisation are rvc_span_refine's, STATED AGAIN here
-// (refine_chain.hip keeps its own so that its instance keeps its instruction stream); the span encoding is span_propose.h's, likewise.
-// tests/test_span_anchors_host_logic.py and tests/test_gpu_span_anchors.py hold the copies to the originals through the round trip
-// out_spans -> rv_span_scores' windows == windows.  The kernel reads f32 rows only, so one library serves both operand flavours.
+// the kernel matches a numpy statement of the rule (tests/span_anchors_oracle.py) bit for bit.  The duration (span_mask_sum, duration_frames), the
+// quantisation of a usable similarity (sim_usable, sim_quantise), the contrast (contrast_f64) and the span encoding (span_encode) are grounding.h's
+// helpers, the ones span_refine_kernel calls.  The kernel reads f32 rows only, so one library serves both operand flavours.
 #include "grounding.h"
 
 #include "../../include/revision_hip_chain.h"
@@ -85,7 +83,7 @@ __device__ __forceinline__ int an_block_scan(int v, int* sc, int& total) {
 }
 
 // One 1024-thread workgroup per row (blockIdx.x).
-// (1) duration: span_refine_kernel's sum of the mask row, bit for bit - waves 0 to 3 add it up as that kernel's four waves do - and D.
+// (1) duration: span_mask_sum, span_refine_kernel's sum of the mask row - waves 0 to 3 add it up as that kernel's four waves do - and D.
 // (2) one walk over the row's D frames in tiles of 4096, four consecutive frames per thread: (q, usable) per frame, the thread's running sums, a
 //     wave-wide inclusive scan of the threads' totals, the waves' totals through LDS (two buffers in turn: one barrier per tile), and the prefix
 //     pair of point t + 1 goes to the row's workspace.
@@ -109,15 +107,7 @@ __global__ __launch_bounds__(AN_TPB) void span_anchors_kernel(const AnchorArgs a
     const int64_t r = blockIdx.x;
     const int L = a.L, N = a.N;
 
-    if (tid < 256) {   // span_scores_kernel's duration: the raw f32 sum with the wave partials added pairwise
-        const float* m = a.mask + (r / a.rpm) * L;
-        float s = 0.f;
-        for (int l = tid; l < L; l += 256) s += m[l];
-        s = wave_sum(s);
-        if (lane == 0) red[wave] = s;
-    }
-    __syncthreads();
-    const float dur = (red[0] + red[1]) + (red[2] + red[3]);
+    const float dur = span_mask_sum<AN_TPB>(a.mask, r, a.rpm, L, red);      // (waves 0 to 3 add; the others wait at its barrier)
     const int D = duration_frames(dur, L);
 
     if (tid == 0) {
@@ -157,8 +147,8 @@ __global__ __launch_bounds__(AN_TPB) void span_anchors_kernel(const AnchorArgs a
                 const bool in = t < D;
                 const float v = in ? s[t] : 0.f;
                 const float w = (in && vr) ? vr[t] : 1.f;
-                const bool ok = in && w != 0.f && v == v;
-                q[e] = ok ? (long long)__float2int_rn(__fmul_rn(fminf(fmaxf(v, -1.f), 1.f), 16777216.f)) : 0;      // exact product, ties to even; +-inf clamps to +-1
+                const bool ok = in && w != 0.f && sim_usable(v);
+                q[e] = ok ? sim_quantise(v) : 0;
                 u[e] = ok ? 1 : 0;
             }
 #pragma unroll
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(AN_TPB) void span_anchors_kernel(const AnchorArgs a
             const long long Sout = (Px.s - Pm.s) + (Pp.s - Py.s);
             const int Cout = (Px.c - Pm.c) + (Pp.c - Py.c);
             ok = ok && Cout > 0;
-            j = __dsub_rn(__ddiv_rn((double)Sin, (double)(Cin > 0 ? Cin : 1)), __ddiv_rn((double)Sout, (double)(Cout > 0 ? Cout : 1)));
+            j = contrast_f64(Sin, Cin > 0 ? Cin : 1, Sout, Cout > 0 ? Cout : 1);
         } else {
             j = __ddiv_rn((double)Sin, (double)(Cin > 0 ? Cin : 1));
         }
@@ -316,10 +306,7 @@ __global__ __launch_bounds__(AN_TPB) void span_anchors_kernel(const AnchorArgs a
                 const int len = sLen[k];
                 const int x = start_of(idx, len, sStride[k]), y = x + len;
                 const int64_t o = r * N + pos;
-                // rv_span_propose's encoding (span_propose.h), operation for operation
-                const float flo = (float)x, fhi = (float)y;
-                a.out_spans[o * 2] = __fdiv_rn(__fmul_rn(__fadd_rn(flo, fhi), 0.5f), dur);
-                a.out_spans[o * 2 + 1] = __fdiv_rn(__fsub_rn(__fsub_rn(fhi, flo), 0.5f), dur);
+                span_encode(x, y, dur, a.out_spans[o * 2], a.out_spans[o * 2 + 1]);      // rv_span_propose's encoding
                 a.scores[o] = __double2float_rn(an_value(key));
                 if (a.windows) {
                     a.windows[o * 2] = x;

@@ -1,6 +1,10 @@
 // What the stages of the CLIP grounding chain share, one definition each: the frame order of the score kernels, the rank key of a score, the bitonic
-// sort of (key, index) pairs, the duration rule, the two window rules (stage 2's shifted windows, stage 1's clipped ones), the sampled frames of a window and the small helpers around them.  Included by the chain's translation units only (sample.hip for
-// rv_topk_cosine / rv_topk_pool, similarity.hip, rank.hip, propose.hip, prefilter.hip, prefilter_ext.hip, prefilter_chain.hip, gather.hip): two stages that have to agree bit for bit call the same code.
+// sort of (key, index) pairs, the two duration sums (block_mask_sum, and span_mask_sum for the span kernels) with the duration rule, the span rules
+// (SPAN_NOT_FINITE and span_slice: a span's frame window; span_encode: a frame window's (centre, width); sim_usable / sim_quantise: a usable similarity as an integer;
+// contrast_f64: the contrast of exact integer sums), the two window rules (stage 2's shifted windows, stage 1's clipped ones), the sampled frames of a
+// window and the small helpers around them.  Included by the chain's translation units only (sample.hip for rv_topk_cosine / rv_topk_pool,
+// similarity.hip, rank.hip, propose.hip, prefilter.hip, prefilter_ext.hip, gather.hip, and the chain library's prefilter_chain.hip, spans_chain.hip,
+// valid_chain.hip, refine_chain.hip, anchors_chain.hip): two stages that have to agree bit for bit call the same code.
 #pragma once
 #include "kernels.h"
 
@@ -114,6 +118,65 @@ __device__ __forceinline__ float block_mask_sum(const float* __restrict__ m, int
 __device__ __forceinline__ int duration_frames(float dur, int L) {
     if (!(fabsf(dur) < INFINITY && dur >= 1.f)) return 0;
     return dur >= (float)L ? L : (int)floorf(dur);
+}
+
+// ---- spans ----
+// The span kernels' sum of the mask row of row `row` - row / rpm of `mask`, L floats a row; the address is made inside the adding threads' branch, where
+// the kernels had it - (span_scores_kernel, span_refine_kernel, span_anchors_kernel), the same bits in every thread of the block: the
+// raw f32 sum over the frames tid, tid + 256, .. of the block's first 256 threads, the wave's sum, then the four wave partials added pairwise,
+// (r0 + r1) + (r2 + r3).  NOT block_mask_sum(): other bits on a mask that is not 0 / 1.  All TPB threads of the block call (TPB >= 256; a larger
+// block's other threads only wait); red: 4 floats of LDS.  One barrier, behind the stores to red and in front of its loads: part of the contract -
+// no thread may leave the kernel before the call, and what the caller stored to LDS before it is visible behind it.
+template <int TPB, typename Row>
+__device__ __forceinline__ float span_mask_sum(const float* __restrict__ mask, Row row, int rpm, int L, float* red) {
+    const int tid = threadIdx.x;
+    if (TPB == 256 || tid < 256) {
+        const float* m = mask + (int64_t)(row / rpm) * L;      // (inside the branch: the threads that only wait do not divide)
+        float s = 0.f;
+        for (int l = tid; l < L; l += 256) s += m[l];
+        s = wave_sum(s);
+        if ((tid & 63) == 0) red[tid >> 6] = s;
+    }
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// f32 -> int32 as torch's .to(torch.int32) gives it for the values the reference meets; outside int32's range (undefined there) the value saturates
+__device__ __forceinline__ int sat_i32(float v) {
+    return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
+}
+// The frame window [lo, hi) of a span in a row of L frames, the reference's rule.  The caller scales the span's ends x1 and x2 (fractions of the duration;
+// c - 0.5 w and c + 0.5 w, or start and end: its form) to frames, p = __fmul_rn(x, dur), and tests them ITSELF, SPAN_NOT_FINITE(p1, p2) -> a void span, the
+// window (-1, -1): the test and its branch stay in the kernel's text because a helper that returns it makes the compiler lay the kernel out otherwise
+// (the block of the void span in front of the body; profiles/grounding_rules_isa.txt).  span_slice then gives, for finite p1 and p2,
+// start = max(0, int(floor(p1))), end = int(ceil(p2)) and Python's range(L)[start:end] over the ARRAY length L: lo = min(start, L),
+// hi = end < 0 ? max(end + L, 0) : min(end, L).
+#define SPAN_NOT_FINITE(p1, p2) (!(fabsf(p1) < INFINITY) || !(fabsf(p2) < INFINITY))      /* NaN or +-inf */
+__device__ __forceinline__ void span_slice(float p1, float p2, int L, int& lo, int& hi) {
+    int start = sat_i32(floorf(p1));
+    start = start < 0 ? 0 : start;
+    const int end = sat_i32(ceilf(p2));
+    lo = start < L ? start : L;
+    if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
+    else hi = end < L ? end : L;
+}
+// The (centre, width) of the frame window [lo, hi) as the span generators hand it on: c = ((lo + hi) * 0.5) / dur, w = ((hi - lo) - 0.5) / dur, every
+// operation rounded to f32 on its own.  span_slice() of it scaled by the same dur gives [lo, hi) back.
+__device__ __forceinline__ void span_encode(int lo, int hi, float dur, float& c, float& w) {
+    const float flo = (float)lo, fhi = (float)hi;
+    c = __fdiv_rn(__fmul_rn(__fadd_rn(flo, fhi), 0.5f), dur);
+    w = __fdiv_rn(__fsub_rn(__fsub_rn(fhi, flo), 0.5f), dur);
+}
+// A similarity that is not a number is never usable; a usable one counts as the integer round(clamp(v, -1, 1) * 2^24): an exact product, ties to even,
+// +-inf clamps to +-1.  Sums of these are exact, so no result depends on the order of a scan or a reduction.  (When the similarity is loaded - behind
+// the validity entry or next to it - is the caller's.)
+__device__ __forceinline__ bool sim_usable(float v) { return v == v; }
+__device__ __forceinline__ long long sim_quantise(float v) {
+    return (long long)__float2int_rn(__fmul_rn(fminf(fmaxf(v, -1.f), 1.f), 16777216.f));
+}
+// J = Sin / Cin - Sout / Cout in float64 from exact integer sums and counts (two divisions and a subtraction, each rounded on its own).  Whether the
+// pair is admissible is the caller's test, and so is what stands in for a count of 0.
+__device__ __forceinline__ double contrast_f64(long long Sin, int Cin, long long Sout, int Cout) {
+    return __dsub_rn(__ddiv_rn((double)Sin, (double)Cin), __ddiv_rn((double)Sout, (double)Cout));
 }
 
 // ---- windows ----

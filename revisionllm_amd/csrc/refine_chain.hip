@@ -3,12 +3,10 @@
 //                     with the largest contrast between the usable frames inside and the usable frames just outside, under the chain's validity
 //                     rows; the result comes back in rv_span_propose's (centre, width) encoding, so rv_span_scores / rv_span_rank read it - one launch
 // Similarities are quantised to integers (2^24 steps to the unit), so every sum is exact and no result depends on the order of any scan or reduction:
-// the kernel matches a numpy statement of the rule bit for bit.  The duration is span_scores_kernel's sum and duration_frames (grounding.h).  The
-// window rule is span_scores.h's, STATED A SECOND TIME here (that header's rule stays inline in its kernel so that the five existing instances keep
-// their instruction streams); the span encoding is span_propose.h's, likewise.  tests/test_span_refine_host_logic.py and tests/test_gpu_span_refine.py
-// hold the copies to the originals through the round trip out_spans -> rv_span_scores' windows == windows.  The kernel reads f32 rows only, so one
-// library serves both operand flavours.
-#include "span_scores.h"
+// the kernel matches a numpy statement of the rule bit for bit.  The duration (span_mask_sum, duration_frames), the window rule (SPAN_NOT_FINITE, span_slice), the
+// span encoding (span_encode), the quantisation (sim_usable, sim_quantise) and the contrast (contrast_f64) are grounding.h's helpers, the ones
+// span_scores_kernel, span_propose_kernel and span_anchors_kernel call.  The kernel reads f32 rows only, so one library serves both operand flavours.
+#include "grounding.h"
 
 #include "../../include/revision_hip_chain.h"
 
@@ -36,8 +34,8 @@ __device__ __forceinline__ void rf_frame(const float* __restrict__ s, const floa
     u = 0;
     if (vr && !(vr[t] != 0.f)) return;
     const float v = s[t];
-    if (v != v) return;
-    q = (long long)__float2int_rn(__fmul_rn(fminf(fmaxf(v, -1.f), 1.f), 16777216.f));      // exact product, ties to even; +-inf clamps to +-1
+    if (!sim_usable(v)) return;
+    q = sim_quantise(v);
     u = 1;
 }
 
@@ -83,8 +81,8 @@ __device__ __forceinline__ bool rf_before(const RfBest& x, const RfBest& y) {
     return x.b < y.b;
 }
 
-// One wave per span (4 spans per block, all of row blockIdx.y), as span_scores_kernel.  The block adds the row's mask row up (that kernel's sum, bit
-// for bit), then each wave: (1) its span's window [lo, hi) by rv_span_scores' rule, cut to the D frames of the duration: (lo0, hi0); (2) the prefix
+// One wave per span (4 spans per block, all of row blockIdx.y), as span_scores_kernel.  The block adds the row's mask row up (that kernel's sum:
+// span_mask_sum), then each wave: (1) its span's window [lo, hi) by rv_span_scores' rule, cut to the D frames of the duration: (lo0, hi0); (2) the prefix
 // pairs (S, C) - int64 sum of the quantised usable similarities, int32 count of usable frames - at every point of the two zones
 // [lo0 - radius - margin, lo0 + radius] and [hi0 - radius, hi0 + radius + margin] cut to [0, D], into the wave's table in LDS (one zone where they
 // meet; else the frames between them enter through one lane-strided integer reduction); (3) the candidate pairs dealt to the lanes, four look-ups, two
@@ -96,21 +94,13 @@ __global__ __launch_bounds__(256) void span_refine_kernel(const RefineArgs a) {
     __shared__ int tabC[4][RF_POINTS];
     const int r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int L = a.L;
-    {   // span_scores_kernel's duration: the raw f32 sum with the wave partials added pairwise
-        const float* m = a.mask + (int64_t)(r / a.rpm) * L;
-        float s = 0.f;
-        for (int l = tid; l < L; l += 256) s += m[l];
-        s = wave_sum(s);
-        if (lane == 0) red[wave] = s;
-    }
-    __syncthreads();
-    const float dur = (red[0] + red[1]) + (red[2] + red[3]);
+    const float dur = span_mask_sum<256>(a.mask, r, a.rpm, L, red);
     const int n = blockIdx.x * 4 + wave;
     if (n >= a.N) return;                                          // (no block-wide barrier behind this line)
     const int D = duration_frames(dur, L);
     const int64_t sp = (int64_t)r * a.N + n;
 
-    // ---- the window: rv_span_scores' rule (span_scores.h), operation for operation ----
+    // ---- the window: rv_span_scores' rule (span_slice), cut to the duration ----
     float x1, x2;
     if (a.form == 1) {
         const float c = a.spans[sp * 2], hw = __fmul_rn(0.5f, a.spans[sp * 2 + 1]);
@@ -122,14 +112,9 @@ __global__ __launch_bounds__(256) void span_refine_kernel(const RefineArgs a) {
     }
     const float p1 = __fmul_rn(x1, dur), p2 = __fmul_rn(x2, dur);
     int lo0 = 0, hi0 = 0;
-    if (fabsf(p1) < INFINITY && fabsf(p2) < INFINITY) {
-        int start = sat_i32(floorf(p1));
-        start = start < 0 ? 0 : start;
-        const int end = sat_i32(ceilf(p2));
-        const int lo = start < L ? start : L;
-        int hi;
-        if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
-        else hi = end < L ? end : L;
+    if (!SPAN_NOT_FINITE(p1, p2)) {
+        int lo, hi;
+        span_slice(p1, p2, L, lo, hi);
         lo0 = lo < D ? lo : D;
         hi0 = hi < D ? hi : D;
     }
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(256) void span_refine_kernel(const RefineArgs a) {
         const long long Sin = Sy - Sx, Sout = (Sx - tS[ixm]) + (tS[iyp] - Sy);
         const int Cin = Cy - Cx, Cout = (Cx - tC[ixm]) + (tC[iyp] - Cy);
         if (!(Cin > 0 && Cout > 0)) return false;
-        j = __dsub_rn(__ddiv_rn((double)Sin, (double)Cin), __ddiv_rn((double)Sout, (double)Cout));
+        j = contrast_f64(Sin, Cin, Sout, Cout);
         return true;
     };
 
@@ -234,10 +219,7 @@ __global__ __launch_bounds__(256) void span_refine_kernel(const RefineArgs a) {
     if (lane == 0) {
         const bool found = best.a >= 0;
         const int ra = found ? best.a : lo0, rb = found ? best.b : hi0;
-        // rv_span_propose's encoding (span_propose.h), operation for operation
-        const float flo = (float)ra, fhi = (float)rb;
-        a.out_spans[sp * 2] = __fdiv_rn(__fmul_rn(__fadd_rn(flo, fhi), 0.5f), dur);
-        a.out_spans[sp * 2 + 1] = __fdiv_rn(__fsub_rn(__fsub_rn(fhi, flo), 0.5f), dur);
+        span_encode(ra, rb, dur, a.out_spans[sp * 2], a.out_spans[sp * 2 + 1]);      // rv_span_propose's encoding
         if (a.windows) {
             a.windows[sp * 2] = ra;
             a.windows[sp * 2 + 1] = rb;

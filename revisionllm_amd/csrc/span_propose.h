@@ -252,9 +252,7 @@ __global__ __launch_bounds__(SP_TPB) void span_propose_kernel(const ProposeArgsO
                         const int pos = base[l] + cnt[l] + before + place[l];
                         if (pos < N) {
                             const int64_t o = (r * N + pos) * 2;
-                            const float flo = (float)lo[l], fhi = (float)(t + 1);
-                            a.spans[o] = __fdiv_rn(__fmul_rn(__fadd_rn(flo, fhi), 0.5f), dur);
-                            a.spans[o + 1] = __fdiv_rn(__fsub_rn(__fsub_rn(fhi, flo), 0.5f), dur);
+                            span_encode(lo[l], t + 1, dur, a.spans[o], a.spans[o + 1]);
                             if (a.windows) {
                                 a.windows[o] = lo[l];
                                 a.windows[o + 1] = t + 1;

@@ -1,15 +1,10 @@
 // The span-score kernel of the CLIP grounding chain, one source for rv_span_scores / rv_span_scores_multi (similarity.hip: the default instances) and
 // rvc_span_scores_masked / rvc_span_scores_masked_rows (spans_chain.hip: MASKED = true, a per-frame validity row and / or the non-finite similarities skipped).  The window rule
-// lives here with it: the two entries agree on a window bit for bit because they run this code.
+// is SPAN_NOT_FINITE / span_slice() of grounding.h, the duration span_mask_sum(): the entries agree on a window bit for bit because they run this code.
 #pragma once
 #include "grounding.h"
 
 namespace {
-
-// f32 -> int32 as torch's .to(torch.int32) gives it for the values the reference meets; outside int32's range (undefined there) the value saturates
-__device__ __forceinline__ int sat_i32(float v) {
-    return v >= 2147483648.f ? 0x7fffffff : (v <= -2147483648.f ? (int)0x80000000 : (int)v);
-}
 
 // What the masked instances take beyond the default ones' arguments (nothing, for those: their argument list is the parent's)
 template <bool MASKED>
@@ -24,9 +19,9 @@ struct SpanMasking<true> {
 
 // One wave per span (4 spans per block, all of row blockIdx.y).  A row is a video (rpm = 1, rv_span_scores) or one of a video's rpm queries
 // (rv_span_scores_multi): similarities, spans and outputs are indexed by the row, the mask - and hence the duration - by row / rpm ("rows per mask").
-// The block adds the row's mask row up first (duration; 0 / 1 masks: exact in any
+// The block adds the row's mask row up first (span_mask_sum: the duration; 0 / 1 masks: exact in any
 // order up to 2^24 frames; every block of a video repeats that sum - N / 4 reads of an L2-resident row of 4 L bytes - which is the price of keeping the
-// matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row:
+// matching call at two launches with no pass of its own for B numbers), then each wave turns its (centre, width) into the reference's slice of the similarity row (span_slice):
 //   x1 = c - 0.5 w, x2 = c + 0.5 w, p = x * duration (every operation rounded to f32 on its own: no contraction), start = max(0, int(floor(p1))),
 //   end = int(ceil(p2)), and Python's range(L)[start:end] over the ARRAY length L: lo = min(start, L), hi = end < 0 ? max(end + L, 0) : min(end, L).
 // Every read of sims lies in [b L + lo, b L + hi).  MODE 0: the sum of the min(k, hi - lo) first entries in rank order (NaN, larger value, smaller
@@ -43,22 +38,14 @@ __global__ __launch_bounds__(256) void span_scores_kernel(const float* __restric
                                                           int32_t* __restrict__ windows, const SpanMasking<MASKED> mk) {
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {   // not block_mask_sum(): the contract here is the raw f32 sum with the wave partials added pairwise - other bits on a mask that is not 0 / 1
-        const float* m = mask + (int64_t)(b / rpm) * L;
-        float s = 0.f;
-        for (int l = tid; l < L; l += 256) s += m[l];
-        s = wave_sum(s);
-        if (lane == 0) red[wave] = s;
-    }
-    __syncthreads();
-    const float duration = (red[0] + red[1]) + (red[2] + red[3]);
+    const float duration = span_mask_sum<256>(mask, b, rpm, L, red);
     const int n = blockIdx.x * 4 + wave;
     if (n >= N) return;
     const int64_t sp = (int64_t)b * N + n;
     const float c = spans[sp * 2], w = spans[sp * 2 + 1];
     const float hw = __fmul_rn(0.5f, w);
     const float p1 = __fmul_rn(__fsub_rn(c, hw), duration), p2 = __fmul_rn(__fadd_rn(c, hw), duration);
-    if (!(fabsf(p1) < INFINITY) || !(fabsf(p2) < INFINITY)) {      // NaN or +-inf
+    if (SPAN_NOT_FINITE(p1, p2)) {
         if (lane == 0) {
             scores[sp] = qnan();
             if (windows) windows[sp * 2] = windows[sp * 2 + 1] = -1;
@@ -68,13 +55,8 @@ __global__ __launch_bounds__(256) void span_scores_kernel(const float* __restric
         }
         return;
     }
-    int start = sat_i32(floorf(p1));
-    start = start < 0 ? 0 : start;
-    const int end = sat_i32(ceilf(p2));
-    const int lo = start < L ? start : L;
-    int hi;
-    if (end < 0) { hi = end + L; hi = hi < 0 ? 0 : hi; }
-    else hi = end < L ? end : L;
+    int lo, hi;
+    span_slice(p1, p2, L, lo, hi);
     if (lane == 0 && windows) {
         windows[sp * 2] = lo;
         windows[sp * 2 + 1] = hi;

@@ -5,6 +5,7 @@ import collections.abc
 import math
 import numbers
 import struct
+import types
 
 import torch
 
@@ -192,6 +193,42 @@ def _f32(v):
         return math.copysign(math.inf, v)
 
 
+def _flag(who, name, v):
+    """The refusal of an on / off keyword -> 0 / 1."""
+    if not (isinstance(v, (bool, numbers.Integral)) and v in (0, 1)):
+        raise ValueError(f"{who}: {name}={v!r} must be True or False")
+    return int(bool(v))
+
+
+def _rows_f32(*tensors):
+    """The f32-contiguous form of each tensor (None stays None), what the kernels read.  The caller keeps what comes back referenced until its call is
+    queued: two temporaries dropped one after the other would share one block of the allocator."""
+    return tuple(None if t is None else t.float().contiguous() for t in tensors)
+
+
+def _shape(t):
+    return tuple(t.shape) if torch.is_tensor(t) else "?"
+
+
+def _valid_rows(who, valid, like, expected):
+    """The one check of a ``valid``: a bool, uint8 or floating-point tensor with the shape of one of the tensors ``like``; ``expected`` is how the caller's
+    refusal describes them -> whether it has the shape of the first."""
+    if not torch.is_tensor(valid) or not all(torch.is_tensor(t) for t in like) or all(valid.shape != t.shape for t in like):
+        raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of {expected})")
+    if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
+        raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+    return valid.shape == like[0].shape
+
+
+def _rows_per_valid(who, valid, mask, sims, rpm):
+    """``span_refine``'s and ``span_anchors``' ``valid``: None, of the mask's shape (a row per mask row: rpm) or of ``sims``' shape (a row per row: 1) ->
+    rows per validity row."""
+    if valid is None or _valid_rows(who, valid, (mask, sims), f"mask's shape {tuple(mask.shape)}, a validity row per mask row, or of sims' shape "
+                                                           f"{tuple(sims.shape)}, one per row"):
+        return rpm
+    return 1
+
+
 def span_propose_keywords(who, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None, max_spans=256):
     """The keyword refusals of ``span_propose`` (raised before any device is looked for) -> (levels as a tuple of floats, relative as 0 / 1, smooth, gap,
     min_len, max_len with None as 0, max_spans) as ``rv_span_propose`` takes them."""
@@ -201,8 +238,7 @@ def span_propose_keywords(who, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth
         raise ValueError(f"{who}: levels={levels!r} must be a sequence of numbers") from None
     if not 1 <= len(levels) <= SPAN_PROPOSE_MAX_LEVELS:
         raise ValueError(f"{who}: {len(levels)} levels (1 to {SPAN_PROPOSE_MAX_LEVELS})")
-    if not (isinstance(relative, (bool, numbers.Integral)) and relative in (0, 1)):
-        raise ValueError(f"{who}: relative={relative!r} must be True or False")
+    _flag(who, "relative", relative)
     as_f32 = [_f32(v) for v in levels]                   # what the kernel compares
     for i, v in enumerate(as_f32):
         if not math.isfinite(v):
@@ -254,12 +290,23 @@ def span_propose(sims, mask, *, levels=SPAN_PROPOSE_LEVELS, relative=True, smoot
     span if its length lies in [min_len, max_len] and the next level has no identical one.  Highest level first, then ascending start;
     ``n_found > n_spans`` shows that ``max_spans`` cut the list.  One launch (a mask that is not f32 adds a cast kernel, ``return_smoothed`` a fill), no
     synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
-    who = "span_propose"
-    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
+    return _span_propose("span_propose", sims, mask, "none", None, False, (levels, relative, smooth, gap, min_len, max_len, max_spans), return_windows,
+                         return_smoothed)
+
+
+def _span_propose(who, sims, mask, validity, valid, skip_nan, keywords, return_windows, return_smoothed):
+    """One body for ``span_propose`` (``validity`` "none": ``rv_span_propose``), ``span_propose_masked`` ("mask": ``valid`` is None or has the mask's shape)
+    and ``span_propose_masked_rows`` ("rows": ``valid`` has ``sims``' shape); each calls its own entry."""
+    lv, relative, smooth, gap, min_len, max_len, N = span_propose_keywords(who, *keywords)
+    if validity != "none":
+        skip_nan = skip_nan_flag(who, skip_nan)
     lead, R, rpm, L = span_propose_shapes(who, sims, mask)
+    if validity == "rows":
+        span_rows_valid(who, valid, sims)
+    elif validity == "mask":
+        window_select_valid(who, valid, mask)
     if sims.dtype != torch.float32:
         raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
-    lv, relative, smooth, gap, min_len, max_len, N = kw
     dev = sims.device
     spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
     n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
@@ -267,9 +314,16 @@ def span_propose(sims, mask, *, levels=SPAN_PROPOSE_LEVELS, relative=True, smoot
     windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
     smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
     table = (hip.C.c_float * len(lv))(*lv)
-    hip.check(hip.lib().rv_span_propose(hip.ptr(sims.contiguous()), hip.ptr(mask.float().contiguous()), R, rpm, L, table, len(lv), relative, smooth, gap, min_len, max_len, N,
-                                        hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows), hip.ptr(smoothed), hip.stream()),
-              "rv_span_propose")
+    sims, mask, valid = _rows_f32(sims, mask, valid)
+    rule = (R, rpm, L, table, len(lv), relative, smooth, gap, min_len, max_len, N)
+    outs = (hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows), hip.ptr(smoothed), hip.stream())
+    if validity == "none":
+        hip.check(hip.lib().rv_span_propose(hip.ptr(sims), hip.ptr(mask), *rule, *outs), "rv_span_propose")
+    elif validity == "rows":
+        hip.chain_check(hip.chain_lib().rvc_span_propose_masked_rows(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), 1, *rule, skip_nan, *outs),
+                        "rvc_span_propose_masked_rows")
+    else:
+        hip.chain_check(hip.chain_lib().rvc_span_propose_masked(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), *rule, skip_nan, *outs), "rvc_span_propose_masked")
     return SpanProposals(spans, n_spans, n_found, windows, smoothed)
 
 
@@ -325,9 +379,18 @@ def window_select(sims, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, ret
     synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
     who = "window_select"
     win, stride, keep, k, min_sep = window_select_keywords(who, win, stride, keep, k, min_sep)
+    return _window_select(who, sims, mask, gt, None, win, stride, keep, min_sep, return_scores, return_bounds, return_order, lambda p: hip.check(
+        hip.lib().rv_window_select(p.sims, p.mask, p.R, p.rpm, p.L, win, stride, k, p.keep, min_sep, p.Wcap, p.gt, p.select, p.n_select, p.n_windows, p.scores,
+                                   p.bounds, p.order, p.hit_rank, hip.stream()), "rv_window_select"))
+
+
+def _window_select(who, sims, mask, gt, valid, win, stride, keep, min_sep, return_scores, return_bounds, return_order, launch, candidates=False):
+    """``window_select``, ``window_select_clipped`` and ``window_select_frames``: the tensor refusals, the outputs and the f32 rows of all three; ``launch``
+    calls the function's own entry with the pointers and sizes it is handed; ``candidates``: the selection has an ``n_candidates``."""
     lead, R, rpm, L = span_propose_shapes(who, sims, mask)
     Wcap = window_select_capacity(who, L, win, stride, min_sep)
     window_select_gt(who, gt, lead)
+    window_select_valid(who, valid, mask)
     if sims.dtype != torch.float32:
         raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
     keep = min(keep, Wcap)
@@ -335,13 +398,17 @@ def window_select(sims, mask, *, win, stride, keep, k=3, min_sep=1, gt=None, ret
     select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
     n_select = torch.empty(lead, dtype=torch.int32, device=dev)
     n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_candidates = torch.empty(lead, dtype=torch.int32, device=dev) if candidates else None
     scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
     bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
     order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
     hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
-    hip.check(hip.lib().rv_window_select(hip.ptr(sims.contiguous()), hip.ptr(mask.float().contiguous()), R, rpm, L, win, stride, k, keep, min_sep, Wcap,
-                                         hip.ptr(gt.float().contiguous()) if gt is not None else None, hip.ptr(select), hip.ptr(n_select), hip.ptr(n_windows),
-                                         hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()), "rv_window_select")
+    sims, mask, valid, gt = _rows_f32(sims, mask, valid, gt)
+    launch(types.SimpleNamespace(sims=hip.ptr(sims), mask=hip.ptr(mask), valid=hip.ptr(valid), gt=hip.ptr(gt), R=R, rpm=rpm, L=L, keep=keep, Wcap=Wcap,
+                                 select=hip.ptr(select), n_select=hip.ptr(n_select), n_windows=hip.ptr(n_windows), n_candidates=hip.ptr(n_candidates),
+                                 scores=hip.ptr(scores), bounds=hip.ptr(bounds), order=hip.ptr(order), hit_rank=hip.ptr(hit_rank)))
+    if candidates:
+        return FrameWindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank, n_candidates)
     return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
 
 
@@ -389,18 +456,35 @@ def window_gather(video, select, *, win, stride, num_frames, mask=None, out_dtyp
     kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
     who = "window_gather"
     win, stride, F = window_gather_keywords(who, win, stride, num_frames)
-    if not torch.is_tensor(video) or not torch.is_tensor(select) or (mask is not None and not torch.is_tensor(mask)):
+    return _window_gather(who, video, select, mask, win, stride, F, out_dtype, return_index, None)
+
+
+def _window_gather(who, video, select, mask, win, stride, F, out_dtype, return_index, rule):
+    """``window_gather`` (``rule`` None: ``rv_window_gather``, a ``select`` is needed) and ``window_gather_clipped`` (``rule``: the window rule handed to
+    ``rv_window_gather_rule``, where ``select=None`` means every window in order): one body."""
+    every = rule is not None and select is None
+    if not torch.is_tensor(video) or not (every or torch.is_tensor(select)) or (mask is not None and not torch.is_tensor(mask)):
         raise ValueError(f"{who}: video, select and mask must be tensors")
-    if video.dim() not in (2, 3) or not 1 <= select.dim() <= 3 or min(video.shape) == 0 or min(select.shape) == 0:
-        raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (expected [L, d] or [B, L, d] and [keep], [R, keep] or [B, Q, keep])")
-    if select.dtype != torch.int32:
-        raise ValueError(f"{who}: select must be int32 (got {select.dtype})")
+    bad_video = video.dim() not in (2, 3) or min(video.shape) == 0
+    bad_select = not every and (not 1 <= select.dim() <= 3 or min(select.shape) == 0)
+    if rule is None:
+        if bad_video or bad_select:
+            raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (expected [L, d] or [B, L, d] and [keep], [R, keep] or [B, Q, keep])")
+    elif bad_video:
+        raise ValueError(f"{who}: video {tuple(video.shape)} (expected [L, d] or [B, L, d])")
+    elif bad_select:
+        raise ValueError(f"{who}: select {tuple(select.shape)} (expected [keep], [R, keep] or [B, Q, keep])")
     M = video.shape[0] if video.dim() == 3 else 1
     L, d = video.shape[-2:]
-    lead, keep = tuple(select.shape[:-1]), select.shape[-1]
-    R = math.prod(lead)
-    if (select.dim() == 3 and (video.dim() != 3 or lead[0] != M)) or R % M != 0:
-        raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (a whole number of rows of select for each video)")
+    if every:
+        lead, keep, R = tuple(video.shape[:-2]), clipped_window_count(L, win), M      # (win <= L below: at least one window, keep >= 1)
+    else:
+        if select.dtype != torch.int32:
+            raise ValueError(f"{who}: select must be int32 (got {select.dtype})")
+        lead, keep = tuple(select.shape[:-1]), select.shape[-1]
+        R = math.prod(lead)
+        if (select.dim() == 3 and (video.dim() != 3 or lead[0] != M)) or R % M != 0:
+            raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (a whole number of rows of select for each video)")
     if mask is not None:
         if mask.shape != tuple(video.shape[:-1]):
             raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected {tuple(video.shape[:-1])})")
@@ -416,9 +500,14 @@ def window_gather(video, select, *, win, stride, num_frames, mask=None, out_dtyp
     dev = video.device
     frames = torch.empty(lead + (keep, F, d), dtype=out_dtype, device=dev)
     index = torch.empty(lead + (keep, F), dtype=torch.int32, device=dev) if return_index else None
-    hip.check(hip.lib(flavour).rv_window_gather(hip.ptr(video), hip.dtype_code(video), video.stride(-2), hip.ptr(mask.float().contiguous()) if mask is not None else None,
-                                                hip.ptr(select.contiguous()), R, R // M, L, d, win, stride, keep, F, hip.ptr(frames), hip.dtype_code(frames),
-                                                hip.ptr(index), hip.stream()), "rv_window_gather")
+    mask, = _rows_f32(mask)
+    select = None if every else select.contiguous()
+    args = (hip.ptr(video), hip.dtype_code(video), video.stride(-2), hip.ptr(mask), hip.ptr(select), R, R // M, L, d, win, stride, keep, F, hip.ptr(frames),
+            hip.dtype_code(frames), hip.ptr(index))
+    if rule is None:
+        hip.check(hip.lib(flavour).rv_window_gather(*args, hip.stream()), "rv_window_gather")
+    else:
+        hip.check(hip.lib(flavour).rv_window_gather_rule(*args, rule, hip.stream()), "rv_window_gather_rule")
     return (frames, index) if return_index else frames
 
 
@@ -446,44 +535,7 @@ def window_gather_clipped(video, *, win, num_frames, select=None, mask=None, out
     cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip.h."""
     who = "window_gather_clipped"
     win, _, F = window_gather_keywords(who, win, 2, num_frames)
-    if not torch.is_tensor(video) or (select is not None and not torch.is_tensor(select)) or (mask is not None and not torch.is_tensor(mask)):
-        raise ValueError(f"{who}: video, select and mask must be tensors")
-    if video.dim() not in (2, 3) or min(video.shape) == 0:
-        raise ValueError(f"{who}: video {tuple(video.shape)} (expected [L, d] or [B, L, d])")
-    M = video.shape[0] if video.dim() == 3 else 1
-    L, d = video.shape[-2:]
-    if select is not None:
-        if not 1 <= select.dim() <= 3 or min(select.shape) == 0:
-            raise ValueError(f"{who}: select {tuple(select.shape)} (expected [keep], [R, keep] or [B, Q, keep])")
-        if select.dtype != torch.int32:
-            raise ValueError(f"{who}: select must be int32 (got {select.dtype})")
-        lead, keep = tuple(select.shape[:-1]), select.shape[-1]
-        R = math.prod(lead)
-        if (select.dim() == 3 and (video.dim() != 3 or lead[0] != M)) or R % M != 0:
-            raise ValueError(f"{who}: video {tuple(video.shape)} / select {tuple(select.shape)} (a whole number of rows of select for each video)")
-    if mask is not None:
-        if mask.shape != tuple(video.shape[:-1]):
-            raise ValueError(f"{who}: mask {tuple(mask.shape)} for video {tuple(video.shape)} (expected {tuple(video.shape[:-1])})")
-        if mask.dtype.is_complex:
-            raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
-    if L > SPAN_PROPOSE_MAX_FRAMES:
-        raise ValueError(f"{who}: L={L} frames (at most {SPAN_PROPOSE_MAX_FRAMES})")
-    if win > L:
-        raise ValueError(f"{who}: win={win} frames for rows of L={L}")
-    out_dtype, flavour = window_gather_dtypes(who, video.dtype, out_dtype)
-    if select is None:
-        lead, keep, R = tuple(video.shape[:-2]), clipped_window_count(L, win), M
-    if video.stride(-1) != 1 or video.stride(-2) < d or (video.dim() == 3 and M > 1 and video.stride(0) != L * video.stride(-2)):
-        video = video.contiguous()
-    dev = video.device
-    frames = torch.empty(lead + (keep, F, d), dtype=out_dtype, device=dev)
-    index = torch.empty(lead + (keep, F), dtype=torch.int32, device=dev) if return_index else None
-    hip.check(hip.lib(flavour).rv_window_gather_rule(hip.ptr(video), hip.dtype_code(video), video.stride(-2),
-                                                     hip.ptr(mask.float().contiguous()) if mask is not None else None,
-                                                     hip.ptr(select.contiguous()) if select is not None else None, R, R // M, L, d, win, 2, keep, F,
-                                                     hip.ptr(frames), hip.dtype_code(frames), hip.ptr(index), hip.RV_WINDOWS_CLIPPED, hip.stream()),
-              "rv_window_gather_rule")      # (win <= L: at least one window, keep >= 1)
-    return (frames, index) if return_index else frames
+    return _window_gather(who, video, select, mask, win, 2, F, out_dtype, return_index, hip.RV_WINDOWS_CLIPPED)
 
 
 def clipped_window_solid(L, win):
@@ -501,25 +553,9 @@ def window_select_clipped(sims, mask, *, win, keep, k=3, min_sep=1, gt=None, ret
     launch (a mask that is not f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip_ext.h."""
     who = "window_select_clipped"
     win, _, keep, k, min_sep = window_select_keywords(who, win, 2, keep, k, min_sep)
-    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
-    Wcap = window_select_capacity(who, L, win, 2, min_sep)
-    window_select_gt(who, gt, lead)
-    if sims.dtype != torch.float32:
-        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
-    keep = min(keep, Wcap)
-    dev = sims.device
-    select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
-    n_select = torch.empty(lead, dtype=torch.int32, device=dev)
-    n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
-    scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
-    bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
-    order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
-    hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
-    hip.ext_check(hip.ext_lib().rvx_window_select_clipped(hip.ptr(sims.contiguous()), hip.ptr(mask.float().contiguous()), R, rpm, L, win, k, keep, min_sep, Wcap,
-                                                          hip.ptr(gt.float().contiguous()) if gt is not None else None, hip.ptr(select), hip.ptr(n_select),
-                                                          hip.ptr(n_windows), hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()),
-                  "rvx_window_select_clipped")
-    return WindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank)
+    return _window_select(who, sims, mask, gt, None, win, 2, keep, min_sep, return_scores, return_bounds, return_order, lambda p: hip.ext_check(
+        hip.ext_lib().rvx_window_select_clipped(p.sims, p.mask, p.R, p.rpm, p.L, win, k, p.keep, min_sep, p.Wcap, p.gt, p.select, p.n_select, p.n_windows,
+                                                p.scores, p.bounds, p.order, p.hit_rank, hip.stream()), "rvx_window_select_clipped"))
 
 
 WINDOW_RULES = {"shifted": hip.RV_WINDOWS_SHIFTED, "clipped": hip.RV_WINDOWS_CLIPPED}
@@ -553,13 +589,8 @@ def window_select_frames_keywords(who, rule, win, stride, keep, frames="all", nu
 
 def window_select_valid(who, valid, mask):
     """The refusals of ``valid``: None, or a bool, uint8 or floating-point tensor of ``mask``'s shape."""
-    if valid is None:
-        return
-    if not torch.is_tensor(valid) or not torch.is_tensor(mask) or valid.shape != mask.shape:
-        raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of mask's shape "
-                         f"{tuple(mask.shape) if torch.is_tensor(mask) else '?'})")
-    if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
-        raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+    if valid is not None:
+        _valid_rows(who, valid, (mask,), f"mask's shape {_shape(mask)}")
 
 
 def window_select_frames(sims, mask, *, rule, win, stride=None, keep, frames="all", num_frames=None, valid=None, k=3, min_sep=1, gt=None, return_scores=False,
@@ -576,30 +607,10 @@ def window_select_frames(sims, mask, *, rule, win, stride=None, keep, frames="al
     include/revision_hip_chain.h."""
     who = "window_select_frames"
     rule, win, stride, keep, frames, F, k, min_sep = window_select_frames_keywords(who, rule, win, stride, keep, frames, num_frames, k, min_sep)
-    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
-    Wcap = window_select_capacity(who, L, win, stride, min_sep)
-    window_select_gt(who, gt, lead)
-    window_select_valid(who, valid, mask)
-    if sims.dtype != torch.float32:
-        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
-    keep = min(keep, Wcap)
-    dev = sims.device
-    select = torch.empty(lead + (keep,), dtype=torch.int32, device=dev)
-    n_select = torch.empty(lead, dtype=torch.int32, device=dev)
-    n_windows = torch.empty(lead, dtype=torch.int32, device=dev)
-    n_candidates = torch.empty(lead, dtype=torch.int32, device=dev)
-    scores = torch.empty(lead + (Wcap,), dtype=torch.float32, device=dev) if return_scores else None
-    bounds = torch.empty((R // rpm, Wcap, 2), dtype=torch.int32, device=dev) if return_bounds else None
-    order = torch.empty(lead + (Wcap,), dtype=torch.int32, device=dev) if return_order else None
-    hit_rank = torch.empty(lead, dtype=torch.int32, device=dev) if gt is not None else None
-    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-    sims, mask = sims.contiguous(), mask.float().contiguous()
-    valid = valid.float().contiguous() if valid is not None else None
-    gt = gt.float().contiguous() if gt is not None else None
-    hip.chain_check(hip.chain_lib().rvc_window_select_frames(
-        hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), R, rpm, L, rule, win, stride, frames, F, k, keep, min_sep, Wcap, hip.ptr(gt), hip.ptr(select), hip.ptr(n_select),
-        hip.ptr(n_windows), hip.ptr(n_candidates), hip.ptr(scores), hip.ptr(bounds), hip.ptr(order), hip.ptr(hit_rank), hip.stream()), "rvc_window_select_frames")
-    return FrameWindowSelection(select, n_select, n_windows, scores, bounds, order, hit_rank, n_candidates)
+    return _window_select(who, sims, mask, gt, valid, win, stride, keep, min_sep, return_scores, return_bounds, return_order, lambda p: hip.chain_check(
+        hip.chain_lib().rvc_window_select_frames(p.sims, p.mask, p.valid, p.R, p.rpm, p.L, rule, win, stride, frames, F, k, p.keep, min_sep, p.Wcap, p.gt,
+                                                 p.select, p.n_select, p.n_windows, p.n_candidates, p.scores, p.bounds, p.order, p.hit_rank, hip.stream()),
+        "rvc_window_select_frames"), candidates=True)
 
 
 MaskedSpanScores = collections.namedtuple("MaskedSpanScores", "scores windows n_usable")
@@ -607,9 +618,7 @@ MaskedSpanScores = collections.namedtuple("MaskedSpanScores", "scores windows n_
 
 def skip_nan_flag(who, skip_nan):
     """The refusal of ``skip_nan`` (raised before any device is looked for) -> 0 / 1."""
-    if not (isinstance(skip_nan, (bool, numbers.Integral)) and skip_nan in (0, 1)):
-        raise ValueError(f"{who}: skip_nan={skip_nan!r} must be True or False")
-    return int(bool(skip_nan))
+    return _flag(who, "skip_nan", skip_nan)
 
 
 def span_scores_masked_checks(who, sims, spans, mask, valid=None, skip_nan=False, k=3, pooling="topk", temperature=0.01):
@@ -657,18 +666,28 @@ def span_scores_masked(sims, spans, mask, *, valid=None, skip_nan=False, k=3, po
     softmax pooling over its usable frames (``"attention"``); a non-empty window without a usable frame scores NaN, an empty one 0.  With
     ``valid=None`` and ``skip_nan=False`` scores and windows equal the other two functions' bit for bit.  One launch (a mask or a valid that is not
     f32 adds a cast kernel), no synchronisation, no host copy.  The full rule stands in include/revision_hip_chain.h."""
-    who = "span_scores_masked"
-    lead, rows, rpm, L, N, mode, k, temperature, skip_nan = span_scores_masked_checks(who, sims, spans, mask, valid, skip_nan, k, pooling, temperature)
+    return _span_scores_masked("span_scores_masked", sims, spans, mask, False, valid, skip_nan, k, pooling, temperature, return_windows, return_usable)
+
+
+def _span_scores_masked(who, sims, spans, mask, rows, valid, skip_nan, k, pooling, temperature, return_windows, return_usable):
+    """``span_scores_masked`` (``valid`` None or of the mask's shape) and ``span_scores_masked_rows`` (``rows``: ``valid`` of ``sims``' shape), each with its
+    own entry: one body."""
+    lead, nrows, rpm, L, N, mode, k, temperature, skip_nan = span_scores_masked_checks(who, sims, spans, mask, None if rows else valid, skip_nan, k, pooling,
+                                                                                      temperature)
+    if rows:
+        span_rows_valid(who, valid, sims)
     dev = sims.device
     scores = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
     win = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
     usable = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_usable else None
     if N > 0:
-        # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-        sims, spans, mask = sims.contiguous(), spans.float().contiguous(), mask.float().contiguous()
-        valid = valid.float().contiguous() if valid is not None else None
-        hip.chain_check(hip.chain_lib().rvc_span_scores_masked(hip.ptr(sims), hip.ptr(spans), hip.ptr(mask), hip.ptr(valid), rows, rpm, L, N, mode, k, temperature,
-                                                               skip_nan, hip.ptr(scores), hip.ptr(win), hip.ptr(usable), hip.stream()), "rvc_span_scores_masked")
+        sims, spans, mask, valid = _rows_f32(sims, spans, mask, valid)
+        rule = (nrows, rpm, L, N, mode, k, temperature, skip_nan, hip.ptr(scores), hip.ptr(win), hip.ptr(usable), hip.stream())
+        if rows:
+            hip.chain_check(hip.chain_lib().rvc_span_scores_masked_rows(hip.ptr(sims), hip.ptr(spans), hip.ptr(mask), hip.ptr(valid), 1, *rule),
+                            "rvc_span_scores_masked_rows")
+        else:
+            hip.chain_check(hip.chain_lib().rvc_span_scores_masked(hip.ptr(sims), hip.ptr(spans), hip.ptr(mask), hip.ptr(valid), *rule), "rvc_span_scores_masked")
     return MaskedSpanScores(scores, win, usable)
 
 
@@ -681,28 +700,8 @@ def span_propose_masked(sims, mask, *, valid=None, skip_nan=False, levels=SPAN_P
     hidden frames inside it).  A row without a usable frame gives no span.  The duration stays the mask's.  With ``valid=None`` and ``skip_nan=False``
     every field equals ``span_propose``'s bit for bit.  One launch (a mask or a valid that is not f32 adds a cast kernel, ``return_smoothed`` a fill),
     no synchronisation, no host copy.  The full rule stands in include/revision_hip_chain.h."""
-    who = "span_propose_masked"
-    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
-    skip_nan = skip_nan_flag(who, skip_nan)
-    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
-    window_select_valid(who, valid, mask)
-    if sims.dtype != torch.float32:
-        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
-    lv, relative, smooth, gap, min_len, max_len, N = kw
-    dev = sims.device
-    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
-    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
-    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
-    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
-    smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
-    table = (hip.C.c_float * len(lv))(*lv)
-    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-    sims, mask = sims.contiguous(), mask.float().contiguous()
-    valid = valid.float().contiguous() if valid is not None else None
-    hip.chain_check(hip.chain_lib().rvc_span_propose_masked(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), R, rpm, L, table, len(lv), relative, smooth, gap, min_len,
-                                                            max_len, N, skip_nan, hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows),
-                                                            hip.ptr(smoothed), hip.stream()), "rvc_span_propose_masked")
-    return SpanProposals(spans, n_spans, n_found, windows, smoothed)
+    return _span_propose("span_propose_masked", sims, mask, "mask", valid, skip_nan, (levels, relative, smooth, gap, min_len, max_len, max_spans), return_windows,
+                         return_smoothed)
 
 
 WINDOWS_VALID_MAX_KEEP = 2048
@@ -732,8 +731,7 @@ def windows_valid_checks(who, select, mask, rule, win, stride=None, frames="all"
     if mask.dtype.is_complex:
         raise ValueError(f"{who}: mask must be bool, integer or floating point (got {mask.dtype})")
     window_select_valid(who, valid, mask)
-    if not (isinstance(return_count, (bool, numbers.Integral)) and return_count in (0, 1)):
-        raise ValueError(f"{who}: return_count={return_count!r} must be True or False")
+    _flag(who, "return_count", return_count)
     return rule, win, stride, frames, F, lead, R, R // M, L, keep
 
 
@@ -752,9 +750,8 @@ def windows_valid(select, mask, *, rule, win, stride=None, frames="all", num_fra
     dev = select.device
     out = torch.empty(lead + (L,), dtype=torch.float32, device=dev)
     n_valid = torch.empty(lead, dtype=torch.int32, device=dev) if return_count else None
-    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-    select, mask = select.contiguous(), mask.float().contiguous()
-    valid = valid.float().contiguous() if valid is not None else None
+    select = select.contiguous()
+    mask, valid = _rows_f32(mask, valid)
     hip.chain_check(hip.chain_lib().rvc_windows_valid(hip.ptr(select), hip.ptr(mask), hip.ptr(valid), R, rpm, L, rule, win, stride, frames, F, keep, hip.ptr(out),
                                                       hip.ptr(n_valid), hip.stream()), "rvc_windows_valid")
     return WindowsValid(out, n_valid)
@@ -762,11 +759,7 @@ def windows_valid(select, mask, *, rule, win, stride=None, frames="all", num_fra
 
 def span_rows_valid(who, valid, sims):
     """The refusals of a per-row ``valid``: a bool, uint8 or floating-point tensor of ``sims``' shape."""
-    if not torch.is_tensor(valid) or not torch.is_tensor(sims) or valid.shape != sims.shape:
-        raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of sims' shape "
-                         f"{tuple(sims.shape) if torch.is_tensor(sims) else '?'}: a validity row per row)")
-    if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
-        raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
+    _valid_rows(who, valid, (sims,), f"sims' shape {_shape(sims)}: a validity row per row")
 
 
 def span_scores_masked_rows(sims, spans, mask, *, valid, skip_nan=False, k=3, pooling="topk", temperature=0.01, return_windows=False, return_usable=False):
@@ -775,20 +768,7 @@ def span_scores_masked_rows(sims, spans, mask, *, valid, skip_nan=False, k=3, po
     usable frames, what ``windows_valid`` makes of a per-query window selection, while the duration stays its video's.  Each (b, q) equals
     ``span_scores_masked`` on that row alone bit for bit.  One launch (a mask or a valid that is not f32 adds a cast kernel), no synchronisation, no
     host copy.  The full rule stands in include/revision_hip_chain.h."""
-    who = "span_scores_masked_rows"
-    lead, rows, rpm, L, N, mode, k, temperature, skip_nan = span_scores_masked_checks(who, sims, spans, mask, None, skip_nan, k, pooling, temperature)
-    span_rows_valid(who, valid, sims)
-    dev = sims.device
-    scores = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
-    win = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
-    usable = torch.empty(lead + (N,), dtype=torch.int32, device=dev) if return_usable else None
-    if N > 0:
-        # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-        sims, spans, mask, valid = sims.contiguous(), spans.float().contiguous(), mask.float().contiguous(), valid.float().contiguous()
-        hip.chain_check(hip.chain_lib().rvc_span_scores_masked_rows(hip.ptr(sims), hip.ptr(spans), hip.ptr(mask), hip.ptr(valid), 1, rows, rpm, L, N, mode, k,
-                                                                    temperature, skip_nan, hip.ptr(scores), hip.ptr(win), hip.ptr(usable), hip.stream()),
-                        "rvc_span_scores_masked_rows")
-    return MaskedSpanScores(scores, win, usable)
+    return _span_scores_masked("span_scores_masked_rows", sims, spans, mask, True, valid, skip_nan, k, pooling, temperature, return_windows, return_usable)
 
 
 def span_propose_masked_rows(sims, mask, *, valid, skip_nan=False, levels=SPAN_PROPOSE_LEVELS, relative=True, smooth=1, gap=0, min_len=1, max_len=None,
@@ -797,27 +777,8 @@ def span_propose_masked_rows(sims, mask, *, valid, skip_nan=False, levels=SPAN_P
     SpanProposals, with ``valid`` of ``sims``' shape ([R,L] or [B,Q,L]; bool, uint8 or float).  Each (b, q) equals ``span_propose_masked`` on that row
     alone bit for bit.  One launch (a mask or a valid that is not f32 adds a cast kernel, ``return_smoothed`` a fill), no synchronisation, no host
     copy.  The full rule stands in include/revision_hip_chain.h."""
-    who = "span_propose_masked_rows"
-    kw = span_propose_keywords(who, levels, relative, smooth, gap, min_len, max_len, max_spans)
-    skip_nan = skip_nan_flag(who, skip_nan)
-    lead, R, rpm, L = span_propose_shapes(who, sims, mask)
-    span_rows_valid(who, valid, sims)
-    if sims.dtype != torch.float32:
-        raise ValueError(f"{who}: sims must be float32 (got {sims.dtype})")
-    lv, relative, smooth, gap, min_len, max_len, N = kw
-    dev = sims.device
-    spans = torch.empty(lead + (N, 2), dtype=torch.float32, device=dev)
-    n_spans = torch.empty(lead, dtype=torch.int32, device=dev)
-    n_found = torch.empty(lead, dtype=torch.int32, device=dev)
-    windows = torch.empty(lead + (N, 2), dtype=torch.int32, device=dev) if return_windows else None
-    smoothed = torch.full(lead + (L,), float("nan"), dtype=torch.float32, device=dev) if return_smoothed else None
-    table = (hip.C.c_float * len(lv))(*lv)
-    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-    sims, mask, valid = sims.contiguous(), mask.float().contiguous(), valid.float().contiguous()
-    hip.chain_check(hip.chain_lib().rvc_span_propose_masked_rows(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), 1, R, rpm, L, table, len(lv), relative, smooth, gap,
-                                                                 min_len, max_len, N, skip_nan, hip.ptr(spans), hip.ptr(n_spans), hip.ptr(n_found),
-                                                                 hip.ptr(windows), hip.ptr(smoothed), hip.stream()), "rvc_span_propose_masked_rows")
-    return SpanProposals(spans, n_spans, n_found, windows, smoothed)
+    return _span_propose("span_propose_masked_rows", sims, mask, "rows", valid, skip_nan, (levels, relative, smooth, gap, min_len, max_len, max_spans),
+                         return_windows, return_smoothed)
 
 
 SPAN_REFINE_MAX_RADIUS = 64
@@ -836,9 +797,8 @@ def span_refine_keywords(who, radius, margin, min_len=1, form="cxw", return_wind
         raise ValueError(f"{who}: margin={margin!r} must be an integer in [1, {SPAN_REFINE_MAX_MARGIN}]")
     if not (_is_int(min_len) and 1 <= min_len < 2 ** 31):
         raise ValueError(f"{who}: min_len={min_len!r} must be a positive integer")
-    for name, v in (("return_windows", return_windows), ("return_contrast", return_contrast)):
-        if not (isinstance(v, (bool, numbers.Integral)) and v in (0, 1)):
-            raise ValueError(f"{who}: {name}={v!r} must be True or False")
+    _flag(who, "return_windows", return_windows)
+    _flag(who, "return_contrast", return_contrast)
     return SPAN_FORMS[form], int(radius), int(margin), int(min_len)
 
 
@@ -856,15 +816,7 @@ def span_refine_checks(who, sims, spans, mask, valid=None):
         raise ValueError(f"{who}: spans must be a floating-point tensor (got {spans.dtype})")
     if rows > 65535:
         raise ValueError(f"{who}: {rows} rows (at most 65535 per call)")
-    rpv = rpm
-    if valid is not None:
-        if not torch.is_tensor(valid) or valid.shape not in (mask.shape, sims.shape):
-            raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of mask's shape "
-                             f"{tuple(mask.shape)}, a validity row per mask row, or of sims' shape {tuple(sims.shape)}, one per row)")
-        if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
-            raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
-        rpv = rpm if valid.shape == mask.shape else 1
-    return lead, rows, rpm, rpv, L, spans.shape[-2]
+    return lead, rows, rpm, _rows_per_valid(who, valid, mask, sims, rpm), L, spans.shape[-2]
 
 
 def span_refine(sims, spans, mask, *, form="cxw", radius, margin, min_len=1, valid=None, return_windows=False, return_contrast=False):
@@ -889,9 +841,7 @@ def span_refine(sims, spans, mask, *, form="cxw", radius, margin, min_len=1, val
     contrast = torch.empty(lead + (N,), dtype=torch.float32, device=dev) if return_contrast else None
     contrast0 = torch.empty(lead + (N,), dtype=torch.float32, device=dev) if return_contrast else None
     if N > 0:
-        # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-        sims, spans, mask = sims.contiguous(), spans.float().contiguous(), mask.float().contiguous()
-        valid = valid.float().contiguous() if valid is not None else None
+        sims, spans, mask, valid = _rows_f32(sims, spans, mask, valid)
         hip.chain_check(hip.chain_lib().rvc_span_refine(hip.ptr(sims), hip.ptr(spans), code, hip.ptr(mask), hip.ptr(valid), rpv, rows, rpm, L, N, radius, margin,
                                                         min_len, hip.ptr(out), hip.ptr(win), hip.ptr(contrast), hip.ptr(contrast0), hip.stream()),
                         "rvc_span_refine")
@@ -934,9 +884,8 @@ def span_anchors_keywords(who, scales, score="contrast", peak=2, min_usable=1, m
         raise ValueError(f"{who}: min_usable={min_usable!r} must be a positive integer")
     if not (_is_int(max_spans) and 1 <= max_spans <= SPAN_RANK_MAX):
         raise ValueError(f"{who}: max_spans={max_spans!r} must be an integer in [1, {SPAN_RANK_MAX}]")
-    for name, v in (("return_windows", return_windows), ("return_scale", return_scale)):
-        if not (isinstance(v, (bool, numbers.Integral)) and v in (0, 1)):
-            raise ValueError(f"{who}: {name}={v!r} must be True or False")
+    _flag(who, "return_windows", return_windows)
+    _flag(who, "return_scale", return_scale)
     return tuple(triples), SPAN_ANCHOR_SCORES[score], int(peak), int(min_usable), int(max_spans)
 
 
@@ -944,15 +893,7 @@ def span_anchors_checks(who, sims, mask, valid=None):
     """The tensor refusals of ``span_anchors`` (raised before any device is looked for) -> (leading shape, rows, rows per mask row, rows per validity
     row, L).  ``valid`` has the mask's shape (a row per mask row) or ``sims``' shape (a row per row), as ``span_refine`` takes it."""
     lead, rows, rpm, L = span_propose_shapes(who, sims, mask)
-    rpv = rpm
-    if valid is not None:
-        if not torch.is_tensor(valid) or valid.shape not in (mask.shape, sims.shape):
-            raise ValueError(f"{who}: valid {tuple(valid.shape) if torch.is_tensor(valid) else type(valid).__name__} (expected a tensor of mask's shape "
-                             f"{tuple(mask.shape)}, a validity row per mask row, or of sims' shape {tuple(sims.shape)}, one per row)")
-        if not (valid.dtype in (torch.bool, torch.uint8) or valid.dtype.is_floating_point):
-            raise ValueError(f"{who}: valid must be bool, uint8 or floating point (got {valid.dtype})")
-        rpv = rpm if valid.shape == mask.shape else 1
-    return lead, rows, rpm, rpv, L
+    return lead, rows, rpm, _rows_per_valid(who, valid, mask, sims, rpm), L
 
 
 def span_anchors(sims, mask, *, scales, score="contrast", peak=2, min_usable=1, valid=None, max_spans=256, return_windows=False, return_scale=False):
@@ -989,9 +930,7 @@ def span_anchors(sims, mask, *, scales, score="contrast", peak=2, min_usable=1, 
     if nbytes < 0:
         hip.chain_check(int(nbytes), "rvc_span_anchors_workspace")
     work = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-    # (the casts stay referenced until the call is queued: two temporaries dropped one after the other would share one block of the allocator)
-    sims, mask = sims.contiguous(), mask.float().contiguous()
-    valid = valid.float().contiguous() if valid is not None else None
+    sims, mask, valid = _rows_f32(sims, mask, valid)
     hip.chain_check(lib.rvc_span_anchors(hip.ptr(sims), hip.ptr(mask), hip.ptr(valid), rpv, rows, rpm, L, flat, len(table), mode, peak, min_usable, N,
                                          hip.ptr(spans), hip.ptr(scores), hip.ptr(n_spans), hip.ptr(n_found), hip.ptr(windows), hip.ptr(scale), hip.ptr(work),
                                          work.numel(), hip.stream()), "rvc_span_anchors")

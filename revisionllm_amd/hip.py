@@ -200,41 +200,65 @@ EXT_SIGNATURES = {
     "rvx_last_error": (C.c_int, [C.c_char_p, _sz]),
     "rvx_window_select_clipped": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
-_ext = None
+
+
+def _load(path, signatures, complaint):
+    """One loader for every library: existence check, CDLL, the signature table, then ``complaint(handle)`` -> what is wrong with this build, or None.
+    Raises HipLibraryError when the library is missing or is not the build that was asked for (there is no fallback)."""
+    if not os.path.exists(path):
+        raise HipLibraryError(f"{path} not found: build it with `python -m revisionllm_amd.build` (hipcc, gfx950). "
+                              "revisionllm_amd has no CPU fallback.")
+    try:
+        h = C.CDLL(path)
+    except OSError as e:
+        raise HipLibraryError(f"cannot load {path}: {e}") from e
+    for name, (res, args) in signatures.items():
+        fn = getattr(h, name)
+        fn.restype, fn.argtypes = res, args
+    wrong = complaint(h)
+    if wrong:
+        raise HipLibraryError(f"{path} {wrong}")
+    return h
+
+
+_companions = {}
+
+
+def _load_versioned(path, signatures, prefix, version):
+    """The f32-only libraries: loaded once each (kept in _companions under their prefix: "rvx", "rvc"), refused unless <prefix>_abi_version() is ``version``."""
+    if prefix not in _companions:
+        def complaint(h):
+            got = getattr(h, prefix + "_abi_version")()
+            return None if got == version else f"has {prefix}_abi_version() = {got} (expected {version})"
+        _companions[prefix] = _load(path, signatures, complaint)
+    return _companions[prefix]
+
+
+def _last_error_of(prefix):
+    if prefix not in _companions:
+        return ""
+    buf = C.create_string_buffer(512)
+    getattr(_companions[prefix], prefix + "_last_error")(buf, 512)
+    return buf.value.decode()
+
+
+def _check_of(prefix, rc, what):
+    if rc != 0:
+        raise HipLibraryError(f"{what} failed (status {rc}): {_last_error_of(prefix)}")
 
 
 def ext_lib():
     """Load (once) and return the ctypes handle of the companion library; raises HipLibraryError when it is missing (there is no fallback)."""
-    global _ext
-    if _ext is None:
-        if not os.path.exists(EXT_LIB_PATH):
-            raise HipLibraryError(f"{EXT_LIB_PATH} not found: build it with `python -m revisionllm_amd.build` (hipcc, gfx950). "
-                                  "revisionllm_amd has no CPU fallback.")
-        try:
-            h = C.CDLL(EXT_LIB_PATH)
-        except OSError as e:
-            raise HipLibraryError(f"cannot load {EXT_LIB_PATH}: {e}") from e
-        for name, (res, args) in EXT_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        if h.rvx_abi_version() != RVX_ABI_VERSION:
-            raise HipLibraryError(f"{EXT_LIB_PATH} has rvx_abi_version() = {h.rvx_abi_version()} (expected {RVX_ABI_VERSION})")
-        _ext = h
-    return _ext
+    return _load_versioned(EXT_LIB_PATH, EXT_SIGNATURES, "rvx", RVX_ABI_VERSION)
 
 
 def ext_last_error():
     """The calling thread's last error message of the companion library ("" when it is not loaded)."""
-    if _ext is None:
-        return ""
-    buf = C.create_string_buffer(512)
-    _ext.rvx_last_error(buf, 512)
-    return buf.value.decode()
+    return _last_error_of("rvx")
 
 
 def ext_check(rc, what):
-    if rc != 0:
-        raise HipLibraryError(f"{what} failed (status {rc}): {ext_last_error()}")
+    _check_of("rvx", rc, what)
 
 
 #: the chain library (include/revision_hip_chain.h): the grounding chain's entries added after the companion library was closed too; f32-only, ONE
@@ -261,65 +285,32 @@ CHAIN_SIGNATURES = {
     "rvc_span_anchors_workspace": (_i64, [_i32, C.POINTER(_i32), _i32, _i32]),
     "rvc_span_anchors": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
-_chain = None
 
 
 def chain_lib():
     """Load (once) and return the ctypes handle of the chain library; raises HipLibraryError when it is missing (there is no fallback)."""
-    global _chain
-    if _chain is None:
-        if not os.path.exists(CHAIN_LIB_PATH):
-            raise HipLibraryError(f"{CHAIN_LIB_PATH} not found: build it with `python -m revisionllm_amd.build` (hipcc, gfx950). "
-                                  "revisionllm_amd has no CPU fallback.")
-        try:
-            h = C.CDLL(CHAIN_LIB_PATH)
-        except OSError as e:
-            raise HipLibraryError(f"cannot load {CHAIN_LIB_PATH}: {e}") from e
-        for name, (res, args) in CHAIN_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        if h.rvc_abi_version() != RVC_ABI_VERSION:
-            raise HipLibraryError(f"{CHAIN_LIB_PATH} has rvc_abi_version() = {h.rvc_abi_version()} (expected {RVC_ABI_VERSION})")
-        _chain = h
-    return _chain
+    return _load_versioned(CHAIN_LIB_PATH, CHAIN_SIGNATURES, "rvc", RVC_ABI_VERSION)
 
 
 def chain_last_error():
     """The calling thread's last error message of the chain library ("" when it is not loaded)."""
-    if _chain is None:
-        return ""
-    buf = C.create_string_buffer(512)
-    _chain.rvc_last_error(buf, 512)
-    return buf.value.decode()
+    return _last_error_of("rvc")
 
 
 def chain_check(rc, what):
-    if rc != 0:
-        raise HipLibraryError(f"{what} failed (status {rc}): {chain_last_error()}")
+    _check_of("rvc", rc, what)
 
 
 def lib(f=None):
     """Load (once) and return the ctypes handle of a flavour's library (f: flavour name, torch dtype, tensor or None = the default
     flavour); raises HipLibraryError when the extension is missing."""
     f = flavour_of(f)
-    h = _libs.get(f)
-    if h is None:
-        path = LIB_PATHS[f]
-        if not os.path.exists(path):
-            raise HipLibraryError(
-                f"{path} not found: build it with `python -m revisionllm_amd.build` (hipcc, gfx950). "
-                "revisionllm_amd has no CPU fallback.")
-        try:
-            h = C.CDLL(path)
-        except OSError as e:
-            raise HipLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        if h.rv_operand_dtype() != _DT[OP_DTYPES[f]]:
-            raise HipLibraryError(f"{path} is not the {f} build of the library (rv_operand_dtype() = {h.rv_operand_dtype()})")
-        _libs[f] = h
-    return h
+    if f not in _libs:
+        def complaint(h):
+            got = h.rv_operand_dtype()
+            return None if got == _DT[OP_DTYPES[f]] else f"is not the {f} build of the library (rv_operand_dtype() = {got})"
+        _libs[f] = _load(LIB_PATHS[f], SIGNATURES, complaint)
+    return _libs[f]
 
 
 _numeric = {}

@@ -166,3 +166,34 @@ def stage2_loop_fixture_files(dirpath, seed=SEED):
     with open(data_path, "w") as f:
         json.dump(ann, f)
     return dict(data_path=data_path, feat_folder=feat_dir, q_feat_dir=q_dir, ann=ann)
+
+
+#: The grounding chain's shared rules: helper -> (its one definition in csrc/grounding.h, the files whose kernels call it, text of the inline form each of
+#: those files held before the rule had one definition[, another spelling of it that is gone from them as well]).
+GROUNDING_RULES = {
+    "span_mask_sum": ("float span_mask_sum(const float* __restrict__ mask, Row row, int rpm, int L, float* red)", ("span_scores.h", "refine_chain.hip", "anchors_chain.hip"),
+                      ("(red[0] + red[1]) + (red[2] + red[3])",)),
+    "span_slice": ("void span_slice(float p1, float p2, int L, int& lo, int& hi)", ("span_scores.h", "refine_chain.hip"), ("sat_i32(", "end + L")),
+    "SPAN_NOT_FINITE": ("#define SPAN_NOT_FINITE(p1, p2)", ("span_scores.h", "refine_chain.hip"), ("fabsf(p1)", "fabsf(p2)")),
+    "span_encode": ("void span_encode(int lo, int hi, float dur, float& c, float& w)", ("span_propose.h", "refine_chain.hip", "anchors_chain.hip"),
+                    ("0.5f), dur)",)),
+    "sim_quantise": ("long long sim_quantise(float v)", ("refine_chain.hip", "anchors_chain.hip"), ("__float2int_rn", "16777216.f")),
+    "sim_usable": ("bool sim_usable(float v)", ("refine_chain.hip", "anchors_chain.hip"), ("v == v",), ("v != v",)),
+    "contrast_f64": ("double contrast_f64(long long Sin, int Cin, long long Sout, int Cout)", ("refine_chain.hip", "anchors_chain.hip"), ("__dsub_rn",)),
+}
+
+
+def assert_grounding_rule_is_shared(helper, csrc):
+    """The rule has ONE definition, in grounding.h; every file named for it calls the helper, and the inline form is gone from each of them."""
+    definition, callers, inline = GROUNDING_RULES[helper][:3]
+    header = open(os.path.join(csrc, "grounding.h")).read()
+    assert header.count(definition) == 1, helper
+    for word in inline:
+        assert word in header, (helper, word)
+    for name in callers:
+        src = open(os.path.join(csrc, name)).read()
+        code = "\n".join(line.split("//")[0] for line in src.split("\n"))               # (comments may name the rule)
+        assert helper + "(" in code or helper + "<" in code, (helper, name)
+        assert definition not in src, (helper, name)
+        for word in inline + sum(GROUNDING_RULES[helper][3:], ()):
+            assert word not in code, (helper, name, word)

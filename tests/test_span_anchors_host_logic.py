@@ -20,6 +20,7 @@ import propose_oracle as PO
 import similarity_oracle as SO
 import span_anchors_oracle as AO
 import span_refine_oracle as RO
+from helpers import assert_grounding_rule_is_shared
 from revisionllm_amd import hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -251,8 +252,10 @@ def test_header_table_and_exports_agree():
     body = src[src.index("namespace {"):]
     atomics = re.findall(r"\batomic\w*\s*\(\s*&?(\w+)", body)
     assert atomics == ["hist"] and "__shared__ int hist[256]" in body                     # the one atomic counts into LDS: no global atomic
-    for fn in ("duration_frames(", "__ddiv_rn", "__dsub_rn", "__float2int_rn", "16777216.f", "blockIdx.x"):
+    for fn in ("duration_frames(", "__ddiv_rn", "contrast_f64(", "sim_quantise(", "sim_usable(", "span_mask_sum<AN_TPB>(", "span_encode(", "blockIdx.x"):
         assert fn in src, fn
+    for helper in ("span_mask_sum", "span_encode", "sim_quantise", "sim_usable", "contrast_f64"):       # the rules it shares with the other stages: one definition each
+        assert_grounding_rule_is_shared(helper, os.path.join(ROOT, "revisionllm_amd", "csrc"))
     assert "blockIdx.y" not in src
 
 

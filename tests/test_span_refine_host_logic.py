@@ -18,6 +18,7 @@ import torch
 
 import similarity_oracle as SO
 import span_refine_oracle as RO
+from helpers import GROUNDING_RULES, assert_grounding_rule_is_shared
 from revisionllm_amd import hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -255,8 +256,10 @@ def test_header_table_and_exports_agree():
         assert word in rule, word
     src = open(os.path.join(ROOT, "revisionllm_amd", "csrc", "refine_chain.hip")).read()
     assert "refine_chain.hip" in build.CHAIN_SOURCES and src.count("__global__") == 1 and "atomic" not in src.split("#include")[1].lower().replace("__atomic_", "")
-    for fn in ("duration_frames(", "sat_i32(", "__ddiv_rn", "__dsub_rn", "__float2int_rn"):
+    for fn in ("duration_frames(", "span_mask_sum<256>(", "SPAN_NOT_FINITE(", "span_slice(", "span_encode(", "sim_usable(", "sim_quantise(", "contrast_f64("):
         assert fn in src, fn
+    for helper in GROUNDING_RULES:                                                          # every rule it shares with the other stages: one definition each
+        assert_grounding_rule_is_shared(helper, os.path.join(ROOT, "revisionllm_amd", "csrc"))
 
 
 def _refused(rc, message):

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import propose_oracle as PO
+from helpers import assert_grounding_rule_is_shared
 import similarity_oracle as SO
 import spans_masked_oracle as MO
 from revisionllm_amd import hip
@@ -123,7 +124,10 @@ def test_header_table_and_exports_agree_and_each_kernel_has_one_source():
     src = {n: open(os.path.join(csrc, n)).read() for n in ("span_scores.h", "span_propose.h", "similarity.hip", "propose.hip", "spans_chain.hip")}
     assert src["span_scores.h"].count("void span_scores_kernel(") == 1 and "template <int MODE, bool MASKED = false>" in src["span_scores.h"]
     assert src["span_propose.h"].count("void span_propose_kernel(") == 1 and "template <bool MASKED = false>" in src["span_propose.h"]
-    assert src["span_propose.h"].count("float sp_smooth(") == 1 and src["span_scores.h"].count("int sat_i32(") == 1
+    assert src["span_propose.h"].count("float sp_smooth(") == 1 and "int sat_i32(" not in src["span_scores.h"]
+    assert open(os.path.join(csrc, "grounding.h")).read().count("int sat_i32(") == 1                       # (it moved with the window rule, span_slice)
+    for helper in ("span_mask_sum", "SPAN_NOT_FINITE", "span_slice", "span_encode"):
+        assert_grounding_rule_is_shared(helper, csrc)
     for tu, head in (("similarity.hip", "span_scores.h"), ("propose.hip", "span_propose.h"), ("spans_chain.hip", "span_scores.h"),
                      ("spans_chain.hip", "span_propose.h")):
         assert f'#include "{head}"' in src[tu], (tu, head)

@@ -20,6 +20,15 @@ The shapes are the smallest that reach every kernel form and edge:
                       and 64; gt; scores, bounds and order
   topk_cosine         n = 3, T = 70; d = 768 (fast kernel) and d = 100 (generic); k = 0, 3, 64; one NaN similarity; 16-bit and f32
   topk_pool, attn_pool  Nv = 2, Nt = 3, T = 70; d = 768 and 100; 16-bit and f32
+The chain library's entries (f32 rows only: one build for both flavours, so they run once, under "chain"; REVISION_HIP_LIB_EXT and REVISION_HIP_LIB_CHAIN
+name the parent's builds), on [3, 3, L] rows with L = 63, 257 and 700, one NaN frame a row, N = 9 spans with an empty, two non-finite and a span past the row:
+  window_select_clipped   win 16 (L = 63) or 64; keep 3 and Wcap; min_sep 1 and 3; k 3 and 64; gt; scores, bounds and order
+  window_select_frames    both rules, both frame sets (5 sampled frames), with a validity row per mask row and without; gt; scores, bounds and order
+  span_scores_masked(_rows)    both poolings, k 1 / 3 / 64, skip_nan on and off; valid None and per mask row (per row for _rows); windows and usable counts
+  span_propose_masked(_rows)   T = 5; smooth 1 / 5; gap 0 / 2; relative on and off; skip_nan on and off; valid as above; windows and smoothed
+  windows_valid           both rules, both frame sets; a select with -1 padding, a duplicate and an index past the windows; valid on and off; the counts
+  span_refine             both forms; radius / margin 3 / 5 and 64 / 128; min_len 1 and 4; valid None, per mask row and per row; windows and contrasts
+  span_anchors            both scores; three scales (8, (16, 4), (33, 5, 7)); peak 0 and 2; max_spans 4 and 256; valid as span_refine; windows and scales
 The stages that take a mask run on [B = 3, Q = 3, L] rows with one mask row per three rows: all ones (D = L), 0 / 1 with min(130, L - 10) ones, and
 fractional values (which hold the order of the duration sum).
 """
@@ -150,16 +159,70 @@ def cases(dt):
             yield "attn_pool/%s/d%d:tau%g" % (fn, d, tau), lambda v=video, t=text, tau=tau: ops.attn_pool(t, v, tau)
 
 
+def chain_cases():
+    """The cases of the companion and the chain library (f32 rows only: no flavour)."""
+    for L in (63, 257, 700):
+        s, m = rows("ch%d" % L, L), masks(L)
+        valid_m = (rnd("ch_vm%d" % L, 3, L, uniform=True) > 0.2).cuda()                # a validity row per mask row
+        valid_r = (rnd("ch_vr%d" % L, 3, 3, L, uniform=True) > 0.2).cuda()             # a validity row per row
+        win, stride = (16, 2) if L == 63 else (64, 4)
+        gt = (rnd("ch_gt%d" % L, 3, 3, 1, uniform=True) * 0.8 * L + torch.tensor([0.0, 0.15 * L])).cuda()
+        gt[2, 2, 1] = gt[2, 2, 0]                                           # a void ground truth
+        outs = dict(gt=gt, return_scores=True, return_bounds=True, return_order=True)
+        for keep, sep, k in itertools.product((3, 10 ** 6), (1, 3), (3, 64)):
+            kw = dict(win=win, keep=keep, k=k, min_sep=sep, **outs)
+            yield "window_select_clipped/L%d/sep%d:keep%d/k%d" % (L, sep, keep, k), lambda s=s, m=m, kw=kw: tuple(ops.window_select_clipped(s, m, **kw))
+        for rule, frames, (vn, v) in itertools.product(("shifted", "clipped"), ("all", "sampled"), (("none", None), ("mask", valid_m))):
+            kw = dict(rule=rule, win=win, stride=stride if rule == "shifted" else None, keep=3, frames=frames, num_frames=5 if frames == "sampled" else None, valid=v, **outs)
+            yield "window_select_frames/L%d/%s:%s/valid-%s" % (L, rule, frames, vn), lambda s=s, m=m, kw=kw: tuple(ops.window_select_frames(s, m, **kw))
+
+        spans = rnd("ch_spans%d" % L, 3, 3, 9, 2, uniform=True) * torch.tensor([1.0, 0.4])
+        spans[:, :, :4] = torch.tensor([[0.5, -0.01], [NAN, 0.1], [0.5, INF], [1.5, 2.0]])      # empty, two non-finite, past the row
+        spans = spans.cuda()
+        xx = torch.stack([spans[..., 0] - 0.5 * spans[..., 1], spans[..., 0] + 0.5 * spans[..., 1]], -1)
+        for (pooling, tau), k, skip in itertools.product((("topk", 0.01), ("attention", 0.01), ("attention", 1.0)), (1, 3, 64), (False, True)):
+            kw = dict(k=k, pooling=pooling, temperature=tau, skip_nan=skip, return_windows=True, return_usable=True)
+            for vn, v in (("none", None), ("mask", valid_m)):
+                yield ("span_scores_masked/L%d/%s%g:k%d/skip%d/valid-%s" % (L, pooling, tau, k, skip, vn),
+                       lambda s=s, m=m, v=v, kw=kw: tuple(ops.span_scores_masked(s, spans, m, valid=v, **kw)))
+            yield ("span_scores_masked_rows/L%d/%s%g:k%d/skip%d" % (L, pooling, tau, k, skip),
+                   lambda s=s, m=m, kw=kw: tuple(ops.span_scores_masked_rows(s, spans, m, valid=valid_r, **kw)))
+        for smooth, gap, relative, skip in itertools.product((1, 5), (0, 2), (True, False), (False, True)):
+            kw = dict(levels=[0.2 + 0.7 * i / 4 for i in range(5)], relative=relative, smooth=smooth, gap=gap, skip_nan=skip, max_spans=9, return_windows=True,
+                      return_smoothed=True)
+            tag = "smooth%d/gap%d/rel%d/skip%d" % (smooth, gap, relative, skip)
+            for vn, v in (("none", None), ("mask", valid_m)):
+                yield "span_propose_masked/L%d:%s/valid-%s" % (L, tag, vn), lambda s=s, m=m, v=v, kw=kw: tuple(ops.span_propose_masked(s, m, valid=v, **kw))
+            yield "span_propose_masked_rows/L%d:%s" % (L, tag), lambda s=s, m=m, kw=kw: tuple(ops.span_propose_masked_rows(s, m, valid=valid_r, **kw))
+
+        select = torch.tensor([0, 2, 2, -1, 5, 999], dtype=torch.int32).repeat(3, 3, 1)
+        select[1, :, 0], select[2, 1] = 1, -1
+        select = select.cuda()
+        for rule, frames, (vn, v) in itertools.product(("shifted", "clipped"), ("all", "sampled"), (("none", None), ("mask", valid_m))):
+            kw = dict(rule=rule, win=win, stride=stride if rule == "shifted" else None, frames=frames, num_frames=5 if frames == "sampled" else None, valid=v,
+                      return_count=True)
+            yield "windows_valid/L%d/%s:%s/valid-%s" % (L, rule, frames, vn), lambda m=m, kw=kw: tuple(ops.windows_valid(select, m, **kw))
+
+        for form, (radius, margin), min_len, (vn, v) in itertools.product(("cxw", "xx"), ((3, 5), (64, 128)), (1, 4), (("none", None), ("mask", valid_m), ("rows", valid_r))):
+            kw = dict(form=form, radius=radius, margin=margin, min_len=min_len, valid=v, return_windows=True, return_contrast=True)
+            yield ("span_refine/L%d/%s:r%d/m%d/min%d/valid-%s" % (L, form, radius, margin, min_len, vn),
+                   lambda s=s, m=m, sp=spans if form == "cxw" else xx, kw=kw: tuple(ops.span_refine(s, sp, m, **kw)))
+        for score, peak, cap, (vn, v) in itertools.product(("mean", "contrast"), (0, 2), (4, 256), (("none", None), ("mask", valid_m), ("rows", valid_r))):
+            kw = dict(scales=(8, (16, 4), (33, 5, 7)), score=score, peak=peak, max_spans=cap, valid=v, return_windows=True, return_scale=True)
+            yield "span_anchors/L%d/%s:peak%d/cap%d/valid-%s" % (L, score, peak, cap, vn), lambda s=s, m=m, kw=kw: tuple(ops.span_anchors(s, m, **kw))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grounding_digest.json"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "grounding_digest needs the GPU"
     res, calls = {}, 0
-    for fl in ("f16", "bf16"):
-        hip.set_flavour(fl)
+    for fl in ("f16", "bf16", "chain"):
+        if fl != "chain":
+            hip.set_flavour(fl)
         groups = {}
-        for name, call in cases(hip.op_dtype(fl)):
+        for name, call in (chain_cases() if fl == "chain" else cases(hip.op_dtype(fl))):
             torch.empty = sentinel_empty
             try:
                 out = call()
@@ -167,9 +230,9 @@ def main():
                 torch.empty = _empty
             h = groups.setdefault(name.split(":")[0], hashlib.sha256())
             h.update(name.encode() + b"\0" + output_bytes(out))
-            calls += fl == "f16"
+            calls += fl != "bf16"
         res[fl] = {g: h.hexdigest() for g, h in groups.items()}
-    out = dict(abi=hip.lib("f16").rv_abi_version(), cases=calls, groups=len(res["f16"]), digests=res)
+    out = dict(abi=hip.lib("f16").rv_abi_version(), cases=calls, groups=len(res["f16"]) + len(res["chain"]), digests=res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
