@@ -10,22 +10,125 @@
 // so there is no LDS traffic and no cross-lane movement besides two shuffles for the row max.  V is
 // kept transposed in memory ([dh][keys]: the KV cache is written that way, the adapter transposes once).
 // K / V^T tiles come straight from L2 (a head's K/V is <= 64 KB at the path's sequence lengths).
+//
+// Two bodies walk the keys - attn_body (every wave fetches its own fragments from L2) and attn_body_lds (a workgroup stages them in LDS once) - and both
+// hand every (query tile, key block) to ONE step, ATTN_BLOCK_STEP: a row's arithmetic is the same text whichever kernel computes it, which is what the
+// bit-identity tests of the staged forms against the per-wave forms rest on.
 #include "kernels.h"
-
-// compile-time probe: 1 = the prefill pair / groups kernel takes 32 query rows per wave (attn_body2: a key block's K / V^T loaded once for two
-// query tiles; 204 registers, needs __launch_bounds__(256, 2) on the kernel to keep two waves per SIMD), 0 (default) = 16 rows (attn_body, three
-// waves per SIMD).  Measured at 4 x 1005 rows: 67.0 vs 62 us per layer - the launch lives on waves in flight, not on L2 bytes.  Bit-identical.
-#ifndef ATTN_PAIR_Q32
-#define ATTN_PAIR_Q32 0
-#endif
 
 namespace {
 
+// What a lane addresses.  Lane (fr = lane & 15, g = lane >> 4) owns query / output row fr of a 16-row tile and keys 8g .. 8g + 7 of a 32-key block.
+// Its query row of the tile that starts at row0 (a row past the problem repeats the last one: loaded, never stored):
+template <int DH>
+__device__ __forceinline__ const op16_t* attn_q_ptr(const AttnArgs& a, int h, int b, int row0, int fr, int g) {
+    return (const op16_t*)a.q + (int64_t)b * a.q_bs + (int64_t)min(row0 + fr, a.Lq - 1) * a.q_rs + h * DH + g * 8;
+}
+// kbase / vbase: its addresses in key 0 / V^T row fr of the (key batch, head); krow: the key of score-tile row fr within a block (+ 4 for tile 1)
+struct AttnKV {
+    const op16_t *kbase, *vbase;
+    int krow;
+};
+__device__ __forceinline__ AttnKV attn_kv_ptrs(const AttnArgs& a, int h, int kb, int fr, int g) {
+    return AttnKV{(const op16_t*)a.k + (int64_t)kb * a.k_bs + (int64_t)h * a.k_hs + g * 8,
+                  (const op16_t*)a.vt + (int64_t)kb * a.vt_bs + (int64_t)h * a.vt_hs + (int64_t)fr * a.vt_ds + g * a.vt_ks, (fr >> 2) * 8 + (fr & 3)};
+}
+
+// the NC 16-byte k-chunks of one operand row (a query row, a key row)
+template <int NC>
+__device__ __forceinline__ void attn_load_row(const op16_t* p, op16x8 (&f)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) f[c] = *(const op16x8*)(p + c * 32);
+}
+
+// THE step of the online softmax: the 32 keys from k0 (fragments kf, vf) against one 16-row query tile (qf; ql = the low halves of the query row under split
+// queries, scores = K.(Qhi + Qlo)); g = lane >> 4 (the lane's keys are k0 + 8g ..), qbase = the position of the tile's row 0, qpos = of the lane's row.
+// PAD: a key-padding mask is present (the text cross-attention of the adapter); without it the per-key byte loads and their branches are compiled out.
+//   - an INTERIOR block (wave-uniform: every key exists and is visible to all 16 rows) takes no per-element masking;
+//   - O is rescaled only when the running maximum moved for some row of this wave (the ballot).
+// The order of the operations below is what "bit-identical" means in this file.  A macro, not a function: every function form compiled cost the kernels with a
+// run-time `causal` their fourth wave per SIMD (profiles/attention_refactor_isa.txt).  Its locals end in _ so that no argument expression can name one.
+#define ATTN_BLOCK_STEP(DH, PAD, QS, a, g, kf, vf, qf, ql, k0, Lk, causal, qbase, qpos, pad, m_run, l_run, o)                 \
+    do {                                                                                                                      \
+        f32x4 s_[2];                                                                                                          \
+        _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_) {                                                                    \
+            s_[t_] = f32x4{0.f, 0.f, 0.f, 0.f};                                                                               \
+            _Pragma("unroll") for (int c_ = 0; c_ < (DH) / 32; ++c_) s_[t_] = rv_mfma16((kf)[t_][c_], (qf)[c_], s_[t_]);      \
+            if constexpr (QS) {                                                                                               \
+                _Pragma("unroll") for (int c_ = 0; c_ < (DH) / 32; ++c_) s_[t_] = rv_mfma16((kf)[t_][c_], (ql)[c_], s_[t_]);  \
+            }                                                                                                                 \
+        }                                                                                                                     \
+        float mx_ = -INFINITY;                                                                                                \
+        const bool interior_ = !(PAD) && (k0) + 32 <= (Lk) && (!(causal) || (k0) + 31 <= (qbase));                            \
+        if (interior_) {                                                                                                      \
+            _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                                  \
+                _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) {                                                            \
+                    s_[t_][r_] *= (a).scale;                                                                                  \
+                    mx_ = fmaxf(mx_, s_[t_][r_]);                                                                             \
+                }                                                                                                             \
+        } else {                                                                                                              \
+            _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                                  \
+                _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) {                                                            \
+                    const int key_ = (k0) + (g) * 8 + t_ * 4 + r_;                                                            \
+                    bool dead_ = key_ >= (Lk) || ((causal) && key_ > (qpos));                                                 \
+                    if ((PAD) && key_ < (Lk)) dead_ = dead_ || (pad)[key_];                                                   \
+                    const float v_ = dead_ ? -INFINITY : s_[t_][r_] * (a).scale;                                              \
+                    s_[t_][r_] = v_;                                                                                          \
+                    mx_ = fmaxf(mx_, v_);                                                                                     \
+                }                                                                                                             \
+        }                                                                                                                     \
+        mx_ = fmaxf(mx_, __shfl_xor(mx_, 16, 64));                                                                            \
+        mx_ = fmaxf(mx_, __shfl_xor(mx_, 32, 64));                                                                            \
+        const float m_new_ = fmaxf(m_run, mx_);                                                                               \
+        const float m_use_ = m_new_ == -INFINITY ? 0.f : m_new_;                                                              \
+        const float alpha_ = __expf((m_run) - m_use_); /* m_run = -inf -> 0 */                                                \
+        float psum_ = 0.f;                                                                                                    \
+        float p_[8];                                                                                                          \
+        _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_)                                                                      \
+            _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) {                                                                \
+                const float e_ = __expf(s_[t_][r_] - m_use_);                                                                 \
+                p_[t_ * 4 + r_] = e_;                                                                                         \
+                psum_ += e_;                                                                                                  \
+            }                                                                                                                 \
+        l_run = (l_run) * alpha_ + psum_;                                                                                     \
+        m_run = m_new_;                                                                                                       \
+        union { op16x8 v; uint32_t u[4]; } pf_;                                                                               \
+        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) pf_.u[i_] = pack_op16x2_bounded(p_[2 * i_], p_[2 * i_ + 1]);         \
+        if (__builtin_amdgcn_ballot_w64(alpha_ != 1.0f) != 0) {                                                               \
+            _Pragma("unroll") for (int dt_ = 0; dt_ < (DH) / 16; ++dt_) (o)[dt_] *= alpha_;                                   \
+        }                                                                                                                     \
+        _Pragma("unroll") for (int dt_ = 0; dt_ < (DH) / 16; ++dt_) (o)[dt_] = rv_mfma16((vf)[dt_], pf_.v, (o)[dt_]);         \
+    } while (0)
+
+// a row's l over the four lanes that hold its keys
+__device__ __forceinline__ float attn_row_sum(float l) {
+    l += __shfl_xor(l, 16, 64);
+    return l + __shfl_xor(l, 32, 64);
+}
+
+// The end of a tile on every path without a key split: O / l to the lane's output row, and with a.out_lo its low half (LO = false: a staged form, never launched
+// with split outputs - the half's code stays out of its kernels).  Whole waves call it (the row sum shuffles); the lanes of rows past the problem store nothing.
+template <int DH, bool PAD, bool LO = true>
+__device__ __forceinline__ void attn_store_tile(const AttnArgs& a, int h, int b, int row0, int fr, int g, float l_run, const f32x4 (&o)[DH / 16]) {
+    constexpr int ND = DH / 16;
+    l_run = attn_row_sum(l_run);
+    if (row0 + fr >= a.Lq) return;
+    const float inv = PAD && l_run == 0.f ? 0.f : 1.0f / l_run;      // (every key padded: a zero row)
+    op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)(row0 + fr) * a.o_rs + h * DH + g * 4;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt)
+        *(u32x2*)(op + dt * 16) = pack_op16x4(f32x4{o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv});
+    if (LO && a.out_lo) {
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt)
+            *(u32x2*)(op + a.out_lo + dt * 16) = u32x2{pack_op16x2_lo(o[dt][0] * inv, o[dt][1] * inv), pack_op16x2_lo(o[dt][2] * inv, o[dt][3] * inv)};
+    }
+}
+
+// PER-WAVE form: every wave fetches its key blocks' fragments from L2 itself.
 // SPLIT (Lq <= 16, i.e. KV-cached decode): the block's 4 waves share the same 16 queries and take key blocks
 // w, w+4, ...; their (m, l, O) partials are merged through LDS.  A decode step is pure latency (one wave would
 // walk all keys serially), so this cuts it ~4x.
-// PAD: a key-padding mask is present (the text cross-attention of the adapter); without it the per-key byte loads and their
-// branches are compiled out.
 template <int DH, bool SPLIT, bool PAD, bool QS = false>
 __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int b, [[maybe_unused]] float* merge = nullptr) {
     constexpr int NC = DH / 32, ND = DH / 16;
@@ -40,18 +143,13 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int 
     if (Lk <= 0 || (a.row_pos && Lk > a.Lk)) return;   // inactive row; a row past the pool's capacity (a.Lk = Smax) is treated like one
     const int q_pos0 = a.row_pos ? Lk - a.Lq : a.q_pos0;
 
-    const op16_t* qp = (const op16_t*)a.q + (int64_t)b * a.q_bs + (int64_t)min(q0 + fr, a.Lq - 1) * a.q_rs + h * DH + g * 8;
+    const op16_t* qp = attn_q_ptr<DH>(a, h, b, q0, fr, g);
     op16x8 qf[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) qf[c] = *(const op16x8*)(qp + c * 32);
-    op16x8 ql[QS ? NC : 1];      // parity precision: the low halves of the query row (scores = K.(Qhi + Qlo))
-    if constexpr (QS) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) ql[c] = *(const op16x8*)(qp + a.q_lo + c * 32);
-    }
+    attn_load_row(qp, qf);
+    op16x8 ql[QS ? NC : 1];      // parity precision: the low halves of the query row
+    if constexpr (QS) attn_load_row(qp + a.q_lo, ql);
+    const AttnKV kv = attn_kv_ptrs(a, h, kb_, fr, g);
 
-    const op16_t* kbase = (const op16_t*)a.k + (int64_t)kb_ * a.k_bs + (int64_t)h * a.k_hs + g * 8;
-    const op16_t* vbase = (const op16_t*)a.vt + (int64_t)kb_ * a.vt_bs + (int64_t)h * a.vt_hs + (int64_t)fr * a.vt_ds + g * a.vt_ks;
     // key blocks inside the prefix this row shares with a sibling row are read from the sibling's (bit-identical) cache rows: L2 hits
     int share_len = 0;
     int64_t share_k = 0, share_v = 0;       // element offsets from this row's bases to the sibling's
@@ -65,7 +163,6 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int 
         share_k = (int64_t)(srow - kb_) * a.k_bs;
         share_v = (int64_t)(srow - kb_) * a.vt_bs;
     }
-    const int krow = (fr >> 2) * 8 + (fr & 3);   // key of score-tile row fr within the 32-key block (+ 4 for tile 1)
     const uint8_t* pad = PAD ? a.key_pad + (int64_t)kb_ * a.Lk : nullptr;
 
     f32x4 o[ND];
@@ -82,80 +179,14 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int 
         const bool shared_blk = SPLIT && k0 + 32 <= share_len;      // (wave-uniform) the whole block lies inside the shared prefix
         const int64_t sk = shared_blk ? share_k : 0, svo = shared_blk ? share_v : 0;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int key = min(k0 + krow + t * 4, Lk - 1);
-            const op16_t* kp = kbase + sk + (int64_t)key * a.k_rs;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) kf[t][c] = *(const op16x8*)(kp + c * 32);
-        }
+        for (int t = 0; t < 2; ++t) attn_load_row(kv.kbase + sk + (int64_t)min(k0 + kv.krow + t * 4, Lk - 1) * a.k_rs, kf[t]);
         op16x8 vf[ND];
 #pragma unroll
-        for (int dt = 0; dt < ND; ++dt) vf[dt] = *(const op16x8*)(vbase + svo + (int64_t)dt * 16 * a.vt_ds + (int64_t)(k0 >> 3) * a.vt_ks);
-        f32x4 s[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < NC; ++c) s[t] = rv_mfma16(kf[t][c], qf[c], s[t]);
-            if constexpr (QS) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) s[t] = rv_mfma16(kf[t][c], ql[c], s[t]);
-            }
-        }
-        float mx = -INFINITY;
-        // interior block (wave-uniform): every key exists and is visible to all 16 rows - no per-element masking
-        const bool interior = !PAD && k0 + 32 <= Lk && (!a.causal || k0 + 31 <= q_pos0 + q0);
-        if (interior) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    s[t][r] *= a.scale;
-                    mx = fmaxf(mx, s[t][r]);
-                }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = k0 + g * 8 + t * 4 + r;
-                    bool dead = key >= Lk || (a.causal && key > qpos);
-                    if (PAD && key < Lk) dead = dead || pad[key];
-                    const float v = dead ? -INFINITY : s[t][r] * a.scale;
-                    s[t][r] = v;
-                    mx = fmaxf(mx, v);
-                }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __expf(m_run - m_use);  // m_run = -inf -> 0
-        float psum = 0.f;
-        float p[8];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __expf(s[t][r] - m_use);
-                p[t * 4 + r] = e;
-                psum += e;
-            }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-        union { op16x8 v; uint32_t u[4]; } pf;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pf.u[i] = pack_op16x2_bounded(p[2 * i], p[2 * i + 1]);
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {   // the running maximum moved for some row of this wave
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
-        }
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) o[dt] = rv_mfma16(vf[dt], pf.v, o[dt]);
+        for (int dt = 0; dt < ND; ++dt) vf[dt] = *(const op16x8*)(kv.vbase + svo + (int64_t)dt * 16 * a.vt_ds + (int64_t)(k0 >> 3) * a.vt_ks);
+        ATTN_BLOCK_STEP(DH, PAD, QS, a, g, kf, vf, qf, ql, k0, Lk, a.causal, q_pos0 + q0, qpos, pad, m_run, l_run, o);
     }
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
     if constexpr (SPLIT) {
+        l_run = attn_row_sum(l_run);
         // (the merge area belongs to the KERNEL: as function-local __shared__ arrays every instantiation of this body a kernel dispatches between - with and
         // without a padding mask - got its own copy, 68.6 KB per workgroup for the decode attention instead of 34.3: two workgroups per CU instead of three)
         float (*sm_o)[16][DH + 4] = (float (*)[16][DH + 4])merge;
@@ -194,174 +225,42 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int bx, int h, int 
             else *(uint32_t*)(op + j) = pack_op16x2(v0 * inv, v1 * inv);
             if (a.out_lo) *(uint32_t*)(op + a.out_lo + j) = pack_op16x2_lo(v0 * inv, v1 * inv);
         }
-        return;
-    }
-    if (q0 + fr >= a.Lq) return;
-    const float inv = PAD && l_run == 0.f ? 0.f : 1.0f / l_run;      // (every key padded: a zero row)
-    op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)(q0 + fr) * a.o_rs + h * DH + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-        *(u32x2*)(op + dt * 16) = pack_op16x4(f32x4{o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv});
-    if (a.out_lo) {
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-            *(u32x2*)(op + a.out_lo + dt * 16) = u32x2{pack_op16x2_lo(o[dt][0] * inv, o[dt][1] * inv), pack_op16x2_lo(o[dt][2] * inv, o[dt][3] * inv)};
+    } else {
+        attn_store_tile<DH, PAD>(a, h, b, q0, fr, g, l_run, o);
     }
 }
 
-// Prefill form with TWO 16-row query tiles per wave (32 rows; a workgroup = 128 rows): a key block's K rows and V^T rows are loaded once and used
-// by both tiles - half the L2 -> CU bytes per query row.  No key split, no padding mask, no per-row positions, bf16 queries: the LLM prefill.
-// Per tile exactly the operations of attn_body in the same order (a tile skips the key blocks past its own causal range): bit-identical rows.
-template <int DH>
-__device__ __forceinline__ void attn_body2(const AttnArgs& a, int bx, int h, int b) {
-    constexpr int NC = DH / 32, ND = DH / 16;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int fr = lane & 15, g = lane >> 4;
-    const int q0 = bx * 128 + wave * 32;
-    if (q0 >= a.Lq) return;
-    const int kb_ = b / a.kv_div;
-    const int Lk = a.Lk, q_pos0 = a.q_pos0;
-    op16x8 qf[2][NC];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const op16_t* qp = (const op16_t*)a.q + (int64_t)b * a.q_bs + (int64_t)min(q0 + qt * 16 + fr, a.Lq - 1) * a.q_rs + h * DH + g * 8;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) qf[qt][c] = *(const op16x8*)(qp + c * 32);
-    }
-    const op16_t* kbase = (const op16_t*)a.k + (int64_t)kb_ * a.k_bs + (int64_t)h * a.k_hs + g * 8;
-    const op16_t* vbase = (const op16_t*)a.vt + (int64_t)kb_ * a.vt_bs + (int64_t)h * a.vt_hs + (int64_t)fr * a.vt_ds + g * a.vt_ks;
-    const int krow = (fr >> 2) * 8 + (fr & 3);
-    f32x4 o[2][ND];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-        for (int i = 0; i < ND; ++i) o[qt][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
-    const bool two = q0 + 16 < a.Lq;                      // (wave-uniform) the second tile holds rows
-    int kend_t[2];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) kend_t[qt] = a.causal ? min(Lk, q_pos0 + q0 + qt * 16 + 16) : Lk;
-    const int kend = two ? kend_t[1] : kend_t[0];
-    for (int k0 = 0; k0 < kend; k0 += 32) {
-        op16x8 kf[2][NC];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int key = min(k0 + krow + t * 4, Lk - 1);
-            const op16_t* kp = kbase + (int64_t)key * a.k_rs;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) kf[t][c] = *(const op16x8*)(kp + c * 32);
-        }
-        op16x8 vf[ND];
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) vf[dt] = *(const op16x8*)(vbase + (int64_t)dt * 16 * a.vt_ds + (int64_t)(k0 >> 3) * a.vt_ks);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-            if (k0 >= kend_t[qt] || (qt == 1 && !two)) continue;      // (wave-uniform)
-            f32x4 s[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < NC; ++c) s[t] = rv_mfma16(kf[t][c], qf[qt][c], s[t]);
-            }
-            float mx = -INFINITY;
-            const int qbase = q_pos0 + q0 + qt * 16;
-            const bool interior = k0 + 32 <= Lk && (!a.causal || k0 + 31 <= qbase);
-            if (interior) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        s[t][r] *= a.scale;
-                        mx = fmaxf(mx, s[t][r]);
-                    }
-            } else {
-                const int qpos = qbase + fr;
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = k0 + g * 8 + t * 4 + r;
-                        const bool dead = key >= Lk || (a.causal && key > qpos);
-                        const float v = dead ? -INFINITY : s[t][r] * a.scale;
-                        s[t][r] = v;
-                        mx = fmaxf(mx, v);
-                    }
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run[qt], mx);
-            const float m_use = m_new == -INFINITY ? 0.f : m_new;
-            const float alpha = __expf(m_run[qt] - m_use);
-            float psum = 0.f;
-            float pp[8];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = __expf(s[t][r] - m_use);
-                    pp[t * 4 + r] = e;
-                    psum += e;
-                }
-            l_run[qt] = l_run[qt] * alpha + psum;
-            m_run[qt] = m_new;
-            union { op16x8 v; uint32_t u[4]; } pf;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pf.u[i] = pack_op16x2_bounded(pp[2 * i], pp[2 * i + 1]);
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-#pragma unroll
-                for (int dt = 0; dt < ND; ++dt) o[qt][dt] *= alpha;
-            }
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt) o[qt][dt] = rv_mfma16(vf[dt], pf.v, o[qt][dt]);
-        }
-    }
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        float l = l_run[qt];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const int row = q0 + qt * 16 + fr;
-        if (row >= a.Lq) continue;
-        const float inv = 1.0f / l;
-        op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)row * a.o_rs + h * DH + g * 4;
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-            *(u32x2*)(op + dt * 16) = pack_op16x4(f32x4{o[qt][dt][0] * inv, o[qt][dt][1] * inv, o[qt][dt][2] * inv, o[qt][dt][3] * inv});
-    }
-}
-
-// LONG-KEY form (round 6): the adapter's self-attention over 257 / 1025 keys, the CLIP towers.  attn_body fetches every key block's K and V^T fragments from L2
-// once PER WAVE: twelve 16-byte-per-lane loads per 32 keys and wave at dh = 96, and the CU's vector-memory path accepts one such instruction per 16 cycles for all
-// four SIMDs together - 768 cycles of address work per block step against 192 of MFMA (32 windows x 1024 frames: 308 us per layer, 0.13 of the MFMA peak).  Here a
-// workgroup is 4 waves x 32 query rows (two 16-row tiles per wave share a block's fragments in registers, as attn_body2) and a key block is staged in LDS ONCE per
-// workgroup by LDS-DMA - each wave moves NF / 4 of its NF fragments, already in the lane order the MFMAs consume, so every ds_read_b128 is one conflict-free 1 KiB
-// run - double-buffered: block i + 1 travels while block i is computed, one barrier per block.  No key split, no padding mask, no per-row positions, not causal.
-// Per tile the operations of attn_body in the same order: rows are BIT-identical to the short-key kernel's.
+// STAGED form (round 6).  attn_body fetches every key block's K and V^T fragments from L2 once PER WAVE: twelve 16-byte-per-lane loads per 32 keys and wave at
+// dh = 96, and the CU's vector-memory path accepts one such instruction per 16 cycles for all four SIMDs together - 768 cycles of address work per block step
+// against 192 of MFMA (32 windows x 1024 frames: 308 us per layer, 0.13 of the MFMA peak).  Here a key block is staged in LDS ONCE per workgroup by LDS-DMA -
+// each wave moves NF / 4 of its NF fragments, already in the lane order the MFMAs consume, so every ds_read_b128 is one conflict-free 1 KiB run -
+// double-buffered: block i + 1 travels while block i is computed, one barrier per block.  No key split, no padding mask, no per-row positions.
+//   NT = 2  the LONG-KEY form: the adapter's self-attention over 257 / 1025 keys, the CLIP towers.  A workgroup is 4 waves x 32 query rows: the two 16-row tiles
+//           of a wave share a block's fragments in registers.  Not causal, and that is a compile-time fact: its kernels hold no masking code but the key count's.
+//   NT = 1  the LLM PREFILL (causal or not, dh = 128, 171 keys at the headline): 64 query rows per workgroup - the tiling of attn_body, so a workgroup's four
+//           waves (which attn_kernel_pair lets fetch the same key blocks four times) share one staged copy.  A wave computes the blocks below its own causal
+//           limit and keeps staging / the barriers for the rest of the workgroup's range.
+// Per tile the step is attn_body's: rows are BIT-identical to the per-wave kernels'.
 typedef const __attribute__((address_space(1))) void* attn_gptr_t;
 typedef __attribute__((address_space(3))) void* attn_lptr_t;
 template <int DH>
+constexpr int ATTN_STAGE = (2 * (DH / 32) + DH / 16) * 1024;      // bytes of one staged key block: a KiB per fragment; a staged kernel holds two
+template <int DH, int NT>
 __device__ __forceinline__ void attn_body_lds(const AttnArgs& a, int bx, int h, int b, char* smem) {
-    constexpr int NC = DH / 32, ND = DH / 16, NF = 2 * NC + ND, STAGE = NF * 1024;
+    constexpr int NC = DH / 32, ND = DH / 16, NF = 2 * NC + ND, STAGE = ATTN_STAGE<DH>;
     static_assert(NF % 4 == 0, "the four waves stage NF / 4 fragments each");
+    static_assert(NT == 1 || NT == 2, "one or two query tiles per wave");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, g = lane >> 4;
-    const int q0 = bx * 128 + wave * 32;
-    const bool active = q0 < a.Lq, two = q0 + 16 < a.Lq;      // (wave-uniform) an idle wave still stages its share and keeps the barriers
-    const int kb_ = b / a.kv_div;
-    const int Lk = a.Lk;
-    op16x8 qf[2][NC];
+    const int q0 = (bx * 4 + wave) * 16 * NT;
+    const bool active = q0 < a.Lq, two = NT == 2 && q0 + 16 < a.Lq;      // (wave-uniform) an idle wave still stages its share and keeps the barriers
+    const int causal = NT == 1 ? a.causal : 0;
+    const int Lk = a.Lk, q_pos0 = a.q_pos0;
+    op16x8 qf[NT][NC];
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        const op16_t* qp = (const op16_t*)a.q + (int64_t)b * a.q_bs + (int64_t)min(q0 + qt * 16 + fr, a.Lq - 1) * a.q_rs + h * DH + g * 8;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) qf[qt][c] = *(const op16x8*)(qp + c * 32);
-    }
-    const op16_t* kbase = (const op16_t*)a.k + (int64_t)kb_ * a.k_bs + (int64_t)h * a.k_hs + g * 8;
-    const op16_t* vbase = (const op16_t*)a.vt + (int64_t)kb_ * a.vt_bs + (int64_t)h * a.vt_hs + (int64_t)fr * a.vt_ds + g * a.vt_ks;
-    const int krow = (fr >> 2) * 8 + (fr & 3);
+    for (int qt = 0; qt < NT; ++qt) attn_load_row(attn_q_ptr<DH>(a, h, b, q0 + qt * 16, fr, g), qf[qt]);
+    const AttnKV kv = attn_kv_ptrs(a, h, b / a.kv_div, fr, g);
     // fragment f of a block: f < 2 NC: score tile t = f / NC, k-chunk c = f % NC of K; else V^T fragment dt = f - 2 NC.  The source address of a lane is the
     // address attn_body loads from; the destination is lane-linear behind the fragment's base.
     auto stage = [&](int k0, char* buf) {
@@ -371,29 +270,36 @@ __device__ __forceinline__ void attn_body_lds(const AttnArgs& a, int bx, int h, 
             const op16_t* src;
             if (f < 2 * NC) {
                 const int t = f / NC, c = f - t * NC;
-                src = kbase + (int64_t)min(k0 + krow + t * 4, Lk - 1) * a.k_rs + c * 32;
+                src = kv.kbase + (int64_t)min(k0 + kv.krow + t * 4, Lk - 1) * a.k_rs + c * 32;
             } else {
-                src = vbase + (int64_t)(f - 2 * NC) * 16 * a.vt_ds + (int64_t)(k0 >> 3) * a.vt_ks;
+                src = kv.vbase + (int64_t)(f - 2 * NC) * 16 * a.vt_ds + (int64_t)(k0 >> 3) * a.vt_ks;
             }
             __builtin_amdgcn_global_load_lds((attn_gptr_t)src, (attn_lptr_t)(buf + f * 1024), 16, 0, 0);
         }
     };
-    f32x4 o[2][ND];
+    f32x4 o[NT][ND];
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
+    for (int qt = 0; qt < NT; ++qt)
 #pragma unroll
         for (int i = 0; i < ND; ++i) o[qt][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
-    const int nblk = (Lk + 31) >> 5;
+    float m_run[NT], l_run[NT];
+#pragma unroll
+    for (int qt = 0; qt < NT; ++qt) m_run[qt] = -INFINITY, l_run[qt] = 0.f;
+    // the causal limits are quantities of the NT = 1 form (one tile per wave, 64 rows per workgroup); with NT = 2 `causal` is the literal 0 and both fold to Lk
+    const int kend = causal ? min(Lk, q_pos0 + q0 + 16) : Lk;                                   // this wave's keys
+    const int kend_wg = causal ? min(Lk, q_pos0 + min(bx * 64 + 64, a.Lq)) : Lk;                 // the workgroup's (its last live row's)
+    const int nblk = (kend_wg + 31) >> 5;
+    const op16x8* const no_ql = nullptr;      // (no split queries and no padding mask in the staged forms: those arms of the step are compiled out)
+    const uint8_t* const no_pad = nullptr;
     stage(0, smem);
     for (int i = 0; i < nblk; ++i) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of block i have landed ...
         __builtin_amdgcn_s_barrier();                         // ... and everyone's; and every wave is done reading the other buffer (block i - 1)
         asm volatile("" ::: "memory");
         if (i + 1 < nblk) stage((i + 1) * 32, smem + ((i + 1) & 1) * STAGE);
-        if (!active) continue;
-        const char* buf = smem + (i & 1) * STAGE + lane * 16;
         const int k0 = i * 32;
+        if (!active || (NT == 1 && k0 >= kend)) continue;
+        const char* buf = smem + (i & 1) * STAGE + lane * 16;
         op16x8 kf[2][NC];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -403,202 +309,14 @@ __device__ __forceinline__ void attn_body_lds(const AttnArgs& a, int bx, int h, 
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) vf[dt] = *(const op16x8*)(buf + (2 * NC + dt) * 1024);
 #pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
+        for (int qt = 0; qt < NT; ++qt) {
             if (qt == 1 && !two) continue;      // (wave-uniform)
-            f32x4 s[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < NC; ++c) s[t] = rv_mfma16(kf[t][c], qf[qt][c], s[t]);
-            }
-            float mx = -INFINITY;
-            if (k0 + 32 <= Lk) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        s[t][r] *= a.scale;
-                        mx = fmaxf(mx, s[t][r]);
-                    }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = k0 + g * 8 + t * 4 + r;
-                        const float v = key >= Lk ? -INFINITY : s[t][r] * a.scale;
-                        s[t][r] = v;
-                        mx = fmaxf(mx, v);
-                    }
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run[qt], mx);
-            const float m_use = m_new == -INFINITY ? 0.f : m_new;
-            const float alpha = __expf(m_run[qt] - m_use);
-            float psum = 0.f;
-            float pp[8];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = __expf(s[t][r] - m_use);
-                    pp[t * 4 + r] = e;
-                    psum += e;
-                }
-            l_run[qt] = l_run[qt] * alpha + psum;
-            m_run[qt] = m_new;
-            union { op16x8 v; uint32_t u[4]; } pf;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pf.u[j] = pack_op16x2_bounded(pp[2 * j], pp[2 * j + 1]);
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-#pragma unroll
-                for (int dt = 0; dt < ND; ++dt) o[qt][dt] *= alpha;
-            }
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt) o[qt][dt] = rv_mfma16(vf[dt], pf.v, o[qt][dt]);
+            const int qbase = q_pos0 + q0 + qt * 16, qpos = qbase + fr;
+            ATTN_BLOCK_STEP(DH, false, false, a, g, kf, vf, qf[qt], no_ql, k0, Lk, causal, qbase, qpos, no_pad, m_run[qt], l_run[qt], o[qt]);
         }
     }
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-        float l = l_run[qt];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const int row = q0 + qt * 16 + fr;
-        if (row >= a.Lq) continue;
-        const float inv = 1.0f / l;
-        op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)row * a.o_rs + h * DH + g * 4;
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-            *(u32x2*)(op + dt * 16) = pack_op16x4(f32x4{o[qt][dt][0] * inv, o[qt][dt][1] * inv, o[qt][dt][2] * inv, o[qt][dt][3] * inv});
-    }
-}
-
-// The same staging for the LLM PREFILL (causal, dh = 128, 171 keys at the headline): one 16-row tile per wave, 64 query rows per workgroup - the tiling of attn_body, so
-// a workgroup's four waves (which attn_kernel_pair lets fetch the same key blocks four times) share one staged copy.  A wave computes the blocks below its own causal
-// limit and keeps staging / the barriers for the rest of the workgroup's range.  Per tile the operations of attn_body in the same order: bit-identical rows.
-template <int DH>
-__device__ __forceinline__ void attn_body_lds1(const AttnArgs& a, int bx, int h, int b, char* smem) {
-    constexpr int NC = DH / 32, ND = DH / 16, NF = 2 * NC + ND, STAGE = NF * 1024;
-    static_assert(NF % 4 == 0, "the four waves stage NF / 4 fragments each");
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int fr = lane & 15, g = lane >> 4;
-    const int q0 = bx * 64 + wave * 16;
-    const bool active = q0 < a.Lq;
-    const int kb_ = b / a.kv_div;
-    const int Lk = a.Lk, q_pos0 = a.q_pos0;
-    const op16_t* qp = (const op16_t*)a.q + (int64_t)b * a.q_bs + (int64_t)min(q0 + fr, a.Lq - 1) * a.q_rs + h * DH + g * 8;
-    op16x8 qf[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) qf[c] = *(const op16x8*)(qp + c * 32);
-    const op16_t* kbase = (const op16_t*)a.k + (int64_t)kb_ * a.k_bs + (int64_t)h * a.k_hs + g * 8;
-    const op16_t* vbase = (const op16_t*)a.vt + (int64_t)kb_ * a.vt_bs + (int64_t)h * a.vt_hs + (int64_t)fr * a.vt_ds + g * a.vt_ks;
-    const int krow = (fr >> 2) * 8 + (fr & 3);
-    auto stage = [&](int k0, char* buf) {
-#pragma unroll
-        for (int i = 0; i < NF / 4; ++i) {
-            const int f = wave + 4 * i;
-            const op16_t* src;
-            if (f < 2 * NC) {
-                const int t = f / NC, c = f - t * NC;
-                src = kbase + (int64_t)min(k0 + krow + t * 4, Lk - 1) * a.k_rs + c * 32;
-            } else {
-                src = vbase + (int64_t)(f - 2 * NC) * 16 * a.vt_ds + (int64_t)(k0 >> 3) * a.vt_ks;
-            }
-            __builtin_amdgcn_global_load_lds((attn_gptr_t)src, (attn_lptr_t)(buf + f * 1024), 16, 0, 0);
-        }
-    };
-    f32x4 o[ND];
-#pragma unroll
-    for (int i = 0; i < ND; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run = -INFINITY, l_run = 0.f;
-    const int qpos = q_pos0 + q0 + fr;
-    const int kend = a.causal ? min(Lk, q_pos0 + q0 + 16) : Lk;                        // this wave's keys
-    const int kend_wg = a.causal ? min(Lk, q_pos0 + min(bx * 64 + 64, a.Lq)) : Lk;      // the workgroup's (its last live row's)
-    const int nblk = (kend_wg + 31) >> 5;
-    stage(0, smem);
-    for (int i = 0; i < nblk; ++i) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (i + 1 < nblk) stage((i + 1) * 32, smem + ((i + 1) & 1) * STAGE);
-        const int k0 = i * 32;
-        if (!active || k0 >= kend) continue;
-        const char* buf = smem + (i & 1) * STAGE + lane * 16;
-        op16x8 kf[2][NC];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int c = 0; c < NC; ++c) kf[t][c] = *(const op16x8*)(buf + (t * NC + c) * 1024);
-        op16x8 vf[ND];
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) vf[dt] = *(const op16x8*)(buf + (2 * NC + dt) * 1024);
-        f32x4 s[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < NC; ++c) s[t] = rv_mfma16(kf[t][c], qf[c], s[t]);
-        }
-        float mx = -INFINITY;
-        const bool interior = k0 + 32 <= Lk && (!a.causal || k0 + 31 <= q_pos0 + q0);
-        if (interior) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    s[t][r] *= a.scale;
-                    mx = fmaxf(mx, s[t][r]);
-                }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = k0 + g * 8 + t * 4 + r;
-                    const bool dead = key >= Lk || (a.causal && key > qpos);
-                    const float v = dead ? -INFINITY : s[t][r] * a.scale;
-                    s[t][r] = v;
-                    mx = fmaxf(mx, v);
-                }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __expf(m_run - m_use);
-        float psum = 0.f;
-        float p[8];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __expf(s[t][r] - m_use);
-                p[t * 4 + r] = e;
-                psum += e;
-            }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-        union { op16x8 v; uint32_t u[4]; } pf;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pf.u[j] = pack_op16x2_bounded(p[2 * j], p[2 * j + 1]);
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
-        }
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt) o[dt] = rv_mfma16(vf[dt], pf.v, o[dt]);
-    }
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (q0 + fr >= a.Lq) return;
-    const float inv = 1.0f / l_run;
-    op16_t* op = (op16_t*)a.out + (int64_t)b * a.o_bs + (int64_t)(q0 + fr) * a.o_rs + h * DH + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-        *(u32x2*)(op + dt * 16) = pack_op16x4(f32x4{o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv});
+    for (int qt = 0; qt < NT; ++qt) attn_store_tile<DH, false, false>(a, h, b, q0 + qt * 16, fr, g, l_run[qt], o[qt]);
 }
 
 // 1-D grid, XCD-aware: workgroup id lands on XCD id % 8 (private L2), so the query tiles of one (batch, head) - which read
@@ -624,66 +342,49 @@ __global__ __launch_bounds__(256, DH <= 128 ? 3 : 1) void attn_kernel(AttnArgs a
     else attn_body<DH, SPLIT, false>(a, bx, h, b, merge);
 }
 
-template <int DH>
+// one problem with the key blocks staged in LDS: NT = 2, 128 query rows per workgroup (long keys, not causal); NT = 1, 64 rows (causal or not; the classic
+// single-generate prefill)
+template <int DH, int NT>
 __global__ __launch_bounds__(256, 2) void attn_kernel_lds(AttnArgs a, int tiles) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * (2 * (DH / 32) + DH / 16) * 1024];
+    __shared__ __attribute__((aligned(16))) char smem[2 * ATTN_STAGE<DH>];
     int bx, h, b;
     if (!attn_map(tiles, a.H, a.H * a.B, bx, h, b)) return;      // (workgroup-uniform)
-    attn_body_lds<DH>(a, bx, h, b, smem);
+    attn_body_lds<DH, NT>(a, bx, h, b, smem);
 }
 
 // Two attention problems of the same head geometry in one launch (the shared-prefix prefill: the prefix rows attend among
-// themselves, the per-call rows attend to prefix + own keys): blockIdx.z < a.B -> problem a, else problem b.
+// themselves, the per-call rows attend to prefix + own keys), G times over (AttnGroups): problem z of the launch -> its group's copy of problem a
+// (z < a.B within the group) or b, with the group's offsets on the four pointers; z becomes the index inside the group.
+__device__ __forceinline__ AttnArgs& attn_pair_problem(AttnArgs& a, AttnArgs& b, const AttnGroups& gr, int& z) {
+    const int per = a.B + b.B, g = z / per;
+    z -= g * per;
+    AttnArgs& p = z < a.B ? a : b;
+    if (gr.G > 1) {      // (uniform per workgroup)
+        p.q = (const op16_t*)p.q + gr.q_off[g];
+        p.out = (op16_t*)p.out + gr.o_off[g];
+        p.k = (const op16_t*)p.k + gr.kv_off[g];
+        p.vt = (const op16_t*)p.vt + gr.kv_off[g];
+    }
+    return p;
+}
 template <int DH, bool QS = false>
 __global__ __launch_bounds__(256, 3) void attn_kernel_pair(AttnArgs a, AttnArgs b, int tiles, AttnGroups gr) {
     int bx, h, z;
-    const int per = a.B + b.B;
-    if (!attn_map(tiles, a.H, a.H * per * gr.G, bx, h, z)) return;
-    const int g = z / per;
-    z -= g * per;
-    AttnArgs& p = z < a.B ? a : b;
-    if (gr.G > 1) {      // (uniform per workgroup)
-        p.q = (const op16_t*)p.q + gr.q_off[g];
-        p.out = (op16_t*)p.out + gr.o_off[g];
-        p.k = (const op16_t*)p.k + gr.kv_off[g];
-        p.vt = (const op16_t*)p.vt + gr.kv_off[g];
-    }
-    if constexpr (!QS && ATTN_PAIR_Q32) {
-        if (bx * 128 >= p.Lq) return;       // (the two problems may differ in length: tiles counts the longer one)
-        attn_body2<DH>(p, bx, h, z < a.B ? z : z - a.B);
-    } else {
-        if (z < a.B) attn_body<DH, false, false, QS>(p, bx, h, z);   // (the LLM prefill has no key padding: checked by the launcher)
-        else attn_body<DH, false, false, QS>(p, bx, h, z - a.B);
-    }
+    if (!attn_map(tiles, a.H, a.H * (a.B + b.B) * gr.G, bx, h, z)) return;
+    AttnArgs& p = attn_pair_problem(a, b, gr, z);
+    if (z < a.B) attn_body<DH, false, false, QS>(p, bx, h, z);   // (the LLM prefill has no key padding: checked by the launcher)
+    else attn_body<DH, false, false, QS>(p, bx, h, z - a.B);
 }
 
-// one problem, 64 query rows per workgroup, key blocks staged in LDS (causal or not; the classic single-generate prefill)
-template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_kernel_lds1(AttnArgs a, int tiles) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * (2 * (DH / 32) + DH / 16) * 1024];
-    int bx, h, b;
-    if (!attn_map(tiles, a.H, a.H * a.B, bx, h, b)) return;      // (workgroup-uniform)
-    attn_body_lds1<DH>(a, bx, h, b, smem);
-}
-
-// attn_kernel_pair with the key blocks staged in LDS (attn_body_lds1); no split queries
+// attn_kernel_pair with the key blocks staged in LDS (one tile per wave); no split queries
 template <int DH>
 __global__ __launch_bounds__(256, 2) void attn_kernel_pair_lds(AttnArgs a, AttnArgs b, int tiles, AttnGroups gr) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * (2 * (DH / 32) + DH / 16) * 1024];
+    __shared__ __attribute__((aligned(16))) char smem[2 * ATTN_STAGE<DH>];
     int bx, h, z;
-    const int per = a.B + b.B;
-    if (!attn_map(tiles, a.H, a.H * per * gr.G, bx, h, z)) return;
-    const int g = z / per;
-    z -= g * per;
-    AttnArgs& p = z < a.B ? a : b;
-    if (gr.G > 1) {      // (uniform per workgroup)
-        p.q = (const op16_t*)p.q + gr.q_off[g];
-        p.out = (op16_t*)p.out + gr.o_off[g];
-        p.k = (const op16_t*)p.k + gr.kv_off[g];
-        p.vt = (const op16_t*)p.vt + gr.kv_off[g];
-    }
+    if (!attn_map(tiles, a.H, a.H * (a.B + b.B) * gr.G, bx, h, z)) return;
+    const AttnArgs& p = attn_pair_problem(a, b, gr, z);
     if (bx * 64 >= p.Lq) return;       // (workgroup-uniform: the two problems may differ in length, tiles counts the longer one)
-    attn_body_lds1<DH>(p, bx, h, z < a.B ? z : z - a.B, smem);
+    attn_body_lds<DH, 1>(p, bx, h, z < a.B ? z : z - a.B, smem);
 }
 
 // Mixed-geometry prefill passes: every group brings its own pair of problems (AttnMixed).  Workgroup -> (problem, head, query tile) as attn_map does it; the problem
@@ -706,12 +407,12 @@ __device__ __forceinline__ void attn_mixed_problem(AttnArgs& p, const AttnMixed&
 }
 template <int DH>
 __global__ __launch_bounds__(256, 2) void attn_kernel_mixed_lds(AttnArgs a, AttnMixed mx, int tiles) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * (2 * (DH / 32) + DH / 16) * 1024];
+    __shared__ __attribute__((aligned(16))) char smem[2 * ATTN_STAGE<DH>];
     int bx, h, z, b;
     if (!attn_map(tiles, a.H, a.H * mx.problems, bx, h, z)) return;
     attn_mixed_problem(a, mx, z, b);
     if (bx * 64 >= a.Lq) return;       // (workgroup-uniform)
-    attn_body_lds1<DH>(a, bx, h, b, smem);
+    attn_body_lds<DH, 1>(a, bx, h, b, smem);
 }
 template <int DH>
 __global__ __launch_bounds__(256, 3) void attn_kernel_mixed(AttnArgs a, AttnMixed mx, int tiles) {
@@ -733,12 +434,37 @@ __global__ void mixed_tables_kernel(AttnMixed mx, QkvGroup* gt, int* last_rows) 
 
 }  // namespace
 
-static int attn_check(const AttnArgs& a) {
-    RV_CHECK_ARG(a.q && a.k && a.vt && a.out, "attention: null tensor");
-    RV_CHECK_ARG(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.kv_div > 0, "attention: empty problem");
+// The launchers' argument checks, each written once.  `who` heads the message: "attention", "attention mixed".
+static int attn_check_tensors(const AttnArgs& a, const char* who) {
+    RV_CHECK_ARG(a.q && a.k && a.vt && a.out, "%s: null tensor", who);
+    return RV_OK;
+}
+static int attn_check_strides(const AttnArgs& a) {
     RV_CHECK_ARG(a.q_rs % 8 == 0 && a.k_rs % 8 == 0 && a.k_hs % 8 == 0 && a.vt_ds % 8 == 0 && a.vt_hs % 8 == 0 && a.vt_bs % 8 == 0 && a.o_rs % 4 == 0,
                  "attention: stride alignment");
-    RV_CHECK_ARG(a.vt_ks != 8 || a.vt_ds >= ((a.Lk + 31) / 32) * 32, "attention: V^T rows must be padded to a multiple of 32 keys");
+    return RV_OK;
+}
+static int attn_check_vt_rows(const AttnArgs& a, int Lk) {
+    RV_CHECK_ARG(a.vt_ks != 8 || a.vt_ds >= ((Lk + 31) / 32) * 32, "attention: V^T rows must be padded to a multiple of 32 keys");
+    return RV_OK;
+}
+static int attn_check(const AttnArgs& a) {
+    if (int rc = attn_check_tensors(a, "attention")) return rc;
+    RV_CHECK_ARG(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.kv_div > 0, "attention: empty problem");
+    if (int rc = attn_check_strides(a)) return rc;
+    return attn_check_vt_rows(a, a.Lk);
+}
+
+// The pair kernel's three forms: split queries; key blocks staged in LDS (the attn_lds option, no per-row positions, no split output); every wave from L2.
+// a.B = 0 (k_attention_groups): every workgroup takes problem b.
+static int attn_launch_pair(const AttnArgs& a, const AttnArgs& b, const AttnGroups& gr, const char* what, hipStream_t st) {
+    const int tiles = (int)cdiv(a.Lq > b.Lq ? a.Lq : b.Lq, 64);
+    const dim3 grid(attn_grid(tiles, a.H * (a.B + b.B) * gr.G));
+    const bool lds = !a.q_lo && rv_cur_opts().attn_lds && !a.row_pos && !b.row_pos && !a.out_lo && !b.out_lo;
+    if (a.q_lo) hipLaunchKernelGGL((attn_kernel_pair<128, true>), grid, dim3(256), 0, st, a, b, tiles, gr);
+    else if (lds) hipLaunchKernelGGL((attn_kernel_pair_lds<128>), grid, dim3(256), 0, st, a, b, tiles, gr);
+    else hipLaunchKernelGGL((attn_kernel_pair<128>), grid, dim3(256), 0, st, a, b, tiles, gr);
+    RV_CHECK_LAUNCH(what);
     return RV_OK;
 }
 
@@ -747,16 +473,10 @@ int k_attention_pair(const AttnArgs& a, const AttnArgs& b, hipStream_t st, const
     if (int rc = attn_check(b)) return rc;
     RV_CHECK_ARG(a.dh == 128 && b.dh == 128 && a.H == b.H && a.Lq > 16 && b.Lq > 16, "attention pair: 128-wide heads, same head count, prefill lengths only");
     RV_CHECK_ARG(!a.key_pad && !b.key_pad, "attention pair: key padding is not supported");
-    const int tiles = (int)cdiv(a.Lq > b.Lq ? a.Lq : b.Lq, (ATTN_PAIR_Q32 && !a.q_lo) ? 128 : 64);
     const AttnGroups gr = groups ? *groups : AttnGroups{};
     RV_CHECK_ARG(gr.G >= 1 && gr.G <= RV_MAX_PREFILL_GROUPS, "attention pair: 1 .. %d groups", RV_MAX_PREFILL_GROUPS);
     RV_CHECK_ARG((a.q_lo != 0) == (b.q_lo != 0), "attention pair: both problems or neither carry split queries");
-    const bool lds = !a.q_lo && !ATTN_PAIR_Q32 && rv_cur_opts().attn_lds && !a.row_pos && !b.row_pos && !a.out_lo && !b.out_lo;
-    if (a.q_lo) hipLaunchKernelGGL((attn_kernel_pair<128, true>), dim3(attn_grid(tiles, a.H * (a.B + b.B) * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
-    else if (lds) hipLaunchKernelGGL((attn_kernel_pair_lds<128>), dim3(attn_grid(tiles, a.H * (a.B + b.B) * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
-    else hipLaunchKernelGGL((attn_kernel_pair<128>), dim3(attn_grid(tiles, a.H * (a.B + b.B) * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
-    RV_CHECK_LAUNCH("attention pair");
-    return RV_OK;
+    return attn_launch_pair(a, b, gr, "attention pair", st);
 }
 
 // G copies of one prefill problem (batched prefills WITHOUT a shared prefix: one-row generates, the stage-1 windows) in one launch: the pair
@@ -767,27 +487,20 @@ int k_attention_groups(const AttnArgs& b, hipStream_t st, const AttnGroups& gr) 
     RV_CHECK_ARG(gr.G >= 1 && gr.G <= RV_MAX_PREFILL_GROUPS, "attention groups: 1 .. %d groups", RV_MAX_PREFILL_GROUPS);
     AttnArgs a = b;
     a.B = 0;      // every workgroup takes problem b
-    const int tiles = (int)cdiv(b.Lq, (ATTN_PAIR_Q32 && !b.q_lo) ? 128 : 64);
-    const bool lds = !b.q_lo && !ATTN_PAIR_Q32 && rv_cur_opts().attn_lds && !b.out_lo;
-    if (b.q_lo) hipLaunchKernelGGL((attn_kernel_pair<128, true>), dim3(attn_grid(tiles, b.H * b.B * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
-    else if (lds) hipLaunchKernelGGL((attn_kernel_pair_lds<128>), dim3(attn_grid(tiles, b.H * b.B * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
-    else hipLaunchKernelGGL((attn_kernel_pair<128>), dim3(attn_grid(tiles, b.H * b.B * gr.G)), dim3(256), 0, st, a, b, tiles, gr);
-    RV_CHECK_LAUNCH("attention groups");
-    return RV_OK;
+    return attn_launch_pair(a, b, gr, "attention groups", st);
 }
 
 int k_attention_mixed(const AttnArgs& a, const AttnMixed& mx, hipStream_t st) {
-    RV_CHECK_ARG(a.q && a.k && a.vt && a.out, "attention mixed: null tensor");
+    if (int rc = attn_check_tensors(a, "attention mixed")) return rc;
     RV_CHECK_ARG(a.dh == 128 && a.H > 0 && !a.key_pad && !a.row_pos && !a.q_lo && !a.out_lo && a.causal && a.kv_div == 1,
                  "attention mixed: causal 128-wide heads, no key padding, no per-row positions, no split operands");
-    RV_CHECK_ARG(a.q_rs % 8 == 0 && a.k_rs % 8 == 0 && a.k_hs % 8 == 0 && a.vt_ds % 8 == 0 && a.vt_hs % 8 == 0 && a.vt_bs % 8 == 0 && a.o_rs % 4 == 0,
-                 "attention: stride alignment");
+    if (int rc = attn_check_strides(a)) return rc;
     RV_CHECK_ARG(mx.G >= 1 && mx.G <= RV_MAX_PREFILL_GROUPS, "attention mixed: 1 .. %d groups", RV_MAX_PREFILL_GROUPS);
     int longest = 0, problems = 0;
     for (int g = 0; g < mx.G; ++g) {
         const QkvGroup& e = mx.gt[g];
         RV_CHECK_ARG(e.B > 0 && e.S > 16 && (e.P0 == 0 || e.P0 > 16) && e.row >= 0 && e.base >= 0, "attention mixed: group %d: prefill lengths only (S > 16, P0 == 0 or > 16)", g);
-        RV_CHECK_ARG(a.vt_ks != 8 || a.vt_ds >= ((e.P0 + e.S + 31) / 32) * 32, "attention: V^T rows must be padded to a multiple of 32 keys");
+        if (int rc = attn_check_vt_rows(a, e.P0 + e.S)) return rc;
         RV_CHECK_ARG(mx.first[g] == problems, "attention mixed: group %d: first problem %d, expected %d", g, mx.first[g], problems);
         problems += (e.P0 > 0 ? 1 : 0) + e.B;
         longest = e.S > longest ? e.S : longest;
@@ -809,50 +522,43 @@ int k_mixed_tables(const AttnMixed& mx, QkvGroup* gt, int* last_rows, hipStream_
     return RV_OK;
 }
 
+// the per-wave kernel of one head dim, key-split or not
+template <int DH, bool QS = false>
+static void attn_launch(const AttnArgs& a, bool split, dim3 grid, int tiles, hipStream_t st) {
+    if (split) hipLaunchKernelGGL((attn_kernel<DH, true, QS>), grid, dim3(256), 0, st, a, tiles);
+    else hipLaunchKernelGGL((attn_kernel<DH, false, QS>), grid, dim3(256), 0, st, a, tiles);
+}
+
 int k_attention(const AttnArgs& a, hipStream_t st) {
-    RV_CHECK_ARG(a.q && a.k && a.vt && a.out, "attention: null tensor");
-    RV_CHECK_ARG(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.kv_div > 0, "attention: empty problem");
-    RV_CHECK_ARG(a.q_rs % 8 == 0 && a.k_rs % 8 == 0 && a.k_hs % 8 == 0 && a.vt_ds % 8 == 0 && a.vt_hs % 8 == 0 && a.vt_bs % 8 == 0 && a.o_rs % 4 == 0,
-                 "attention: stride alignment");
-    RV_CHECK_ARG(a.vt_ks != 8 || a.vt_ds >= ((a.Lk + 31) / 32) * 32, "attention: V^T rows must be padded to a multiple of 32 keys");
+    if (int rc = attn_check(a)) return rc;
     const bool split = a.Lq <= 16 && !a.no_split;
     const int tiles = (int)cdiv(a.Lq, split ? 16 : 64);
     const dim3 grid(attn_grid(tiles, a.H * a.B));
     if (a.q_lo) {      // parity precision: split queries (the LLM's 128-wide heads, no key padding)
         RV_CHECK_ARG(a.dh == 128 && !a.key_pad, "attention: split queries are instantiated for 128-wide heads without key padding");
-        if (split) hipLaunchKernelGGL((attn_kernel<128, true, true>), grid, dim3(256), 0, st, a, tiles);
-        else hipLaunchKernelGGL((attn_kernel<128, false, true>), grid, dim3(256), 0, st, a, tiles);
+        attn_launch<128, true>(a, split, grid, tiles, st);
         RV_CHECK_LAUNCH("attention");
         return RV_OK;
     }
-    // long-key problems without a mask (the adapter's self-attention, the CLIP towers): key blocks staged in LDS once per 128 query rows (attn_body_lds)
+    // long-key problems without a mask (the adapter's self-attention, the CLIP towers): key blocks staged in LDS once per 128 query rows (attn_body_lds, two tiles)
     const bool lds = !split && !a.key_pad && !a.causal && !a.row_pos && !a.row_share && !a.out_packed && !a.out_lo && a.Lk >= 96 && a.Lq >= 48 &&
                      (a.dh == 64 || a.dh == 96) && rv_cur_opts().attn_lds;
     if (lds) {
         const int t128 = (int)cdiv(a.Lq, 128);
         const dim3 g128(attn_grid(t128, a.H * a.B));
-        if (a.dh == 64) hipLaunchKernelGGL((attn_kernel_lds<64>), g128, dim3(256), 0, st, a, t128);
-        else hipLaunchKernelGGL((attn_kernel_lds<96>), g128, dim3(256), 0, st, a, t128);
+        if (a.dh == 64) hipLaunchKernelGGL((attn_kernel_lds<64, 2>), g128, dim3(256), 0, st, a, t128);
+        else hipLaunchKernelGGL((attn_kernel_lds<96, 2>), g128, dim3(256), 0, st, a, t128);
         RV_CHECK_LAUNCH("attention (LDS-staged keys)");
         return RV_OK;
     }
     if (!split && a.dh == 128 && !a.key_pad && !a.row_pos && !a.row_share && !a.out_packed && !a.out_lo && a.Lk >= 64 && a.Lq > 16 && rv_cur_opts().attn_lds) {
-        hipLaunchKernelGGL((attn_kernel_lds1<128>), grid, dim3(256), 0, st, a, tiles);      // the LLM prefill of one generate: 64-row workgroups share a staged copy
+        hipLaunchKernelGGL((attn_kernel_lds<128, 1>), grid, dim3(256), 0, st, a, tiles);      // the LLM prefill of one generate: 64-row workgroups share a staged copy
         RV_CHECK_LAUNCH("attention (LDS-staged keys, dh 128)");
         return RV_OK;
     }
-    if (a.dh == 64 && !split)
-        hipLaunchKernelGGL((attn_kernel<64, false>), grid, dim3(256), 0, st, a, tiles);
-    else if (a.dh == 64)
-        hipLaunchKernelGGL((attn_kernel<64, true>), grid, dim3(256), 0, st, a, tiles);
-    else if (a.dh == 96 && !split)
-        hipLaunchKernelGGL((attn_kernel<96, false>), grid, dim3(256), 0, st, a, tiles);
-    else if (a.dh == 96)
-        hipLaunchKernelGGL((attn_kernel<96, true>), grid, dim3(256), 0, st, a, tiles);
-    else if (a.dh == 128 && !split)
-        hipLaunchKernelGGL((attn_kernel<128, false>), grid, dim3(256), 0, st, a, tiles);
-    else if (a.dh == 128)
-        hipLaunchKernelGGL((attn_kernel<128, true>), grid, dim3(256), 0, st, a, tiles);
+    if (a.dh == 64) attn_launch<64>(a, split, grid, tiles, st);
+    else if (a.dh == 96) attn_launch<96>(a, split, grid, tiles, st);
+    else if (a.dh == 128) attn_launch<128>(a, split, grid, tiles, st);
     else if (a.dh == 512) {
         // the 4096-d cross_attn ClipEncoder (8 heads of 512): the same body with 16 query / 32 output fragments per wave - 256 + 250 registers,
         // one wave per SIMD.  A coverage path (no shipped script selects this adapter), not a tuned one; short query counts take the same

@@ -26,7 +26,7 @@ struct RvOpts {
     int adapter_fold_t2v = 1;   // ClipEncoder text -> video layers with <= 32 text tokens: Q projection + cross-attention + output projection as two skinny GEMMs around a
                                 // softmax (rowops.hip t2v_fold_kernel); 0 = the three separate steps
     int attn_lds = 1;           // attention with >= 96 keys, no mask, dh 64 / 96 (the adapter's self-attention, the CLIP towers) and the LLM prefill's attention (causal, dh 128): key
-                                // blocks staged in LDS once per workgroup (attention.hip attn_body_lds / attn_body_lds1); 0 = every wave fetches its fragments from L2 (rounds 1 - 5).
+                                // blocks staged in LDS once per workgroup (attention.hip attn_body_lds); 0 = every wave fetches its fragments from L2 (rounds 1 - 5).
                                 // Bit-identical rows.
     int qkv_lds = 1;            // prefill (persistent 256-column QKV GEMM): the fused RoPE / KV-cache epilogue of a whole panel is staged through LDS and stored as whole row slabs /
                                 // 16-byte V^T pieces (gemm_pp.hip pp_epilogue_rope_lds); 0 = every lane stores what it holds (rounds 1 - 5).  Same bytes.

@@ -181,7 +181,7 @@ def test_batched_prefill_groups_match_separate_prefills(G, P0):
 
 @pytest.mark.parametrize("G,B,P0,S", [(4, 7, 32, 139), (3, 7, 40, 96), (2, 7, 0, 96), (1, 5, 32, 171)])
 def test_prefill_attention_with_lds_staged_keys_is_bit_identical(G, B, P0, S):
-    """The prefill's causal attention with its key blocks staged in LDS once per 64-row workgroup (attention.hip attn_body_lds1, option ``attn_lds``) against the
+    """The prefill's causal attention with its key blocks staged in LDS once per 64-row workgroup (attention.hip attn_body_lds<128, 1>, option ``attn_lds``) against the
     per-wave form of rounds 1 - 5: logits AND every byte of the KV pool equal - shared prefix + per-call rows (the pair launch), several prefills to a pass
     (groups), no shared prefix (the groups launch), a lone prefill."""
     eng = _engine()
